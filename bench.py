@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X path-tracing hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,9 +15,15 @@ differing pixels on every BASELINE Cornell configuration — tests/test_toleranc
 default kernel's row is measured beside it in the same run (other_configs.headline_frame_bit_exact_kernel), and --exact
 makes it the headline.  With N > 1 the image is dealt out in interleaved
 8-row bands (band b -> rank b mod N; total work fixed => "strong"), and one RCCL gather to rank 0
-ends every step inside the timed region.  metric = Msamples/s = W*H*spp / s, whole job.
+ends every step inside the timed region.  metric = Msamples/s = W*H*spp / s, whole job; ms_per_step = wall time of the K
+timed steps / K.
 
-Extra objects on the JSON line:
+A plain run sets up, runs the W warm-up steps and one instrumented step (rtm_stats: the variant the library ran and the
+counters in "config"), times the K steps, writes --dump-outputs and prints the line.  --dump-outputs DIR writes the frame
+the last timed step delivered (rank 0's float32 image) as DIR/image.npy; a frame over 64 MB (the 4K workload) as
+DIR/image_sample.npy, a fixed seeded sample of its pixels.
+
+With --full, the line also carries (all measured outside the timed region):
   roofline     — the binding roof of the render kernel is the fp64 vector ALU, so
                  achieved = algorithmic flops per launch / average kernel time (HIP events on the
                  launch stream); an "hbm" sub-object carries the achieved HBM GB/s the metric asks
@@ -501,6 +507,25 @@ class stdout_to_stderr:
         return False
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the frame of the last timed step as out_dir/image.npy (float32 [rows, W, 3]); a frame over
+    DUMP_LIMIT_BYTES as out_dir/image_sample.npy (float32 [DUMP_SAMPLE_PIXELS, 3]): the pixels at a sorted sample of
+    flat indices drawn with seed 0, so the same arguments give the same pixels on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = image.detach().cpu().numpy()
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), img)
+        return
+    px = img.reshape(-1, img.shape[-1])
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=min(DUMP_SAMPLE_PIXELS, px.shape[0]), replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), px[idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -527,7 +552,14 @@ def main():
                          "libm returns them, bit-identical to the oracle on every scene).  ~2 %% faster; the headline frame is "
                          "bit-identical either way (tests/test_parity_gpu.py), adversarial scenes are not")
     ap.add_argument("--host-trig", action="store_true", help="(default; kept for old command lines)")
-    ap.add_argument("--no-extras", action="store_true", help="skip with_d2h and other_configs")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well: roofline (with the replayed profiles), "
+                         "cpu_baseline, with_d2h, the measured fp64 peak, other_configs and, with N > 1, the line's "
+                         "multi-GPU evidence")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the frame of the last timed step to DIR/image.npy (float32; a frame over 64 MB as "
+                         "DIR/image_sample.npy, a fixed seeded sample of its pixels)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip with_d2h, the fp64 peak and other_configs")
     ap.add_argument("--no-full-c5", action="store_true", help="(kept for old command lines: the full frame of the 100k-sphere "
                                                               "scene is a quarter of a second through the grid kernel)")
     ap.add_argument("--full-c5-exhaustive", action="store_true", help="(default since round 4; kept for old command lines)")
@@ -543,7 +575,7 @@ def main():
                          "N-rank path on one GPU; given explicitly with N = 1 the one-rank group is created too and "
                          "every step goes through the gather")
     ap.add_argument("--same-device", action="store_true", help="every rank uses cuda:0 (rehearsal only)")
-    ap.add_argument("--cpu-rows", type=int, default=64, help="rows of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-rows", type=int, default=64, help="with --full: rows of the CPU baseline sample (0 = skip)")
     ap.add_argument("--stage-timeout", type=float, default=300.0,
                     help="seconds a start-up / collective stage may take before the rank exits with code 3 naming it "
                          "(render stages get 10x this)")
@@ -551,6 +583,8 @@ def main():
                     help="bring the N ranks and their process group up, all-reduce the ranks, print one JSON line and stop "
                          "(no GPU touched: the CPU rehearsal of the launch path)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))  # nothing below has run yet: no torch import, no GPU call in this process
@@ -686,11 +720,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, kernel_ms = float(t[0]), float(t[1])
     sr.renderer.stream_status()  # the timed steps ran without rtm_stats: a truncated path would surface here
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sr.image)
 
     # SURVEY.md §8(d) wall time: kernel(s) + the final D2H of the frame (rank 0 holds it after the gather)
     with_d2h = None
-    dog.enter("extras: with_d2h steps, CPU baseline, other configs", 30 * args.stage_timeout)
-    if not args.no_extras:
+    if args.full:
+        dog.enter("extras: with_d2h steps, CPU baseline, other configs", 30 * args.stage_timeout)
+    if args.full and not args.no_extras:
         host = torch.empty(sr.image.shape, dtype=sr.image.dtype, pin_memory=True) if rank == 0 and sr.image is not None else None
         barrier()
         t1 = time.perf_counter()
@@ -704,7 +741,7 @@ def main():
     # an N-rank line proves itself, outside the timed region: the assembled frame against rank 0's own
     # single-launch render bit for bit, every rank's kernel time / rows / counters, the gather alone timed
     evidence = None
-    if use_group:
+    if use_group and args.full:
         dog.enter("multi-GPU evidence: per-rank stats, the gather alone, rank 0's single-GPU frame", 30 * args.stage_timeout)
         from raytracingmin_amd.distributed import multi_gpu_evidence
         evidence = multi_gpu_evidence(sr, stats, kernel_ms_local, args.steps, barrier, use_group=True)
@@ -719,7 +756,7 @@ def main():
         cpu = None
         extras_failed = {}
         d4 = 0.93
-        if world == 1 and args.cpu_rows > 0:
+        if args.full and world == 1 and args.cpu_rows > 0:
             try:
                 cpu = cpu_baseline(cfg, args.cpu_rows)
                 d4 = cpu["d4_fraction"]
@@ -727,7 +764,7 @@ def main():
                 cpu, extras_failed = None, {"cpu_baseline": repr(exc)}
         extras_failed = dict(extras_failed)
         pk = None
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             try:
                 pk = measured_fp64_peak(rtm)
             except Exception as exc:
@@ -741,14 +778,14 @@ def main():
         replay = None
         if args.variant == 18:
             tpath = os.path.join(ROOT, "profiles", "r4", "tolerance_traffic.json")
-        if world == 1 and headline and args.variant in (0, 18) and os.path.exists(tpath):
+        if args.full and world == 1 and headline and args.variant in (0, 18) and os.path.exists(tpath):
             tj = json.load(open(tpath))
             replay = {"traffic": tj["bytes_per_launch"],  # PMC bytes of a committed rocprofv3 --pmc pass of this command
                       "traffic_source": {"measured_in_run": False, "file": os.path.relpath(tpath, ROOT),
                                          "profile": tj.get("source", "profiles/r1/default_pmc_summary.json"),
                                          "what": "FETCH_SIZE + WRITE_SIZE per launch, corrected as MI355X_MICROARCH.md prescribes",
                                          "note": tj.get("note")}}
-        if stats["variant"] == 17:
+        if args.full and stats["variant"] == 17:
             replay = grid_replay()
             if world == 1 and not args.no_extras:  # the walks' sphere tests: one counting render of this rank's rows
                 try:
@@ -762,13 +799,6 @@ def main():
         resolved = rtm.lib().rtm_variant_name(stats["variant"]).decode()  # what the library ran (rtm_stats.variant)
         # the Cornell scenes' D4 >= 0 share comes from this run's oracle sample; other scenes' is not measured
         d4_here = None if args.workload == "c5" else d4
-        roof = roofline_of(stats, kernel_ms, n_spheres, cfg["width"], d4_here, pk["value"] if pk else None, replay)
-        roof["achieved_source"] = {"measured_in_run": True, "what": "the work model of the kernel the library reports "
-                                   "(rtm_stats.variant; roofline_of in bench.py) x this run's kernel counters / HIP-event kernel time"}
-        if roof["bound"] == "valu-fp64":
-            roof["note"] = ("no MFMA and not HBM-bound: ~1 kflop fp64 per sample vs 0.012 B of HBM traffic; peak counts FMA as 2 "
-                            "flops" + ("; this is the labelled tolerance row, compiled with contraction" if stats["variant"] == 18 else
-                                       " but parity forbids contraction, so the attainable ceiling is <= 0.5"))
         line = {
             "metric": "Msamples/s (W*H*spp/s), Cornell box 1080p@1024spp" if args.workload == "c3" else
                       f"Msamples/s (W*H*spp/s), BASELINE configs workload {args.workload}", "value": value,
@@ -784,8 +814,16 @@ def main():
                        "variant": resolved, "sample_split_waves_per_tile": stats["split"],
                        "collective": (f"{backend} gather, {world} rank(s)" if use_group else "none (one rank, frame stays in HBM)"),
                        "casts_per_sample": cps, "bounces_per_sample": bps},
-            "roofline": roof,
         }
+        if args.full:
+            roof = roofline_of(stats, kernel_ms, n_spheres, cfg["width"], d4_here, pk["value"] if pk else None, replay)
+            roof["achieved_source"] = {"measured_in_run": True, "what": "the work model of the kernel the library reports "
+                                       "(rtm_stats.variant; roofline_of in bench.py) x this run's kernel counters / HIP-event kernel time"}
+            if roof["bound"] == "valu-fp64":
+                roof["note"] = ("no MFMA and not HBM-bound: ~1 kflop fp64 per sample vs 0.012 B of HBM traffic; peak counts FMA as 2 "
+                                "flops" + ("; this is the labelled tolerance row, compiled with contraction" if stats["variant"] == 18 else
+                                           " but parity forbids contraction, so the attainable ceiling is <= 0.5"))
+            line["roofline"] = roof
         if evidence is not None:
             line["frame_matches_single_gpu"] = evidence["frame_matches_single_gpu"]
             line["gather_ms"] = evidence["gather_ms"]
@@ -798,7 +836,7 @@ def main():
         if args.variant == 18:
             ppath = os.path.join(ROOT, "profiles", "r4", "tolerance_pmc_summary.json")
             ppath = ppath if os.path.exists(ppath) else ""
-        if world == 1 and headline and args.variant in (0, 18) and ppath:
+        if args.full and world == 1 and headline and args.variant in (0, 18) and ppath:
             line["roofline"]["valu_issue"] = valu_issue_view(json.load(open(ppath)), os.path.relpath(ppath, ROOT))
         if pk is not None:
             line["roofline"]["peak_measured"] = pk
@@ -816,7 +854,7 @@ def main():
                                 "ms_per_step": with_d2h / args.steps * 1e3, "measured_in_run": True,
                                 "what": "the same K steps with the gathered frame copied to pinned host memory each step "
                                         "(SURVEY.md §8d wall time = kernel + final D2H/gather); not the headline value"}
-        if world == 1 and not args.no_extras and headline:
+        if args.full and world == 1 and not args.no_extras and headline:
             try:
                 line["other_configs"] = other_configs(rtm, cfg, local_rank, host_trig, full_c5=not args.no_full_c5_exhaustive,
                                                       cpu_rows=args.cpu_rows, d4_cornell=(cpu["d4_fraction"] if cpu else None),

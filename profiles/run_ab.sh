@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 $rounds); do
   for n in "$@"; do
     lib=$R/ab_libs/librtm_$n.so; [ "$n" = "tree" ] && lib=$R/raytracingmin_amd/librtm_hip.so
-    RTM_LIB_OVERRIDE=$lib python bench.py --cpu-rows 0 --no-extras "${args[@]}" 2>/dev/null | python -c "
+    RTM_LIB_OVERRIDE=$lib python bench.py --full --cpu-rows 0 --no-extras "${args[@]}" 2>/dev/null | python -c "
 import json,sys
 b=json.loads(sys.stdin.read()); print('$n round $r: %.2f ms/step  kernel %.2f ms  %.0f Msamples/s' % (b['ms_per_step'], b['roofline']['kernel_ms'], b['value']))" | tee -a gpurun_out/ab.log
   done

@@ -80,7 +80,8 @@ def test_bench_gpus_2_self_launch_renders_on_the_gpu():
     """The real thing on the one GPU of this box: two ranks share cuda:0 (gloo gather), started by bench.py itself."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "2",
                         "--warmup", "1", "--width", "256", "--height", "144", "--samples", "4", "--super-samples", "2",
-                        "--no-extras", "--cpu-rows", "0"], capture_output=True, text=True, timeout=600, env=_clean_env())
+                        "--full", "--no-extras", "--cpu-rows", "0"], capture_output=True, text=True, timeout=600,
+                       env=_clean_env())
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -95,3 +96,29 @@ def test_bench_gpus_2_self_launch_renders_on_the_gpu():
     assert [p["rank"] for p in per_rank] == [0, 1] and sum(p["rows"] for p in per_rank) == 144
     assert all(p["kernel_ms"] > 0 and p["casts"] >= p["samples"] > 0 for p in per_rank)
     assert sum(p["samples"] for p in per_rank) == 256 * 144 * 16
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_the_last_frame(tmp_path):
+    """A plain run prints the headline line without the --full extras, and --dump-outputs writes the frame the timed path
+    delivered: bit for bit the float32 image a Renderer of the same arguments returns."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "128", "--height",
+                        "64", "--samples", "2", "--super-samples", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, env=_clean_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "Msamples/s"
+    assert not {"roofline", "cpu_baseline", "with_d2h", "other_configs"} & set(j)
+    img = np.load(out / "image.npy")
+    assert img.dtype == np.float32 and img.shape == (64, 128, 3)
+    import raytracingmin_amd as rtm
+    data = rtm.LoadData(os.path.join(ROOT, "scenes", "cornellBoxSetting.json")).data
+    data.width, data.height, data.samples, data.superSamples = 128, 64, 2, 2
+    # bench.py's default for this workload: the fp64 tolerance row (variant 18), host sin/cos, cap 8, seed 0x5EED
+    ref, _ = rtm.Renderer(data, mode="repaired", max_bounces=8, seed=0x5EED, device=0, variant=18).render_rows_device(
+        want=("f32",), stats=False)
+    assert np.array_equal(img.view(np.uint32), ref["f32"].cpu().numpy().view(np.uint32))
