@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds A/B copies of librtm_hip.so with different -D switches into ab_libs/ (travels to the GPU box, not committed):
-#   profiles/build_ab.sh name1 "-DRTM_OPT_GUARD=0 ..." name2 "..." ...
+#   profiles/build_ab.sh name1 "-DSOME_SWITCH=0 ..." name2 "..." ...
 # Run them with RTM_LIB_OVERRIDE=ab_libs/librtm_<name>.so python bench.py ...  (profiles/run_ab.sh)
 set -e
 cd "$(dirname "$0")/../raytracingmin_amd/csrc"

@@ -26,10 +26,7 @@
 
 namespace rtm {
 
-#ifndef RTM_GRID_WPE
-#define RTM_GRID_WPE 4
-#endif
-constexpr int kGridWavesPerSimd = RTM_GRID_WPE;  // launch bound of the grid kernel (profiles/r3/grid_variants.txt)
+constexpr int kGridWavesPerSimd = 4;  // launch bound of the grid kernel (profiles/r3/grid_variants.txt)
 // a term's slot: three doubles padded to 32 bytes — one aligned 32-byte sector, written whole by two 16-byte stores (24-byte
 // slots straddle sectors: L2 then FETCHES around every store, 55 GB per configs[4] frame, profiles/r3/README.md)
 constexpr int kGridTermDoubles = 4;
@@ -123,7 +120,6 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
             if (walking) walking = walk.advance(sc, org, dir);
         }
         if (busy && !walking) {
-            RTM_GRID_OCC(8);
             if constexpr (COUNT) n_tests += walk.tests;
             D3 term;
             bool cont = path_shade_spec(sc, walk.best, walk.dis, P.mode, P.max_bounces, org, dir, depth, rng, term, pc, push, ShadeLds(trig, unit_tab));
@@ -133,7 +129,6 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
                 depth = 0;
             }
             if (!cont) {
-                RTM_GRID_OCC(9);
                 const bool deep = depth > LDS_D;
                 const D3 L = (__builtin_amdgcn_ballot_w64(deep) == 0)
                                  ? path_fold_blocked(sc, term, depth, [&](int d) { return (int)rec[d * 64 + lane]; })
@@ -171,18 +166,6 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
 __global__ __launch_bounds__(64) void grid_finalize_kernel(const RenderParams P, const unsigned tile_base) {
     const int lane = threadIdx.x;
     const unsigned tile = tile_base + blockIdx.x;
-#ifdef RTM_GRID_EXP_OCC
-    if (blockIdx.x == 0 && lane == 0) {
-        const char* names[10] = {"begin", "advance", "step", "test0", "test1", "test2", "test3", "sqrt", "shade", "path end"};
-        for (int r = 0; r < 10; ++r) {
-            // (one value per call: device printf mangled three 64-bit arguments in one)
-            printf("[grid occ] %s:", names[r]);
-            printf(" executions %llu", g_grid_occ[2 * r]);
-            printf(" lanes %llu\n", g_grid_occ[2 * r + 1]);
-            g_grid_occ[2 * r] = g_grid_occ[2 * r + 1] = 0ull;
-        }
-    }
-#endif
     const int px = (int)(tile % (unsigned)P.tiles_x) * 8 + (lane & 7);
     const int py = band_row(P, (int)(tile / (unsigned)P.tiles_x), lane >> 3);
     const bool valid = px < P.W && py < P.row_end;

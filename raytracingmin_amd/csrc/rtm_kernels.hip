@@ -357,10 +357,7 @@ static SceneView scene_view(const double* geom, const double* mat, const double*
 // covers more than kGridBigCells cells goes to the list every ray tests.  No grid (the other kernels serve the scene)
 // for fewer than kGridMinSpheres gridded spheres (below that the packed-record kernels are as fast or faster:
 // profiles/r3/grid_crossover.txt), non-finite geometry, more than kGridMaxBig big spheres or planes.
-#ifndef RTM_GRID_MIN
-#define RTM_GRID_MIN 64
-#endif
-constexpr size_t kGridMinSpheres = RTM_GRID_MIN;  // gridded spheres a scene needs to get a grid (profiles/r3/grid_crossover.txt)
+constexpr size_t kGridMinSpheres = 64;  // gridded spheres a scene needs to get a grid (profiles/r3/grid_crossover.txt)
 constexpr int kGridBigCells = 125, kGridMaxBig = 1024, kGridMaxDim = 1024;
 constexpr double kGridDdTol = 4e-7;  // |dir.dir - 1| the pads cover: twice what the reference's float-sqrt Normalize leaves (1.8e-7)
 static double grid_cells_per_sphere() {
@@ -1160,7 +1157,6 @@ static void launch_render_depth(const RenderParams& P_in, unsigned grid, hipStre
             if constexpr (DEFER && UNROLL == -8) {
                 // scenes under 8 spheres (every shipped scene): the instantiation for exactly n spheres
                 const size_t lds = with_unit_table(P, tab + kFoldQueueBytesS + (STEAL ? kStealLdsBytes : 0));
-#if RTM_OPT_AXIS
 #define RTM_AXIS_CASE(k, sig)                                                                                                  \
     if (P.scene.n == k && P.scene.axis_pat == sig && P.mode == RTM_MODE_REPAIRED && P.unit_tab == 1u) { /* rtm_path.h: sphere_disc */                        \
         render_tiles_kernel<M, LDS_TAB, axis_unroll(k, sig), RecT, 16, WPE, PARK, STAMP, true, SPLIT, true, false, false, false, STEAL> \
@@ -1169,7 +1165,6 @@ static void launch_render_depth(const RenderParams& P_in, unsigned grid, hipStre
     }
                 RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
 #undef RTM_AXIS_CASE
-#endif
                 switch (P.scene.n) {
 #define RTM_EXACT_N(k)                                                                                     \
     case k:                                                                                                \
@@ -1195,7 +1190,6 @@ static void launch_render_depth(const RenderParams& P_in, unsigned grid, hipStre
     if constexpr (DEFER && sizeof(RecT) == 1) {
         if (P.scene.n < 256) {  // any depth: packed records + pooled stack, deferred fold
             const size_t lds = with_unit_table(P, tab + kFoldQueueBytesLS);  // (8 280 bytes for a 7-sphere scene; 10 072 with the FIFO form: no room for the table then)
-#if RTM_OPT_AXIS
             if constexpr (UNROLL == -8) {
 #define RTM_AXIS_CASE(k, sig)                                                                                              \
     if (P.scene.n == k && P.scene.axis_pat == sig && P.mode == RTM_MODE_REPAIRED && P.unit_tab == 1u) { /* rtm_path.h: sphere_disc */                    \
@@ -1206,7 +1200,6 @@ static void launch_render_depth(const RenderParams& P_in, unsigned grid, hipStre
                 RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
 #undef RTM_AXIS_CASE
             }
-#endif
             render_tiles_kernel<M, LDS_TAB, UNROLL, RecT, 0, WPE, PARK, STAMP, false, SPLIT, true, true>
                 <<<grid, 64, lds, stream>>>(P);
             return;

@@ -34,18 +34,11 @@ namespace rtm_tol {
 // seq_sqrt_batch, LIGHT): for compact scenes seen by a camera that is within the same extent — anything else runs the plain
 // exact-n kernels with the full roots.
 static bool compact_launch(const RenderParams& P) {
-#if RTM_TOL_LIGHT_ROOTS
     const double cam = std::sqrt(P.cam_org.x * P.cam_org.x + P.cam_org.y * P.cam_org.y + P.cam_org.z * P.cam_org.z);
     return (P.scene.fold_flags & kSceneCompact) != 0u && cam <= kCompactExtent;
-#else
-    (void)P;
-    return true;
-#endif
 }
 
-#ifndef RTM_TOL_WPE
-#define RTM_TOL_WPE 4  // waves per SIMD of the depth-capped kernel's launch bound (A/B knob: profiles/r4/tol_wpe_ab.txt)
-#endif
+constexpr int kTolWavesPerSimd = 4;  // launch bound of the depth-capped kernel (profiles/r4/tol_wpe_ab.txt)
 template <int UNROLL, bool SPLIT>
 static void launch_one(const RenderParams& P_in, unsigned grid, size_t lds_pad, hipStream_t stream) {
     RenderParams P = P_in;
@@ -55,7 +48,7 @@ static void launch_one(const RenderParams& P_in, unsigned grid, size_t lds_pad, 
     P.unit_tab = unit_table_fits(lds) ? 1u : 0u;
     if (P.unit_tab) lds += (size_t)(kShadeConstCount - kTrigConstCount) * sizeof(double);
     // <M, LDS_TAB, UNROLL, RecT, LDS_D, WPE, PARK, STAMP, PACK8, SPLIT, DEFER, PACKL, REUSE, PLANES, STEAL>
-    render_tiles_kernel<MathFast, true, UNROLL, uint8_t, 16, RTM_TOL_WPE, true, false, true, SPLIT, true, false, false, false, true>
+    render_tiles_kernel<MathFast, true, UNROLL, uint8_t, 16, kTolWavesPerSimd, true, false, true, SPLIT, true, false, false, false, true>
         <<<grid, 64, lds, stream>>>(P);
 }
 // Any depth (max_bounces < 0 — the reference's own semantics — or > 8): the deferred fold with records packed by position
@@ -71,21 +64,18 @@ static void launch_one_any(const RenderParams& P_in, unsigned grid, size_t lds_p
 }
 template <bool SPLIT>
 static void launch_n_any(const RenderParams& P, unsigned grid, size_t lds_pad, hipStream_t stream) {
-#if RTM_OPT_AXIS
     const bool table_fits = unit_table_fits(lds_table_bytes(P.scene.n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) +
                                             kFoldQueueBytesLS + lds_pad);  // (launch_one_any's rule)
     if (P.scene.n == 7 && P.scene.axis_pat == kAxisSigCornell7 && P.mode == RTM_MODE_REPAIRED && table_fits && compact_launch(P)) {  // (the shipped Cornell box: rtm_path.h, sphere_disc)
         launch_one_any<axis_unroll(7, kAxisSigCornell7), SPLIT>(P, grid, lds_pad, stream);
         return;
     }
-#endif
     if (P.scene.n < 8) launch_one_any<-8, SPLIT>(P, grid, lds_pad, stream);
     else launch_one_any<8, SPLIT>(P, grid, lds_pad, stream);
 }
 
 template <bool SPLIT>
 static void launch_n(const RenderParams& P, unsigned grid, size_t lds_pad, hipStream_t stream) {
-#if RTM_OPT_AXIS
     // (the axis-signature instantiations take the near-unit Normalize table's presence as a compile-time fact: launch_one's rule)
     const bool table_fits = unit_table_fits(lds_table_bytes(P.scene.n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) +
                                             kFoldQueueBytesS + 2 * 64 * sizeof(unsigned) + 64 * sizeof(unsigned long long) + lds_pad);
@@ -96,7 +86,6 @@ static void launch_n(const RenderParams& P, unsigned grid, size_t lds_pad, hipSt
     }
     RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
 #undef RTM_AXIS_CASE
-#endif
     switch (P.scene.n) {  // the shipped scenes' sizes run the instantiation for exactly their sphere count
         case 3: launch_one<-103, SPLIT>(P, grid, lds_pad, stream); return;
         case 5: launch_one<-105, SPLIT>(P, grid, lds_pad, stream); return;

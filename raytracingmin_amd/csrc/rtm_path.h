@@ -7,39 +7,6 @@
 #include <cfloat>
 #include <type_traits>
 
-// A/B switches of the round-2 instruction trimming (profiles/r2/ab_*.txt); all on by default.
-#ifndef RTM_OPT_GUARD
-#define RTM_OPT_GUARD 1
-#endif
-#ifndef RTM_OPT_SEL64
-#define RTM_OPT_SEL64 1
-#endif
-#ifndef RTM_OPT_TRIGLOAD
-#define RTM_OPT_TRIGLOAD 1
-#endif
-#ifndef RTM_OPT_ONB
-#define RTM_OPT_ONB RTM_OPT_GUARD  // rides on the guards' "no zero component" guarantee
-#endif
-
-#ifndef RTM_OPT_AXIS
-#define RTM_OPT_AXIS 1  // axis-signature instantiations of the exact-n kernels (sphere_disc; A/B switch)
-#endif
-#ifndef RTM_OPT_CTMODE
-#define RTM_OPT_CTMODE 1  // what an instantiation knows at compile time: its mode (axis signatures), "no planes" (SceneLds) ...
-#endif
-#ifndef RTM_TOL_LIGHT_ROOTS
-#define RTM_TOL_LIGHT_ROOTS 1  // the tolerance unit's search roots without the residual step in compact scenes (A/B switch)
-#endif
-#ifndef RTM_TOL_PACKID
-#define RTM_TOL_PACKID 1  // (with the light roots: the sphere's index in the near root's last three bits — accept_batch; A/B switch)
-#endif
-#ifndef RTM_OPT_FOLDMUL
-#define RTM_OPT_FOLDMUL 1  // the packed folds leave a bounce level's "+ (+0, +0, +0)" out (SceneView::fold_flags; A/B switch)
-#endif
-#ifndef RTM_OPT_CTN
-#define RTM_OPT_CTN 0     // ... and (NOT kept: profiles/r4/ctn_ab.txt — nothing for the tolerance row, +3 % for the exact kernel,
-#endif                    // whose register allocation it upsets) its sphere count in the exact-n instantiations; A/B switches
-
 #include "../../include/rtm.h"
 #include "rtm_device.h"
 
@@ -233,7 +200,6 @@ struct MathFast {
     // D4 = +0 has a real hit at t = b).
     template <int K, bool LIGHT = false>
     static __device__ __forceinline__ void sqrt64_batch_hit(const double (&x)[K], double (&out)[K]) {
-#if RTM_OPT_GUARD
         // "every high word >= 0x10000000" as ONE compare of their unsigned minimum (v_min3_u32): the K
         // compare / select / shift / or steps hipcc makes of the && chain were ~25 instructions per cast
         unsigned lowest = (unsigned)__double2hiint(x[0]);
@@ -243,11 +209,6 @@ struct MathFast {
             lowest = h < lowest ? h : lowest;
         }
         const bool ok = lowest >= 0x10000000u;
-#else
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < K; ++k) ok = ok && ((unsigned)__double2hiint(x[k]) >= 0x10000000u);
-#endif
         if (__builtin_amdgcn_ballot_w64(!ok) != 0) {
 #pragma unroll
             for (int k = 0; k < K; ++k) out[k] = ::sqrt(x[k]);
@@ -488,7 +449,7 @@ struct MathSpecT {
         return __builtin_amdgcn_div_fixup(seq_quot(x, y, r), y, x);
     }
 };
-using MathSpec = MathSpecT<RTM_OPT_GUARD != 0>;
+using MathSpec = MathSpecT<true>;
 using MathSpecZ = MathSpecT<false>;
 template <class T>
 struct is_spec : std::false_type {};
@@ -696,7 +657,7 @@ struct SceneLds {
                           // on the sphere, (double)sqrtf((float)(r*r)), its refined reciprocal, the float r*r
     static constexpr bool kHasNormTable = true;
     static constexpr bool kPlanes = false;
-    static constexpr bool kNeverPlanes = RTM_OPT_CTMODE != 0;  // the launchers hand scenes that hold planes to SceneLdsObjects (v.plane is null here)
+    static constexpr bool kNeverPlanes = true;  // the launchers hand scenes that hold planes to SceneLdsObjects (v.plane is null here)
     __device__ __forceinline__ double norm_m(int id) const { return lnrm[id * 3]; }
     __device__ __forceinline__ double norm_rinv(int id) const { return lnrm[id * 3 + 1]; }
     __device__ __forceinline__ float norm_r2f(int id) const { return reinterpret_cast<const float*>(lnrm + id * 3 + 2)[0]; }
@@ -798,19 +759,12 @@ __device__ __forceinline__ void sphere_update(const double4 g, const D3 org, con
 __device__ __forceinline__ void accept_update(const double b, const double sq, const int index, double& dis,
                                               int& hit_object) {
     const double t1 = b - sq, t2 = b + sq;
-#if RTM_OPT_SEL64
     // masks straight from the compares (SGPR pairs); NaN t: "t < dis" is false, so nothing is accepted
     const double t = sel_f64_mask(__builtin_amdgcn_ballot_w64(t1 > 0.001), t1, t2);
     const unsigned long long accept =
         __builtin_amdgcn_ballot_w64(t < dis) & ~__builtin_amdgcn_ballot_w64(t < (double)1e-5f);
     dis = sel_f64_mask(accept, t, dis);
     hit_object = sel_index_mask(accept, index, hit_object);
-#else
-    const double t = (t1 > 0.001) ? t1 : t2;
-    const bool accept = (t < dis) && !(t < (double)1e-5f);
-    dis = accept ? t : dis;
-    hit_object = accept ? index : hit_object;
-#endif
 }
 
 // The K acceptance updates of a chunk, NEAR ROOTS FIRST.  Intersect returns t1 when t1 > 0.001 and otherwise the far root
@@ -822,9 +776,6 @@ __device__ __forceinline__ void accept_update(const double b, const double sq, c
 // v_min_f64(dis, t1v) (the instruction returns the other operand for a quiet NaN; equal operands: the same bits, and the
 // strict compare keeps the lower index) and the index follows the one compare t1v < dis: 8 vector instructions per
 // sphere instead of 10, the same (dis, index) in every case.  Otherwise: the general updates, from the same b and sq.
-#ifndef RTM_OPT_NEARFIRST
-#define RTM_OPT_NEARFIRST 1
-#endif
 //   PACKID  (the tolerance unit's light-root searches: ONE chunk of at most 7 spheres from index 0, dis = DBL_MAX on entry) the
 //           sphere's index rides in the last three bits of its near root — a perturbation of at most 7 ulps, under the light
 //           root's 35 — so that v_min_f64 alone carries distance AND index (ties between equal upper bits go to the lower
@@ -833,7 +784,7 @@ __device__ __forceinline__ void accept_update(const double b, const double sq, c
 template <int K, bool PACKID = false>
 __device__ __forceinline__ void accept_batch(const double (&b)[K], const double (&sq)[K], const int i0, double& dis,
                                              int& hit_object) {
-#if RTM_OPT_NEARFIRST && defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__)
     static_assert(!PACKID || K <= 7, "three bits of index, 7 = none");
     double t1v[K];
     unsigned long long far = 0ull;
@@ -1010,10 +961,7 @@ __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, cons
         double b[K], D4[K], sq[K];
         if constexpr (SIG != 0u) {  // the scene's axis signature is a compile-time constant: sphere_disc's branches fold
             const AxisShared A(org, dir);
-#ifndef RTM_AXIS_PHASE
-#define RTM_AXIS_PHASE 2  // spheres whose geometry is fetched together in the axis form (A/B knob; an axis sphere needs 4 SGPRs, not 8)
-#endif
-            constexpr int PA = RTM_AXIS_PHASE;
+            constexpr int PA = 2;  // spheres whose geometry is fetched together (an axis sphere needs 4 SGPRs, not 8)
 #pragma unroll
             for (int k0 = 0; k0 < K; k0 += PA) {
                 double4 g[PA];
@@ -1026,8 +974,8 @@ __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, cons
                 __builtin_amdgcn_sched_barrier(0);
             }
             // (the tolerance unit's axis-signature instantiations are launched for compact scenes only: light roots, above)
-            M::template sqrt64_batch_hit<K, (RTM_TOL != 0) && (RTM_TOL_LIGHT_ROOTS != 0)>(D4, sq);
-            accept_batch<K, (RTM_TOL != 0) && (RTM_TOL_LIGHT_ROOTS != 0) && (RTM_TOL_PACKID != 0)>(b, sq, i0, dis, hit_object);
+            M::template sqrt64_batch_hit<K, RTM_TOL != 0>(D4, sq);
+            accept_batch<K, RTM_TOL != 0>(b, sq, i0, dis, hit_object);
             return;
         }
 #pragma unroll
@@ -1140,33 +1088,8 @@ __device__ __forceinline__ void object_chunk(const Scene& sc, const int i0, cons
 // spheres the geometric ray passes at a distance) take the exhaustive loop; rays with a non-finite component hit
 // nothing in the reference loop either (every t is NaN or infinite).
 // Spheres in `big` (padded box over too many cells) are tested for every ray.
-#ifndef RTM_GRID_K
-#define RTM_GRID_K 4
-#endif
-#ifndef RTM_GRID_SPILL
-#define RTM_GRID_SPILL 1
-#endif
-constexpr int kGridBatch = RTM_GRID_K;  // records in flight per trip of the walk (profiles/r3/grid_crossover.txt)
-#ifndef RTM_GRID_SHADE_AT
-#define RTM_GRID_SHADE_AT 5
-#endif
-constexpr int kGridShadeAt8 = RTM_GRID_SHADE_AT;  // the render loop shades when this many eighths of a wave's lanes have finished their walks
-
-// EXPERIMENT build (-DRTM_GRID_EXP_OCC): how often each region of the grid kernel runs and with how many lanes
-// (profiles/r3/grid_occupancy.txt); the counters are printed and cleared by grid_finalize_kernel.
-#ifdef RTM_GRID_EXP_OCC
-__device__ unsigned long long g_grid_occ[32];
-#define RTM_GRID_OCC(region)                                                                          \
-    do {                                                                                              \
-        const unsigned long long occ_m = __builtin_amdgcn_ballot_w64(true);                           \
-        if ((int)(threadIdx.x & 63) == __builtin_ctzll(occ_m)) {                                      \
-            atomicAdd(&g_grid_occ[2 * (region)], 1ull);                                               \
-            atomicAdd(&g_grid_occ[2 * (region) + 1], (unsigned long long)__builtin_popcountll(occ_m)); \
-        }                                                                                             \
-    } while (0)
-#else
-#define RTM_GRID_OCC(region) do { } while (0)
-#endif
+constexpr int kGridBatch = 4;  // records in flight per trip of the walk (profiles/r3/grid_crossover.txt)
+constexpr int kGridShadeAt8 = 5;  // the render loop shades when this many eighths of a wave's lanes have finished their walks
 
 // One ray's walk through the grid, as per-lane state that can be advanced a trip at a time: the render kernel's lanes
 // walk independently and are shaded in groups (rtm_grid_kernel.h), the probe runs it to the end.
@@ -1212,7 +1135,6 @@ struct GridWalk {
         const double b = dot(p_o, dir);                            // :199
         const double D4 = b * b - dot(p_o, p_o) + g.w;             // :200
         if (D4 >= 0.0) {                                           // :202 (a NaN D4 ends in a NaN t: never accepted)
-            RTM_GRID_OCC(7);
             const double sq = M::sqrt64(D4);
             const double t1 = b - sq, t2 = b + sq;
             const double t = (t1 > 0.001) ? t1 : t2;  // :212-223; accepted as in sphere_update, ties to the lower index
@@ -1254,7 +1176,6 @@ struct GridWalk {
     // (false: dis / best are final — a miss of the box, a non-finite ray, or the exhaustive loop has run).
     __device__ __forceinline__ bool begin(const Scene& sc, const D3 org, const D3 dir) {
         HdrPtr G = header(sc);
-        RTM_GRID_OCC(0);
         best = -1;
         dis = DBL_MAX;
         pending = 0u;
@@ -1352,10 +1273,8 @@ struct GridWalk {
     // Returns whether the walk goes on (false: dis / best are final).
     __device__ __forceinline__ bool advance(const Scene& sc, const D3 org, const D3 dir) {
         HdrPtr G = header(sc);
-        RTM_GRID_OCC(1);
         if (pending == 0u) {
             if (j >= jend) {
-                RTM_GRID_OCC(2);
                 // this cell is done and its candidates are settled: every sphere that can be hit before its exit has been
                 // tested (see above)
                 if (dis <= t_exit || !next_ok) return false;
@@ -1368,8 +1287,7 @@ struct GridWalk {
             // records left issues two loads): the walk is bound by the vector memory pipeline, which pays per lane and
             // distinct line (profiles/r3/grid_perturbation.txt: the same loads issued twice cost +31 %, the tests'
             // arithmetic twice +8 %), so nothing is fetched that is not needed.
-#if RTM_GRID_SPILL
-            // (round 4, profiles/r4/grid_spill.txt: 201.0 -> 197.1 ms for the configs[4] frame; RTM_GRID_SPILL=0 is the twin)
+            // (round 4, profiles/r4/grid_spill.txt: 201.0 -> 197.1 ms for the configs[4] frame)
             // A lane whose cell has fewer than kGridBatch records left fills its free slots with the first records of the
             // NEXT cell on its ray (their range is known already), unless the walk is known to end in this cell.  Testing
             // a sphere early, or one the walk would never have reached, changes nothing (see above: any order, ties by
@@ -1387,18 +1305,6 @@ struct GridWalk {
 #pragma unroll
             for (unsigned k = 0; k < (unsigned)kGridBatch; ++k) {
                 if (left > k) {
-#else
-            const double4* recs = G->recs + j;
-            const unsigned left = jend - j;
-            double4 r[kGridBatch];
-#pragma unroll
-            for (unsigned k = 0; k < (unsigned)kGridBatch; ++k)
-                if (left > k) r[k] = recs[k];
-#pragma unroll
-            for (unsigned k = 0; k < (unsigned)kGridBatch; ++k) {
-                if (left > k) {
-#endif
-                    RTM_GRID_OCC(3 + k);
                     if constexpr (COUNT) ++tests;
                     // src/SettingData.cpp:198-200; the sphere's index rides in the low 29 mantissa bits of the float-valued r*r
                     const unsigned long long w = (unsigned long long)__double_as_longlong(r[k].w);
@@ -1414,14 +1320,9 @@ struct GridWalk {
                     }
                 }
             }
-#if RTM_GRID_SPILL
             j += left1;
-#else
-            j = left > (unsigned)kGridBatch ? j + (unsigned)kGridBatch : jend;
-#endif
         }
         if (pending != 0u) {  // one candidate per lane and trip: :205-223 and the caller's acceptance (src/Renderer.cpp:67)
-            RTM_GRID_OCC(7);
             --pending;
             const unsigned at = pending * (unsigned)q_stride;
             const double b = q_b[at], D4 = q_d[at];
@@ -1684,14 +1585,11 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
         }
     }
     // :82-83  w = Dot(n, d) < 0 ? n : n * -1.0  (multiplying by -1.0 flips the sign bit, exactly)
-#ifndef RTM_OPT_NOFLIP
-#define RTM_OPT_NOFLIP 1  // (A/B switch)
-#endif
     const bool turn = !(dot(normal, dir) < 0.0);
     D3 w = normal;
     // (a sphere hit from outside — every hit in a room seen from inside — never turns its normal: one scalar test for the wave,
     // and the mask and the three sign flips are skipped)
-    if (!RTM_OPT_NOFLIP || __builtin_amdgcn_ballot_w64(turn) != 0) {
+    if (__builtin_amdgcn_ballot_w64(turn) != 0) {
         const LaneMask flip = lane_mask(turn);
         w = d3(negate_where(flip, normal.x), negate_where(flip, normal.y), negate_where(flip, normal.z));
     }
@@ -1699,7 +1597,7 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
     // :88 r1 = 2 PI u with u = m * 2^-24: (2 PI * 2^-24) * m is the same correctly rounded product as 2 PI * (m * 2^-24)
     const double m24 = rng_next_m(rng);  // (r1 is formed where its sin / cos are taken: sincos_draw)
     const double r2 = rng_next(rng);                      // :89
-#if RTM_OPT_TRIGLOAD && !RTM_TOL  // (the tolerance unit takes the device's sin / cos: launch_tol)
+#if !RTM_TOL  // (the tolerance unit takes the device's sin / cos: launch_tol)
     TrigFixWord fixw{0u, 0};
     if (sc.v.trig_fix) fixw = trig_fix_load(sc.v.trig_fix, rng);  // wave-uniform; consumed after the sincos
 #endif
@@ -1708,7 +1606,6 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
     const bool use_y = fabs(w.x) > (double)FLT_MIN;
     const bool some_x_axis = __builtin_amdgcn_ballot_w64(!use_y) != 0;  // some lane has |w.x| <= FLT_MIN (e.g. literal mode)
     double sn, cs;
-#if RTM_OPT_ONB
     if constexpr (std::is_same<MI, MathSpecT<true>>::value) {  // the guarded flavour only: it has excluded zero components
         if (!some_x_axis) {
             // The orthonormal basis with the structural zeros of Cross((0,1,0), w) taken out — exact, not
@@ -1724,11 +1621,8 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
             m.normalize_xz(w.z, -w.x, ux, uz);
             const double vx = w.y * uz, vy = -w.x * uz + w.z * ux, vz = -(w.y * ux);
             m.sincos_draw(m24, sn, cs);
-#if RTM_TOL
-#elif RTM_OPT_TRIGLOAD
+#if !RTM_TOL
             if (sc.v.trig_fix) trig_fix_apply(fixw, sn, cs);  // wave-uniform
-#else
-            if (sc.v.trig_fix) apply_trig_fix(sc.v.trig_fix, rng, sn, cs);
 #endif
             const double s1 = m.sqrt64_unit(1.0 - r2);
             out.dir = m.normalize_near_unit(d3(((ux * cs) * r2s + (vx * sn) * r2s) + w.x * s1, (vy * sn) * r2s + w.y * s1,
@@ -1738,7 +1632,6 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
             return;
         }
     }
-#endif
     D3 c = cross(d3(0, 1, 0), w);
     D3 u;
     if (some_x_axis) {
@@ -1750,11 +1643,8 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
     }
     const D3 v = cross(w, u);  // :102
     m.sincos_draw(m24, sn, cs);
-#if RTM_TOL
-#elif RTM_OPT_TRIGLOAD
+#if !RTM_TOL
     if (sc.v.trig_fix) trig_fix_apply(fixw, sn, cs);  // wave-uniform
-#else
-    if (sc.v.trig_fix) apply_trig_fix(sc.v.trig_fix, rng, sn, cs);  // wave-uniform
 #endif
     out.dir = m.normalize_near_unit((u * cs) * r2s + (v * sn) * r2s + w * m.sqrt64_unit(1.0 - r2));  // :103-107
     out.org = hit_point;
@@ -1952,7 +1842,6 @@ template <class Scene>
 __device__ __forceinline__ D3 path_fold_packed8_all(const Scene& sc, const int term_id, const unsigned long long rec) {
     D3 L = sc.emission(term_id);
     const unsigned lo = (unsigned)rec, hi = (unsigned)(rec >> 32);
-#if RTM_OPT_FOLDMUL
     if (sc.v.fold_flags & kFoldNoLevelEmission) {  // wave-uniform: a bounce level adds (+0, +0, +0) — SceneView::fold_flags
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
@@ -1965,7 +1854,6 @@ __device__ __forceinline__ D3 path_fold_packed8_all(const Scene& sc, const int t
         }
         return L;
     }
-#endif
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         const unsigned word = g ? hi : lo;
@@ -1999,7 +1887,6 @@ __device__ __forceinline__ D3 path_fold_packed16(const Scene& sc, const int term
     }
     auto word = [&](const unsigned long long w) {
         const unsigned half[2] = {(unsigned)(w >> 32), (unsigned)w};  // levels 7..4, then 3..0
-#if RTM_OPT_FOLDMUL
         if (sc.v.fold_flags & kFoldNoLevelEmission) {  // wave-uniform: a bounce level adds (+0, +0, +0)
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
@@ -2011,7 +1898,6 @@ __device__ __forceinline__ D3 path_fold_packed16(const Scene& sc, const int term
             }
             return;
         }
-#endif
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
             D3 c[4], e[4];

@@ -252,15 +252,11 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, bool valid, i
 //           performs); different work per sample than the reference, hence the label.
 constexpr int kFoldRing = 128;  // entries of the ring: < 64 waiting + <= 64 appended per iteration
 constexpr size_t kFoldQueueBytes = kFoldRing * 16 + 3 * 64 * 8 + 64 * 8 + 64 * 4;  // the FIFO form: ring, terms, FIFO, counts
-constexpr size_t kFoldQueueBytesL = kFoldQueueBytes + kFoldRing * 8 + 64 * 8;  // + word 1 of the entries and of the lanes
-#ifndef RTM_OPT_SCATTER
-#define RTM_OPT_SCATTER 1  // the folding lane adds its term to the entry's pixel (render_tiles_kernel: kScatter; A/B switch)
-#endif
 // kScatter kernels (every deferred-fold kernel but the primary-hit-reuse row): no staged terms, no FIFO — ring, the pixels'
 // counts of added entries (a small wave's tags in their place), the lanes' counts: 1 792 bytes less per wave, which is what lets
 // the any-depth kernels keep the near-unit Normalize table at 16 waves per CU
-constexpr size_t kFoldQueueBytesS = RTM_OPT_SCATTER ? kFoldRing * 16 + 64 * 4 + 64 * 4 : kFoldQueueBytes;
-constexpr size_t kFoldQueueBytesLS = RTM_OPT_SCATTER ? kFoldQueueBytesS + kFoldRing * 8 + 64 * 8 : kFoldQueueBytesL;
+constexpr size_t kFoldQueueBytesS = kFoldRing * 16 + 64 * 4 + 64 * 4;
+constexpr size_t kFoldQueueBytesLS = kFoldQueueBytesS + kFoldRing * 8 + 64 * 8;
 // (SPLIT: a small wave's ring entries carry a 2-byte tag (owner lane, sample).  The tags live in the per-lane FIFO array,
 // which a small wave does not use: 256 of its 512 bytes.  A separate array put the any-depth kernel at 10 328 bytes of LDS per
 // wave — 15 instead of 16 waves per CU, 5 % on every unlimited-depth frame, profiles/r3/ab_r2_vs_r3.txt.)
@@ -291,10 +287,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     const int lane = threadIdx.x;
     // The exact-n instantiations (UNROLL in -101 .. -107, or an axis signature: UNROLL <= -1000) are launched for scenes of
     // exactly that many spheres, so the count COULD be a compile-time constant there (the LDS tables' offsets, the identity
-    // row's index and the empty record word as immediates).  Measured and not kept (RTM_OPT_CTN, profiles/r4/ctn_ab.txt): the
+    // row's index and the empty record word as immediates).  Measured and not kept (profiles/r4/ctn_ab.txt): the
     // tolerance row does not move, the exact kernel loses 3 %.
-    const int scene_n = (RTM_OPT_CTN && UNROLL <= -1000) ? ((-UNROLL - 1000) & 7)
-                        : (RTM_OPT_CTN && UNROLL <= -101 && UNROLL >= -107) ? (-UNROLL - 100) : P.scene.n;
+    const int scene_n = P.scene.n;
     double* lgeom = reinterpret_cast<double*>(lds_raw);
     double* lmat = lgeom + (LDS_TAB ? scene_n * 4 : 0);
     double* lnrm = lmat + (LDS_TAB ? (scene_n + 1) * 8 : 0);
@@ -303,16 +298,13 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // the shading constants: sincos and — where the launcher found the LDS for it — the near-unit Normalize table
     // wave-uniform; the axis-signature instantiations are launched only when the table is there (the launchers check), so it is
     // a compile-time constant for them
-#ifndef RTM_OPT_CTTAB
-#define RTM_OPT_CTTAB 1  // (A/B switch)
-#endif
-    const bool unit_tab = (RTM_OPT_CTTAB && UNROLL <= -1000) ? true : (P.unit_tab != 0u);
+    const bool unit_tab = UNROLL <= -1000 ? true : (P.unit_tab != 0u);
     double* park = trig + (unit_tab ? kShadeConstCount : kTrigConstCount);
     const ShadeLds shade_lds(trig, unit_tab);
     RecT* rec = reinterpret_cast<RecT*>(park + (PARK ? 6 * 64 : 0));
     // DEFER: [ring 128 x uint4][terms 3 x 64 doubles][per-lane FIFO of ring positions][per-lane count]; kScatter (below):
     // [ring][per pixel: entries added so far, 64 words — a small wave's 128 two-byte tags in their place][per-lane count]
-    constexpr bool kScatter = (RTM_OPT_SCATTER != 0) && DEFER && (PACK8 || PACKL) && !REUSE;
+    constexpr bool kScatter = DEFER && (PACK8 || PACKL) && !REUSE;
     uint4* fq_in = reinterpret_cast<uint4*>(park + 6 * 64);
     double* fq_out = reinterpret_cast<double*>(fq_in + kFoldRing);  // (the FIFO form only)
     unsigned long long* fq_fifo = kScatter ? reinterpret_cast<unsigned long long*>(fq_in + kFoldRing)
@@ -379,7 +371,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // The axis-signature instantiations (UNROLL <= -1000) are launched for RTM_MODE_REPAIRED only: the mode is a compile-time
     // constant there (the shading block's "literal mode: the normal stays 0" arm and its wave-uniform test go away; a literal-mode
     // render of such a scene takes the plain exact-n kernel)
-    const int mode = (RTM_OPT_CTMODE && UNROLL <= -1000) ? (int)RTM_MODE_REPAIRED : P.mode;
+    const int mode = UNROLL <= -1000 ? (int)RTM_MODE_REPAIRED : P.mode;
     if constexpr (LDS_TAB) {
         sc.lgeom = lgeom;
         sc.lmat = lmat;
@@ -408,18 +400,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // "the contracted search does not find the reference's hit for this sub-pixel's primary ray" (an exact tie in real
     // arithmetic: rtm_path.h, nearest_hit_exactfp) —, in LDS so that a lane that steals a sample of another pixel finds it.
     // Sub-pixels from 64 up have no bit and always take the exact loop.
-#ifndef RTM_DIR_PIXEL_MAJOR
-#define RTM_DIR_PIXEL_MAJOR 0  // layout of RenderParams::prim_dirs (A/B: profiles/r4/dir_table_ab.txt)
-#endif
-#ifndef RTM_DIR_NT
-#define RTM_DIR_NT 0           // non-temporal reads of it
-#endif
-#ifndef RTM_TOL_PRIMFIX
-#define RTM_TOL_PRIMFIX 1  // (A/B switch: 0 compiles the exact-tie handling out — NOT within tolerance on the Cornell diagonals)
-#endif
     // (round 4, later: the any-depth kernels too — PACKL has no stealing, a lane only ever asks for its OWN pixel's word and
     // reads it from the pre-pass's table when it moves on to a sub-pixel: no LDS, no register pair across the loop)
-    constexpr bool kPrimFix = (RTM_TOL != 0) && (STEAL || PACKL) && (RTM_TOL_PRIMFIX != 0);
+    constexpr bool kPrimFix = (RTM_TOL != 0) && (STEAL || PACKL);
     unsigned long long* prim_mask = reinterpret_cast<unsigned long long*>(fq_pend + 3 * 64);  // STEAL: behind its two arrays
     [[maybe_unused]] auto own_prim_mask = [&]() -> unsigned long long {
         if constexpr (STEAL) {
@@ -492,20 +475,10 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 unsigned col = pl & 63u;
                 asm volatile("" : "+v"(col));  // (opaque: hipcc otherwise hoists the lane's table address out of the render
                                                // loop into a register pair it then spills — 28 GB of scratch reloads per frame)
-#if RTM_DIR_PIXEL_MAJOR
-                // [tile][pixel][sub-pixel][component]: a lane's three doubles share a line
-                const double* q = P.prim_dirs + ((first * 64u + (unsigned long long)col * all) + (sub < all ? sub : all - 1u)) * 3;
-                constexpr int kStep = 1;
-#else
                 // [tile][sub-pixel][component][pixel]
                 const double* q = P.prim_dirs + (first + (sub < all ? sub : all - 1u)) * 192 + col;
                 constexpr int kStep = 64;
-#endif
-#if RTM_DIR_NT
-                return D3{__builtin_nontemporal_load(q), __builtin_nontemporal_load(q + kStep), __builtin_nontemporal_load(q + 2 * kStep)};
-#else
                 return D3{q[0], q[kStep], q[2 * kStep]};
-#endif
             }
         }
         return primary_dir_lds(P, cam, px, py, (int)(sub / (unsigned)P.SS) + 1, (int)(sub % (unsigned)P.SS) + 1);
@@ -679,9 +652,6 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     (void)fold_pass;
     // wave-level counters of the DEFER loop (scalar registers): every live lane casts once per trip
     unsigned w_casts = 0, w_bounces = 0, w_draws = 0;
-#ifdef RTM_EXP_TRIPS
-    unsigned w_trips64 = 0;
-#endif
     if constexpr (DEFER && REUSE) {
         // ---- primary-hit reuse (see REUSE above) ----
         // the primary hit of the lane's current sub-pixel: recomputed when the sub-pixel changes (once per S samples)
@@ -834,9 +804,6 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             if (P.max_bounces >= 0) m_drew &= ~__builtin_amdgcn_ballot_w64(depth_before >= P.max_bounces);
             const unsigned n_cont = (unsigned)__builtin_popcountll(m_cont);
             w_casts += (unsigned)__builtin_popcountll(m_live);
-#ifdef RTM_EXP_TRIPS
-            w_trips64 += 64u;
-#endif
             w_draws += (unsigned)__builtin_popcountll(m_drew) + 2u * n_cont;
             w_bounces += n_cont;
             if (!cont) {
@@ -1000,9 +967,6 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             w_casts += (unsigned)__builtin_popcountll(m_busy);
             w_draws += (unsigned)__builtin_popcountll(m_drew) + 2u * n_cont;
             w_bounces += n_cont;
-#ifdef RTM_EXP_TRIPS
-            w_trips64 += 64u;
-#endif
             const bool ended = busy && !cont;
             const bool need = !busy || !cont;  // this lane wants a new sample
             if (ended) {
@@ -1224,11 +1188,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             if (lane == 0) {
                 atomicAdd(P.counters + 0, (unsigned long long)w_casts);
                 atomicAdd(P.counters + 1, (unsigned long long)w_bounces);
-#ifdef RTM_EXP_TRIPS
-                atomicAdd(P.counters + 2, (unsigned long long)w_trips64);  // EXPERIMENT: "draws" = 64 x trips of the wave
-#else
                 atomicAdd(P.counters + 2, (unsigned long long)w_draws);
-#endif
             }
         } else {
             wave_add_counter(P.counters + 0, pc.casts);
@@ -1340,13 +1300,8 @@ __global__ __launch_bounds__(64) void prim_prepass_kernel(const RenderParams P, 
     const unsigned tile = blockIdx.x;
     auto store_dir = [&](const unsigned sub, const D3 d) {  // RenderParams::prim_dirs: [tile][pixel][sub-pixel][component]
         const unsigned all_s = (unsigned)(P.SS * P.SS);
-#if RTM_DIR_PIXEL_MAJOR
-        double* q = dirs + (((size_t)tile * 64 + (unsigned)lane) * all_s + sub) * 3;
-        constexpr int kStep = 1;
-#else
         double* q = dirs + ((size_t)tile * all_s + sub) * 192 + (unsigned)lane;
         constexpr int kStep = 64;
-#endif
         __builtin_nontemporal_store(d.x, q);
         __builtin_nontemporal_store(d.y, q + kStep);
         __builtin_nontemporal_store(d.z, q + 2 * kStep);
