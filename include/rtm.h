@@ -187,7 +187,8 @@ int rtm_release_scratch(int device);
  * directions a pre-pass leaves for the default kernels (1.5 KiB per tile and sub-pixel, at most 4 GiB).  The buffers are per
  * (device, stream), grown on demand and kept until rtm_release_scratch / rtm_stream_release; a stream that has rendered
  * larger frames already holds more.  Where the device cannot give an OPTIONAL buffer (terms, stolen rows) the render
- * runs without the feature or in more launches — same image. */
+ * runs without the feature or in more launches — same image.  The figure for a whole frame is an upper bound for any pass of it
+ * (rtm_render_scene_samples). */
 int rtm_scratch_bytes(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
                       uint64_t out_bytes[6]);
 /* The same for ONE stream: waits for that stream's queued work (and, like rtm_release_scratch, for every render call
@@ -248,6 +249,26 @@ size_t rtm_scene_size(const rtm_scene* scene);
 int rtm_render_scene(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
                      double* out_f64_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream,
                      rtm_stats* stats);
+/* Progressive rendering: samples [sample_begin, sample_end) of every pixel of the call's rows.  The sample index is
+ * k = ((sx-1)*SS + (sy-1))*S + s, in the order of src/Renderer.cpp:223-225, with N = SS*SS*S.
+ * accum_f64_dev (DEVICE, required, layout of out_f64) is the pixel accumulator:
+ *   sample_begin == 0 : write-only; the fold starts at +0 exactly like rtm_render_scene
+ *   sample_begin  > 0 : must hold what the call that ended at sample_begin left; the fold continues from it
+ * After the pass that ends at N, accum / out_f32 / out_u8 are rtm_render_scene's out_f64 / out_f32 / out_u8 bit for bit
+ * (the accumulator goes +0 -> +t0 -> ... and never holds -0, so continuing the fold from the stored value is exact).
+ * Before that, out_f32 / out_u8 are a PREVIEW: the accumulator times N / sample_end, rounded or quantised like a final
+ * frame.  The caller passes the same settings, scene and options (mode, seed, rows, bands, variant, max_bounces) to every
+ * pass of a frame.
+ * A null accumulator, sample_begin > sample_end or sample_end > N: RTM_ERR_INVALID_ARGUMENT, checked before the scene
+ * pointer is looked at.  sample_begin == sample_end: RTM_OK, nothing enqueued.  Enqueueing, stats (rtm_stats.samples counts
+ * the pass's rows x width x (sample_end - sample_begin)) and the sticky overflow flag are rtm_render_scene's.  Every variant
+ * variant 0 resolves to serves any range, and so does variant 18; variants 7, 15 and 16 render [0, N) only and return
+ * RTM_ERR_UNSUPPORTED for any other range without writing anything.  rtm_scratch_bytes' figure for the whole frame bounds
+ * what any pass of it asks for.
+ * Added after RTM_ABI_VERSION 5 without changing it: callers detect the entry point by looking the symbol up. */
+int rtm_render_scene_samples(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                             uint32_t sample_begin, uint32_t sample_end, double* accum_f64_dev, float* out_f32_dev,
+                             uint8_t* out_u8_dev, void* stream, rtm_stats* stats);
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);

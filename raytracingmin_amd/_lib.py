@@ -85,6 +85,8 @@ SIGNATURES = {
     "rtm_stream_status": (C.c_int, [C.c_int, C.c_void_p]),
     "rtm_render_scene": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
+    "rtm_render_scene_samples": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), C.c_uint32, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),

@@ -72,6 +72,12 @@ int rtm_render_scene(const rtm_settings* settings, const rtm_scene* scene, const
                      rtm_stats* stats) {
     RTM_GUARD(rtm::render_scene(settings, scene, options, out_f64_dev, out_f32_dev, out_u8_dev, stream, stats))
 }
+int rtm_render_scene_samples(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                             uint32_t sample_begin, uint32_t sample_end, double* accum_f64_dev, float* out_f32_dev,
+                             uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {
+    RTM_GUARD(rtm::render_scene_samples(settings, scene, options, sample_begin, sample_end, accum_f64_dev, out_f32_dev,
+                                        out_u8_dev, stream, stats))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {

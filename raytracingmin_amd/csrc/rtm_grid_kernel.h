@@ -73,9 +73,11 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
     const unsigned local_tile = grid_tile_of_block(P, blockIdx.x);
     const unsigned tile = tile_base + local_tile;
     const int tile_x8 = (int)(tile % (unsigned)P.tiles_x) * 8, tile_y = (int)(tile / (unsigned)P.tiles_x);
-    const unsigned total_units = P.total_samples * 64u;
-    double* const terms = reinterpret_cast<double*>(P.contrib) + (size_t)local_tile * P.total_samples * (64 * kGridTermDoubles);
-    unsigned* const nz_bits = P.nz_bits + (size_t)local_tile * P.total_samples * 2;  // 64 bits per sample of the tile
+    // units and term rows cover the pass's samples [sample_begin, sample_end), row r = sample sample_begin + r
+    const unsigned pass = P.sample_end - P.sample_begin;
+    const unsigned total_units = pass * 64u;
+    double* const terms = reinterpret_cast<double*>(P.contrib) + (size_t)local_tile * pass * (64 * kGridTermDoubles);
+    unsigned* const nz_bits = P.nz_bits + (size_t)local_tile * pass * 2;  // 64 bits per sample of the tile
 
     PathCounters pc = {0, 0, 0};
     RecordStack<RecT, LDS_D> stack{rec, lane, &P};
@@ -98,7 +100,7 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
             py = band_row(P, tile_y, (int)((unit >> 3) & 7u));
             if (px < P.W && py < P.row_end) break;
         }
-        const unsigned s = unit >> 6;  // sample index ((sx-1)*SS + (sy-1))*S + s
+        const unsigned s = P.sample_begin + (unit >> 6);  // sample index ((sx-1)*SS + (sy-1))*S + s
         const int sub = (int)(s / (unsigned)P.S);
         org = P.cam_org;
         dir = primary_dir_lds(P, cam, px, py, sub / P.SS + 1, sub % P.SS + 1);
@@ -162,7 +164,8 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
 }
 
 // image[pixel] = ((0 + term[0]) + term[1]) + ... in sample order (src/Renderer.cpp:241-248).  One wave per tile, lane =
-// pixel; a sample's 64 terms are one contiguous 2 048-byte row.
+// pixel; a sample's 64 terms are one contiguous 2 048-byte row.  A pass that continues a frame starts from the stored
+// accumulator instead of 0 (never -0, so a term that is not stored still changes nothing).
 __global__ __launch_bounds__(64) void grid_finalize_kernel(const RenderParams P, const unsigned tile_base) {
     const int lane = threadIdx.x;
     const unsigned tile = tile_base + blockIdx.x;
@@ -171,13 +174,14 @@ __global__ __launch_bounds__(64) void grid_finalize_kernel(const RenderParams P,
     const bool valid = px < P.W && py < P.row_end;
     if (!valid) return;  // (its units were never traced: the rows hold nothing for it)
     constexpr int kRow = 64 * kGridTermDoubles;  // doubles per sample row
-    const double* t = reinterpret_cast<const double*>(P.contrib) + (size_t)blockIdx.x * P.total_samples * kRow + lane * kGridTermDoubles;
+    const unsigned pass = P.sample_end - P.sample_begin;  // rows of the pass, row r = sample sample_begin + r
+    const double* t = reinterpret_cast<const double*>(P.contrib) + (size_t)blockIdx.x * pass * kRow + lane * kGridTermDoubles;
     // this pixel's column of the tile's "term stored" bits: word (sample, half) holds 32 pixels
-    const unsigned* bits = P.nz_bits + (size_t)blockIdx.x * P.total_samples * 2 + (lane >> 5);
+    const unsigned* bits = P.nz_bits + (size_t)blockIdx.x * pass * 2 + (lane >> 5);
     const unsigned my_bit = 1u << (lane & 31);
-    D3 acc = d3(0, 0, 0);
+    D3 acc = seed_of(P, true, px, py);
     unsigned s = 0;
-    for (; s + 4 <= P.total_samples; s += 4) {  // four rows in flight; the additions stay in order
+    for (; s + 4 <= pass; s += 4) {  // four rows in flight; the additions stay in order
         unsigned w[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) w[k] = bits[(size_t)(s + k) * 2];
@@ -196,7 +200,7 @@ __global__ __launch_bounds__(64) void grid_finalize_kernel(const RenderParams P,
         for (int k = 0; k < 4; ++k)
             if (w[k] & my_bit) acc = acc + v[k];
     }
-    for (; s < P.total_samples; ++s) {
+    for (; s < pass; ++s) {
         if (!(bits[(size_t)s * 2] & my_bit)) continue;
         const double* r = t + (size_t)s * kRow;
         acc = acc + d3(r[0], r[1], r[2]);

@@ -31,6 +31,8 @@ int stream_status(int device, void* stream);
 int scratch_bytes(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint64_t out[6]);
 int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, double* out64, float* out32,
                  uint8_t* out8, void* stream, rtm_stats* stats);
+int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
+                         uint32_t sample_end, double* accum, float* out32, uint8_t* out8, void* stream, rtm_stats* stats);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);

@@ -1067,7 +1067,12 @@ constexpr int kAutoLdsTableSpheres = 24, kAutoWavefrontSpheres = 512;
 int num_variants() { return (int)(sizeof(kVariantNames) / sizeof(kVariantNames[0])); }
 const char* variant_name(int v) { return (v >= 0 && v < num_variants()) ? kVariantNames[v] : nullptr; }
 
-static void fill_render_params(RenderParams& P, const rtm_settings* st, const rtm_options* opt) {
+// The samples [begin, end) of every pixel a call traces (rtm_render_scene_samples); end = ~0u: the frame's N.  A pass that
+// starts past 0 continues the accumulator out64 holds.
+struct SamplePass {
+    unsigned begin = 0u, end = ~0u;
+};
+static void fill_render_params(RenderParams& P, const rtm_settings* st, const rtm_options* opt, const SamplePass& pass) {
     using namespace host;
     const H3 origin = {st->camera.origin[0], st->camera.origin[1], st->camera.origin[2]};
     const H3 target = {st->camera.target[0], st->camera.target[1], st->camera.target[2]};
@@ -1090,6 +1095,10 @@ static void fill_render_params(RenderParams& P, const rtm_settings* st, const rt
     P.mode = opt->mode & ~kModeFlags;
     P.max_bounces = opt->max_bounces;
     P.total_samples = (unsigned)st->super_samples * st->super_samples * st->samples;
+    P.sample_begin = pass.begin;
+    P.sample_end = pass.end == ~0u ? P.total_samples : pass.end;
+    P.seeded = P.sample_begin != 0u ? 1u : 0u;
+    P.preview_scale = P.sample_end != 0u ? (double)P.total_samples / (double)P.sample_end : 1.0;
     P.rate = (float)(1.0 / (1 + st->super_samples));
     P.dSS = (double)st->super_samples;
     P.dS = (double)st->samples;
@@ -1561,7 +1570,7 @@ struct SplitPlan {
     unsigned head;   // samples wave 0 of a split tile keeps (a multiple of total / g)
 };
 constexpr unsigned kSplitMaxLen = 64;  // samples per small wave: split_finalize_kernel sorts one small wave's terms in LDS (1.5 KB per sample)
-static SplitPlan choose_split(unsigned n_tiles, unsigned total_samples, int device, bool forced) {
+static SplitPlan choose_split(unsigned n_tiles, unsigned samples, int device, bool forced) {
     static const long env = [] {
         const char* e = std::getenv("RTM_DEBUG_SPLIT");  // tuning knob: 1 = never split, g = every tile with that granularity
         return e ? std::strtol(e, nullptr, 10) : 0L;
@@ -1573,7 +1582,7 @@ static SplitPlan choose_split(unsigned n_tiles, unsigned total_samples, int devi
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     const unsigned slots = (unsigned)cus * 16u;
-    const SplitPlan none{1u, 0u, total_samples};
+    const SplitPlan none{1u, 0u, samples};
     // wave 0 keeps about half of the samples (its terms never leave the chip, and it starts in the launch's first rounds,
     // so the small waves still set the tail: profiles/r2/tail_split.txt); an odd g: the larger half
     static const long env_head = [] {
@@ -1581,29 +1590,29 @@ static SplitPlan choose_split(unsigned n_tiles, unsigned total_samples, int devi
         return e ? std::strtol(e, nullptr, 10) : 0L;
     }();
     auto head_of = [&](unsigned g) {
-        if (env_head > 0 && (unsigned)env_head < g) return (total_samples / g) * (unsigned)env_head;
+        if (env_head > 0 && (unsigned)env_head < g) return (samples / g) * (unsigned)env_head;
         // 9 of 16 shares: as fast as 8 (headline 170.8 / 170.6 ms, 512x512x256spp 6.68 / 6.72, one GPU's share of eight equal),
         // an eighth fewer terms to store; 10 of 16 costs the headline frame 0.5 % (profiles/r3/head_ab.txt)
-        if (g % 16u == 0u) return (total_samples / g) * (9u * (g / 16u));
-        return g >= 4 ? (total_samples / g) * ((g + 1u) / 2u) : total_samples / g;
+        if (g % 16u == 0u) return (samples / g) * (9u * (g / 16u));
+        return g >= 4 ? (samples / g) * ((g + 1u) / 2u) : samples / g;
     };
     auto valid_g = [&](unsigned g) {
-        return g >= 2 && total_samples % g == 0 && total_samples / g >= 8 && total_samples / g <= kSplitMaxLen;
+        return g >= 2 && samples % g == 0 && samples / g >= 8 && samples / g <= kSplitMaxLen;
     };
     // a small wave traces 1/16 of a pixel's samples (profiles/r1/band_split_sweep_final.json), at least 8 and at most
     // kSplitMaxLen of them: the divisor of the sample count nearest to that from below, else from above
     auto pick_g = [&]() -> unsigned {
-        unsigned want = total_samples / 16u;
+        unsigned want = samples / 16u;
         want = want < 8u ? 8u : (want > kSplitMaxLen ? kSplitMaxLen : want);
         for (unsigned len = want; len >= 8u; --len)
-            if (total_samples % len == 0 && valid_g(total_samples / len)) return total_samples / len;
+            if (samples % len == 0 && valid_g(samples / len)) return samples / len;
         for (unsigned len = want + 1u; len <= kSplitMaxLen; ++len)
-            if (total_samples % len == 0 && valid_g(total_samples / len)) return total_samples / len;
+            if (samples % len == 0 && valid_g(samples / len)) return samples / len;
         return 1u;
     };
     // the terms of the split tiles: a 1 664-byte row per (tile, deferred sample), at most 24 GiB per stream
     auto fits = [&](unsigned g, unsigned tiles) {
-        return (double)tiles * (double)(total_samples - head_of(g)) * (double)kTermRowBytes <= 24.0 * 1024 * 1024 * 1024;
+        return (double)tiles * (double)(samples - head_of(g)) * (double)kTermRowBytes <= 24.0 * 1024 * 1024 * 1024;
     };
     if (env > 0) {
         const unsigned g = (unsigned)env;
@@ -1682,9 +1691,10 @@ static int run_wavefront_impl(const RenderParams& P, int rows, StreamCtx& ctx, b
 
     const unsigned shade_grid = grid;
     // (a call WITH rtm_stats waits for the stream anyway: it follows the count and skips the empty launches)
+    const unsigned pass_len = P.sample_end - P.sample_begin;  // (a pass of a frame: its own samples)
     if (!may_block && P.max_bounces >= 0 &&
-        (unsigned long long)P.total_samples * (unsigned long long)(P.max_bounces + 1) <= kWfAsyncTrips) {
-        const unsigned trips = P.total_samples * (unsigned)(P.max_bounces + 1);
+        (unsigned long long)pass_len * (unsigned long long)(P.max_bounces + 1) <= kWfAsyncTrips) {
+        const unsigned trips = pass_len * (unsigned)(P.max_bounces + 1);
         const unsigned near_grid = wf_nearest_grid(S.npix, P.scene.n);
         int cur = 0;
         for (unsigned t = 0; t < trips; ++t, cur ^= 1) {
@@ -1706,8 +1716,8 @@ static int run_wavefront_impl(const RenderParams& P, int rows, StreamCtx& ctx, b
 
     unsigned na = S.npix;  // last count the host has seen (an upper bound of the device's)
     int cur = 0;
-    // every cast of every pixel is one trip; a pixel needs at most total_samples * (depth cap + 1)
-    const unsigned long long max_trips = (unsigned long long)P.total_samples * (unsigned long long)(S.levels + 1) + 8;
+    // every cast of every pixel is one trip; a pixel needs at most pass_len * (depth cap + 1)
+    const unsigned long long max_trips = (unsigned long long)pass_len * (unsigned long long)(S.levels + 1) + 8;
     unsigned long long trip = 0;
     for (unsigned long long b = 0;; ++b) {
         if (trip > max_trips + 64) {
@@ -1881,10 +1891,13 @@ static int wavefront_levels(const RenderParams& P, size_t npix) {
 }
 
 // Fills P (camera, sizes, split fields) and the plan.  `view`: what the scene offers (planes, grid).
+// Every choice made from a sample count is made from the PASS's (rtm_render_scene_samples); the divisors stay the frame's N.
 static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, const rtm_options* opt, RenderParams& P,
-                       RenderPlan& plan) {
+                       RenderPlan& plan, const SamplePass& pass = SamplePass{}) {
     std::memset(&P, 0, sizeof P);
-    fill_render_params(P, st, opt);
+    fill_render_params(P, st, opt, pass);
+    const unsigned pass_len = P.sample_end - P.sample_begin;
+    const bool whole_frame = P.sample_begin == 0u && P.sample_end == P.total_samples;
     P.scene = view;
     plan.rows = output_rows(opt);
     plan.count_tests = (opt->mode & RTM_MODE_COUNT_TESTS) != 0;
@@ -1894,7 +1907,7 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     int variant = opt->variant;
     P.n_tiles = grid;
     P.split = 1;
-    P.split_len = P.split_head = P.total_samples;
+    P.split_len = P.split_head = pass_len;
     // auto (profiles/r1/variant_thresholds.txt): LDS tables up to 24 spheres (8.5 KB of LDS per wave keeps
     // 16 waves per CU); global-memory tables up to 511 (the tables no longer cost occupancy); from 512
     // spheres the wavefront pipeline with its rejection test wins over the monolithic kernel
@@ -1925,6 +1938,11 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
         set_last_error("variant 19 is chosen by RTM_MODE_SURFACE_SAMPLE in rtm_options.mode");
         return RTM_ERR_UNSUPPORTED;
     }
+    if (!whole_frame && (variant == kVariantStamped || variant == kVariantPrimaryReuse || variant == kVariantFp32)) {
+        set_last_error(std::string("variant ") + std::to_string(variant) + " renders whole frames only: sample range [0, " +
+                       std::to_string(P.total_samples) + ")");
+        return RTM_ERR_UNSUPPORTED;
+    }
     if (variant == kVariantAuto)
         variant = n <= (size_t)kAutoLdsTableSpheres ? kVariantFastLds :
                   view.grid != nullptr ? kVariantGrid :  // (grid_for: the scene has one and the camera is within its reach)
@@ -1942,7 +1960,7 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     const bool tol = variant == kVariantTol;
     plan.tol = tol;
     if (tol) {
-        if (!(n >= 1 && n <= (size_t)kAutoLdsTableSpheres && view.plane == nullptr && P.total_samples < 65536u)) {
+        if (!(n >= 1 && n <= (size_t)kAutoLdsTableSpheres && view.plane == nullptr && P.sample_end < 65536u)) {
             set_last_error("variant 18 (fp64 tolerance row) serves all-sphere scenes of 1..24 spheres with fewer than 65 536 samples per pixel");
             return RTM_ERR_UNSUPPORTED;
         }
@@ -1977,16 +1995,16 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     // the sample split rides on the packed-record kernels (explicit variant 2 never splits)
     if (n < 256 && (opt->variant == kVariantAuto || plan.force_split || tol) &&
         (variant == kVariantFastLds || variant == kVariantGlobalDefer)) {
-        const SplitPlan sp = choose_split(grid, P.total_samples, opt->device, plan.force_split);
+        const SplitPlan sp = choose_split(grid, pass_len, opt->device, plan.force_split);
         P.split = sp.g;
         if (P.split > 1) {
             P.n_tiles = sp.tiles;
             P.split_first = grid - sp.tiles;
-            P.split_len = P.total_samples / P.split;
+            P.split_len = pass_len / P.split;
             P.split_head = sp.head;
-            P.split = 1u + (P.total_samples - P.split_head) / P.split_len;
+            P.split = 1u + (pass_len - P.split_head) / P.split_len;
             const size_t part = (size_t)P.n_tiles * 192 * sizeof(double);
-            const size_t terms = (size_t)P.n_tiles * (P.total_samples - P.split_head) * kTermRowBytes;  // a row per (tile, sample)
+            const size_t terms = (size_t)P.n_tiles * (pass_len - P.split_head) * kTermRowBytes;  // a row per (tile, sample)
             plan.bytes[kScratchTerms] = part + terms;
             plan.optional[kScratchTerms] = true;  // no room for the terms: the launch runs unsplit (same image, a longer tail)
         }
@@ -2001,13 +2019,13 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     }();
     const unsigned n_whole = P.split > 1 ? P.split_first : grid;
     if (!steal_off && variant == kVariantFastLds && view.plane == nullptr && n >= 1 && n < 256 /* packed records: PACK8 */ &&
-        P.max_bounces >= 0 && P.max_bounces <= 8 && P.total_samples >= 16 && P.total_samples < 65536u && st->samples < 65536 &&
+        P.max_bounces >= 0 && P.max_bounces <= 8 && pass_len >= 16 && P.sample_end < 65536u && st->samples < 65536 &&
         opt->variant != kVariantFastLds /* explicit variant 2 stays the plain kernel: the A/B twin */ &&
         !(tol && std::getenv("RTM_DEBUG_TOL_NOSTEAL") != nullptr) /* test knob: the tolerance row's stealing-free path */ &&
         n_whole != 0) {
-        unsigned rows = 2u * (unsigned)std::ceil(std::sqrt((double)P.total_samples)) + 4u;
+        unsigned rows = 2u * (unsigned)std::ceil(std::sqrt((double)pass_len)) + 4u;
         rows = rows < 8u ? 8u : (rows > 68u ? 68u : rows);
-        unsigned depth = P.total_samples / 2u;
+        unsigned depth = pass_len / 2u;
         depth = depth > 256u ? 256u : depth;
         plan.steal = true;
         plan.steal_rows = rows;
@@ -2044,7 +2062,7 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
         plan.bytes[kScratchWavefront] = wavefront_bytes(npix, plan.wf_levels);
     }
     if (variant == kVariantGrid) {
-        const size_t per_tile = grid_tile_term_bytes(P.total_samples) + grid_tile_bit_bytes(P.total_samples);
+        const size_t per_tile = grid_tile_term_bytes(pass_len) + grid_tile_bit_bytes(pass_len);
         plan.grid_chunk_tiles = std::min<size_t>(grid, std::max<size_t>(1, grid_term_budget() / per_tile));
         plan.bytes[kScratchTerms] = plan.grid_chunk_tiles * per_tile;
         plan.optional[kScratchTerms] = true;  // what the device will not give is made up for by more launches of fewer tiles
@@ -2062,7 +2080,8 @@ static int run_grid(RenderParams& P, unsigned tiles, StreamCtx& ctx, const Rende
         const char* e = std::getenv("RTM_DEBUG_GRID_XCD");  // tuning knob: 0 = blocks render tiles in launch order
         return e && e[0] == '0';
     }();
-    const size_t per_tile = grid_tile_term_bytes(P.total_samples) + grid_tile_bit_bytes(P.total_samples);
+    const unsigned pass_len = P.sample_end - P.sample_begin;  // (the term rows of the pass's samples)
+    const size_t per_tile = grid_tile_term_bytes(pass_len) + grid_tile_bit_bytes(pass_len);
     size_t chunk = plan.grid_chunk_tiles;
     void* ws = nullptr;
     // What the device can give, asked once (a failed multi-GB hipMalloc after the old buffer has been freed costs a stream
@@ -2086,7 +2105,7 @@ static int run_grid(RenderParams& P, unsigned tiles, StreamCtx& ctx, const Rende
         chunk = (chunk + 1) / 2;
     }
     P.contrib = static_cast<unsigned char*>(ws);
-    P.nz_bits = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ws) + chunk * grid_tile_term_bytes(P.total_samples));
+    P.nz_bits = reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ws) + chunk * grid_tile_term_bytes(pass_len));
     const bool deep = needs_pool(P);
     const bool planes = P.scene.plane != nullptr;
     size_t lds = (10 + kTrigConstCount) * sizeof(double) + (size_t)(deep ? 32 : 16) * 64 * sizeof(uint32_t) + 16 +
@@ -2098,7 +2117,7 @@ static int run_grid(RenderParams& P, unsigned tiles, StreamCtx& ctx, const Rende
         P.xcd_on = xcd_off ? 0u : 1u;
         P.xcd_q = cnt / 8u;
         P.xcd_rem = cnt % 8u;
-        RTM_HIP_CHECK(hipMemsetAsync(P.nz_bits, 0, (size_t)cnt * grid_tile_bit_bytes(P.total_samples), ctx.stream));
+        RTM_HIP_CHECK(hipMemsetAsync(P.nz_bits, 0, (size_t)cnt * grid_tile_bit_bytes(pass_len), ctx.stream));
         launch_grid_kernel(P, base, cnt, lds, deep, planes, plan.count_tests, ctx.stream);
         grid_finalize_kernel<<<cnt, 64, 0, ctx.stream>>>(P, base);
     }
@@ -2107,7 +2126,8 @@ static int run_grid(RenderParams& P, unsigned tiles, StreamCtx& ctx, const Rende
 }
 
 static int render_view(const rtm_settings* st, const SceneView& view, size_t n, const rtm_options* opt,
-                       double* out64, float* out32, uint8_t* out8, hipStream_t stream, rtm_stats* stats) {
+                       double* out64, float* out32, uint8_t* out8, hipStream_t stream, rtm_stats* stats,
+                       const SamplePass& pass = SamplePass{}) {
     RTM_HIP_CHECK(hipSetDevice(opt->device));
     if (stats) std::memset(stats, 0, sizeof *stats);
     StreamCtx& ctx = *get_ctx(opt->device, stream);
@@ -2120,7 +2140,7 @@ static int render_view(const rtm_settings* st, const SceneView& view, size_t n, 
 
     RenderParams P;
     RenderPlan plan;
-    rc = plan_render(st, view, n, opt, P, plan);
+    rc = plan_render(st, view, n, opt, P, plan, pass);
     if (rc != RTM_OK) return rc;
     const int rows = plan.rows;
     const unsigned grid = plan.grid;
@@ -2149,7 +2169,7 @@ static int render_view(const rtm_settings* st, const SceneView& view, size_t n, 
             P.split = 1;
             P.n_tiles = grid;
             P.split_first = 0;
-            P.split_len = P.split_head = P.total_samples;
+            P.split_len = P.split_head = P.sample_end - P.sample_begin;
         }
     }
     if (plan.bytes[kScratchSteal] != 0) {
@@ -2261,7 +2281,7 @@ static int render_view(const rtm_settings* st, const SceneView& view, size_t n, 
     RTM_HIP_CHECK(hipStreamSynchronize(stream));
     float ms = 0.f;
     RTM_HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    stats->samples = (uint64_t)rows * st->width * P.total_samples;
+    stats->samples = (uint64_t)rows * st->width * (P.sample_end - P.sample_begin);
     stats->casts = c[0];
     stats->bounces = c[1];
     stats->draws = c[2];
@@ -2317,8 +2337,9 @@ int scratch_bytes(const rtm_settings* st, const rtm_scene* scene, const rtm_opti
     return RTM_OK;
 }
 
-int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, double* out64, float* out32,
-                 uint8_t* out8, void* stream_v, rtm_stats* stats) {
+// rtm_render_scene is the pass [0, N) of rtm_render_scene_samples: one path
+static int render_scene_pass(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const SamplePass& pass,
+                             double* out64, float* out32, uint8_t* out8, void* stream_v, rtm_stats* stats) {
     if (!scene) {
         set_last_error("null scene");
         return RTM_ERR_INVALID_ARGUMENT;
@@ -2334,9 +2355,44 @@ int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_optio
     reap_scenes(false);
     rc = render_view(st, scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
                                     scene->has_planes ? scene->plane.as<double>() : nullptr, grid_for(scene, st, opt), scene->surf.as<double>(), scene->axis_pat, scene->fold_flags),
-                     scene->n, opt, out64, out32, out8, (hipStream_t)stream_v, stats);
+                     scene->n, opt, out64, out32, out8, (hipStream_t)stream_v, stats, pass);
     note_scene_use(scene, (hipStream_t)stream_v);  // also after a failure: part of the work may have been queued
     return rc;
+}
+
+int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, double* out64, float* out32,
+                 uint8_t* out8, void* stream_v, rtm_stats* stats) {
+    return render_scene_pass(st, scene, opt, SamplePass{}, out64, out32, out8, stream_v, stats);
+}
+
+// The range and the accumulator are checked before anything else (the scene included), so that a caller can test them alone.
+int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
+                         uint32_t sample_end, double* accum, float* out32, uint8_t* out8, void* stream_v, rtm_stats* stats) {
+    if (!accum) {
+        set_last_error("accum_f64_dev: the pixel accumulator is null");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (sample_begin > sample_end) {
+        set_last_error("sample range [" + std::to_string(sample_begin) + ", " + std::to_string(sample_end) +
+                       "): sample_begin > sample_end");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (!st) {
+        set_last_error("null settings");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    const uint64_t ss = st->super_samples > 0 ? (uint64_t)st->super_samples : 0u, s1 = st->samples > 0 ? (uint64_t)st->samples : 0u;
+    const uint64_t total = ss * ss * s1;  // N (validate() rejects non-positive sizes below)
+    if (sample_end > total) {
+        set_last_error("sample range [" + std::to_string(sample_begin) + ", " + std::to_string(sample_end) +
+                       "): sample_end > N = superSamples^2 x samples = " + std::to_string(total));
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (sample_begin == sample_end) {  // nothing to trace: nothing is enqueued
+        if (stats) std::memset(stats, 0, sizeof *stats);
+        return RTM_OK;
+    }
+    return render_scene_pass(st, scene, opt, SamplePass{sample_begin, sample_end}, accum, out32, out8, stream_v, stats);
 }
 
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int on_device,

@@ -155,7 +155,7 @@ int launch_tol(const void* params, size_t params_bytes, unsigned grid, size_t ld
     hipStream_t stream = (hipStream_t)stream_v;
     const bool any_depth = P.max_bounces < 0 || P.max_bounces > 8;
     if ((!any_depth && P.steal_ws == nullptr) || P.scene.n < 1 || P.scene.n > 24 || P.scene.plane != nullptr ||
-        P.total_samples >= 65536u) {
+        P.sample_end >= 65536u) {
         set_last_error("variant 18 (fp64 tolerance row) serves all-sphere scenes of 1..24 spheres with fewer than 65 536 samples per pixel");
         return RTM_ERR_UNSUPPORTED;
     }

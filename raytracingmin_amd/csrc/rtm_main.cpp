@@ -5,6 +5,7 @@
 //           [--mode literal|repaired] [--max-bounces N] [--seed N] [--device N] [--out STEM] [--device-trig]
 //           [--gpus N] [--virtual-strips N] [--force-rccl]   (interleaved 8-row bands over N GPUs + one RCCL gather)
 //           [--dump-f32 FILE]                    (the gathered float3 buffer, raw little-endian floats)
+//           [--passes N]                         (progressive: the frame's samples in N passes on one GPU, same image)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -37,7 +38,9 @@ static void usage() {
         "              to a CPU run of the reference even where deep paths amplify one-ulp differences; device-trig is ~2 %% faster)\n"
         "--gpus N : interleaved 8-row bands over N GPUs of this node, one RCCL gather of the float3 buffer;\n"
         "--force-rccl : take the RCCL exchange with --gpus 1 too; --virtual-strips N : N parts on one GPU, no RCCL\n"
-        "--dump-f32 FILE : write the float3 accumulation buffer (raw floats, row-major RGB)\n");
+        "--dump-f32 FILE : write the float3 accumulation buffer (raw floats, row-major RGB)\n"
+        "--passes N : render the frame's samples in N near-equal passes on one GPU (rtm_render_scene_samples), printing\n"
+        "             each pass's sample range and time; the image is the one-pass image bit for bit\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -49,6 +52,7 @@ int main(int argc, char* argv[]) {
     std::string json_file = "settingData.json", stem = "result";
     int width = 0, height = 0, samples = 0, super_samples = 0, spp = 0;
     int mode = RTM_MODE_REPAIRED, max_bounces = -1, device = 0, gpus = 1, virtual_strips = 0, host_trig = 1, force_rccl = 0;
+    int passes = 0;
     std::string dump_f32;
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
@@ -76,6 +80,7 @@ int main(int argc, char* argv[]) {
         else if (c == "--device") next_int(device);
         else if (c == "--gpus") next_int(gpus);
         else if (c == "--virtual-strips") next_int(virtual_strips);
+        else if (c == "--passes") next_int(passes);
         else if (c == "--host-trig") host_trig = 1;
         else if (c == "--device-trig") host_trig = 0;
         else if (c == "--force-rccl") force_rccl = 1;
@@ -91,6 +96,10 @@ int main(int argc, char* argv[]) {
                 return 2;
             }
         }
+    }
+    if (passes > 0 && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--passes renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
+        return 2;
     }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
         std::printf("saving the sample scene json file: %s\n", json_file.c_str());
@@ -132,7 +141,15 @@ int main(int argc, char* argv[]) {
     std::vector<uint8_t> rgb8(vals);
     std::vector<float> rgb32(dump_f32.empty() ? 0 : vals);
     rtm_stats stats;
-    if (gpus > 1 || virtual_strips > 0 || force_rccl) {
+    if (passes > 0) {
+        std::string err;
+        rc = rtm_node_render_passes(&st, spheres.data(), n, &opt, passes, rgb32.empty() ? nullptr : rgb32.data(), rgb8.data(),
+                                    &stats, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "render failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+    } else if (gpus > 1 || virtual_strips > 0 || force_rccl) {
         int have = 0;
         if (rtm_device_count(&have) != RTM_OK || have < gpus) {
             std::fprintf(stderr, "--gpus %d requested, %d HIP device(s) present\n", gpus, have);

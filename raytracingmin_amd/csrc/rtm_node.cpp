@@ -310,3 +310,64 @@ int rtm_node_render(const rtm_settings* st, const rtm_object* objects, size_t n,
     stages.enter(false, "release of the parts' scenes, buffers and streams");
     return RTM_OK;
 }
+
+// --passes (rtm_node.h): the frame as `passes` contiguous, near-equal sample ranges through rtm_render_scene_samples on one
+// device, a progress line per pass; the outputs of the last pass are the frame.  Stats are summed over the passes.
+int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int passes,
+                           float* out_f32_host, uint8_t* out_u8_host, rtm_stats* total, std::string& err) {
+    const unsigned N = (unsigned)st->super_samples * (unsigned)st->super_samples * (unsigned)st->samples;
+    if (passes < 1 || (unsigned)passes > N) {
+        err = "--passes " + std::to_string(passes) + ": must be in [1, " + std::to_string(N) + "] (the frame's samples per pixel)";
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (hipSetDevice(opt->device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(opt->device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    rtm_scene* scene = nullptr;
+    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
+    if (rc != RTM_OK) {
+        err = std::string("scene: ") + rtm_last_error_detail();
+        return rc;
+    }
+    const size_t vals = (size_t)st->width * st->height * 3;
+    double* accum = nullptr;
+    float* d32 = nullptr;
+    uint8_t* d8 = nullptr;
+    if (hipMalloc((void**)&accum, vals * sizeof(double)) != hipSuccess ||
+        (out_f32_host && hipMalloc((void**)&d32, vals * sizeof(float)) != hipSuccess) ||
+        (out_u8_host && hipMalloc((void**)&d8, vals) != hipSuccess)) {
+        err = "no device memory for the frame";
+        rc = RTM_ERR_HIP;
+    }
+    std::memset(total, 0, sizeof *total);
+    const unsigned q = N / (unsigned)passes, r = N % (unsigned)passes;
+    unsigned a = 0;
+    for (int i = 0; rc == RTM_OK && i < passes; ++i) {
+        const unsigned b = a + q + ((unsigned)i < r ? 1u : 0u);
+        rtm_stats s;
+        rc = rtm_render_scene_samples(st, scene, opt, a, b, accum, d32, d8, nullptr, &s);
+        if (rc != RTM_OK) {
+            err = rtm_last_error_detail();
+            break;
+        }
+        std::printf("pass %d/%d: samples [%u, %u) %.3f ms\n", i + 1, passes, a, b, s.kernel_ms);
+        total->samples += s.samples;
+        total->casts += s.casts;
+        total->bounces += s.bounces;
+        total->draws += s.draws;
+        total->kernel_ms += s.kernel_ms;
+        total->variant = s.variant;
+        a = b;
+    }
+    if (rc == RTM_OK && ((out_u8_host && hipMemcpy(out_u8_host, d8, vals, hipMemcpyDeviceToHost) != hipSuccess) ||
+                         (out_f32_host && hipMemcpy(out_f32_host, d32, vals * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
+        err = "copying the frame back failed";
+        rc = RTM_ERR_HIP;
+    }
+    (void)hipFree(accum);
+    (void)hipFree(d32);
+    (void)hipFree(d8);
+    (void)rtm_scene_destroy(scene);
+    return rc;
+}

@@ -12,3 +12,7 @@
 int rtm_node_render(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* base,
                     int n_devices, int virtual_strips, int force_rccl, float* out_f32_host, uint8_t* out_u8_host,
                     rtm_stats* total, std::string& err);
+// The frame's samples in `passes` contiguous, near-equal ranges on options->device (rtm_render_scene_samples, rtm_cli
+// --passes), printing "pass i/N: samples [a, b) <ms> ms" per pass.  The outputs are rtm_render_scene's frame.
+int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options, int passes,
+                           float* out_f32_host, uint8_t* out_u8_host, rtm_stats* total, std::string& err);

@@ -19,8 +19,12 @@ struct RenderParams {
     int band_count, band_index;  // interleaved 8-row bands (rtm_options); 1, 0 = every band
     int tiles_x;
     int mode, max_bounces;
-    unsigned total_samples;  // SS*SS*S per pixel
-    float rate;              // 1.0 / (1 + SS) as float, src/Renderer.cpp:227
+    unsigned total_samples;  // SS*SS*S per pixel: the frame's N (the divisors below are the frame's, whatever the pass)
+    // this call's samples [sample_begin, sample_end) of every pixel (rtm_render_scene_samples; [0, N) for a whole frame);
+    // seeded: every accumulator starts from the value out64 holds (a pass that continues a frame), else from +0
+    unsigned sample_begin, sample_end, seeded;
+    double preview_scale;    // N / sample_end: the f32 / u8 views of a pass that ends before N
+    float rate;             // 1.0 / (1 + SS) as float, src/Renderer.cpp:227
     double dSS, dS;          // divisors of src/Renderer.cpp:240
     double inv_ss, inv_s;    // exact reciprocals when SS and S are powers of two, else 0
     D3 cam_org, ax, by, cz;  // origin, camX*fovx, camY*fovy, camZ (src/Renderer.cpp:202-208)
@@ -184,16 +188,33 @@ __device__ __forceinline__ int band_row(const RenderParams& P, int local_band, i
     return P.row_begin + (local_band * P.band_count + P.band_index) * 8 + sub;
 }
 
-__device__ __forceinline__ void store_pixel(const RenderParams& P, bool valid, int x, int y, D3 acc) {
-    if (!valid) return;
+__device__ __forceinline__ size_t out_index(const RenderParams& P, int x, int y) {
     const int rel = y - P.row_begin;
     const int out_row = (P.band_count > 1) ? ((rel >> 3) / P.band_count) * 8 + (rel & 7) : rel;
-    const size_t o = ((size_t)out_row * P.W + x) * 3;
-    const double r = 0.0 + acc.x, g = 0.0 + acc.y, b = 0.0 + acc.z;  // :246-248
+    return ((size_t)out_row * P.W + x) * 3;
+}
+
+// The value a pixel's accumulator starts from: what the previous pass of the frame left in out64 (never -0: it went
+// +0 -> +t0 -> ..., so continuing the fold from it is the one-shot fold), or +0
+__device__ __forceinline__ D3 seed_of(const RenderParams& P, bool valid, int x, int y) {
+    if (!P.seeded || !valid) return d3(0, 0, 0);
+    const size_t o = out_index(P, x, y);
+    return d3(P.out64[o], P.out64[o + 1], P.out64[o + 2]);
+}
+
+__device__ __forceinline__ void store_pixel(const RenderParams& P, bool valid, int x, int y, D3 acc) {
+    if (!valid) return;
+    const size_t o = out_index(P, x, y);
+    double r = 0.0 + acc.x, g = 0.0 + acc.y, b = 0.0 + acc.z;  // :246-248
     if (P.out64) {
         P.out64[o] = r;
         P.out64[o + 1] = g;
         P.out64[o + 2] = b;
+    }
+    if (P.sample_end != P.total_samples) {  // a pass before the last: the views preview the frame (wave-uniform)
+        r *= P.preview_scale;
+        g *= P.preview_scale;
+        b *= P.preview_scale;
     }
     if (P.out32) {
         P.out32[o] = (float)r;
@@ -421,7 +442,8 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     if constexpr (PACKL) {
         if (P.pool) stack.slot = (int)((blockIdx.x * 64u + (unsigned)lane) * 2u);  // two pooled stacks per lane, no allocator
     }
-    D3 acc = d3(0, 0, 0);
+    // (a small wave of a split tile accumulates nothing: its seed is never used)
+    D3 acc = seed_of(P, valid, x, y);
 
     // this wave's samples [n_first, n_end) of the pixel (wave-uniform)
     const bool whole = !SPLIT || blockIdx.x < P.split_first;  // this wave traces all samples of its tile
@@ -435,12 +457,13 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
         f = (b - P.split_first) / P.n_tiles;
         tile = (b - P.split_first) % P.n_tiles;  // index into partial / contrib
     };
-    unsigned n_first = 0u, n_end = P.total_samples;
+    // (a pass of a frame, rtm_render_scene_samples: the same, offset by sample_begin — split_head / split_len cut the pass)
+    unsigned n_first = P.sample_begin, n_end = P.sample_end;
     if (!whole) {
         unsigned f, tile;
         split_wave(f, tile);
-        n_first = f != 0u ? P.split_head + (f - 1u) * P.split_len : 0u;
-        n_end = f != 0u ? n_first + P.split_len : P.split_head;
+        n_first = f != 0u ? P.sample_begin + P.split_head + (f - 1u) * P.split_len : P.sample_begin;
+        n_end = f != 0u ? n_first + P.split_len : P.sample_begin + P.split_head;
     }
     // a SMALL wave of the sample split (wave-uniform; its first sample is never 0: wave 0 keeps at least one share):
     // it accumulates nothing — every term goes to P.contrib in the order the wave folds them, 64 to a row, and
@@ -490,9 +513,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     const RngPixelKey pkey = rng_pixel_key(P.seed_mult, pixel);
     RngStream rng = rng_open(pkey, n_first);
     if constexpr (PARK) {
-        park[0 * 64 + lane] = 0.0;
-        park[1 * 64 + lane] = 0.0;
-        park[2 * 64 + lane] = 0.0;
+        park[0 * 64 + lane] = acc.x;
+        park[1 * 64 + lane] = acc.y;
+        park[2 * 64 + lane] = acc.z;
         park[3 * 64 + lane] = pdir.x;
         park[4 * 64 + lane] = pdir.y;
         park[5 * 64 + lane] = pdir.z;
@@ -913,19 +936,19 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
         while (fq_count > 0u) fold_pass(mode_tag);
       };
       if constexpr (SPLIT) {
-          if (n_first != 0u) trace(ModeSmall{});  // (a small wave's first sample is never 0: wave 0 keeps at least one share)
+          if (n_first != P.sample_begin) trace(ModeSmall{});  // (a small wave's first sample is never the pass's first: wave 0 keeps at least one share)
           else trace(ModeWhole{});
       } else {
           trace(ModeWhole{});
       }
       if constexpr (STEAL) {
        if (whole) {
-        unsigned end_own = valid ? P.total_samples : 0u;  // one past the last sample this lane's pixel accumulated itself
+        unsigned end_own = valid ? P.sample_end : 0u;  // one past the last sample this lane's pixel accumulated itself
         if (to_tail) {
           // ---- the tail loop of a whole tile (see STEAL above) ----
           unsigned* st_next = reinterpret_cast<unsigned*>(fq_pend + 64);  // per pixel: the next own sample its lane will START
           unsigned* st_end = st_next + 64;                               // per pixel: one past its last OWN sample
-          const unsigned total = P.total_samples;
+          const unsigned total = P.sample_end;
           bool busy = n < n_end;                                         // this lane has a path in flight ...
           if constexpr (kPrimFix) prim_fix = prim_fix && busy;
           unsigned cur = ((unsigned)lane << 16) | (busy ? n : 0u);       // ... of (pixel lane, sample)
@@ -1175,7 +1198,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
         int px, py;
         pixel_xy(px, py);
         store_pixel(P, (px < P.W) && (py < P.row_end), px, py, acc);
-    } else if (n_first == 0u) {  // the head wave of a split tile
+    } else if (n_first == P.sample_begin) {  // the head wave of a split tile
         unsigned hf, split_tile;
         split_wave(hf, split_tile);
         double* dst = P.partial + (size_t)split_tile * 192 + lane;
@@ -1259,12 +1282,12 @@ __global__ __launch_bounds__(64) void steal_finalize_kernel(const RenderParams P
     unsigned end_own = reinterpret_cast<const unsigned short*>(blk + 128)[lane];
     // (never out of range when the render kernel wrote the block; a stale or foreign block must not turn into a fault)
     n_terms = n_terms <= P.steal_rows * 64u ? n_terms : 0u;
-    const unsigned floor_chk = P.total_samples > P.steal_depth ? P.total_samples - P.steal_depth : 0u;
-    end_own = (n_terms != 0u && end_own >= floor_chk && end_own <= P.total_samples) ? end_own : P.total_samples;
+    const unsigned floor_chk = P.sample_end > P.steal_depth ? P.sample_end - P.steal_depth : 0u;
+    end_own = (n_terms != 0u && end_own >= floor_chk && end_own <= P.sample_end) ? end_own : P.sample_end;
     const double* part = reinterpret_cast<const double*>(blk + kStealHdrBytes) + lane;
     D3 acc = d3(part[0], part[64], part[128]);
     if (n_terms != 0u) {  // wave-uniform
-        const unsigned total = P.total_samples;
+        const unsigned total = P.sample_end;
         const unsigned floor_s = total > P.steal_depth ? total - P.steal_depth : 0u;
         const unsigned char* rows = blk + kStealHdrBytes + 3 * 64 * sizeof(double);
         for (unsigned e = (unsigned)lane; e < n_terms; e += 64u) {
@@ -1311,7 +1334,9 @@ __global__ __launch_bounds__(64) void prim_prepass_kernel(const RenderParams P, 
     const double cam[9] = {P.ax.x, P.ax.y, P.ax.z, P.by.x, P.by.y, P.by.z, P.cz.x, P.cz.y, P.cz.z};
     [[maybe_unused]] unsigned long long mask = 0ull;
     const unsigned all = (unsigned)(P.SS * P.SS);
-    for (unsigned sub = 0; sub < all; ++sub) {
+    // the sub-pixels of the pass's samples, and the next one (a lane past its range asks for it: render_tiles_kernel's primary_of)
+    const unsigned sub_end = (P.sample_end - 1u) / (unsigned)P.S + 2u;
+    for (unsigned sub = P.sample_begin / (unsigned)P.S; sub < (sub_end < all ? sub_end : all); ++sub) {
         if (dirs == nullptr && (masks == nullptr || sub >= 64u)) break;
         const D3 d = primary_dir_lds(P, cam, x, y, (int)(sub / (unsigned)P.SS) + 1, (int)(sub % (unsigned)P.SS) + 1);
 #if RTM_TOL

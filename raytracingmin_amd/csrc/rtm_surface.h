@@ -191,23 +191,23 @@ __global__ __launch_bounds__(64) void render_surface_kernel(const RenderParams P
     };
     const int capacity = P.pool ? kSurfLdsLevels + kPoolLevels : kSurfLdsLevels;
     unsigned casts = 0, bounces = 0, draws = 0;
-    D3 acc = d3(0, 0, 0);
+    D3 acc = seed_of(P, valid, x, y);
     if (valid) {
         const RngPixelKey pkey = rng_pixel_key(P.seed_mult, (uint32_t)y * (uint32_t)P.W + (uint32_t)x);
-        for (int sx = 1; sx <= P.SS; ++sx)
-            for (int sy = 1; sy <= P.SS; ++sy) {
-                const D3 pdir = primary_dir(P, x, y, sx, sy);
-                for (int s = 0; s < P.S; ++s) {
-                    RngStream rng = rng_open(pkey, (uint32_t)(((sx - 1) * P.SS + (sy - 1)) * P.S + s));
-                    const SurfOut o = surface_sample_core(sc, K, P.mode, P.max_bounces, P.cam_org, pdir, rng, capacity, push, pop);
-                    overflow = overflow || o.overflow;
-                    casts += o.casts;
-                    bounces += o.bounces;
-                    draws += o.draws;
-                    const D3 cal = ((o.L / P.dSS) / P.dSS) / P.dS;                      // :240
-                    acc = acc + d3(clamp01(cal.x), clamp01(cal.y), clamp01(cal.z));  // :241-242
-                }
-            }
+        // samples k = ((sx-1)*SS + (sy-1))*S + s of the pass, [sample_begin, sample_end), in that order
+        D3 pdir = d3(0, 0, 0);
+        for (unsigned k = P.sample_begin; k < P.sample_end; ++k) {
+            const int sub = (int)(k / (unsigned)P.S);
+            if (k == P.sample_begin || k % (unsigned)P.S == 0u) pdir = primary_dir(P, x, y, sub / P.SS + 1, sub % P.SS + 1);
+            RngStream rng = rng_open(pkey, (uint32_t)k);
+            const SurfOut o = surface_sample_core(sc, K, P.mode, P.max_bounces, P.cam_org, pdir, rng, capacity, push, pop);
+            overflow = overflow || o.overflow;
+            casts += o.casts;
+            bounces += o.bounces;
+            draws += o.draws;
+            const D3 cal = ((o.L / P.dSS) / P.dSS) / P.dS;                      // :240
+            acc = acc + d3(clamp01(cal.x), clamp01(cal.y), clamp01(cal.z));  // :241-242
+        }
     }
     store_pixel(P, valid, x, y, acc);
     if (P.counters) {

@@ -91,17 +91,19 @@ __global__ __launch_bounds__(256) void wf_init_kernel(const RenderParams P, cons
     }
     int x, y;
     wf_pixel_xy(P, p, x, y);
-    const D3 pd = primary_dir(P, x, y, 1, 1);
+    const int sub = (int)(P.sample_begin / (unsigned)P.S);  // the pass's first sample (0 for a whole frame)
+    const D3 pd = primary_dir(P, x, y, sub / P.SS + 1, sub % P.SS + 1);
     const unsigned N = S.npix;
     S.org[p] = P.cam_org.x; S.org[N + p] = P.cam_org.y; S.org[2 * N + p] = P.cam_org.z;
     S.dir[p] = pd.x; S.dir[N + p] = pd.y; S.dir[2 * N + p] = pd.z;
     S.pdir[p] = pd.x; S.pdir[N + p] = pd.y; S.pdir[2 * N + p] = pd.z;
-    S.acc[p] = 0.0; S.acc[N + p] = 0.0; S.acc[2 * N + p] = 0.0;
-    const RngStream r = rng_open(rng_pixel_key(P.seed_mult, (uint32_t)y * (uint32_t)P.W + (uint32_t)x), 0u);
+    const D3 a = seed_of(P, true, x, y);
+    S.acc[p] = a.x; S.acc[N + p] = a.y; S.acc[2 * N + p] = a.z;
+    const RngStream r = rng_open(rng_pixel_key(P.seed_mult, (uint32_t)y * (uint32_t)P.W + (uint32_t)x), P.sample_begin);
     S.rng_ctr[p] = r.ctr;
     S.rng_k1[p] = r.k1;
-    S.n[p] = 0;
-    S.left[p] = P.S;
+    S.n[p] = P.sample_begin;
+    S.left[p] = P.S - (int)(P.sample_begin % (unsigned)P.S);
     S.depth[p] = 0;
     S.active[0][p] = p;
 }
@@ -417,7 +419,7 @@ __global__ __launch_bounds__(256) void wf_shade_kernel(const RenderParams P, con
             int left = S.left[p] - 1;
             int x, y;
             wf_pixel_xy(P, p, x, y);
-            if (n < P.total_samples) {
+            if (n < P.sample_end) {
                 D3 pd;
                 if (left == 0) {
                     left = P.S;
@@ -437,7 +439,7 @@ __global__ __launch_bounds__(256) void wf_shade_kernel(const RenderParams P, con
             S.left[p] = left;
             S.n[p] = n;
         }
-        alive = n < P.total_samples;
+        alive = n < P.sample_end;
         if (alive) {
             S.org[p] = org.x; S.org[N + p] = org.y; S.org[2 * N + p] = org.z;
             S.dir[p] = dir.x; S.dir[N + p] = dir.y; S.dir[2 * N + p] = dir.z;

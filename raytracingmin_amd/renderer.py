@@ -133,6 +133,55 @@ class Renderer:
                                                C.byref(s) if stats else None), "rtm_render_scene")
         return out, (s.as_dict() if stats else None)
 
+    # ---- progressive rendering: the frame's samples in passes (rtm_render_scene_samples) -------
+    def total_samples(self):
+        """N = superSamples^2 x samples: the samples of every pixel of a frame."""
+        return self.data.superSamples * self.data.superSamples * self.data.samples
+
+    def render_samples_device(self, sample_begin, sample_end, accum, want=("u8",), stats=True, stream=None,
+                              row_begin=0, row_end=None, band=None):
+        """Trace samples [sample_begin, sample_end) of every pixel of the rows into `accum`, a float64 CUDA tensor laid out
+        like render_rows_device's "f64" and updated in place: a pass that starts past 0 continues the fold from what `accum`
+        holds.  Returns (dict, stats): "f64" is `accum` itself; "f32" / "u8" are the frame's views after the last pass and
+        a preview (accum x N / sample_end) before it."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        row_end = self.data.height if row_end is None else row_end
+        opt = self._options(row_begin, row_end, band)
+        rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
+        dev = torch.device("cuda", self.device)
+        if accum.dtype != torch.float64 or accum.device != dev or not accum.is_contiguous() or accum.numel() != rows * W * 3:
+            raise ValueError(f"accum must be a contiguous float64 tensor of {rows}x{W}x3 on {dev}")
+        out = {"f64": accum}
+        if "f32" in want:
+            out["f32"] = torch.empty((rows, W, 3), dtype=torch.float32, device=dev)
+        if "u8" in want:
+            out["u8"] = torch.empty((rows, W, 3), dtype=torch.uint8, device=dev)
+        st = self.data.settings_c()
+        s = rtm_stats()
+        hip_stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out and rows > 0 else None
+        _lib.check(_lib.lib().rtm_render_scene_samples(C.byref(st), self._scene_handle(), C.byref(opt), int(sample_begin),
+                                                       int(sample_end), ptr("f64"), ptr("f32"), ptr("u8"),
+                                                       C.c_void_p(hip_stream), C.byref(s) if stats else None),
+                   "rtm_render_scene_samples")
+        return out, (s.as_dict() if stats else None)
+
+    def progressive(self, passes=None, samples_per_pass=None, want=("u8",), stats=True, stream=None,
+                    row_begin=0, row_end=None, band=None):
+        """Render the frame in contiguous, near-equal passes (plan_passes); yields (sample_end, outputs, stats) after each.
+        The outputs of the last pass are rtm_render_scene's frame bit for bit; "f64" is the accumulator every pass shares."""
+        import torch
+        row_end = self.data.height if row_end is None else row_end
+        opt = self._options(row_begin, row_end, band)
+        rows = _lib.lib().rtm_output_rows(C.byref(opt))
+        accum = torch.empty((rows, self.data.width, 3), dtype=torch.float64, device=torch.device("cuda", self.device))
+        for a, b in plan_passes(self.total_samples(), passes=passes, samples_per_pass=samples_per_pass):
+            out, st = self.render_samples_device(a, b, accum, want=want, stats=stats, stream=stream,
+                                                 row_begin=row_begin, row_end=row_end, band=band)
+            yield b, out, st
+
     # ---- host-buffer render (the blocking C entry point) ------------------------------------
     def render_rows(self, row_begin=0, row_end=None, want=("f64",), band=None):
         row_end = self.data.height if row_end is None else row_end
@@ -159,11 +208,19 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName):
-        """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp."""
-        out, _ = self.render_rows(0, self.data.height, want=("f64", "u8"))
-        self.image = out["f64"]
-        rgb8 = np.ascontiguousarray(out["u8"])
+    def Render(self, fileName, passes=1):
+        """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
+        frame progressively on the device (Renderer.progressive): the same files and the same self.image."""
+        if passes > 1:
+            last = None
+            for _, out, st in self.progressive(passes=passes, want=("u8",)):
+                last = out
+            self.image = last["f64"].cpu().numpy()
+            rgb8 = np.ascontiguousarray(last["u8"].cpu().numpy())
+        else:
+            out, _ = self.render_rows(0, self.data.height, want=("f64", "u8"))
+            self.image = out["f64"]
+            rgb8 = np.ascontiguousarray(out["u8"])
         L = _lib.lib()
         H, W = self.data.height, self.data.width
         ok_j = L.rtm_write_jpg(os.fsencode(fileName + ".jpg"), W, H, 3, rgb8.ctypes.data, 60)
@@ -171,6 +228,31 @@ class Renderer:
         if not (ok_j and ok_b):
             raise _lib.RtmError(-3, f"could not write {fileName}.jpg/.bmp")
         return rgb8
+
+
+def plan_passes(n_samples, passes=None, samples_per_pass=None):
+    """The passes [a, b) of a progressive frame of n_samples samples per pixel: contiguous, covering [0, n_samples), sizes
+    that differ by at most one sample.  Give `passes`, or `samples_per_pass` (the pass count is then its ceiling share);
+    neither: one pass."""
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError("a frame has at least one sample per pixel")
+    if passes is not None and samples_per_pass is not None:
+        raise ValueError("give passes or samples_per_pass, not both")
+    if samples_per_pass is not None:
+        if int(samples_per_pass) < 1:
+            raise ValueError("samples_per_pass must be at least 1")
+        passes = -(-n_samples // int(samples_per_pass))
+    passes = 1 if passes is None else int(passes)
+    if passes < 1 or passes > n_samples:
+        raise ValueError(f"passes must be in [1, {n_samples}] (one sample per pass at most that many), got {passes}")
+    q, r = divmod(n_samples, passes)
+    out, a = [], 0
+    for i in range(passes):
+        b = a + q + (1 if i < r else 0)
+        out.append((a, b))
+        a = b
+    return out
 
 
 # ---- seams below the renderer, for parity tests --------------------------------------------------
