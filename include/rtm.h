@@ -269,6 +269,41 @@ int rtm_render_scene(const rtm_settings* settings, const rtm_scene* scene, const
 int rtm_render_scene_samples(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
                              uint32_t sample_begin, uint32_t sample_end, double* accum_f64_dev, float* out_f32_dev,
                              uint8_t* out_u8_dev, void* stream, rtm_stats* stats);
+/* ---- first-hit feature buffers (AOVs) of a frame: what a preview's denoiser, compositor or object picker needs ----
+ * Primary rays have no jitter (src/Renderer.cpp:224-232), so every value below is a deterministic function of the scene
+ * and the camera.  Sub-pixels are visited in the reference's loop order, sx = 1..SS outer, sy = 1..SS inner; for each:
+ *   ray     org = camera.origin, dir = the primary direction of src/Renderer.cpp:227-232 (the render kernels' bits)
+ *   hit     the nearest-hit loop of :58-73 in the reference's own arithmetic (hit needs t < dis && t > 0, the lowest index
+ *           wins ties; spheres through SphereObject::Intersect, planes through the build-defined square above)
+ *   n       the orienting normal PathTracing holds at that hit (:80-83): Dot(normal, dir) < 0.0 ? normal : normal * -1.0,
+ *           where normal is what Intersect reports for the mode: RTM_MODE_REPAIRED Normalize(hitPoint - centre) (float-sqrtf
+ *           magnitude; a plane's m_normal); RTM_MODE_LITERAL vec3(), lost as in the reference, so n = (-0, -0, -0)
+ *   albedo  the hit object's raw material colour (rtm_sphere.color / rtm_object.color, not colorKD)
+ * Per pixel, in float (any plane pointer may be null; only the non-null ones are written):
+ *   depth   1 float      the CENTRE sub-pixel's dis rounded to float, +inf on a miss
+ *   object  1 int32      the centre sub-pixel's object index, -1 on a miss
+ *   normal  3 floats     sum of n over the SS^2 sub-pixels, divided by (double)(SS*SS), rounded to float (RGB-interleaved
+ *                        like out_f32); literal mode gives +0 everywhere (the sum starts at +0.0)
+ *   albedo  3 floats     the same reduction over the albedo
+ * The centre sub-pixel is c = (SS + 1) / 2 (integer division) in both axes: the one nearest the pixel centre, the first
+ * in loop order on ties.  Sums are taken in double from +0.0 in loop order; a miss adds +0. */
+typedef struct rtm_aov_buffers {
+    float* depth;     /* DEVICE, rows x width          */
+    float* normal;    /* DEVICE, rows x width x 3      */
+    float* albedo;    /* DEVICE, rows x width x 3      */
+    int32_t* object;  /* DEVICE, rows x width          */
+} rtm_aov_buffers;
+/* The AOVs of the rows [row_begin, row_end) (bands as for a render; rows stored back to back, rtm_output_rows of them).
+ * Only ENQUEUES one kernel on `stream` and allocates nothing; serialised per (device, stream) like a render, and recorded
+ * as a use of the scene (rtm_scene_destroy right after the call is safe).  Variant 0: the scene's uniform grid where a
+ * render would take it (see rtm_scene_create), else the chunked exhaustive loop; 1: the general per-object
+ * loop; 17: the grid (RTM_ERR_UNSUPPORTED for a scene without one); any other variant: RTM_ERR_UNSUPPORTED.  seed,
+ * max_bounces and the mode flags (RTM_MODE_HOST_TRIG, _COUNT_TESTS, _SURFACE_SAMPLE) are ignored: there are no draws and
+ * no trigonometry.  Null settings, options, out_dev or scene, bad rows or bands, a bad mode: RTM_ERR_INVALID_ARGUMENT,
+ * before any device call.  Added after RTM_ABI_VERSION 5 without changing it: callers look the symbol up. */
+int rtm_render_aov(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                   const rtm_aov_buffers* out_dev, void* stream);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);
@@ -353,6 +388,10 @@ int rtm_quantise(const double* image, size_t n_values, uint8_t* out);
  * like stb (0 on failure) so real stb can replace them. */
 int rtm_write_bmp(const char* filename, int w, int h, int comp, const void* data);
 int rtm_write_jpg(const char* filename, int w, int h, int comp, const void* data, int quality);
+/* Portable float map (the AOV planes): "PF" (comp 3) or "Pf" (comp 1), "w h", scale -1.0 (little-endian), rows
+ * bottom-up; data is HOST, rows top-down like the writers above.  1 on success, 0 on failure.  Added after
+ * RTM_ABI_VERSION 5 (callers look the symbol up). */
+int rtm_write_pfm(const char* filename, int w, int h, int comp /* 1 or 3 */, const float* data);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,10 @@ class rtm_stats(C.Structure):
                 "split": int(self.split), "object_tests": int(self.object_tests)}
 
 
+class rtm_aov_buffers(C.Structure):  # DEVICE pointers, any may be null (include/rtm.h: rtm_render_aov)
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("object", C.c_void_p)]
+
+
 # every symbol include/rtm.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -87,6 +91,7 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
     "rtm_render_scene_samples": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
+    "rtm_render_aov": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), _P(rtm_aov_buffers), C.c_void_p]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),
@@ -118,6 +123,7 @@ SIGNATURES = {
     "rtm_quantise": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtm_write_bmp": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rtm_write_jpg": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "rtm_write_pfm": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 # test and diagnostic hooks: include/rtm_debug.h (not part of the drop-in boundary)
 DEBUG_SIGNATURES = {

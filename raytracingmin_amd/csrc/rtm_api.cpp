@@ -78,6 +78,10 @@ int rtm_render_scene_samples(const rtm_settings* settings, const rtm_scene* scen
     RTM_GUARD(rtm::render_scene_samples(settings, scene, options, sample_begin, sample_end, accum_f64_dev, out_f32_dev,
                                         out_u8_dev, stream, stats))
 }
+int rtm_render_aov(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                   const rtm_aov_buffers* out_dev, void* stream) {
+    RTM_GUARD(rtm::render_aov(settings, scene, options, out_dev, stream))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {
@@ -168,6 +172,13 @@ int rtm_write_bmp(const char* filename, int w, int h, int comp, const void* data
 int rtm_write_jpg(const char* filename, int w, int h, int comp, const void* data, int quality) {
     try {
         return rtm::write_jpg(filename, w, h, comp, data, quality);
+    } catch (...) {
+        return 0;
+    }
+}
+int rtm_write_pfm(const char* filename, int w, int h, int comp, const float* data) {
+    try {
+        return rtm::write_pfm(filename, w, h, comp, data);
     } catch (...) {
         return 0;
     }

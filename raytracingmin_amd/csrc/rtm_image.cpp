@@ -52,6 +52,24 @@ struct File {
 };
 }  // namespace
 
+// Portable float map: "PF" (3 channels) or "Pf" (1), "w h", scale -1.0 (little-endian samples), then the rows bottom-up,
+// each w x comp floats.  The AOV planes of rtm_render_aov (depth, normal, albedo) keep their exact float bits this way.
+int write_pfm(const char* filename, int w, int h, int comp, const float* data) {
+    if (!filename || !data || w <= 0 || h <= 0 || (comp != 1 && comp != 3)) return 0;
+    File out(filename);
+    if (!out.f) return 0;
+    std::fprintf(out.f, "%s\n%d %d\n-1.0\n", comp == 3 ? "PF" : "Pf", w, h);
+    for (int y = h - 1; y >= 0; --y) {
+        const float* row = data + (size_t)y * w * comp;
+        for (size_t i = 0; i < (size_t)w * comp; ++i) {
+            uint32_t bits;
+            std::memcpy(&bits, &row[i], sizeof bits);
+            out.le32(bits);
+        }
+    }
+    return out.ok() ? 1 : 0;
+}
+
 // stbi_write_bmp layout for comp = 3: "BM", file size, 0, 0, data offset 54; BITMAPINFOHEADER
 // (40, w, h, 1 plane, 24 bpp, no compression, zeros); rows bottom-up, BGR, padded to 4 bytes.
 int write_bmp(const char* filename, int w, int h, int comp, const void* data) {

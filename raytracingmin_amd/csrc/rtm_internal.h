@@ -33,6 +33,8 @@ int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_optio
                  uint8_t* out8, void* stream, rtm_stats* stats);
 int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
                          uint32_t sample_end, double* accum, float* out32, uint8_t* out8, void* stream, rtm_stats* stats);
+int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const rtm_aov_buffers* out,
+               void* stream);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);
@@ -78,5 +80,6 @@ int scene_make_stress(uint64_t seed, size_t n, rtm_settings* st, rtm_sphere* sph
 int quantise(const double* image, size_t n_values, uint8_t* out);
 int write_bmp(const char* filename, int w, int h, int comp, const void* data);
 int write_jpg(const char* filename, int w, int h, int comp, const void* data, int quality);
+int write_pfm(const char* filename, int w, int h, int comp, const float* data);
 
 }  // namespace rtm

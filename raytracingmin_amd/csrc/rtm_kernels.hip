@@ -42,6 +42,7 @@
 #include "rtm_fp32.h"
 #include "rtm_seam_kernels.h"
 #include "rtm_surface.h"
+#include "rtm_aov_kernel.h"
 
 namespace rtm {
 
@@ -2393,6 +2394,79 @@ int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const r
         return RTM_OK;
     }
     return render_scene_pass(st, scene, opt, SamplePass{sample_begin, sample_end}, accum, out32, out8, stream_v, stats);
+}
+
+// rtm_render_aov: the first-hit feature buffers of the call's rows (rtm_aov_kernel.h).  Every argument is checked before
+// anything touches the device; then the call only enqueues one launch, serialised with the other calls on (device, stream).
+int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const rtm_aov_buffers* out,
+               void* stream_v) {
+    if (!out) {
+        set_last_error("out_dev: the buffer set is null");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (!opt) {
+        set_last_error("null argument");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    rtm_options o = *opt;
+    o.max_bounces = -1;  // (no paths are traced: the depth cap does not apply)
+    int rc = validate(st, nullptr, 0, &o);
+    if (rc != RTM_OK) return rc;
+    if (!scene) {
+        set_last_error("null scene");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (scene->device != opt->device) {
+        set_last_error("the scene lives on another device than rtm_options.device");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    std::shared_lock<std::shared_mutex> gate(g_gate);
+    reap_scenes(false);
+    const void* grid = grid_for(scene, st, opt);
+    int search;
+    if (opt->variant == kVariantAuto) {
+        search = grid != nullptr ? kAovGrid : kAovChunked;  // the grid exactly where a render would take it
+    } else if (opt->variant == kVariantRef) {
+        search = kAovGeneral;
+    } else if (opt->variant == kVariantGrid) {
+        if (grid == nullptr) {
+            set_last_error("variant 17 (uniform grid): this scene has no grid");
+            return RTM_ERR_UNSUPPORTED;
+        }
+        search = kAovGrid;
+    } else {
+        set_last_error("rtm_render_aov serves variants 0, 1 and 17");
+        return RTM_ERR_UNSUPPORTED;
+    }
+    const int rows = output_rows(opt);
+    if (rows == 0 || (!out->depth && !out->normal && !out->albedo && !out->object)) return RTM_OK;
+    RTM_HIP_CHECK(hipSetDevice(opt->device));
+    const hipStream_t stream = (hipStream_t)stream_v;
+    StreamCtx& ctx = *get_ctx(opt->device, stream);
+    std::lock_guard<std::mutex> lock(ctx.mu);
+    RenderParams P;
+    std::memset(&P, 0, sizeof P);
+    fill_render_params(P, st, opt, SamplePass{});
+    P.scene = scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
+                         scene->has_planes ? scene->plane.as<double>() : nullptr, grid, scene->surf.as<double>(), scene->axis_pat,
+                         scene->fold_flags);
+    const unsigned tiles = (unsigned)P.tiles_x * (unsigned)((rows + 7) / 8);
+    const size_t lds = aov_lds_bytes(search);
+    if (search == kAovGrid)
+        aov_kernel<kAovGrid, SceneGlobal><<<tiles, 64, lds, stream>>>(P, *out);
+    else if (search == kAovGeneral)
+        aov_kernel<kAovGeneral, SceneGlobal><<<tiles, 64, lds, stream>>>(P, *out);
+    else if (scene->has_planes)
+        aov_kernel<kAovChunked, SceneGlobalObjects><<<tiles, 64, lds, stream>>>(P, *out);
+    else
+        aov_kernel<kAovChunked, SceneGlobal><<<tiles, 64, lds, stream>>>(P, *out);
+    const hipError_t e = hipGetLastError();
+    note_scene_use(scene, stream);
+    if (e != hipSuccess) {
+        set_last_error(std::string("AOV kernel launch: ") + hipGetErrorString(e));
+        return RTM_ERR_HIP;
+    }
+    return RTM_OK;
 }
 
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int on_device,

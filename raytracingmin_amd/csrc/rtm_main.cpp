@@ -6,6 +6,7 @@
 //           [--gpus N] [--virtual-strips N] [--force-rccl]   (interleaved 8-row bands over N GPUs + one RCCL gather)
 //           [--dump-f32 FILE]                    (the gathered float3 buffer, raw little-endian floats)
 //           [--passes N]                         (progressive: the frame's samples in N passes on one GPU, same image)
+//           [--aov]                              (first-hit feature buffers next to the image: STEM_depth/_normal/_albedo.pfm, .bmp)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -40,7 +41,9 @@ static void usage() {
         "--force-rccl : take the RCCL exchange with --gpus 1 too; --virtual-strips N : N parts on one GPU, no RCCL\n"
         "--dump-f32 FILE : write the float3 accumulation buffer (raw floats, row-major RGB)\n"
         "--passes N : render the frame's samples in N near-equal passes on one GPU (rtm_render_scene_samples), printing\n"
-        "             each pass's sample range and time; the image is the one-pass image bit for bit\n");
+        "             each pass's sample range and time; the image is the one-pass image bit for bit\n"
+        "--aov : also write the first-hit feature buffers on one GPU (rtm_render_aov): STEM_depth.pfm, STEM_normal.pfm,\n"
+        "        STEM_albedo.pfm and the quantised STEM_normal.bmp (0.5 n + 0.5), STEM_albedo.bmp\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -52,7 +55,7 @@ int main(int argc, char* argv[]) {
     std::string json_file = "settingData.json", stem = "result";
     int width = 0, height = 0, samples = 0, super_samples = 0, spp = 0;
     int mode = RTM_MODE_REPAIRED, max_bounces = -1, device = 0, gpus = 1, virtual_strips = 0, host_trig = 1, force_rccl = 0;
-    int passes = 0;
+    int passes = 0, aov = 0;
     std::string dump_f32;
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
@@ -84,6 +87,7 @@ int main(int argc, char* argv[]) {
         else if (c == "--host-trig") host_trig = 1;
         else if (c == "--device-trig") host_trig = 0;
         else if (c == "--force-rccl") force_rccl = 1;
+        else if (c == "--aov") aov = 1;
         else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
         else if (c == "--seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 0);
         else if (c == "--out" && i + 1 < argc) stem = argv[++i];
@@ -99,6 +103,10 @@ int main(int argc, char* argv[]) {
     }
     if (passes > 0 && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
         std::fprintf(stderr, "--passes renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
+        return 2;
+    }
+    if (aov && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--aov renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
         return 2;
     }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
@@ -185,5 +193,16 @@ int main(int argc, char* argv[]) {
     // src/Renderer.cpp:256-257
     const int ok_jpg = rtm_write_jpg((stem + ".jpg").c_str(), st.width, st.height, 3, rgb8.data(), 60);
     const int ok_bmp = rtm_write_bmp((stem + ".bmp").c_str(), st.width, st.height, 3, rgb8.data());
-    return (ok_jpg && ok_bmp) ? 0 : 1;
+    if (!(ok_jpg && ok_bmp)) return 1;
+    if (aov) {
+        std::string err;
+        rc = rtm_node_write_aov(&st, spheres.data(), n, &opt, stem, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "aov failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        std::printf("aov: %s_depth.pfm, %s_normal.pfm, %s_albedo.pfm, %s_normal.bmp, %s_albedo.bmp\n", stem.c_str(), stem.c_str(),
+                    stem.c_str(), stem.c_str(), stem.c_str());
+    }
+    return 0;
 }

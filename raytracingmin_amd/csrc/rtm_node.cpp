@@ -371,3 +371,60 @@ int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, si
     (void)rtm_scene_destroy(scene);
     return rc;
 }
+
+// --aov (rtm_node.h): one rtm_render_aov of the frame on the default stream, then the five files.
+int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
+                       const std::string& stem, std::string& err) {
+    if (hipSetDevice(opt->device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(opt->device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    rtm_scene* scene = nullptr;
+    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
+    if (rc != RTM_OK) {
+        err = std::string("scene: ") + rtm_last_error_detail();
+        return rc;
+    }
+    const size_t pix = (size_t)st->width * st->height;
+    rtm_aov_buffers dev;
+    std::memset(&dev, 0, sizeof dev);
+    if (hipMalloc((void**)&dev.depth, pix * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&dev.normal, pix * 3 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&dev.albedo, pix * 3 * sizeof(float)) != hipSuccess) {
+        err = "no device memory for the AOV planes";
+        rc = RTM_ERR_HIP;
+    }
+    std::vector<float> depth(pix), normal(pix * 3), albedo(pix * 3);
+    if (rc == RTM_OK) {
+        rc = rtm_render_aov(st, scene, opt, &dev, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    if (rc == RTM_OK && (hipMemcpy(depth.data(), dev.depth, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(normal.data(), dev.normal, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(albedo.data(), dev.albedo, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
+        err = "copying the AOV planes back failed";
+        rc = RTM_ERR_HIP;
+    }
+    (void)hipFree(dev.depth);
+    (void)hipFree(dev.normal);
+    (void)hipFree(dev.albedo);
+    (void)rtm_scene_destroy(scene);
+    if (rc != RTM_OK) return rc;
+    const int w = st->width, h = st->height;
+    bool ok = rtm_write_pfm((stem + "_depth.pfm").c_str(), w, h, 1, depth.data()) == 1 &&
+              rtm_write_pfm((stem + "_normal.pfm").c_str(), w, h, 3, normal.data()) == 1 &&
+              rtm_write_pfm((stem + "_albedo.pfm").c_str(), w, h, 3, albedo.data()) == 1;
+    std::vector<double> v(pix * 3);
+    std::vector<uint8_t> rgb8(pix * 3);
+    for (size_t i = 0; i < v.size(); ++i) v[i] = 0.5 * (double)normal[i] + 0.5;
+    ok = ok && rtm_quantise(v.data(), v.size(), rgb8.data()) == RTM_OK &&
+         rtm_write_bmp((stem + "_normal.bmp").c_str(), w, h, 3, rgb8.data()) == 1;
+    for (size_t i = 0; i < v.size(); ++i) v[i] = (double)albedo[i];
+    ok = ok && rtm_quantise(v.data(), v.size(), rgb8.data()) == RTM_OK &&
+         rtm_write_bmp((stem + "_albedo.bmp").c_str(), w, h, 3, rgb8.data()) == 1;
+    if (!ok) {
+        err = "cannot write the AOV files of " + stem;
+        return RTM_ERR_IO;
+    }
+    return RTM_OK;
+}

@@ -16,3 +16,8 @@ int rtm_node_render(const rtm_settings* st, const rtm_object* objects, size_t n,
 // --passes), printing "pass i/N: samples [a, b) <ms> ms" per pass.  The outputs are rtm_render_scene's frame.
 int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options, int passes,
                            float* out_f32_host, uint8_t* out_u8_host, rtm_stats* total, std::string& err);
+// The first-hit feature buffers of the whole frame on options->device (rtm_render_aov, rtm_cli --aov), written next to the
+// image: <stem>_depth.pfm, <stem>_normal.pfm, <stem>_albedo.pfm (the exact float planes), <stem>_normal.bmp (the quantised
+// 0.5 n + 0.5) and <stem>_albedo.bmp (the quantised albedo).
+int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
+                       const std::string& stem, std::string& err);

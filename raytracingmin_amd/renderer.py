@@ -182,6 +182,56 @@ class Renderer:
                                                  row_begin=row_begin, row_end=row_end, band=band)
             yield b, out, st
 
+    # ---- first-hit feature buffers (rtm_render_aov) ------------------------------------------
+    AOV_PLANES = ("depth", "normal", "albedo", "object")
+
+    def render_aov(self, row_begin=0, row_end=None, band=None, want=AOV_PLANES, stream=None):
+        """The first-hit AOVs of rows [row_begin, row_end) as torch CUDA tensors: "depth" (rows, W) float32, "normal" and
+        "albedo" (rows, W, 3) float32, "object" (rows, W) int32 (include/rtm.h: rtm_render_aov).  Only the planes named in
+        `want` are allocated and computed.  Enqueued on `stream` (default: the current stream); nothing waits for it."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        unknown = set(want) - set(self.AOV_PLANES)
+        if unknown:
+            raise ValueError(f"unknown AOV plane(s) {sorted(unknown)}; the planes are {self.AOV_PLANES}")
+        row_end = self.data.height if row_end is None else row_end
+        opt = self._options(row_begin, row_end, band)
+        rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
+        dev = torch.device("cuda", self.device)
+        shapes = {"depth": ((rows, W), torch.float32), "normal": ((rows, W, 3), torch.float32),
+                  "albedo": ((rows, W, 3), torch.float32), "object": ((rows, W), torch.int32)}
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in self.AOV_PLANES if k in want}
+        bufs = _lib.rtm_aov_buffers()
+        for k, v in out.items():
+            setattr(bufs, k, v.data_ptr() if rows > 0 else None)
+        st = self.data.settings_c()
+        hip_stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        _lib.check(_lib.lib().rtm_render_aov(C.byref(st), self._scene_handle(), C.byref(opt), C.byref(bufs),
+                                             C.c_void_p(hip_stream)), "rtm_render_aov")
+        return out
+
+    def write_aov(self, fileName):
+        """<fileName>_depth.pfm, _normal.pfm, _albedo.pfm (exact float planes) and _normal.bmp (quantised 0.5 n + 0.5),
+        _albedo.bmp (quantised albedo) of the whole frame — what rtm_cli --aov writes."""
+        import torch
+        out = self.render_aov(want=("depth", "normal", "albedo"))
+        torch.cuda.synchronize(self.device)
+        H, W = self.data.height, self.data.width
+        L = _lib.lib()
+        planes = {k: np.ascontiguousarray(v.cpu().numpy()) for k, v in out.items()}
+        ok = True
+        for k, comp in (("depth", 1), ("normal", 3), ("albedo", 3)):
+            ok = ok and L.rtm_write_pfm(os.fsencode(f"{fileName}_{k}.pfm"), W, H, comp, planes[k].ctypes.data) == 1
+        for k, v in (("normal", 0.5 * planes["normal"].astype(np.float64) + 0.5), ("albedo", planes["albedo"].astype(np.float64))):
+            v = np.ascontiguousarray(v)
+            rgb8 = np.zeros(v.shape, dtype=np.uint8)
+            _lib.check(L.rtm_quantise(v.ctypes.data, v.size, rgb8.ctypes.data), "rtm_quantise")
+            ok = ok and L.rtm_write_bmp(os.fsencode(f"{fileName}_{k}.bmp"), W, H, 3, rgb8.ctypes.data) == 1
+        if not ok:
+            raise _lib.RtmError(-3, f"could not write the AOV files of {fileName}")
+        return planes
+
     # ---- host-buffer render (the blocking C entry point) ------------------------------------
     def render_rows(self, row_begin=0, row_end=None, want=("f64",), band=None):
         row_end = self.data.height if row_end is None else row_end
@@ -208,9 +258,10 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1):
+    def Render(self, fileName, passes=1, aov=False):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
-        frame progressively on the device (Renderer.progressive): the same files and the same self.image."""
+        frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
+        writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp)."""
         if passes > 1:
             last = None
             for _, out, st in self.progressive(passes=passes, want=("u8",)):
@@ -227,6 +278,8 @@ class Renderer:
         ok_b = L.rtm_write_bmp(os.fsencode(fileName + ".bmp"), W, H, 3, rgb8.ctypes.data)
         if not (ok_j and ok_b):
             raise _lib.RtmError(-3, f"could not write {fileName}.jpg/.bmp")
+        if aov:
+            self.write_aov(fileName)
         return rgb8
 
 
