@@ -1130,175 +1130,121 @@ static size_t debug_lds_pad() {
     return pad;
 }
 
-// Scenes that hold planes (render_view: up to kLdsTableMaxSpheres objects): the deferred-fold kernels with the object
-// chunk, packed records for a depth cap of at most 8 (PACK8), by position for any depth (PACKL)
-constexpr size_t kUnitTableBytes = (size_t)(kShadeConstCount - kTrigConstCount) * sizeof(double);  // rtm_device.h: the near-unit Normalize table
-// The launch's LDS with the near-unit Normalize table where it does not cost a wave per CU (P.unit_tab tells the kernel)
-static size_t with_unit_table(RenderParams& P, size_t lds) {
-    P.unit_tab = unit_table_fits(lds) ? 1u : 0u;
-    return lds + (P.unit_tab ? kUnitTableBytes : 0);
-}
-template <bool SPLIT>
-static void launch_render_planes(const RenderParams& P_in, unsigned grid, hipStream_t stream) {
-    RenderParams P = P_in;
-    const size_t tab = lds_table_bytes(P.scene.n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) + debug_lds_pad();
-    constexpr size_t tag = SPLIT ? kFoldTagBytes : 0;
-    if (P.max_bounces >= 0 && P.max_bounces <= 8) {
-        const size_t lds = with_unit_table(P, tab + kFoldQueueBytesS + tag);
-        render_tiles_kernel<MathFast, true, 8, uint8_t, 16, 4, true, false, true, SPLIT, true, false, false, true>
-            <<<grid, 64, lds, stream>>>(P);
-    } else {
-        const size_t lds = with_unit_table(P, tab + kFoldQueueBytesLS + tag);
-        render_tiles_kernel<MathFast, true, 8, uint8_t, 0, 4, true, false, false, SPLIT, true, true, false, true>
-            <<<grid, 64, lds, stream>>>(P);
+// The instantiations for exactly the scene's sphere count (rtm_path.h: sphere_disc): an axis signature in repaired mode where
+// the launch holds the near-unit Normalize table (a compile-time fact for them), and with packed records (kPack8) any n of
+// 1..7.  false: none of them, the caller launches the generic kernel.
+template <class M, unsigned F, typename RecT, int LDS_D, int WPE>
+static bool launch_exact_n(const RenderParams& P, unsigned grid, hipStream_t stream) {
+    const size_t pad = debug_lds_pad();
+    unsigned unit_tab;
+    render_lds_bytes<F, RecT, LDS_D>(P.scene.n, pad, &unit_tab);
+#define RTM_AXIS_CASE(k, sig)                                                                           \
+    if (P.scene.n == k && P.scene.axis_pat == sig && P.mode == RTM_MODE_REPAIRED && unit_tab == 1u) {   \
+        launch_tiles<M, F, axis_unroll(k, sig), RecT, LDS_D, WPE>(P, grid, pad, stream);                \
+        return true;                                                                                    \
     }
+    RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
+#undef RTM_AXIS_CASE
+    if constexpr ((F & kPack8) != 0) {
+        switch (P.scene.n) {
+#define RTM_EXACT_N(k)                                                             \
+    case k:                                                                        \
+        launch_tiles<M, F, -100 - k, RecT, LDS_D, WPE>(P, grid, pad, stream);      \
+        return true;
+            RTM_EXACT_N(1) RTM_EXACT_N(2) RTM_EXACT_N(3) RTM_EXACT_N(4) RTM_EXACT_N(5) RTM_EXACT_N(6) RTM_EXACT_N(7)
+#undef RTM_EXACT_N
+            default: break;
+        }
+    }
+    return false;
 }
 
-constexpr size_t kStealLdsBytes = 2 * 64 * sizeof(unsigned);  // STEAL: every pixel's next own sample and own-sample end
-template <class M, bool LDS_TAB, int UNROLL, typename RecT, int WPE = 1, bool PARK = false, bool STAMP = false,
-          bool TRY_PACK8 = false, bool SPLIT = false, bool DEFER = false, bool STEAL = false>
-static void launch_render_depth(const RenderParams& P_in, unsigned grid, hipStream_t stream) {
-    RenderParams P = P_in;  // (unit_tab: the near-unit Normalize table where the launch's LDS has the room, with_unit_table)
-    const size_t tab = (LDS_TAB ? lds_table_bytes(P.scene.n) : 0) + (10 + kTrigConstCount) * sizeof(double) +
-                       (PARK ? 6 * 64 * sizeof(double) : 0) + debug_lds_pad() + (SPLIT ? kFoldTagBytes : 0);
-    constexpr int DEEP = deep_lds_levels<RecT>();
-    if constexpr (TRY_PACK8 && sizeof(RecT) == 1) {
-        if (P.max_bounces >= 0 && P.max_bounces <= 8 && P.scene.n < 256) {  // ids and the identity index in a byte
-            if constexpr (DEFER && UNROLL == -8) {
-                // scenes under 8 spheres (every shipped scene): the instantiation for exactly n spheres
-                const size_t lds = with_unit_table(P, tab + kFoldQueueBytesS + (STEAL ? kStealLdsBytes : 0));
-#define RTM_AXIS_CASE(k, sig)                                                                                                  \
-    if (P.scene.n == k && P.scene.axis_pat == sig && P.mode == RTM_MODE_REPAIRED && P.unit_tab == 1u) { /* rtm_path.h: sphere_disc */                        \
-        render_tiles_kernel<M, LDS_TAB, axis_unroll(k, sig), RecT, 16, WPE, PARK, STAMP, true, SPLIT, true, false, false, false, STEAL> \
-            <<<grid, 64, lds, stream>>>(P);                                                                                    \
-        return;                                                                                                                \
-    }
-                RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
-#undef RTM_AXIS_CASE
-                switch (P.scene.n) {
-#define RTM_EXACT_N(k)                                                                                     \
-    case k:                                                                                                \
-        render_tiles_kernel<M, LDS_TAB, -100 - k, RecT, 16, WPE, PARK, STAMP, true, SPLIT, true, false, false, false, STEAL> \
-            <<<grid, 64, lds, stream>>>(P);                                                                \
-        return;
-                    RTM_EXACT_N(1) RTM_EXACT_N(2) RTM_EXACT_N(3) RTM_EXACT_N(4) RTM_EXACT_N(5) RTM_EXACT_N(6) RTM_EXACT_N(7)
-#undef RTM_EXACT_N
-                    default: break;
-                }
+// The kernel of shape F for the scene's size and depth cap.  kPack8 in F asks for hit records packed in a register where the
+// cap allows it (at most 8 bounces, ids and the identity index in a byte); a kDefer shape takes records packed by position
+// (kPackL) at any other depth; everything else keeps its records in LDS (16 levels when the cap keeps every path shallower,
+// else deep_lds_levels and the pool).  UNROLL -8 (scenes under 8 spheres: every shipped scene) tries the exact-n kernels first.
+template <class M, int UNROLL, typename RecT, int WPE, unsigned F>
+static void launch_render_depth(const RenderParams& P, unsigned grid, hipStream_t stream) {
+    const size_t pad = debug_lds_pad();
+    if constexpr ((F & kPack8) != 0 && sizeof(RecT) == 1) {
+        if (P.max_bounces >= 0 && P.max_bounces <= 8 && P.scene.n < 256) {
+            if constexpr ((F & kDefer) != 0 && UNROLL == -8) {
+                if (launch_exact_n<M, F, RecT, 16, WPE>(P, grid, stream)) return;
             }
-            if constexpr (DEFER) {
-                const size_t lds = with_unit_table(P, tab + kFoldQueueBytesS + (STEAL ? kStealLdsBytes : 0));
-                render_tiles_kernel<M, LDS_TAB, UNROLL, RecT, 16, WPE, PARK, STAMP, true, SPLIT, true, false, false, false, STEAL>
-                    <<<grid, 64, lds, stream>>>(P);
-            } else {
-                const size_t lds = with_unit_table(P, tab);
-                render_tiles_kernel<M, LDS_TAB, UNROLL, RecT, 16, WPE, PARK, STAMP, true, false><<<grid, 64, lds, stream>>>(P);  // (never split: the split rides on the fold queue)
-            }
+            launch_tiles<M, F, UNROLL, RecT, 16, WPE>(P, grid, pad, stream);
             return;
         }
     }
-    if constexpr (DEFER && sizeof(RecT) == 1) {
-        if (P.scene.n < 256) {  // any depth: packed records + pooled stack, deferred fold
-            const size_t lds = with_unit_table(P, tab + kFoldQueueBytesLS);  // (8 280 bytes for a 7-sphere scene; 10 072 with the FIFO form: no room for the table then)
+    if constexpr ((F & kDefer) != 0 && sizeof(RecT) == 1) {
+        if (P.scene.n < 256) {  // any depth: packed records + pooled stack, deferred fold, no stealing
+            constexpr unsigned FL = (F & ~(kPack8 | kSteal)) | kPackL;
             if constexpr (UNROLL == -8) {
-#define RTM_AXIS_CASE(k, sig)                                                                                              \
-    if (P.scene.n == k && P.scene.axis_pat == sig && P.mode == RTM_MODE_REPAIRED && P.unit_tab == 1u) { /* rtm_path.h: sphere_disc */                    \
-        render_tiles_kernel<M, LDS_TAB, axis_unroll(k, sig), RecT, 0, WPE, PARK, STAMP, false, SPLIT, true, true>           \
-            <<<grid, 64, lds, stream>>>(P);                                                                                \
-        return;                                                                                                            \
-    }
-                RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
-#undef RTM_AXIS_CASE
+                if (launch_exact_n<M, FL, RecT, 0, WPE>(P, grid, stream)) return;
             }
-            render_tiles_kernel<M, LDS_TAB, UNROLL, RecT, 0, WPE, PARK, STAMP, false, SPLIT, true, true>
-                <<<grid, 64, lds, stream>>>(P);
+            launch_tiles<M, FL, UNROLL, RecT, 0, WPE>(P, grid, pad, stream);
             return;
         }
     }
-    if (!needs_pool(P)) {
-        const size_t lds = with_unit_table(P, tab + 16 * 64 * sizeof(RecT));
-        render_tiles_kernel<M, LDS_TAB, UNROLL, RecT, 16, WPE, PARK, STAMP, false, false><<<grid, 64, lds, stream>>>(P);
+    constexpr unsigned FR = F & (kLdsTab | kPark | kStamp);  // (never split: the split rides on the fold queue)
+    if (!needs_pool(P)) launch_tiles<M, FR, UNROLL, RecT, 16, WPE>(P, grid, pad, stream);
+    else launch_tiles<M, FR, UNROLL, RecT, deep_lds_levels<RecT>(), WPE>(P, grid, pad, stream);
+}
+
+// A deferred-fold render (render_view: n < 256): the sample split where the planner asked for one (the split tiles' blocks
+// behind the whole tiles', then split_finalize_kernel), and steal_finalize_kernel behind a stealing one
+template <int UNROLL, unsigned F>
+static void launch_fold(const RenderParams& P, unsigned grid, hipStream_t stream) {
+    if (P.split > 1) {
+        launch_render_depth<MathFast, UNROLL, uint8_t, 4, F | kSplit>(P, P.split_first + P.n_tiles * P.split, stream);
+        launch_split_finalize(P, stream);
     } else {
-        const size_t lds = with_unit_table(P, tab + DEEP * 64 * sizeof(RecT));
-        render_tiles_kernel<M, LDS_TAB, UNROLL, RecT, DEEP, WPE, PARK, STAMP, false, false><<<grid, 64, lds, stream>>>(P);
+        launch_render_depth<MathFast, UNROLL, uint8_t, 4, F>(P, grid, stream);
     }
+    if constexpr ((F & kSteal) != 0) launch_steal_finalize(P, grid, stream);
+}
+// (n < 8: no full chunk of 8, the instantiation without the chunk loop)
+template <unsigned F>
+static void launch_fold_lds(const RenderParams& P, unsigned grid, hipStream_t stream) {
+    if (P.scene.n < 8) launch_fold<-8, F>(P, grid, stream);
+    else launch_fold<8, F>(P, grid, stream);
 }
 
 // `variant` is resolved (render_view): one of ref, fast-lds, fast-global, stamped, global-defer, primary-reuse, fp32.
 static void launch_render(int variant, const RenderParams& P, unsigned grid, hipStream_t stream) {
     const int n = P.scene.n;
-    const unsigned split_grid = P.split_first + P.n_tiles * P.split;
+    constexpr unsigned kFold = kPark | kPack8 | kDefer;  // packed records where the cap allows, the deferred fold
     if (variant == kVariantFastLds && n > kLdsTableMaxSpheres) variant = kVariantFastGlobal;
     switch (variant) {
         case kVariantRef:
-            if (n <= 256) launch_render_depth<MathRef, false, 1, uint8_t>(P, grid, stream);
-            else launch_render_depth<MathRef, false, 1, uint32_t>(P, grid, stream);
+            if (n <= 256) launch_render_depth<MathRef, 1, uint8_t, 1, 0>(P, grid, stream);
+            else launch_render_depth<MathRef, 1, uint32_t, 1, 0>(P, grid, stream);
             return;
-        case kVariantFastLds:  // (n < 8: no full chunk of 8, the instantiation without the chunk loop)
-            if (P.scene.plane != nullptr) {  // render_view: n <= kLdsTableMaxSpheres (ids and the identity index in a byte: n < 256)
-                if (P.split > 1) {
-                    launch_render_planes<true>(P, split_grid, stream);
-                    split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
-                } else {
-                    launch_render_planes<false>(P, grid, stream);
-                }
-                return;
-            }
-            if (P.steal_ws != nullptr) {  // render_view: depth cap <= 8; the whole tiles balance their lanes by sample stealing
-                if (P.split > 1) {
-                    if (n < 8) launch_render_depth<MathFast, true, -8, uint8_t, 4, true, false, true, true, true, true>(P, split_grid, stream);
-                    else launch_render_depth<MathFast, true, 8, uint8_t, 4, true, false, true, true, true, true>(P, split_grid, stream);
-                    split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
-                } else if (n < 8) {
-                    launch_render_depth<MathFast, true, -8, uint8_t, 4, true, false, true, false, true, true>(P, grid, stream);
-                } else {
-                    launch_render_depth<MathFast, true, 8, uint8_t, 4, true, false, true, false, true, true>(P, grid, stream);
-                }
-                const unsigned n_whole = P.split > 1 ? P.split_first : grid;
-                if (n_whole) steal_finalize_kernel<<<n_whole, 64, (size_t)P.steal_depth * 64 * sizeof(unsigned short), stream>>>(P);
-                return;
-            }
-            if (P.split > 1) {
-                if (n < 8) launch_render_depth<MathFast, true, -8, uint8_t, 4, true, false, true, true, true>(P, split_grid, stream);
-                else launch_render_depth<MathFast, true, 8, uint8_t, 4, true, false, true, true, true>(P, split_grid, stream);
-                split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
-            } else if (n < 8) {
-                launch_render_depth<MathFast, true, -8, uint8_t, 4, true, false, true, false, true>(P, grid, stream);
-            } else {
-                launch_render_depth<MathFast, true, 8, uint8_t, 4, true, false, true, false, true>(P, grid, stream);
-            }
+        case kVariantFastLds:
+            // scenes that hold planes (render_view: n < 256): the object chunk, records packed in a register for a depth cap
+            // of at most 8, by position for any depth
+            if (P.scene.plane != nullptr) launch_fold<8, kLdsTab | kFold | kPlanes>(P, grid, stream);
+            // render_view: depth cap <= 8; the whole tiles balance their lanes by sample stealing
+            else if (P.steal_ws != nullptr) launch_fold_lds<kLdsTab | kFold | kSteal>(P, grid, stream);
+            else launch_fold_lds<kLdsTab | kFold>(P, grid, stream);
             return;
         case kVariantGlobalDefer:  // render_view: n < 256
-            if (P.split > 1) {
-                launch_render_depth<MathFast, false, 8, uint8_t, 4, true, false, true, true, true>(P, split_grid, stream);
-                split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
-            } else {
-                launch_render_depth<MathFast, false, 8, uint8_t, 4, true, false, true, false, true>(P, grid, stream);
-            }
+            launch_fold<8, kFold>(P, grid, stream);
             return;
         case kVariantFp32: {  // validated by render_view: repaired mode, 1 <= n <= 256
             const size_t lds = (((size_t)n * kFp32Row * sizeof(float) + 15) & ~(size_t)15) + 10 * sizeof(double);
             render_fp32_kernel<<<grid, 64, lds, stream>>>(P);
             return;
         }
-        case kVariantPrimaryReuse: {  // validated by render_view: 1 <= n <= 24, 0 <= max_bounces <= 8
-            RenderParams Q = P;
-            const size_t lds = with_unit_table(Q, lds_table_bytes(n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) +
-                                                      kFoldQueueBytes + debug_lds_pad());
-            if (n < 8)
-                render_tiles_kernel<MathFast, true, -8, uint8_t, 16, 4, true, false, true, false, true, false, true>
-                    <<<grid, 64, lds, stream>>>(Q);
-            else
-                render_tiles_kernel<MathFast, true, 8, uint8_t, 16, 4, true, false, true, false, true, false, true>
-                    <<<grid, 64, lds, stream>>>(Q);
+        case kVariantPrimaryReuse:  // validated by render_view: 1 <= n <= 24, 0 <= max_bounces <= 8
+            if (n < 8) launch_tiles<MathFast, kLdsTab | kFold | kReuse, -8, uint8_t, 16, 4>(P, grid, debug_lds_pad(), stream);
+            else launch_tiles<MathFast, kLdsTab | kFold | kReuse, 8, uint8_t, 16, 4>(P, grid, debug_lds_pad(), stream);
             return;
-        }
         case kVariantStamped:  // render_view: n <= kLdsTableMaxSpheres
-            launch_render_depth<MathFast, true, 8, uint8_t, 4, true, true, true>(P, grid, stream);
+            launch_render_depth<MathFast, 8, uint8_t, 4, kLdsTab | kPark | kStamp | kPack8>(P, grid, stream);
             return;
         default:  // kVariantFastGlobal: the chunked kernel with global-memory tables, any n
-            if (n <= 256) launch_render_depth<MathFast, false, 8, uint8_t, 4>(P, grid, stream);
-            else launch_render_depth<MathFast, false, 8, uint32_t, 4>(P, grid, stream);
+            if (n <= 256) launch_render_depth<MathFast, 8, uint8_t, 4, 0>(P, grid, stream);
+            else launch_render_depth<MathFast, 8, uint32_t, 4, 0>(P, grid, stream);
     }
 }
 
@@ -2010,7 +1956,7 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
             plan.optional[kScratchTerms] = true;  // no room for the terms: the launch runs unsplit (same image, a longer tail)
         }
     }
-    // In-wave sample stealing for the whole tiles of the packed-record LDS-table kernel (rtm_render_kernel.h, STEAL): a
+    // In-wave sample stealing for the whole tiles of the packed-record LDS-table kernel (rtm_render_kernel.h, kSteal): a
     // block per whole tile for the accumulators and the stolen samples' terms.  Rows per tile: the stolen share of a tile
     // shrinks like 1 / sqrt(samples) (2.2 % of 64 x 1024 samples, 4.5 % of 64 x 256), i.e. ~0.7 sqrt(spp) rows; capacity
     // is three times that.  Without room for the blocks the launch runs without stealing (same image).
@@ -2019,7 +1965,7 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
         return e && e[0] == '0';
     }();
     const unsigned n_whole = P.split > 1 ? P.split_first : grid;
-    if (!steal_off && variant == kVariantFastLds && view.plane == nullptr && n >= 1 && n < 256 /* packed records: PACK8 */ &&
+    if (!steal_off && variant == kVariantFastLds && view.plane == nullptr && n >= 1 && n < 256 /* packed records: kPack8 */ &&
         P.max_bounces >= 0 && P.max_bounces <= 8 && pass_len >= 16 && P.sample_end < 65536u && st->samples < 65536 &&
         opt->variant != kVariantFastLds /* explicit variant 2 stays the plain kernel: the A/B twin */ &&
         !(tol && std::getenv("RTM_DEBUG_TOL_NOSTEAL") != nullptr) /* test knob: the tolerance row's stealing-free path */ &&
@@ -2034,7 +1980,7 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
         plan.bytes[kScratchSteal] = (size_t)n_whole * steal_tile_bytes(rows);
         plan.optional[kScratchSteal] = !tol;
     } else if (tol && P.max_bounces >= 0 && P.max_bounces <= 8) {
-        // the depth-capped tolerance row has the STEAL instantiation only: frames the stealing declines (fewer than 16 samples
+        // the depth-capped tolerance row has the kSteal instantiation only: frames the stealing declines (fewer than 16 samples
         // per pixel) run it with no row to steal into — every lane traces its own samples, the tile's block carries the
         // accumulators to steal_finalize_kernel.  (Any other depth: the any-depth kernel, which has no stealing.)
         plan.bytes[kScratchSteal] = (size_t)(n_whole ? n_whole : 1) * steal_tile_bytes(0);
@@ -2048,7 +1994,7 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     }
     // deep-path record pool.  Kernels with an LDS record stack take a slot only for the
     // rare path beyond 64/32 levels (65536 slots x 960 records: 60 MiB u8 / 240 MiB u32); the packed-record
-    // kernels (PACKL) keep levels >= 16 there, which nearly every pixel needs once: one slot per lane.
+    // kernels (kPackL) keep levels >= 16 there, which nearly every pixel needs once: one slot per lane.
     plan.packl = n < 256 && !(P.max_bounces >= 0 && P.max_bounces <= 8) &&
                  (variant == kVariantFastLds || variant == kVariantGlobalDefer);
     if (needs_pool(P) && variant != kVariantWavefrontRejectF32 && variant != kVariantFp32) {

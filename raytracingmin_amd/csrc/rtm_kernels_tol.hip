@@ -13,9 +13,10 @@
 //     sample's value stays a function of its path's hit ids alone: the image differs from the exact kernel's only where
 //     a last-bit difference in a distance or a direction changes WHICH sphere a ray hits.
 // What is instantiated: the default kernels of scenes up to 24 spheres — with a depth cap of at most 8 the LDS tables, chunked
-// search, packed records, deferred fold, in-wave sample stealing and the sample split of a launch's last tiles; for any other
-// depth (the reference's own unlimited recursion) the same with records packed by position and the pooled stack, no
-// stealing — the class of every BASELINE Cornell configuration.  Never the default; bench.py reports it as a labelled row with its own
+// search, packed records, deferred fold and in-wave sample stealing (kTolCapped: kLdsTab | kPark | kPack8 | kDefer | kSteal);
+// for any other depth (the reference's own unlimited recursion) the same with records packed by position and the pooled
+// stack, no stealing (kTolAny: kPackL in place of kPack8 | kSteal); each with and without the sample split of a launch's
+// last tiles (kSplit) — the class of every BASELINE Cornell configuration.  Never the default; bench.py reports it as a labelled row with its own
 // roofline fraction and the count of pixels that differ from the exact frame (tests/test_tolerance_gpu.py).
 #define RTM_NS rtm_tol
 #define RTM_TOL 1
@@ -38,62 +39,53 @@ static bool compact_launch(const RenderParams& P) {
     return (P.scene.fold_flags & kSceneCompact) != 0u && cam <= kCompactExtent;
 }
 
-constexpr int kTolWavesPerSimd = 4;  // launch bound of the depth-capped kernel (profiles/r4/tol_wpe_ab.txt)
-template <int UNROLL, bool SPLIT>
-static void launch_one(const RenderParams& P_in, unsigned grid, size_t lds_pad, hipStream_t stream) {
-    RenderParams P = P_in;
-    size_t lds = lds_table_bytes(P.scene.n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) +
-                 kFoldQueueBytesS + 2 * 64 * sizeof(unsigned) + 64 * sizeof(unsigned long long) /* prim_mask */ + lds_pad;
-    // the near-unit Normalize table (rtm_device.h) where its 256 bytes do not cost a wave per CU
-    P.unit_tab = unit_table_fits(lds) ? 1u : 0u;
-    if (P.unit_tab) lds += (size_t)(kShadeConstCount - kTrigConstCount) * sizeof(double);
-    // <M, LDS_TAB, UNROLL, RecT, LDS_D, WPE, PARK, STAMP, PACK8, SPLIT, DEFER, PACKL, REUSE, PLANES, STEAL>
-    render_tiles_kernel<MathFast, true, UNROLL, uint8_t, 16, kTolWavesPerSimd, true, false, true, SPLIT, true, false, false, false, true>
-        <<<grid, 64, lds, stream>>>(P);
-}
-// Any depth (max_bounces < 0 — the reference's own semantics — or > 8): the deferred fold with records packed by position
-// and the pooled stack from level 16 (PACKL, rtm_render_kernel.h), no in-wave stealing; a whole tile stores its own pixels.
-template <int UNROLL, bool SPLIT>
-static void launch_one_any(const RenderParams& P_in, unsigned grid, size_t lds_pad, hipStream_t stream) {
-    RenderParams P = P_in;
-    size_t lds = lds_table_bytes(P.scene.n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) + kFoldQueueBytesLS + lds_pad;
-    P.unit_tab = unit_table_fits(lds) ? 1u : 0u;
-    if (P.unit_tab) lds += (size_t)(kShadeConstCount - kTrigConstCount) * sizeof(double);
-    // <M, LDS_TAB, UNROLL, RecT, LDS_D, WPE, PARK, STAMP, PACK8, SPLIT, DEFER, PACKL>
-    render_tiles_kernel<MathFast, true, UNROLL, uint8_t, 0, 4, true, false, false, SPLIT, true, true><<<grid, 64, lds, stream>>>(P);
-}
-template <bool SPLIT>
-static void launch_n_any(const RenderParams& P, unsigned grid, size_t lds_pad, hipStream_t stream) {
-    const bool table_fits = unit_table_fits(lds_table_bytes(P.scene.n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) +
-                                            kFoldQueueBytesLS + lds_pad);  // (launch_one_any's rule)
-    if (P.scene.n == 7 && P.scene.axis_pat == kAxisSigCornell7 && P.mode == RTM_MODE_REPAIRED && table_fits && compact_launch(P)) {  // (the shipped Cornell box: rtm_path.h, sphere_disc)
-        launch_one_any<axis_unroll(7, kAxisSigCornell7), SPLIT>(P, grid, lds_pad, stream);
-        return;
+// The row's two shapes: a depth cap of at most 8 (kTolCapped: packed records, in-wave stealing) and any other depth (kTolAny:
+// records packed by position and the pooled stack from level 16, rtm_render_kernel.h; no stealing, a whole tile stores its
+// own pixels); both with the LDS tables and the deferred fold, and kSplit where the launch splits its last tiles
+constexpr unsigned kTolCapped = kLdsTab | kPark | kPack8 | kDefer | kSteal;
+constexpr unsigned kTolAny = kLdsTab | kPark | kDefer | kPackL;
+constexpr int kTolWavesPerSimd = 4;  // launch bound of both (the depth-capped kernel's: profiles/r4/tol_wpe_ab.txt)
+
+// The kernel of shape F for the scene: an axis signature (kTolAny: the shipped Cornell box only) where its roots may skip the
+// residual step and the launch holds the near-unit Normalize table (a compile-time fact for them), else with kTolCapped the
+// shipped scenes' exact sphere counts, else the generic kernel for n < 8 or any n
+template <unsigned F>
+static void launch_n(const RenderParams& P, unsigned grid, size_t lds_pad, hipStream_t stream) {
+    constexpr int LDS_D = (F & kPackL) != 0 ? 0 : 16;
+    unsigned unit_tab;
+    render_lds_bytes<F, uint8_t, LDS_D>(P.scene.n, lds_pad, &unit_tab);
+    const bool axis = P.mode == RTM_MODE_REPAIRED && unit_tab == 1u && compact_launch(P);  // rtm_path.h: sphere_disc
+#define RTM_AXIS_CASE(k, sig)                                                                                    \
+    if (P.scene.n == k && P.scene.axis_pat == sig && axis) {                                                     \
+        launch_tiles<MathFast, F, axis_unroll(k, sig), uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream); \
+        return;                                                                                                  \
     }
-    if (P.scene.n < 8) launch_one_any<-8, SPLIT>(P, grid, lds_pad, stream);
-    else launch_one_any<8, SPLIT>(P, grid, lds_pad, stream);
+    if constexpr ((F & kPackL) != 0) {
+        RTM_AXIS_CASE(7, kAxisSigCornell7)
+    } else {
+        RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
+        switch (P.scene.n) {
+            case 3: launch_tiles<MathFast, F, -103, uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream); return;
+            case 5: launch_tiles<MathFast, F, -105, uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream); return;
+            case 7: launch_tiles<MathFast, F, -107, uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream); return;
+            default: break;
+        }
+    }
+#undef RTM_AXIS_CASE
+    if (P.scene.n < 8) launch_tiles<MathFast, F, -8, uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream);
+    else launch_tiles<MathFast, F, 8, uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream);
 }
 
-template <bool SPLIT>
-static void launch_n(const RenderParams& P, unsigned grid, size_t lds_pad, hipStream_t stream) {
-    // (the axis-signature instantiations take the near-unit Normalize table's presence as a compile-time fact: launch_one's rule)
-    const bool table_fits = unit_table_fits(lds_table_bytes(P.scene.n) + (10 + kTrigConstCount) * sizeof(double) + 6 * 64 * sizeof(double) +
-                                            kFoldQueueBytesS + 2 * 64 * sizeof(unsigned) + 64 * sizeof(unsigned long long) + lds_pad);
-#define RTM_AXIS_CASE(k, sig)                                                                   \
-    if (P.scene.n == k && P.scene.axis_pat == sig && P.mode == RTM_MODE_REPAIRED && table_fits && compact_launch(P)) { /* rtm_path.h: sphere_disc */ \
-        launch_one<axis_unroll(k, sig), SPLIT>(P, grid, lds_pad, stream);                       \
-        return;                                                                                 \
+// A render of shape F: the sample split where the caller planned one, steal_finalize_kernel behind a stealing one
+template <unsigned F>
+static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hipStream_t stream) {
+    if (P.split > 1) {
+        launch_n<F | kSplit>(P, P.split_first + P.n_tiles * P.split, lds_pad, stream);
+        launch_split_finalize(P, stream);
+    } else {
+        launch_n<F>(P, grid, lds_pad, stream);
     }
-    RTM_AXIS_SIGNATURES(RTM_AXIS_CASE)
-#undef RTM_AXIS_CASE
-    switch (P.scene.n) {  // the shipped scenes' sizes run the instantiation for exactly their sphere count
-        case 3: launch_one<-103, SPLIT>(P, grid, lds_pad, stream); return;
-        case 5: launch_one<-105, SPLIT>(P, grid, lds_pad, stream); return;
-        case 7: launch_one<-107, SPLIT>(P, grid, lds_pad, stream); return;
-        default: break;
-    }
-    if (P.scene.n < 8) launch_one<-8, SPLIT>(P, grid, lds_pad, stream);
-    else launch_one<8, SPLIT>(P, grid, lds_pad, stream);
+    if constexpr ((F & kSteal) != 0) launch_steal_finalize(P, grid, stream);
 }
 
 // rtm_debug_math_probe ops 32..: this translation unit's arithmetic on caller data (tests/test_tolerance_gpu.py measures the
@@ -175,23 +167,8 @@ int launch_tol(const void* params, size_t params_bytes, unsigned grid, size_t ld
     else
         rtm_tol::prim_prepass_kernel<<<n_tiles_all, 64, 0, stream>>>(P, const_cast<unsigned long long*>(P.prim_masks),
                                                                  const_cast<double*>(P.prim_dirs));
-    if (any_depth) {  // (no stealing: every whole tile stores its pixels itself)
-        if (P.split > 1) {
-            rtm_tol::launch_n_any<true>(P, P.split_first + P.n_tiles * P.split, lds_pad, stream);
-            rtm_tol::split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
-        } else {
-            rtm_tol::launch_n_any<false>(P, grid, lds_pad, stream);
-        }
-    } else {
-        if (P.split > 1) {
-            rtm_tol::launch_n<true>(P, P.split_first + P.n_tiles * P.split, lds_pad, stream);
-            rtm_tol::split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
-        } else {
-            rtm_tol::launch_n<false>(P, grid, lds_pad, stream);
-        }
-        const unsigned n_whole = P.split > 1 ? P.split_first : grid;
-        if (n_whole) rtm_tol::steal_finalize_kernel<<<n_whole, 64, (size_t)P.steal_depth * 64 * sizeof(unsigned short), stream>>>(P);
-    }
+    if (any_depth) rtm_tol::launch_row<rtm_tol::kTolAny>(P, grid, lds_pad, stream);
+    else rtm_tol::launch_row<rtm_tol::kTolCapped>(P, grid, lds_pad, stream);
     if (hipGetLastError() != hipSuccess) {
         set_last_error("tolerance row: launch failed");
         return RTM_ERR_HIP;

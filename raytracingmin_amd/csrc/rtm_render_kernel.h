@@ -128,15 +128,16 @@ struct RecordStack {
     static constexpr int kCapacity = LDS_D + kPoolLevels;
 };
 
-// LDS copy of the scene tables: n geometry rows (4 doubles) + n+1 material rows (8 doubles, the last
-// one is the identity row) + n normal-length rows (3 doubles: |hit - centre| as Magnitude returns it, its refined
-// reciprocal, and the float r*r in the low word of the third)
+constexpr size_t kUnitTableBytes = (size_t)(kShadeConstCount - kTrigConstCount) * sizeof(double);  // rtm_device.h: the near-unit Normalize table
 // Does a launch whose workgroups (one wave each) take `lds` bytes keep its waves per CU with the near-unit Normalize table's
 // 256 bytes on top?  160 KB of LDS per CU, at most 16 waves (4 per SIMD at the kernels' 128 registers).
 inline bool unit_table_fits(size_t lds) {
     auto waves = [](size_t b) { const size_t w = b ? (size_t)163840 / b : 16; return w > 16 ? (size_t)16 : w; };
-    return waves(lds) == waves(lds + (size_t)(kShadeConstCount - kTrigConstCount) * sizeof(double));
+    return waves(lds) == waves(lds + kUnitTableBytes);
 }
+// LDS copy of the scene tables: n geometry rows (4 doubles) + n+1 material rows (8 doubles, the last
+// one is the identity row) + n normal-length rows (3 doubles: |hit - centre| as Magnitude returns it, its refined
+// reciprocal, and the float r*r in the low word of the third)
 __host__ __device__ inline size_t lds_table_bytes(int n) { return ((size_t)n * 7 + ((size_t)n + 1) * 8) * sizeof(double); }
 
 // src/Renderer.cpp:227-232; sx, sy in 1..SS
@@ -231,26 +232,32 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, bool valid, i
 }
 
 // ------------------------------------------------------------------------------------------------
-// The render kernel.
+// Shape flags of the render kernel (its template parameter F)
+constexpr unsigned kLdsTab = 1u << 0, kPark = 1u << 1, kStamp = 1u << 2, kPack8 = 1u << 3, kSplit = 1u << 4;
+constexpr unsigned kDefer = 1u << 5, kPackL = 1u << 6, kReuse = 1u << 7, kPlanes = 1u << 8, kSteal = 1u << 9;
+
+// The render kernel, render_tiles_kernel<M, F, UNROLL, RecT, LDS_D, WPE>.
 //   M       Math policy (rtm_path.h)
-//   LDS_TAB scene tables (centres + materials) copied to LDS for the per-lane look-ups
+//   F       the shape: an OR of the flags below (the kernel body reads them as the bools LDS_TAB, PARK, ...)
 //   UNROLL  spheres whose geometry is fetched together (wave-uniform loads)
 //   RecT    hit-record type (u8 when n_spheres <= 256), LDS_D: record depth staged in LDS per lane
-// Dynamic LDS layout (16-byte aligned base): [geom n*4 doubles][mat (n+1)*8][norm n*2] (LDS_TAB), [camera 10]
-// [sincos constants 16][accumulator + primary direction 6 x 64] (PARK), then the record stack
-// [LDS_D][64] or the fold queue (DEFER).
-//   PARK    the pixel accumulator and the cached primary direction live in LDS ([component][lane]),
+//   WPE     launch bound: waves per SIMD
+// Dynamic LDS layout (16-byte aligned base): [geom n*4 doubles][mat (n+1)*8][norm n*2] (kLdsTab), [camera 10]
+// [sincos constants 16][accumulator + primary direction 6 x 64] (kPark), then the record stack
+// [LDS_D][64] or the fold queue (kDefer).  render_lds_bytes, just above the kernel, is a launch's size of it.
+//   kLdsTab scene tables (centres + materials) copied to LDS for the per-lane look-ups
+//   kPark   the pixel accumulator and the cached primary direction live in LDS ([component][lane]),
 //           not in VGPRs: they are touched once per sample, and the 12 registers they would pin
 //           are what the unrolled sphere chunk needs to stay under 128 VGPRs without scratch spills
-//   STAMP   diagnostic build: s_memtime around the three segments of an iteration (never timed itself)
-//   PACK8   max_bounces <= 8 and n < 256: hit records packed in a 64-bit register, no LDS stack
-//   SPLIT   P.split waves per tile, each tracing a contiguous range of the pixel's samples.  Wave 0
+//   kStamp  diagnostic build: s_memtime around the three segments of an iteration (never timed itself)
+//   kPack8  max_bounces <= 8 and n < 256: hit records packed in a 64-bit register, no LDS stack
+//   kSplit  P.split waves per tile, each tracing a contiguous range of the pixel's samples.  Wave 0
 //           accumulates as usual and leaves its accumulator in P.partial; the others store every
 //           sample's term (src/Renderer.cpp:240-242, after the clamp) to P.contrib, and
 //           split_finalize_kernel adds them IN THE REFERENCE'S ORDER, so the image does not change by
 //           a bit.  Used when a strip has too few tiles to keep every SIMD busy to the end (few rows
 //           per GPU, small images): the launch's tail is then the spread of per-tile cost.
-//   DEFER   (with PACK8 + PARK) path ends are queued and folded 64 at a time.  The fold, the /SS/SS/S and
+//   kDefer  (with kPack8 + kPark) path ends are queued and folded 64 at a time.  The fold, the /SS/SS/S and
 //           the clamp of a finished path are a pure function of its hit ids, but only ~22 % of the
 //           lanes finish a path in a given iteration, so doing that work on the spot runs ~100
 //           instructions with a fifth of the lanes (13 % of the frame, measured).  Instead the ending
@@ -259,12 +266,12 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, bool valid, i
 //           the term in LDS, and every owner then adds its terms to its accumulator in the order its
 //           paths ended (a per-lane FIFO of ring positions keeps that order) — the accumulation order
 //           of src/Renderer.cpp:241-242 is untouched.
-//   PACKL   (with DEFER) packed records for paths of ANY depth (max_bounces < 0 or > 8): level d in byte
+//   kPackL  (with kDefer) packed records for paths of ANY depth (max_bounces < 0 or > 8): level d in byte
 //           d & 7 of word d >> 3 — word 0 in a register, word 1 in LDS per lane, levels from 16 up (about
 //           kd^16 of the paths) in the pooled global stack.  A queue entry carries both words and the pool
 //           slot; a lane that queues a path deeper than 16 forces a pass, so its slot is free again
 //           before its next path can reach level 16.
-//   REUSE   (with DEFER + PACK8; variant 15, a SEPARATELY LABELLED row, never the default) the S samples of a
+//   kReuse  (with kDefer + kPack8; variant 15, a SEPARATELY LABELLED row, never the default) the S samples of a
 //           sub-pixel share one primary ray (no jitter, src/Renderer.cpp:224-232), so its nearest hit is computed
 //           once per sub-pixel and reused: a lane whose path ended restarts at "primary hit known" in the SAME
 //           trip and joins the shading block with the lanes that bounced.  Every trip is then one nearest-hit
@@ -278,12 +285,11 @@ constexpr size_t kFoldQueueBytes = kFoldRing * 16 + 3 * 64 * 8 + 64 * 8 + 64 * 4
 // the any-depth kernels keep the near-unit Normalize table at 16 waves per CU
 constexpr size_t kFoldQueueBytesS = kFoldRing * 16 + 64 * 4 + 64 * 4;
 constexpr size_t kFoldQueueBytesLS = kFoldQueueBytesS + kFoldRing * 8 + 64 * 8;
-// (SPLIT: a small wave's ring entries carry a 2-byte tag (owner lane, sample).  The tags live in the per-lane FIFO array,
+// (kSplit: a small wave's ring entries carry a 2-byte tag (owner lane, sample).  The tags live in the per-lane FIFO array,
 // which a small wave does not use: 256 of its 512 bytes.  A separate array put the any-depth kernel at 10 328 bytes of LDS per
 // wave — 15 instead of 16 waves per CU, 5 % on every unlimited-depth frame, profiles/r3/ab_r2_vs_r3.txt.)
-constexpr size_t kFoldTagBytes = 0;
 
-//   STEAL   (with DEFER + PACK8) in-wave sample stealing for WHOLE tiles.  All 64 lanes of a wave trace the same number of
+//   kSteal  (with kDefer + kPack8) in-wave sample stealing for WHOLE tiles.  All 64 lanes of a wave trace the same number of
 //           samples but not the same number of casts, so a wave runs until its slowest lane is done: 4.4 % of the lane-trips
 //           of the headline frame are spent by lanes that have finished (8.9 % at 256 spp, 15 % at 64 spp:
 //           profiles/r3/ragged_end.txt).  When the first lane runs out of samples the wave leaves the main loop for a
@@ -292,12 +298,32 @@ constexpr size_t kFoldTagBytes = 0;
 //           leaves its clamped term, tagged (pixel, sample), in the tile's row buffer in HBM; a pixel's own lane
 //           accumulates samples [0, end) in order as before, and steal_finalize_kernel adds the stolen terms [end, total)
 //           in order on top.  Only the ORDER of the additions is observable, and it is the reference's.
-//   PLANES  (with LDS_TAB) the scene holds png::PlaneObject entries: SceneLdsObjects / object_chunk / MathSpecZ
+//   kPlanes (with kLdsTab) the scene holds png::PlaneObject entries: SceneLdsObjects / object_chunk / MathSpecZ
 //           (rtm_path.h) — a plane's test in its index slot of the chunk, its normal from the LDS table
-template <class M, bool LDS_TAB, int UNROLL, typename RecT, int LDS_D, int WPE = 1, bool PARK = false,
-          bool STAMP = false, bool PACK8 = false, bool SPLIT = false, bool DEFER = false, bool PACKL = false,
-          bool REUSE = false, bool PLANES = false, bool STEAL = false>
+
+// The dynamic LDS bytes of a render_tiles_kernel launch of shape F for a scene of n objects, `pad` bytes on top (the
+// RTM_DEBUG_LDS_PAD knob): the carve-up at the top of the kernel, term by term.  *unit_tab: the launch holds the near-unit
+// Normalize table too (where its bytes do not cost a wave per CU: unit_table_fits) — RenderParams::unit_tab.
+template <unsigned F, typename RecT, int LDS_D>
+inline size_t render_lds_bytes(int n, size_t pad, unsigned* unit_tab) {
+    size_t b = (F & kLdsTab) ? lds_table_bytes(n) : 0;  // scene tables
+    b += (10 + kTrigConstCount) * sizeof(double);        // camera, sincos constants
+    if (F & kPark) b += 6 * 64 * sizeof(double);         // accumulator + primary direction
+    if (!(F & (kPack8 | kPackL))) b += (size_t)LDS_D * 64 * sizeof(RecT);  // record stack: unpacked records only
+    if (F & kDefer) b += (F & kReuse) ? kFoldQueueBytes : (F & kPackL) ? kFoldQueueBytesLS : kFoldQueueBytesS;
+    // every pixel's next own sample and own-sample end; the tolerance unit's primary-ray masks
+    if (F & kSteal) b += 2 * 64 * sizeof(unsigned) + (RTM_TOL ? 64 * sizeof(unsigned long long) : 0);
+    b += pad;
+    *unit_tab = unit_table_fits(b) ? 1u : 0u;
+    return b + (*unit_tab ? kUnitTableBytes : 0);
+}
+
+template <class M, unsigned F, int UNROLL, typename RecT, int LDS_D, int WPE>
 __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParams P) {
+    constexpr bool LDS_TAB = (F & kLdsTab) != 0, PARK = (F & kPark) != 0, STAMP = (F & kStamp) != 0;
+    constexpr bool PACK8 = (F & kPack8) != 0, SPLIT = (F & kSplit) != 0, DEFER = (F & kDefer) != 0;
+    constexpr bool PACKL = (F & kPackL) != 0, REUSE = (F & kReuse) != 0, PLANES = (F & kPlanes) != 0;
+    constexpr bool STEAL = (F & kSteal) != 0;
     static_assert(!STEAL || (DEFER && PACK8 && !REUSE && !PACKL), "sample stealing rides on the deferred fold with packed records");
     static_assert(!PLANES || (LDS_TAB && !REUSE), "plane scenes ride on the LDS tables");
     static_assert(!SPLIT || DEFER, "the sample split's small waves store their terms from the fold queue");
@@ -1306,6 +1332,23 @@ __global__ __launch_bounds__(64) void steal_finalize_kernel(const RenderParams P
         }
     }
     store_pixel(P, valid, px, py, acc);
+}
+
+// Host side: every launch of the three kernels above goes through these.
+// render_tiles_kernel<M, F, UNROLL, RecT, LDS_D, WPE> over `grid` tiles with render_lds_bytes' LDS and RenderParams::unit_tab
+template <class M, unsigned F, int UNROLL, typename RecT, int LDS_D, int WPE>
+void launch_tiles(RenderParams P, unsigned grid, size_t pad, hipStream_t stream) {
+    const size_t lds = render_lds_bytes<F, RecT, LDS_D>(P.scene.n, pad, &P.unit_tab);
+    render_tiles_kernel<M, F, UNROLL, RecT, LDS_D, WPE><<<grid, 64, lds, stream>>>(P);
+}
+// after a split launch (kSplit): one block per split tile
+inline void launch_split_finalize(const RenderParams& P, hipStream_t stream) {
+    split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
+}
+// after a stealing launch (kSteal) of `grid` blocks: one block per whole tile
+inline void launch_steal_finalize(const RenderParams& P, unsigned grid, hipStream_t stream) {
+    const unsigned n_whole = P.split > 1 ? P.split_first : grid;
+    if (n_whole) steal_finalize_kernel<<<n_whole, 64, (size_t)P.steal_depth * 64 * sizeof(unsigned short), stream>>>(P);
 }
 
 // The pre-pass of the deferred-fold kernels, one wave per tile of the launch, lane = pixel: every sub-pixel's primary direction
