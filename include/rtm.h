@@ -304,6 +304,52 @@ typedef struct rtm_aov_buffers {
 int rtm_render_aov(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
                    const rtm_aov_buffers* out_dev, void* stream);
 
+/* ---- denoiser: an edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) guided by the AOVs above, with the albedo
+ * demodulated (SVGF-style) and no temporal part ----
+ * Inputs: a frame of width x height pixels; color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32); the
+ * guide planes in the rtm_aov_buffers layout of the whole frame (rows = height, no bands).  guide_dev itself and any of its
+ * four pointers may be null: a null plane switches its term off.  Depths are positive or +inf, as rtm_render_aov writes
+ * them.  Arithmetic in float:
+ *   1 demodulate  a_p,k = albedo_p,k > 1e-3f ? albedo_p,k : 1.0f (1.0f without an albedo plane); e0_p = c_p / a_p per
+ *                 channel (the Cornell light has albedo 0: it is filtered as its own emission)
+ *   2 iterate     for i = 0 .. K-1, step s = 2^i:  e(i+1)_p = sum_q w_i(p,q) e(i)_q / sum_q w_i(p,q), over the taps
+ *                 q = (x + s dx, y + s dy), dx, dy in -2..2; taps outside the frame are skipped (not clamped); the sums run
+ *                 dy outer, dx inner.  w_i(p,q) = h[dx] h[dy] g(p,q) w_c, h = {1/16, 1/4, 3/8, 1/4, 1/16}.
+ *                 g(p,q), the geometry weight:
+ *                   q == p: 1 (so sum w >= h[2]^2 = (3/8)^2 > 0: never a division by zero)
+ *                   else, object given and obj_p != obj_q: 0
+ *                   else, depth given: both depths +inf (two misses): 1, the terms below skipped; exactly one +inf: 0;
+ *                         otherwise w_z = sigma_depth > 0 ? exp(-|z_p - z_q| / (sigma_depth s max(z_p, z_q))) : 1
+ *                   w_n = (normal given && sigma_normal > 0) ? max(0, n_p . n_q)^sigma_normal : 1;  g = w_z w_n
+ *                 w_c = sigma_color > 0 ? exp(-|e(i)_p - e(i)_q|^2 4^i / sigma_color^2) : 1 (Dammertz's sigma halved
+ *                 at each level)
+ *   3 remodulate  out_p = e(K)_p a_p
+ *   K = 0 copies color to out_f32 bit for bit.  out_u8 (if non-null) is rtm_quantise of (double)out_f32, bit for bit.
+ * exp and pow may be the device's fast forms: against a float64 evaluation of the steps above every output component is
+ * within 1e-4 max(1, |ref|).  No atomics: the same inputs give the same bits on every call, on any stream.
+ * Defaults: RTM_DENOISE_DEFAULTS below (what Renderer.Render(denoise=True) and rtm_cli --denoise use, chosen on the Cornell
+ * box): iterations 4, sigma_color 16, sigma_normal 64, sigma_depth 0.05. */
+typedef struct rtm_denoise_params {
+    int32_t iterations; /* K, 0..10 */
+    float sigma_color;  /* >= 0, finite; 0 switches the term off */
+    float sigma_normal; /* >= 0, finite: an exponent; 0 switches the term off */
+    float sigma_depth;  /* >= 0, finite: relative depth; 0 switches w_z off (the +inf rules stay) */
+} rtm_denoise_params;
+#define RTM_DENOISE_DEFAULTS {4, 16.0f, 64.0f, 0.05f} /* an initializer of rtm_denoise_params */
+/* Bytes of the work buffer rtm_denoise needs for a frame: 48 per pixel (two ping-pong planes and the packed guides, one
+ * 16-byte record per pixel each); 0 for a non-positive size. */
+size_t rtm_denoise_work_bytes(int32_t width, int32_t height);
+/* Filters `color_dev` into out_f32_dev and / or out_u8_dev (DEVICE, height x width x 3; either may be null, not both).
+ * The caller owns every buffer; work_dev (DEVICE, 16-byte aligned, rtm_denoise_work_bytes bytes) holds the intermediate
+ * planes, so the call allocates nothing and only ENQUEUES its launches (K + 1, or one for K = 0) on `stream` of `device`.
+ * It keeps no per-(device, stream) state and needs no serialisation: calls on different streams with different work
+ * buffers run side by side.  Null params, color_dev or work_dev, both outputs null, a non-positive size, iterations outside
+ * 0..10, a negative, NaN or infinite sigma, color_dev equal to out_f32_dev or to work_dev, a misaligned work_dev, a negative
+ * device: RTM_ERR_INVALID_ARGUMENT, before any device call.  Added after RTM_ABI_VERSION 5 without changing it: callers
+ * look the symbols up. */
+int rtm_denoise(const rtm_denoise_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);

@@ -69,6 +69,10 @@ class rtm_aov_buffers(C.Structure):  # DEVICE pointers, any may be null (include
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("object", C.c_void_p)]
 
 
+class rtm_denoise_params(C.Structure):  # include/rtm.h: rtm_denoise
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 # every symbol include/rtm.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -92,6 +96,9 @@ SIGNATURES = {
     "rtm_render_scene_samples": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
     "rtm_render_aov": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), _P(rtm_aov_buffers), C.c_void_p]),
+    "rtm_denoise_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtm_denoise": (C.c_int, [_P(rtm_denoise_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),

@@ -82,6 +82,11 @@ int rtm_render_aov(const rtm_settings* settings, const rtm_scene* scene, const r
                    const rtm_aov_buffers* out_dev, void* stream) {
     RTM_GUARD(rtm::render_aov(settings, scene, options, out_dev, stream))
 }
+size_t rtm_denoise_work_bytes(int32_t width, int32_t height) { return rtm::denoise_work_bytes(width, height); }
+int rtm_denoise(const rtm_denoise_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
+    RTM_GUARD(rtm::denoise(params, width, height, device, color_dev, guide_dev, work_dev, out_f32_dev, out_u8_dev, stream))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {

@@ -35,6 +35,10 @@ int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const r
                          uint32_t sample_end, double* accum, float* out32, uint8_t* out8, void* stream, rtm_stats* stats);
 int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const rtm_aov_buffers* out,
                void* stream);
+// denoiser (rtm_denoise.hip)
+size_t denoise_work_bytes(int32_t width, int32_t height);
+int denoise(const rtm_denoise_params* params, int32_t width, int32_t height, int device, const float* color,
+            const rtm_aov_buffers* guide, void* work, float* out32, uint8_t* out8, void* stream);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);

@@ -7,6 +7,7 @@
 //           [--dump-f32 FILE]                    (the gathered float3 buffer, raw little-endian floats)
 //           [--passes N]                         (progressive: the frame's samples in N passes on one GPU, same image)
 //           [--aov]                              (first-hit feature buffers next to the image: STEM_depth/_normal/_albedo.pfm, .bmp)
+//           [--denoise]                          (the à-trous denoiser next to the image: STEM_denoised.bmp, .jpg)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -43,7 +44,9 @@ static void usage() {
         "--passes N : render the frame's samples in N near-equal passes on one GPU (rtm_render_scene_samples), printing\n"
         "             each pass's sample range and time; the image is the one-pass image bit for bit\n"
         "--aov : also write the first-hit feature buffers on one GPU (rtm_render_aov): STEM_depth.pfm, STEM_normal.pfm,\n"
-        "        STEM_albedo.pfm and the quantised STEM_normal.bmp (0.5 n + 0.5), STEM_albedo.bmp\n");
+        "        STEM_albedo.pfm and the quantised STEM_normal.bmp (0.5 n + 0.5), STEM_albedo.bmp\n"
+        "--denoise : also write the frame denoised on one GPU (rtm_denoise at its default parameters, guided by the\n"
+        "            frame's first-hit feature buffers): STEM_denoised.bmp and STEM_denoised.jpg\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -55,7 +58,7 @@ int main(int argc, char* argv[]) {
     std::string json_file = "settingData.json", stem = "result";
     int width = 0, height = 0, samples = 0, super_samples = 0, spp = 0;
     int mode = RTM_MODE_REPAIRED, max_bounces = -1, device = 0, gpus = 1, virtual_strips = 0, host_trig = 1, force_rccl = 0;
-    int passes = 0, aov = 0;
+    int passes = 0, aov = 0, denoise = 0;
     std::string dump_f32;
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
@@ -88,6 +91,7 @@ int main(int argc, char* argv[]) {
         else if (c == "--device-trig") host_trig = 0;
         else if (c == "--force-rccl") force_rccl = 1;
         else if (c == "--aov") aov = 1;
+        else if (c == "--denoise") denoise = 1;
         else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
         else if (c == "--seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 0);
         else if (c == "--out" && i + 1 < argc) stem = argv[++i];
@@ -107,6 +111,10 @@ int main(int argc, char* argv[]) {
     }
     if (aov && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
         std::fprintf(stderr, "--aov renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
+        return 2;
+    }
+    if (denoise && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--denoise runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
         return 2;
     }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
@@ -147,7 +155,7 @@ int main(int argc, char* argv[]) {
 
     const size_t vals = (size_t)st.width * st.height * 3;
     std::vector<uint8_t> rgb8(vals);
-    std::vector<float> rgb32(dump_f32.empty() ? 0 : vals);
+    std::vector<float> rgb32(dump_f32.empty() && !denoise ? 0 : vals);
     rtm_stats stats;
     if (passes > 0) {
         std::string err;
@@ -203,6 +211,15 @@ int main(int argc, char* argv[]) {
         }
         std::printf("aov: %s_depth.pfm, %s_normal.pfm, %s_albedo.pfm, %s_normal.bmp, %s_albedo.bmp\n", stem.c_str(), stem.c_str(),
                     stem.c_str(), stem.c_str(), stem.c_str());
+    }
+    if (denoise) {
+        std::string err;
+        rc = rtm_node_write_denoised(&st, spheres.data(), n, &opt, rgb32.data(), stem, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "denoise failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        std::printf("denoise: %s_denoised.bmp, %s_denoised.jpg\n", stem.c_str(), stem.c_str());
     }
     return 0;
 }

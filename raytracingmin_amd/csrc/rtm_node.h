@@ -21,3 +21,8 @@ int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, si
 // 0.5 n + 0.5) and <stem>_albedo.bmp (the quantised albedo).
 int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
                        const std::string& stem, std::string& err);
+// The frame's f32 (HOST, height x width x 3) denoised on options->device at the default parameters (rtm_denoise guided by
+// the frame's rtm_render_aov planes, rtm_cli --denoise) and written next to the image: <stem>_denoised.jpg (quality 60)
+// and <stem>_denoised.bmp.
+int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
+                            const float* f32_host, const std::string& stem, std::string& err);

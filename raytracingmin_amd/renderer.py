@@ -258,10 +258,12 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1, aov=False):
+    def Render(self, fileName, passes=1, aov=False, denoise=False):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
-        writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp)."""
+        writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
+        denoise=True also writes <fileName>_denoised.jpg (q=60) and _denoised.bmp: the frame's f32 filtered by denoise() at
+        the default parameters, guided by its AOVs (write_denoised); the plain files and self.image do not change."""
         if passes > 1:
             last = None
             for _, out, st in self.progressive(passes=passes, want=("u8",)):
@@ -280,7 +282,85 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write {fileName}.jpg/.bmp")
         if aov:
             self.write_aov(fileName)
+        if denoise:
+            self.write_denoised(fileName)
         return rgb8
+
+    def write_denoised(self, fileName):
+        """<fileName>_denoised.jpg (q=60) and <fileName>_denoised.bmp: self.image (the frame just rendered) rounded to float
+        like out_f32, filtered by denoise() at the default parameters with the frame's four AOVs as guides, quantised on
+        the device — what rtm_cli --denoise writes.  Returns the (H, W, 3) uint8 pixels."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        guides = self.render_aov()
+        rgb8 = np.ascontiguousarray(denoise(color, guides, want=("u8",))["u8"].cpu().numpy())
+        L = _lib.lib()
+        H, W = self.data.height, self.data.width
+        ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_denoised.jpg"), W, H, 3, rgb8.ctypes.data, 60)
+        ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_denoised.bmp"), W, H, 3, rgb8.ctypes.data)
+        if not (ok_j and ok_b):
+            raise _lib.RtmError(-3, f"could not write {fileName}_denoised.jpg/.bmp")
+        return rgb8
+
+
+# include/rtm.h: RTM_DENOISE_DEFAULTS
+DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 16.0, "sigma_normal": 64.0, "sigma_depth": 0.05}
+
+
+def denoise(color, aov=None, iterations=DENOISE_DEFAULTS["iterations"], sigma_color=DENOISE_DEFAULTS["sigma_color"],
+            sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_DEFAULTS["sigma_depth"], want=("f32",),
+            stream=None):
+    """The à-trous denoiser (include/rtm.h: rtm_denoise) on the device.  `color` is an (H, W, 3) float32 torch CUDA tensor;
+    `aov` a dict like Renderer.render_aov returns ("depth" (H, W) float32, "normal" / "albedo" (H, W, 3) float32, "object"
+    (H, W) int32), missing planes switch their terms off.  Returns {"f32": (H, W, 3) float32, "u8": (H, W, 3) uint8} for
+    the names in `want`.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current
+    stream) with a work buffer allocated here; nothing waits for it."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("denoise needs a HIP device; there is no CPU fallback")
+    unknown = set(want) - {"f32", "u8"}
+    if unknown or not want:
+        raise ValueError(f"want names outputs among ('f32', 'u8'), got {tuple(want)}")
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
+            and color.shape[2] == 3 and color.is_contiguous()):
+        raise ValueError("color must be a contiguous (H, W, 3) float32 CUDA tensor")
+    H, W = int(color.shape[0]), int(color.shape[1])
+    dev = color.device
+    aov = {} if aov is None else aov
+    layout = {"depth": ((H, W), torch.float32), "normal": ((H, W, 3), torch.float32),
+              "albedo": ((H, W, 3), torch.float32), "object": ((H, W), torch.int32)}
+    unknown = set(aov) - set(layout)
+    if unknown:
+        raise ValueError(f"unknown AOV plane(s) {sorted(unknown)}; the planes are {tuple(layout)}")
+    guides = _lib.rtm_aov_buffers()
+    for k, v in aov.items():
+        shape, dtype = layout[k]
+        if v is None:
+            continue
+        if not (isinstance(v, torch.Tensor) and v.device == dev and v.dtype == dtype and tuple(v.shape) == shape
+                and v.is_contiguous()):
+            raise ValueError(f"aov[{k!r}] must be a contiguous {shape} {dtype} tensor on {dev}")
+        setattr(guides, k, v.data_ptr())
+    if stream is None:
+        s = torch.cuda.current_stream(dev)
+    elif isinstance(stream, torch.cuda.Stream):
+        s = stream
+    else:
+        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    L = _lib.lib()
+    prm = _lib.rtm_denoise_params(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth))
+    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
+        work = torch.empty(max(1, L.rtm_denoise_work_bytes(W, H)), dtype=torch.uint8, device=dev)
+        out = {}
+        if "f32" in want:
+            out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+        if "u8" in want:
+            out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    _lib.check(L.rtm_denoise(C.byref(prm), W, H, dev.index, color.data_ptr(), C.byref(guides), work.data_ptr(),
+                             ptr("f32"), ptr("u8"), C.c_void_p(s.cuda_stream)), "rtm_denoise")
+    return out
 
 
 def plan_passes(n_samples, passes=None, samples_per_pass=None):
