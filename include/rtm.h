@@ -269,6 +269,54 @@ int rtm_render_scene(const rtm_settings* settings, const rtm_scene* scene, const
 int rtm_render_scene_samples(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
                              uint32_t sample_begin, uint32_t sample_end, double* accum_f64_dev, float* out_f32_dev,
                              uint8_t* out_u8_dev, void* stream, rtm_stats* stats);
+/* rtm_render_scene_samples restricted to a DEVICE list of tiles.  A tile is an 8x8 block of the call's output rows:
+ * tiles_x = ceil(width / 8), tiles_y = ceil(output rows / 8); tile t covers columns 8 (t % tiles_x) .. +7 and the call's
+ * local row block t / tiles_x, whose rows map to image rows as for a render (row range, interleaved bands).
+ * Listed tiles get exactly the accumulator, f32 and u8 values of rtm_render_scene_samples over the same range (preview rule
+ * included); pixels of tiles that are not listed are neither read nor written in any of the three buffers.  List order
+ * changes no value.  An entry of tiles_x * tiles_y or more makes its blocks return before any load or store; duplicate entries
+ * give unspecified pixels of those tiles but stay in bounds.  n_tiles == 0: RTM_OK, nothing enqueued; a null list with
+ * n_tiles > 0: RTM_ERR_INVALID_ARGUMENT.  Range and accumulator errors are rtm_render_scene_samples'.  rtm_stats.samples
+ * counts the in-frame pixels of the listed tiles x (sample_end - sample_begin) (a call with stats reads the list back).
+ * Every variant that serves partial ranges serves lists (variant 0's choices, 1 and 18) except the wavefront pipeline:
+ * variant 12, and variant 0 where it resolves to 12 (512 spheres or more without a grid), returns RTM_ERR_UNSUPPORTED before
+ * writing anything, as do variants 7, 15 and 16.  rtm_scratch_bytes' figure for the whole frame bounds a call whose list has
+ * at most tiles_x * tiles_y entries.
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbol up. */
+int rtm_render_scene_tiles(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                           uint32_t sample_begin, uint32_t sample_end, const uint32_t* tiles_dev, uint32_t n_tiles,
+                           double* accum_f64_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats);
+/* ---- tile-adaptive sampling on top of rtm_render_scene_tiles ----
+ * N = SS*SS*S, m = min_samples.  Pass ends b_0 = min(m, N), b_i = min(2^i m, N).  Pass 0 traces [0, b_0) of every tile and
+ * snapshots the accumulator; pass i >= 1 traces [b_{i-1}, b_i) of the tiles still active, then each of them is checked:
+ *   sb = (double)N / b_i, sa = (double)N / b_{i-1};  I_c = acc_c * sb, J_c = snap_c * sa  (c = R, G, B)
+ *   d = (|I_R - J_R| + |I_G - J_G|) + |I_B - J_B|;   e_p = d / (1e-3 + sqrt((I_R + I_G) + I_B))
+ *   E = max of e_p over the tile's in-frame pixels (a NaN e_p makes E NaN)
+ * in double, without contraction, sqrt correctly rounded.  (I - J is half the difference of the means of samples [0, a) and
+ * [a, b): a relative noise estimate weighted towards dark pixels.)  The tile stays active iff b_i < N && !(E <= threshold):
+ * a negative threshold stops nothing, a NaN E keeps the tile.  An active tile copies acc -> snapshot; every checked tile
+ * records b_i.  The active tiles form the next list in ascending order (a deterministic scan, no atomics).
+ * Result, tile by tile, with k = tile_samples[t]: the accumulator is rtm_render_scene_samples' over [0, k) bit for bit, f32
+ * and u8 that pass's preview; tiles that ran to N hold rtm_render_scene's bytes.
+ * tile_samples_dev (nullable, DEVICE): tiles_y x tiles_x words.  work_dev (DEVICE, 256-byte aligned): at least
+ * rtm_adaptive_work_bytes = round256(24 x width x rows) (the snapshot) + 3 x round256(4 x tiles) (two lists, the flags) + 256
+ * (the counts); 0 for a call without rows.
+ * The call BLOCKS: after each checkpoint it copies the 4-byte active count to the host and waits for the stream.  It stops
+ * when no tile is active or b_i = N.  It allocates nothing beyond the per-stream render scratch.  With stats: the passes'
+ * counters summed, kernel_ms including the checkpoints, variant the resolved one.
+ * A null params, accumulator or work buffer, min_samples == 0, a NaN or infinite threshold or a misaligned work_dev:
+ * RTM_ERR_INVALID_ARGUMENT before any device call (a null scene too).  A variant that refuses tile lists (7, 15, 16, the
+ * wavefront pipeline 12 and variant 0 where it resolves to 12) returns RTM_ERR_UNSUPPORTED having written only work_dev: the
+ * accumulator, the views and tile_samples are untouched.  Rows and bands as for a render; one device (no adaptive multi-GPU).
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+typedef struct rtm_adaptive_params {
+    uint32_t min_samples; /* m >= 1; m >= N renders the frame in one pass */
+    float threshold;      /* finite; < 0: no tile stops (the full frame) */
+} rtm_adaptive_params;
+size_t rtm_adaptive_work_bytes(const rtm_settings* settings, const rtm_options* options);
+int rtm_render_adaptive(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                        const rtm_adaptive_params* params, double* accum_f64_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                        uint32_t* tile_samples_dev, void* work_dev, void* stream, rtm_stats* stats);
 /* ---- first-hit feature buffers (AOVs) of a frame: what a preview's denoiser, compositor or object picker needs ----
  * Primary rays have no jitter (src/Renderer.cpp:224-232), so every value below is a deterministic function of the scene
  * and the camera.  Sub-pixels are visited in the reference's loop order, sx = 1..SS outer, sy = 1..SS inner; for each:

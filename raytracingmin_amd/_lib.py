@@ -69,6 +69,10 @@ class rtm_aov_buffers(C.Structure):  # DEVICE pointers, any may be null (include
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("object", C.c_void_p)]
 
 
+class rtm_adaptive_params(C.Structure):  # include/rtm.h: rtm_render_adaptive
+    _fields_ = [("min_samples", C.c_uint32), ("threshold", C.c_float)]
+
+
 class rtm_denoise_params(C.Structure):  # include/rtm.h: rtm_denoise
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
@@ -95,6 +99,12 @@ SIGNATURES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
     "rtm_render_scene_samples": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), C.c_uint32, C.c_uint32,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
+    "rtm_render_scene_tiles": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), C.c_uint32, C.c_uint32,
+                                         C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         _P(rtm_stats)]),
+    "rtm_adaptive_work_bytes": (C.c_size_t, [_P(rtm_settings), _P(rtm_options)]),
+    "rtm_render_adaptive": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), _P(rtm_adaptive_params), C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
     "rtm_render_aov": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), _P(rtm_aov_buffers), C.c_void_p]),
     "rtm_denoise_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_denoise": (C.c_int, [_P(rtm_denoise_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),

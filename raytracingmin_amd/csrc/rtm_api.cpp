@@ -78,6 +78,21 @@ int rtm_render_scene_samples(const rtm_settings* settings, const rtm_scene* scen
     RTM_GUARD(rtm::render_scene_samples(settings, scene, options, sample_begin, sample_end, accum_f64_dev, out_f32_dev,
                                         out_u8_dev, stream, stats))
 }
+int rtm_render_scene_tiles(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                           uint32_t sample_begin, uint32_t sample_end, const uint32_t* tiles_dev, uint32_t n_tiles,
+                           double* accum_f64_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {
+    RTM_GUARD(rtm::render_scene_tiles(settings, scene, options, sample_begin, sample_end, tiles_dev, n_tiles, accum_f64_dev,
+                                      out_f32_dev, out_u8_dev, stream, stats))
+}
+size_t rtm_adaptive_work_bytes(const rtm_settings* settings, const rtm_options* options) {
+    return rtm::adaptive_work_bytes(settings, options);
+}
+int rtm_render_adaptive(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
+                        const rtm_adaptive_params* params, double* accum_f64_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                        uint32_t* tile_samples_dev, void* work_dev, void* stream, rtm_stats* stats) {
+    RTM_GUARD(rtm::render_adaptive(settings, scene, options, params, accum_f64_dev, out_f32_dev, out_u8_dev, tile_samples_dev,
+                                   work_dev, stream, stats))
+}
 int rtm_render_aov(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
                    const rtm_aov_buffers* out_dev, void* stream) {
     RTM_GUARD(rtm::render_aov(settings, scene, options, out_dev, stream))

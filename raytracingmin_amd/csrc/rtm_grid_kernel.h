@@ -51,6 +51,9 @@ template <typename RecT, int LDS_D, bool COUNT = false>
 __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(const RenderParams P, const unsigned tile_base) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int lane = threadIdx.x;
+    const unsigned local_tile = grid_tile_of_block(P, blockIdx.x);
+    const unsigned tile = frame_tile(P, tile_base + local_tile);  // (a tile-list render: a bad entry returns here)
+    if (tile == ~0u) return;
     double* cam = reinterpret_cast<double*>(lds_raw);  // 9 camera doubles + pad
     double* trig = cam + 10;                           // the shading constants (sincos, near-unit Normalize)
     const bool unit_tab = P.unit_tab != 0u;            // wave-uniform: the launcher found the LDS for the near-unit Normalize table
@@ -70,8 +73,6 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
 
     SceneGlobal sc;
     sc.v = P.scene;
-    const unsigned local_tile = grid_tile_of_block(P, blockIdx.x);
-    const unsigned tile = tile_base + local_tile;
     const int tile_x8 = (int)(tile % (unsigned)P.tiles_x) * 8, tile_y = (int)(tile / (unsigned)P.tiles_x);
     // units and term rows cover the pass's samples [sample_begin, sample_end), row r = sample sample_begin + r
     const unsigned pass = P.sample_end - P.sample_begin;
@@ -168,7 +169,8 @@ __global__ __launch_bounds__(64, kGridWavesPerSimd) void render_grid_kernel(cons
 // accumulator instead of 0 (never -0, so a term that is not stored still changes nothing).
 __global__ __launch_bounds__(64) void grid_finalize_kernel(const RenderParams P, const unsigned tile_base) {
     const int lane = threadIdx.x;
-    const unsigned tile = tile_base + blockIdx.x;
+    const unsigned tile = frame_tile(P, tile_base + blockIdx.x);
+    if (tile == ~0u) return;
     const int px = (int)(tile % (unsigned)P.tiles_x) * 8 + (lane & 7);
     const int py = band_row(P, (int)(tile / (unsigned)P.tiles_x), lane >> 3);
     const bool valid = px < P.W && py < P.row_end;

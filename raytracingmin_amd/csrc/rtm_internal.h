@@ -33,6 +33,14 @@ int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_optio
                  uint8_t* out8, void* stream, rtm_stats* stats);
 int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
                          uint32_t sample_end, double* accum, float* out32, uint8_t* out8, void* stream, rtm_stats* stats);
+int render_scene_tiles(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
+                       uint32_t sample_end, const uint32_t* tiles, uint32_t n_tiles, double* accum, float* out32, uint8_t* out8,
+                       void* stream, rtm_stats* stats);
+// tile-adaptive sampling (rtm_adaptive.hip)
+size_t adaptive_work_bytes(const rtm_settings* st, const rtm_options* opt);
+int render_adaptive(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const rtm_adaptive_params* prm,
+                    double* accum, float* out32, uint8_t* out8, uint32_t* tile_samples, void* work, void* stream,
+                    rtm_stats* stats);
 int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const rtm_aov_buffers* out,
                void* stream);
 // denoiser (rtm_denoise.hip)

@@ -1069,9 +1069,12 @@ int num_variants() { return (int)(sizeof(kVariantNames) / sizeof(kVariantNames[0
 const char* variant_name(int v) { return (v >= 0 && v < num_variants()) ? kVariantNames[v] : nullptr; }
 
 // The samples [begin, end) of every pixel a call traces (rtm_render_scene_samples); end = ~0u: the frame's N.  A pass that
-// starts past 0 continues the accumulator out64 holds.
+// starts past 0 continues the accumulator out64 holds.  tiles: a DEVICE list of n_tiles frame tiles the call renders
+// (rtm_render_scene_tiles); null: every tile of the call's rows.
 struct SamplePass {
     unsigned begin = 0u, end = ~0u;
+    const unsigned* tiles = nullptr;
+    unsigned n_tiles = 0u;
 };
 static void fill_render_params(RenderParams& P, const rtm_settings* st, const rtm_options* opt, const SamplePass& pass) {
     using namespace host;
@@ -1849,7 +1852,10 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     plan.rows = output_rows(opt);
     plan.count_tests = (opt->mode & RTM_MODE_COUNT_TESTS) != 0;
     const unsigned tiles_y = (unsigned)((plan.rows + 7) / 8);
-    const unsigned grid = (unsigned)P.tiles_x * tiles_y;
+    // a tile-list render launches its list's tiles: split, stealing, pre-pass, grid term rows and launches are planned for them
+    P.frame_tiles = (unsigned)P.tiles_x * tiles_y;
+    P.tile_map = pass.tiles;
+    const unsigned grid = pass.tiles ? pass.n_tiles : P.frame_tiles;
     plan.grid = grid;
     int variant = opt->variant;
     P.n_tiles = grid;
@@ -1890,11 +1896,21 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
                        std::to_string(P.total_samples) + ")");
         return RTM_ERR_UNSUPPORTED;
     }
+    if (pass.tiles && (variant == kVariantStamped || variant == kVariantPrimaryReuse || variant == kVariantFp32)) {
+        set_last_error(std::string("variant ") + std::to_string(variant) + " renders whole frames only: no tile lists");
+        return RTM_ERR_UNSUPPORTED;
+    }
     if (variant == kVariantAuto)
         variant = n <= (size_t)kAutoLdsTableSpheres ? kVariantFastLds :
                   view.grid != nullptr ? kVariantGrid :  // (grid_for: the scene has one and the camera is within its reach)
                   n < 256 ? kVariantGlobalDefer :
                   n < (size_t)kAutoWavefrontSpheres ? kVariantFastGlobal : kVariantWavefrontRejectF32;
+    if (pass.tiles && variant == kVariantWavefrontRejectF32) {
+        // the pipeline's path state is indexed by pixel of the call's rows: it renders whole rows only
+        set_last_error("variant 12 (wavefront pipeline, also variant 0's choice from 512 spheres without a grid) does not "
+                       "render tile lists");
+        return RTM_ERR_UNSUPPORTED;
+    }
     if (variant == kVariantGrid && view.grid == nullptr) {
         set_last_error("variant 17 (uniform grid) serves scenes of 64 gridded spheres or more held by an rtm_scene "
                        "(rtm_scene_create*, rtm_render_rows*) or made per call from a device array; this scene has no grid");
@@ -2228,7 +2244,19 @@ static int render_view(const rtm_settings* st, const SceneView& view, size_t n, 
     RTM_HIP_CHECK(hipStreamSynchronize(stream));
     float ms = 0.f;
     RTM_HIP_CHECK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    stats->samples = (uint64_t)rows * st->width * (P.sample_end - P.sample_begin);
+    if (P.tile_map) {  // the in-frame pixels of the listed tiles (the call has waited for the stream already)
+        std::vector<unsigned> h(grid);
+        RTM_HIP_CHECK(hipMemcpy(h.data(), P.tile_map, (size_t)grid * sizeof(unsigned), hipMemcpyDeviceToHost));
+        uint64_t px = 0;
+        for (unsigned t : h) {
+            if (t >= P.frame_tiles) continue;
+            const int x0 = (int)(t % (unsigned)P.tiles_x) * 8, y0 = (int)(t / (unsigned)P.tiles_x) * 8;
+            px += (uint64_t)std::min(8, st->width - x0) * (uint64_t)std::min(8, rows - y0);
+        }
+        stats->samples = px * (P.sample_end - P.sample_begin);
+    } else {
+        stats->samples = (uint64_t)rows * st->width * (P.sample_end - P.sample_begin);
+    }
     stats->casts = c[0];
     stats->bounces = c[1];
     stats->draws = c[2];
@@ -2313,8 +2341,11 @@ int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_optio
 }
 
 // The range and the accumulator are checked before anything else (the scene included), so that a caller can test them alone.
-int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
-                         uint32_t sample_end, double* accum, float* out32, uint8_t* out8, void* stream_v, rtm_stats* stats) {
+// list: rtm_render_scene_tiles' (tiles, n_tiles) — a null list with entries is an argument error, an empty one enqueues
+// nothing; !list: every tile of the call's rows.
+static int render_range(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
+                        uint32_t sample_end, bool list, const uint32_t* tiles, uint32_t n_tiles, double* accum, float* out32,
+                        uint8_t* out8, void* stream_v, rtm_stats* stats) {
     if (!accum) {
         set_last_error("accum_f64_dev: the pixel accumulator is null");
         return RTM_ERR_INVALID_ARGUMENT;
@@ -2335,11 +2366,27 @@ int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const r
                        "): sample_end > N = superSamples^2 x samples = " + std::to_string(total));
         return RTM_ERR_INVALID_ARGUMENT;
     }
-    if (sample_begin == sample_end) {  // nothing to trace: nothing is enqueued
+    if (list && tiles == nullptr && n_tiles != 0u) {
+        set_last_error("tiles_dev: the tile list is null and n_tiles = " + std::to_string(n_tiles));
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (sample_begin == sample_end || (list && n_tiles == 0u)) {  // nothing to trace: nothing is enqueued
         if (stats) std::memset(stats, 0, sizeof *stats);
         return RTM_OK;
     }
-    return render_scene_pass(st, scene, opt, SamplePass{sample_begin, sample_end}, accum, out32, out8, stream_v, stats);
+    return render_scene_pass(st, scene, opt, SamplePass{sample_begin, sample_end, list ? tiles : nullptr, n_tiles}, accum,
+                             out32, out8, stream_v, stats);
+}
+
+int render_scene_samples(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
+                         uint32_t sample_end, double* accum, float* out32, uint8_t* out8, void* stream_v, rtm_stats* stats) {
+    return render_range(st, scene, opt, sample_begin, sample_end, false, nullptr, 0u, accum, out32, out8, stream_v, stats);
+}
+
+int render_scene_tiles(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
+                       uint32_t sample_end, const uint32_t* tiles, uint32_t n_tiles, double* accum, float* out32, uint8_t* out8,
+                       void* stream_v, rtm_stats* stats) {
+    return render_range(st, scene, opt, sample_begin, sample_end, true, tiles, n_tiles, accum, out32, out8, stream_v, stats);
 }
 
 // rtm_render_aov: the first-hit feature buffers of the call's rows (rtm_aov_kernel.h).  Every argument is checked before

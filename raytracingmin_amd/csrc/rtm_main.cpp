@@ -5,6 +5,7 @@
 //           [--mode literal|repaired] [--max-bounces N] [--seed N] [--device N] [--out STEM] [--device-trig]
 //           [--gpus N] [--virtual-strips N] [--force-rccl]   (interleaved 8-row bands over N GPUs + one RCCL gather)
 //           [--dump-f32 FILE]                    (the gathered float3 buffer, raw little-endian floats)
+//           [--adaptive T [--adaptive-min M]]   (tile-adaptive sampling on one GPU, + STEM_spp.pfm)
 //           [--passes N]                         (progressive: the frame's samples in N passes on one GPU, same image)
 //           [--aov]                              (first-hit feature buffers next to the image: STEM_depth/_normal/_albedo.pfm, .bmp)
 //           [--denoise]                          (the à-trous denoiser next to the image: STEM_denoised.bmp, .jpg)
@@ -45,6 +46,8 @@ static void usage() {
         "             each pass's sample range and time; the image is the one-pass image bit for bit\n"
         "--aov : also write the first-hit feature buffers on one GPU (rtm_render_aov): STEM_depth.pfm, STEM_normal.pfm,\n"
         "        STEM_albedo.pfm and the quantised STEM_normal.bmp (0.5 n + 0.5), STEM_albedo.bmp\n"
+        "--adaptive T [--adaptive-min M] : tile-adaptive sampling on one GPU (rtm_render_adaptive, threshold T, first pass\n"
+        "             M samples, default 16); also writes STEM_spp.pfm, the samples each pixel traced\n"
         "--denoise : also write the frame denoised on one GPU (rtm_denoise at its default parameters, guided by the\n"
         "            frame's first-hit feature buffers): STEM_denoised.bmp and STEM_denoised.jpg\n");
 }
@@ -58,7 +61,8 @@ int main(int argc, char* argv[]) {
     std::string json_file = "settingData.json", stem = "result";
     int width = 0, height = 0, samples = 0, super_samples = 0, spp = 0;
     int mode = RTM_MODE_REPAIRED, max_bounces = -1, device = 0, gpus = 1, virtual_strips = 0, host_trig = 1, force_rccl = 0;
-    int passes = 0, aov = 0, denoise = 0;
+    int passes = 0, aov = 0, denoise = 0, adaptive = 0, adaptive_min = 16;
+    float adaptive_threshold = 0.f;
     std::string dump_f32;
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
@@ -87,6 +91,10 @@ int main(int argc, char* argv[]) {
         else if (c == "--gpus") next_int(gpus);
         else if (c == "--virtual-strips") next_int(virtual_strips);
         else if (c == "--passes") next_int(passes);
+        else if (c == "--adaptive" && i + 1 < argc) {
+            adaptive = 1;
+            adaptive_threshold = (float)std::strtod(argv[++i], nullptr);  // (double first, as Python's float() then C float)
+        } else if (c == "--adaptive-min") next_int(adaptive_min);
         else if (c == "--host-trig") host_trig = 1;
         else if (c == "--device-trig") host_trig = 0;
         else if (c == "--force-rccl") force_rccl = 1;
@@ -107,6 +115,11 @@ int main(int argc, char* argv[]) {
     }
     if (passes > 0 && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
         std::fprintf(stderr, "--passes renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
+        return 2;
+    }
+    if (adaptive && (passes > 0 || gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--adaptive renders on one GPU: it does not combine with --passes, --gpus > 1, --virtual-strips or "
+                             "--force-rccl\n");
         return 2;
     }
     if (aov && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
@@ -157,7 +170,19 @@ int main(int argc, char* argv[]) {
     std::vector<uint8_t> rgb8(vals);
     std::vector<float> rgb32(dump_f32.empty() && !denoise ? 0 : vals);
     rtm_stats stats;
-    if (passes > 0) {
+    std::vector<uint32_t> tile_samples;
+    if (adaptive) {
+        std::string err;
+        rtm_adaptive_params prm;
+        prm.min_samples = adaptive_min > 0 ? (uint32_t)adaptive_min : 0u;
+        prm.threshold = adaptive_threshold;
+        rc = rtm_node_render_adaptive(&st, spheres.data(), n, &opt, &prm, rgb32.empty() ? nullptr : rgb32.data(), rgb8.data(),
+                                      tile_samples, &stats, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "render failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+    } else if (passes > 0) {
         std::string err;
         rc = rtm_node_render_passes(&st, spheres.data(), n, &opt, passes, rgb32.empty() ? nullptr : rgb32.data(), rgb8.data(),
                                     &stats, err);
@@ -202,6 +227,13 @@ int main(int argc, char* argv[]) {
     const int ok_jpg = rtm_write_jpg((stem + ".jpg").c_str(), st.width, st.height, 3, rgb8.data(), 60);
     const int ok_bmp = rtm_write_bmp((stem + ".bmp").c_str(), st.width, st.height, 3, rgb8.data());
     if (!(ok_jpg && ok_bmp)) return 1;
+    if (adaptive) {  // <stem>_spp.pfm: every pixel's sample count
+        const int tiles_x = (st.width + 7) / 8;
+        std::vector<float> spp((size_t)st.width * st.height);
+        for (int y = 0; y < st.height; ++y)
+            for (int x = 0; x < st.width; ++x) spp[(size_t)y * st.width + x] = (float)tile_samples[(size_t)(y / 8) * tiles_x + x / 8];
+        if (rtm_write_pfm((stem + "_spp.pfm").c_str(), st.width, st.height, 1, spp.data()) != 1) return 1;
+    }
     if (aov) {
         std::string err;
         rc = rtm_node_write_aov(&st, spheres.data(), n, &opt, stem, err);

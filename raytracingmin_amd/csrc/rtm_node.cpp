@@ -14,6 +14,7 @@
 
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <cstdarg>
@@ -368,6 +369,64 @@ int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, si
     (void)hipFree(accum);
     (void)hipFree(d32);
     (void)hipFree(d8);
+    (void)rtm_scene_destroy(scene);
+    return rc;
+}
+
+// --adaptive (rtm_node.h): rtm_render_adaptive of the whole frame on the default stream, outputs and sample map copied back.
+int rtm_node_render_adaptive(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
+                             const rtm_adaptive_params* prm, float* out_f32_host, uint8_t* out_u8_host,
+                             std::vector<uint32_t>& tile_samples, rtm_stats* total, std::string& err) {
+    if (hipSetDevice(opt->device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(opt->device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    rtm_scene* scene = nullptr;
+    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
+    if (rc != RTM_OK) {
+        err = std::string("scene: ") + rtm_last_error_detail();
+        return rc;
+    }
+    const size_t vals = (size_t)st->width * st->height * 3;
+    const size_t tiles = (size_t)((st->width + 7) / 8) * (size_t)((st->height + 7) / 8);
+    tile_samples.assign(tiles, 0u);
+    double* accum = nullptr;
+    float* d32 = nullptr;
+    uint8_t* d8 = nullptr;
+    uint32_t* dts = nullptr;
+    void* work = nullptr;
+    if (hipMalloc((void**)&accum, vals * sizeof(double)) != hipSuccess ||
+        (out_f32_host && hipMalloc((void**)&d32, vals * sizeof(float)) != hipSuccess) ||
+        (out_u8_host && hipMalloc((void**)&d8, vals) != hipSuccess) ||
+        hipMalloc((void**)&dts, tiles * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&work, rtm_adaptive_work_bytes(st, opt)) != hipSuccess) {
+        err = "no device memory for the frame";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        rc = rtm_render_adaptive(st, scene, opt, prm, accum, d32, d8, dts, work, nullptr, total);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    if (rc == RTM_OK && ((out_u8_host && hipMemcpy(out_u8_host, d8, vals, hipMemcpyDeviceToHost) != hipSuccess) ||
+                         (out_f32_host && hipMemcpy(out_f32_host, d32, vals * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
+                         hipMemcpy(tile_samples.data(), dts, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)) {
+        err = "copying the frame back failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        double sum = 0.0;
+        for (size_t t = 0; t < tiles; ++t) {
+            const int tx = (int)(t % (size_t)((st->width + 7) / 8)), ty = (int)(t / (size_t)((st->width + 7) / 8));
+            sum += (double)tile_samples[t] * std::min(8, st->width - 8 * tx) * std::min(8, st->height - 8 * ty);
+        }
+        std::printf("adaptive: threshold %g, min_samples %u: mean %.2f samples per pixel of %d\n", (double)prm->threshold,
+                    prm->min_samples, sum / ((double)st->width * st->height), st->super_samples * st->super_samples * st->samples);
+    }
+    (void)hipFree(accum);
+    (void)hipFree(d32);
+    (void)hipFree(d8);
+    (void)hipFree(dts);
+    (void)hipFree(work);
     (void)rtm_scene_destroy(scene);
     return rc;
 }

@@ -1,6 +1,7 @@
 // rtm_node.h — single-process multi-GPU render + RCCL gather used by rtm_cli (rtm_node.cpp).
 #pragma once
 #include <string>
+#include <vector>
 
 #include "../../include/rtm.h"
 
@@ -16,6 +17,11 @@ int rtm_node_render(const rtm_settings* st, const rtm_object* objects, size_t n,
 // --passes), printing "pass i/N: samples [a, b) <ms> ms" per pass.  The outputs are rtm_render_scene's frame.
 int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options, int passes,
                            float* out_f32_host, uint8_t* out_u8_host, rtm_stats* total, std::string& err);
+// The frame rendered tile-adaptively on options->device (rtm_render_adaptive, rtm_cli --adaptive), printing the mean
+// samples per pixel.  tile_samples receives the per-tile sample map (tiles_y x tiles_x).  Outputs as rtm_node_render_passes.
+int rtm_node_render_adaptive(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
+                             const rtm_adaptive_params* params, float* out_f32_host, uint8_t* out_u8_host,
+                             std::vector<uint32_t>& tile_samples, rtm_stats* total, std::string& err);
 // The first-hit feature buffers of the whole frame on options->device (rtm_render_aov, rtm_cli --aov), written next to the
 // image: <stem>_depth.pfm, <stem>_normal.pfm, <stem>_albedo.pfm (the exact float planes), <stem>_normal.bmp (the quantised
 // 0.5 n + 0.5) and <stem>_albedo.bmp (the quantised albedo).

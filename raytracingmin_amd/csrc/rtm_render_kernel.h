@@ -74,6 +74,11 @@ struct RenderParams {
     // it is added to (the accumulator starts at +0 and no term is negative zero's only partner), so it is neither stored nor
     // read: 94 % of the samples of BASELINE configs[4] (a path that reaches no emitter returns 0).
     unsigned* __restrict__ nz_bits;
+    // tile-list renders (rtm_render_scene_tiles): launch-local tile t renders frame tile tile_map[t] (tx = % tiles_x, ty =
+    // / tiles_x); an entry of frame_tiles or more makes its blocks return before any load or store.  Null: tile t is frame
+    // tile t (every other call).  The work buffers above stay indexed by launch-local tile.
+    const unsigned* __restrict__ tile_map;
+    unsigned frame_tiles;
 };
 constexpr size_t kTermRowBytes = 3 * 64 * sizeof(double) + 64 * sizeof(unsigned short);  // 1664 = 13 lines of 128 B
 constexpr size_t kStealRowBytes = 3 * 64 * sizeof(double) + 64 * sizeof(unsigned);       // 1792 = 14 lines of 128 B
@@ -187,6 +192,14 @@ __device__ __forceinline__ void wave_add_counter(unsigned long long* dst, unsign
 // band_index, band_index + band_count, ... of [row_begin, row_end) and stores them back to back.
 __device__ __forceinline__ int band_row(const RenderParams& P, int local_band, int sub) {
     return P.row_begin + (local_band * P.band_count + P.band_index) * 8 + sub;
+}
+
+// The frame tile that launch-local tile t renders (RenderParams::tile_map); ~0u: a list entry past the frame.  Every
+// tile -> (x, y) mapping of the render kernels goes through here (render_tiles_kernel through the LDS slot it fills from it).
+__device__ __forceinline__ unsigned frame_tile(const RenderParams& P, unsigned t) {
+    if (P.tile_map == nullptr) return t;
+    const unsigned m = P.tile_map[t];
+    return m < P.frame_tiles ? m : ~0u;
 }
 
 __device__ __forceinline__ size_t out_index(const RenderParams& P, int x, int y) {
@@ -332,6 +345,11 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     static_assert(!PACKL || (DEFER && !PACK8 && LDS_D == 0 && sizeof(RecT) == 1), "PACKL: deferred fold, byte records, pooled stack only");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int lane = threadIdx.x;
+    // this block's tile of the launch, and the frame tile it renders (a tile-list render: a bad entry returns here)
+    const unsigned block_tile = (SPLIT && blockIdx.x >= P.split_first) ? P.split_first + (blockIdx.x - P.split_first) % P.n_tiles
+                                                                        : blockIdx.x;
+    const unsigned block_frame_tile = frame_tile(P, block_tile);
+    if (block_frame_tile == ~0u) return;
     // The exact-n instantiations (UNROLL in -101 .. -107, or an axis signature: UNROLL <= -1000) are launched for scenes of
     // exactly that many spheres, so the count COULD be a compile-time constant there (the LDS tables' offsets, the identity
     // row's index and the empty record word as immediates).  Measured and not kept (profiles/r4/ctn_ab.txt): the
@@ -385,11 +403,11 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
         for (int k = 1; k < 9; ++k) pick = (lane == k) ? v9[k] : pick;
         cam[lane] = pick;
     }
-    {  // the spare slot: this tile's first entry of the pre-pass's direction table (primary_of below)
-        const unsigned tile_of_block = (SPLIT && blockIdx.x >= P.split_first) ? P.split_first + (blockIdx.x - P.split_first) % P.n_tiles
-                                                                               : blockIdx.x;
-        const double first = __longlong_as_double((long long)((unsigned long long)tile_of_block * (unsigned long long)(unsigned)(P.SS * P.SS)));
-        if (lane == 9) cam[9] = first;
+    {  // the spare slot: word 0 this tile's first entry of the pre-pass's direction table (primary_of below; the table holds
+       // at most 4 GiB / 1.5 KiB entries), word 1 the frame tile the block renders (pixel_xy)
+        const unsigned first = block_tile * (unsigned)(P.SS * P.SS);
+        const double slot = __longlong_as_double((long long)(((unsigned long long)block_frame_tile << 32) | first));
+        if (lane == 9) cam[9] = slot;
     }
     __syncthreads();
     if constexpr (LDS_TAB) {
@@ -430,8 +448,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     auto pixel_xy = [&](int& px, int& py) {
         int l = lane;
         asm volatile("" : "+v"(l));
-        const unsigned tile = (SPLIT && blockIdx.x >= P.split_first)
-                                  ? P.split_first + (blockIdx.x - P.split_first) % P.n_tiles : blockIdx.x;
+        const unsigned tile = (unsigned)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<const unsigned*>(cam + 9)[1]);
         const int tx = tile % P.tiles_x, ty = tile / P.tiles_x;
         px = tx * 8 + (l & 7);
         py = band_row(P, ty, l >> 3);
@@ -520,7 +537,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 // (a lane that is past its range keeps tracing dummies and keeps asking: its "next sub-pixel" may be one
                 // past the pixel's last — clamped, the table ends with the last tile's last sub-pixel)
                 const unsigned all = (unsigned)(P.SS * P.SS);
-                const unsigned long long first = (unsigned long long)__double_as_longlong(cam[9]);
+                const unsigned long long first = reinterpret_cast<const unsigned*>(cam + 9)[0];
                 unsigned col = pl & 63u;
                 asm volatile("" : "+v"(col));  // (opaque: hipcc otherwise hoists the lane's table address out of the render
                                                // loop into a register pair it then spills — 28 GB of scratch reloads per frame)
@@ -984,7 +1001,8 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
           unsigned claimed = 0u;                                         // samples taken from other pixels so far (wave-uniform)
           const unsigned cap = P.steal_rows * 64u;
           const unsigned floor_s = total > P.steal_depth ? total - P.steal_depth : 0u;
-          const unsigned tile_x8 = (blockIdx.x % (unsigned)P.tiles_x) * 8u, tile_y = blockIdx.x / (unsigned)P.tiles_x;
+          const unsigned ftile = (unsigned)__builtin_amdgcn_readfirstlane((int)reinterpret_cast<const unsigned*>(cam + 9)[1]);
+          const unsigned tile_x8 = (ftile % (unsigned)P.tiles_x) * 8u, tile_y = ftile / (unsigned)P.tiles_x;
           for (;;) {
             const unsigned long long m_busy = __builtin_amdgcn_ballot_w64(busy);
             if (m_busy == 0ull) break;
@@ -1258,7 +1276,8 @@ __global__ __launch_bounds__(256) void split_finalize_kernel(const RenderParams 
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     double* slot = reinterpret_cast<double*>(lds_raw);  // [channel][sample][lane]
     const int tid = threadIdx.x, lane = tid & 63, chan = tid >> 6;
-    const unsigned tile = P.split_first + blockIdx.x;  // blockIdx.x: index among the split tiles
+    const unsigned tile = frame_tile(P, P.split_first + blockIdx.x);  // blockIdx.x: index among the split tiles
+    if (tile == ~0u) return;
     const int tx = tile % P.tiles_x, ty = tile / P.tiles_x;
     const int px = tx * 8 + (lane & 7), py = band_row(P, ty, lane >> 3);
     const bool valid = (px < P.W) && (py < P.row_end);
@@ -1300,7 +1319,9 @@ __global__ __launch_bounds__(64) void steal_finalize_kernel(const RenderParams P
     unsigned short* idx = reinterpret_cast<unsigned short*>(lds_raw);  // [sample - floor][pixel lane] -> position in the rows
     const int lane = threadIdx.x;
     const unsigned tile = blockIdx.x;
-    const int tx = tile % P.tiles_x, ty = tile / P.tiles_x;
+    const unsigned ftile = frame_tile(P, tile);
+    if (ftile == ~0u) return;
+    const int tx = ftile % P.tiles_x, ty = ftile / P.tiles_x;
     const int px = tx * 8 + (lane & 7), py = band_row(P, ty, lane >> 3);
     const bool valid = (px < P.W) && (py < P.row_end);
     const unsigned char* blk = P.steal_ws + (size_t)tile * steal_tile_bytes(P.steal_rows);
@@ -1364,6 +1385,8 @@ __global__ __launch_bounds__(64) void prim_prepass_kernel(const RenderParams P, 
                                                           double* __restrict__ dirs) {
     const int lane = threadIdx.x;
     const unsigned tile = blockIdx.x;
+    const unsigned ftile = frame_tile(P, tile);
+    if (ftile == ~0u) return;
     auto store_dir = [&](const unsigned sub, const D3 d) {  // RenderParams::prim_dirs: [tile][pixel][sub-pixel][component]
         const unsigned all_s = (unsigned)(P.SS * P.SS);
         double* q = dirs + ((size_t)tile * all_s + sub) * 192 + (unsigned)lane;
@@ -1372,8 +1395,8 @@ __global__ __launch_bounds__(64) void prim_prepass_kernel(const RenderParams P, 
         __builtin_nontemporal_store(d.y, q + kStep);
         __builtin_nontemporal_store(d.z, q + 2 * kStep);
     };
-    const int x = (int)(tile % (unsigned)P.tiles_x) * 8 + (lane & 7);
-    const int y = band_row(P, (int)(tile / (unsigned)P.tiles_x), lane >> 3);
+    const int x = (int)(ftile % (unsigned)P.tiles_x) * 8 + (lane & 7);
+    const int y = band_row(P, (int)(ftile / (unsigned)P.tiles_x), lane >> 3);
     const double cam[9] = {P.ax.x, P.ax.y, P.ax.z, P.by.x, P.by.y, P.by.z, P.cz.x, P.cz.y, P.cz.z};
     [[maybe_unused]] unsigned long long mask = 0ull;
     const unsigned all = (unsigned)(P.SS * P.SS);

@@ -156,7 +156,8 @@ __global__ __launch_bounds__(64) void render_surface_kernel(const RenderParams P
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     uint2* rec = reinterpret_cast<uint2*>(lds_raw);  // [kSurfLdsLevels][64]
     const int lane = threadIdx.x;
-    const unsigned tile = blockIdx.x;
+    const unsigned tile = frame_tile(P, blockIdx.x);
+    if (tile == ~0u) return;
     const int x = (int)(tile % (unsigned)P.tiles_x) * 8 + (lane & 7);
     const int y = band_row(P, (int)(tile / (unsigned)P.tiles_x), lane >> 3);
     const bool valid = x < P.W && y < P.row_end;

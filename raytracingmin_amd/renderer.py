@@ -18,6 +18,16 @@ from . import _lib
 from ._lib import rtm_options, rtm_stats
 from .settings import SettingData
 
+# tile-adaptive sampling: the Python / rtm_cli defaults ("Tile-adaptive sampling")
+ADAPTIVE_DEFAULTS = {"min_samples": 16, "threshold": 0.05}
+
+
+def adaptive_preview(accum, tile_samples, n_samples):
+    """The f64 view of an adaptive frame: every pixel's accumulator times N / k, k its tile's sample count (the preview
+    rule of rtm_render_scene_samples, computed in double like the device's f32 / u8 views; a tile at N is its accumulator)."""
+    k = np.repeat(np.repeat(np.asarray(tile_samples, dtype=np.float64), 8, axis=0), 8, axis=1)[:accum.shape[0], :accum.shape[1]]
+    return accum * (np.float64(n_samples) / k)[..., None]
+
 
 class Renderer:
     def __init__(self, data: SettingData, mode="repaired", max_bounces=-1, seed=0x5EED, device=0,
@@ -182,6 +192,88 @@ class Renderer:
                                                  row_begin=row_begin, row_end=row_end, band=band)
             yield b, out, st
 
+    # ---- tile lists and tile-adaptive sampling (rtm_render_scene_tiles, rtm_render_adaptive) ----
+    def tiles_shape(self, row_begin=0, row_end=None, band=None):
+        """(tiles_y, tiles_x): the 8x8 tiles of the call's output rows; tile t is (t // tiles_x, t % tiles_x)."""
+        row_end = self.data.height if row_end is None else row_end
+        opt = self._options(row_begin, row_end, band)
+        rows = _lib.lib().rtm_output_rows(C.byref(opt))
+        return (rows + 7) // 8, (self.data.width + 7) // 8
+
+    def render_tiles_device(self, tiles, sample_begin, sample_end, accum, want=("u8",), out=None, stats=True, stream=None,
+                            row_begin=0, row_end=None, band=None):
+        """render_samples_device restricted to the listed tiles (`tiles`: a uint32/int32 CUDA tensor or a sequence of tile
+        indices): their pixels get the pass's accumulator and f32 / u8 views; every other pixel of `accum` and of the
+        tensors in `out` (reused when given, so that unlisted tiles keep what they held) is neither read nor written."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        row_end = self.data.height if row_end is None else row_end
+        opt = self._options(row_begin, row_end, band)
+        rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
+        dev = torch.device("cuda", self.device)
+        if accum.dtype != torch.float64 or accum.device != dev or not accum.is_contiguous() or accum.numel() != rows * W * 3:
+            raise ValueError(f"accum must be a contiguous float64 tensor of {rows}x{W}x3 on {dev}")
+        if not torch.is_tensor(tiles):
+            tiles = torch.tensor(np.asarray(tiles, dtype=np.int64).astype(np.uint32).view(np.int32), device=dev)
+        tiles = tiles.to(dev).contiguous()
+        if tiles.element_size() != 4:
+            raise ValueError("tiles must hold 32-bit tile indices")
+        res = dict(out or {})
+        res["f64"] = accum
+        for k, dt in (("f32", torch.float32), ("u8", torch.uint8)):
+            if k in want and k not in res:
+                res[k] = torch.empty((rows, W, 3), dtype=dt, device=dev)
+        st = self.data.settings_c()
+        s = rtm_stats()
+        hip_stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda k: C.c_void_p(res[k].data_ptr()) if k in res and rows > 0 else None
+        _lib.check(_lib.lib().rtm_render_scene_tiles(C.byref(st), self._scene_handle(), C.byref(opt), int(sample_begin),
+                                                     int(sample_end), C.c_void_p(tiles.data_ptr()), int(tiles.numel()),
+                                                     ptr("f64"), ptr("f32"), ptr("u8"), C.c_void_p(hip_stream),
+                                                     C.byref(s) if stats else None), "rtm_render_scene_tiles")
+        return res, (s.as_dict() if stats else None)
+
+    def adaptive(self, threshold=ADAPTIVE_DEFAULTS["threshold"], min_samples=ADAPTIVE_DEFAULTS["min_samples"], want=("u8",),
+                 stats=True, stream=None, row_begin=0, row_end=None, band=None):
+        """Tile-adaptive rendering (include/rtm.h: rtm_render_adaptive).  Returns (outputs, tile_samples, stats): outputs as
+        render_samples_device's ("f64" is the accumulator), tile_samples a (tiles_y, tiles_x) int64 CUDA tensor of the
+        samples each tile traced.  Tile t equals rtm_render_scene_samples [0, tile_samples[t]) bit for bit.  Blocks."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        row_end = self.data.height if row_end is None else row_end
+        opt = self._options(row_begin, row_end, band)
+        L = _lib.lib()
+        rows, W = L.rtm_output_rows(C.byref(opt)), self.data.width
+        dev = torch.device("cuda", self.device)
+        st = self.data.settings_c()
+        out = {"f64": torch.empty((rows, W, 3), dtype=torch.float64, device=dev)}
+        for k, dt in (("f32", torch.float32), ("u8", torch.uint8)):
+            if k in want:
+                out[k] = torch.empty((rows, W, 3), dtype=dt, device=dev)
+        ty, tx = (rows + 7) // 8, (W + 7) // 8
+        tile_samples = torch.zeros((ty, tx), dtype=torch.int32, device=dev)
+        work = torch.empty(max(256, L.rtm_adaptive_work_bytes(C.byref(st), C.byref(opt))), dtype=torch.uint8, device=dev)
+        prm = _lib.rtm_adaptive_params(int(min_samples), float(threshold))
+        s = rtm_stats()
+        hip_stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        ptr = lambda k: C.c_void_p(out[k].data_ptr()) if k in out and rows > 0 else None
+        _lib.check(L.rtm_render_adaptive(C.byref(st), self._scene_handle(), C.byref(opt), C.byref(prm), ptr("f64"), ptr("f32"),
+                                         ptr("u8"), C.c_void_p(tile_samples.data_ptr()) if rows > 0 else None,
+                                         C.c_void_p(work.data_ptr()), C.c_void_p(hip_stream),
+                                         C.byref(s) if stats else None), "rtm_render_adaptive")
+        return out, tile_samples.to(torch.int64), (s.as_dict() if stats else None)
+
+    def write_spp(self, fileName, tile_samples):
+        """<fileName>_spp.pfm: the samples each pixel traced, as floats (one channel), from a (tiles_y, tiles_x) map."""
+        H, W = self.data.height, self.data.width
+        ts = np.asarray(tile_samples.cpu() if hasattr(tile_samples, "cpu") else tile_samples)
+        spp = np.ascontiguousarray(np.repeat(np.repeat(ts, 8, axis=0), 8, axis=1)[:H, :W].astype(np.float32))
+        if not _lib.lib().rtm_write_pfm(os.fsencode(fileName + "_spp.pfm"), W, H, 1, spp.ctypes.data):
+            raise _lib.RtmError(-3, f"could not write {fileName}_spp.pfm")
+        return spp
+
     # ---- first-hit feature buffers (rtm_render_aov) ------------------------------------------
     AOV_PLANES = ("depth", "normal", "albedo", "object")
 
@@ -258,13 +350,22 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1, aov=False, denoise=False):
+    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
         denoise=True also writes <fileName>_denoised.jpg (q=60) and _denoised.bmp: the frame's f32 filtered by denoise() at
-        the default parameters, guided by its AOVs (write_denoised); the plain files and self.image do not change."""
-        if passes > 1:
+        the default parameters, guided by its AOVs (write_denoised); the plain files and self.image do not change.
+        adaptive=T renders tile-adaptively (Renderer.adaptive, threshold T, the default min_samples) and also writes
+        <fileName>_spp.pfm, the per-pixel sample count (write_spp); the AOV and denoised files then come from that frame."""
+        if adaptive is not None:
+            if passes > 1:
+                raise ValueError("adaptive and passes > 1 do not combine")
+            out, tile_samples, _ = self.adaptive(float(adaptive), want=("u8",))
+            self.image = adaptive_preview(out["f64"].cpu().numpy(), tile_samples.cpu().numpy(), self.total_samples())
+            rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
+            self.write_spp(fileName, tile_samples)
+        elif passes > 1:
             last = None
             for _, out, st in self.progressive(passes=passes, want=("u8",)):
                 last = out
