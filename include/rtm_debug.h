@@ -53,6 +53,13 @@ int rtm_debug_grid_build(const rtm_sphere* spheres, size_t n, uint64_t* info, do
  * folds then leave a bounce level's "+ emission" out: SceneView::fold_flags), bit 1: every |centre| + radius is at most 1e7 (a
  * compact scene: the tolerance row's search may take its square roots without the residual step). */
 int rtm_debug_scene_facts(const rtm_sphere* spheres, size_t n, uint64_t facts[2]);
+/* Two more such facts, also on the HOST (rtm_debug_scene_facts' two words are compared whole by its callers, so these have an
+ * entry of their own): facts[0] = 1 where a path end whose terminal object does not emit provably adds (+0, +0, +0) — bit 0 of
+ * rtm_debug_scene_facts' facts[1] holds, every colorKD of an object a path can bounce off is finite and there are at most 63
+ * objects —, so that the deferred-fold kernels neither queue nor fold nor store it (SceneView::emit_mask), else 0; facts[1] =
+ * the mask those kernels get: bit i = object i's emission is not (+0, +0, +0), all ones where facts[0] is 0.  (RTM_DEBUG_ZERO_SKIP=0
+ * in the environment of a render call makes it queue and fold every path end whatever these facts say.) */
+int rtm_debug_zero_term_facts(const rtm_sphere* spheres, size_t n, uint64_t facts[2]);
 /* isolated nearest-hit / shading loops timed with s_memtime (profiles/component_bench.py) */
 int rtm_debug_component_bench(int which, const rtm_sphere* spheres, size_t n, int reps, int blocks, int lds_pad,
                               double* cycles_per_rep);

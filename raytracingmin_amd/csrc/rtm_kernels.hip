@@ -150,6 +150,23 @@ static unsigned fold_flags_of(const double* mat, size_t n) {
     }
     return kFoldNoLevelEmission;
 }
+// ... and kFoldZeroTermSkippable with SceneView::emit_mask, from the same rows: on top of kFoldNoLevelEmission every colorKD of
+// an object a path can bounce off is finite (0 x inf is NaN, not +0) and there are at most 63 objects, so that each — and the
+// identity row, which never emits — has a bit of the mask.  *emit_mask: bit i = object i's emission row is not (+0, +0, +0);
+// all ones where the flag is not proven (every path end is then queued and folded, as before).
+static unsigned zero_term_flags_of(const double* mat, size_t n, uint64_t* emit_mask) {
+    *emit_mask = ~(uint64_t)0;
+    if (n > 63 || fold_flags_of(mat, n) == 0u) return 0u;
+    uint64_t mask = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const double* m = mat + i * 8;
+        if (m[6] > 0.0 && !(std::isfinite(m[0]) && std::isfinite(m[1]) && std::isfinite(m[2]))) return 0u;
+        // (kFoldNoLevelEmission: no emission is NaN or carries a sign bit, so "not +0" is "> 0")
+        if (m[3] > 0.0 || m[4] > 0.0 || m[5] > 0.0) mask |= (uint64_t)1 << i;
+    }
+    *emit_mask = mask;
+    return kFoldZeroTermSkippable;
+}
 
 __global__ void flatten_scene_kernel(const rtm_sphere* __restrict__ sp, size_t n,
                                      double* __restrict__ geom, double* __restrict__ mat, double* __restrict__ surf = nullptr) {
@@ -299,7 +316,8 @@ struct rtm_scene {
     rtm::GridHeader grid_hdr;           // host copy (grid_for: is the camera within the pads' reach?)
     bool grid_far_bounces = false;      // a diffuse sphere encloses the gridded ones from beyond the pads' reach (build_scene_grid)
     bool has_planes = false;
-    unsigned fold_flags = 0;            // SceneView::fold_flags (fold_flags_of)
+    unsigned fold_flags = 0;            // SceneView::fold_flags (fold_flags_of, zero_term_flags_of)
+    uint64_t emit_mask = ~(uint64_t)0;  // SceneView::emit_mask (zero_term_flags_of)
     uint64_t axis_pat = 0;              // SceneView::axis_pat: which of the first 32 spheres sit on a coordinate axis (axis_pattern)
     uint64_t content_hash = 0;            // cache entries only ...
     std::vector<unsigned char> content;   // ... and the bytes the hash was taken of (compared on a hash hit)
@@ -335,10 +353,13 @@ static int launch_scene_aux(const double* geom, size_t n, double* aux, hipStream
 }
 static SceneView scene_view(const double* geom, const double* mat, const double* aux, size_t n,
                             const double* plane = nullptr, const void* grid = nullptr, const double* surf = nullptr,
-                            uint64_t axis_pat = 0, unsigned fold_flags = 0) {
+                            uint64_t axis_pat = 0, unsigned fold_flags = 0, uint64_t emit_mask = ~(uint64_t)0) {
     SceneView v{(const double4*)geom, mat, (int)n};
     v.axis_pat = axis_pat;
     v.fold_flags = fold_flags;
+    // RTM_DEBUG_ZERO_SKIP=0 (A/B and test knob, read per call): every path end is queued and folded whatever the scene proves
+    const char* zs = std::getenv("RTM_DEBUG_ZERO_SKIP");
+    v.emit_mask = ((fold_flags & kFoldZeroTermSkippable) && !(zs && zs[0] == '0')) ? emit_mask : ~(uint64_t)0;
     v.plane = plane;
     v.surf = surf;
     v.grid = static_cast<const GridHeader*>(grid);
@@ -568,6 +589,15 @@ int scene_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts) {
     facts[1] = fold_flags_of(hm.data(), n) | compact_flag_of(hg.data(), n);
     return RTM_OK;
 }
+// rtm_debug_zero_term_facts: zero_term_flags_of on the HOST — facts[0] 1 where kFoldZeroTermSkippable is proven, facts[1] the
+// emit mask (tests/test_zero_term_host.py)
+int zero_term_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts) {
+    if ((!sp && n) || !facts) return RTM_ERR_INVALID_ARGUMENT;
+    std::vector<double> hg, hm;
+    flatten_scene(sp, n, hg, hm);
+    facts[0] = zero_term_flags_of(hm.data(), n, &facts[1]) != 0u ? 1u : 0u;
+    return RTM_OK;
+}
 
 // Build + upload; a scene that gets no grid keeps sc.grid empty (not an error).  `hg`: the host copy of the geometry rows.
 // `hm`: the material rows (kd in column 6), or null.
@@ -647,7 +677,7 @@ static int scene_build_host(rtm_scene& sc, const rtm_sphere* sp, size_t n, int d
     std::vector<double> hg, hm, hs;
     flatten_scene(sp, n, hg, hm, &hs);
     sc.axis_pat = axis_pattern(hg.data(), n);
-    sc.fold_flags = fold_flags_of(hm.data(), n) | compact_flag_of(hg.data(), n);
+    sc.fold_flags = fold_flags_of(hm.data(), n) | compact_flag_of(hg.data(), n) | zero_term_flags_of(hm.data(), n, &sc.emit_mask);
     int rc = sc.geom.alloc_pooled((n ? n : 1) * 4 * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.mat.alloc_pooled((n + 1) * 8 * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.aux.alloc_pooled(scene_aux_doubles(n) * sizeof(double), device);
@@ -682,7 +712,7 @@ static int scene_build_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n,
         sc.axis_pat = axis_pattern(rows.data(), n);
         std::vector<double> mrows((n + 1) * 8);
         RTM_HIP_CHECK(hipMemcpy(mrows.data(), sc.mat.p, mrows.size() * sizeof(double), hipMemcpyDeviceToHost));
-        sc.fold_flags = fold_flags_of(mrows.data(), n) | compact_flag_of(rows.data(), n);
+        sc.fold_flags = fold_flags_of(mrows.data(), n) | compact_flag_of(rows.data(), n) | zero_term_flags_of(mrows.data(), n, &sc.emit_mask);
     }
     if (n < kGridMinSpheres) return RTM_OK;
     std::vector<double> hg(n * 4);  // the grid is built on the host: the geometry rows come back once
@@ -1968,7 +1998,8 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
             P.split = 1u + (pass_len - P.split_head) / P.split_len;
             const size_t part = (size_t)P.n_tiles * 192 * sizeof(double);
             const size_t terms = (size_t)P.n_tiles * (pass_len - P.split_head) * kTermRowBytes;  // a row per (tile, sample)
-            plan.bytes[kScratchTerms] = part + terms;
+            // (+ a count per (tile, small wave): RenderParams::split_counts; the rows stay sized for a term per sample)
+            plan.bytes[kScratchTerms] = part + terms + (size_t)P.n_tiles * P.split * sizeof(unsigned);
             plan.optional[kScratchTerms] = true;  // no room for the terms: the launch runs unsplit (same image, a longer tail)
         }
     }
@@ -2127,6 +2158,7 @@ static int render_view(const rtm_settings* st, const SceneView& view, size_t n, 
         if (rc == RTM_OK) {
             P.partial = split_ws;
             P.contrib = reinterpret_cast<unsigned char*>(split_ws) + (size_t)P.n_tiles * 192 * sizeof(double);
+            P.split_counts = reinterpret_cast<unsigned*>(P.contrib + (size_t)P.n_tiles * (P.sample_end - P.sample_begin - P.split_head) * kTermRowBytes);
         } else {  // no room for the terms: the launch runs unsplit (same image, a longer tail) instead of failing
             (void)hipGetLastError();
             P.split = 1;
@@ -2298,7 +2330,7 @@ int scratch_bytes(const rtm_settings* st, const rtm_scene* scene, const rtm_opti
     RenderParams P;
     RenderPlan plan;
     const SceneView view = scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
-                                      scene->has_planes ? scene->plane.as<double>() : nullptr, grid_for(scene, st, opt), scene->surf.as<double>(), scene->axis_pat, scene->fold_flags);
+                                      scene->has_planes ? scene->plane.as<double>() : nullptr, grid_for(scene, st, opt), scene->surf.as<double>(), scene->axis_pat, scene->fold_flags, scene->emit_mask);
     for (int k = 0; k < 6; ++k) out[k] = 0;
     if (output_rows(opt) == 0) return RTM_OK;
     rc = plan_render(st, view, scene->n, opt, P, plan);
@@ -2329,7 +2361,7 @@ static int render_scene_pass(const rtm_settings* st, const rtm_scene* scene, con
     std::shared_lock<std::shared_mutex> gate(g_gate);
     reap_scenes(false);
     rc = render_view(st, scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
-                                    scene->has_planes ? scene->plane.as<double>() : nullptr, grid_for(scene, st, opt), scene->surf.as<double>(), scene->axis_pat, scene->fold_flags),
+                                    scene->has_planes ? scene->plane.as<double>() : nullptr, grid_for(scene, st, opt), scene->surf.as<double>(), scene->axis_pat, scene->fold_flags, scene->emit_mask),
                      scene->n, opt, out64, out32, out8, (hipStream_t)stream_v, stats, pass);
     note_scene_use(scene, (hipStream_t)stream_v);  // also after a failure: part of the work may have been queued
     return rc;
@@ -2442,7 +2474,7 @@ int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options
     fill_render_params(P, st, opt, SamplePass{});
     P.scene = scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
                          scene->has_planes ? scene->plane.as<double>() : nullptr, grid, scene->surf.as<double>(), scene->axis_pat,
-                         scene->fold_flags);
+                         scene->fold_flags, scene->emit_mask);
     const unsigned tiles = (unsigned)P.tiles_x * (unsigned)((rows + 7) / 8);
     const size_t lds = aov_lds_bytes(search);
     if (search == kAovGrid)
@@ -2474,7 +2506,7 @@ int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int on
         std::shared_ptr<rtm_scene> sc;
         rc = cached_scene(sp, n, opt->device, &sc);
         if (rc != RTM_OK) return rc;
-        rc = render_view(st, scene_view(sc->geom.as<double>(), sc->mat.as<double>(), sc->aux.as<double>(), n, nullptr, grid_for(sc.get(), st, opt), sc->surf.as<double>(), sc->axis_pat, sc->fold_flags),
+        rc = render_view(st, scene_view(sc->geom.as<double>(), sc->mat.as<double>(), sc->aux.as<double>(), n, nullptr, grid_for(sc.get(), st, opt), sc->surf.as<double>(), sc->axis_pat, sc->fold_flags, sc->emit_mask),
                          n, opt, out64, out32, out8, stream, stats);
         note_scene_use(sc.get(), stream);  // an eviction while this render is queued parks the tables instead of waiting
         return rc;
@@ -2488,7 +2520,7 @@ int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int on
         std::shared_ptr<rtm_scene> sc;
         rc = cached_device_scene(sp, n, opt->device, stream, &sc);
         if (rc != RTM_OK) return rc;
-        rc = render_view(st, scene_view(sc->geom.as<double>(), sc->mat.as<double>(), sc->aux.as<double>(), n, nullptr, grid_for(sc.get(), st, opt), sc->surf.as<double>(), sc->axis_pat, sc->fold_flags),
+        rc = render_view(st, scene_view(sc->geom.as<double>(), sc->mat.as<double>(), sc->aux.as<double>(), n, nullptr, grid_for(sc.get(), st, opt), sc->surf.as<double>(), sc->axis_pat, sc->fold_flags, sc->emit_mask),
                          n, opt, out64, out32, out8, stream, stats);
         note_scene_use(sc.get(), stream);
         return rc;

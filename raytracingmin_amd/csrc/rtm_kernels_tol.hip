@@ -16,8 +16,9 @@
 // search, packed records, deferred fold and in-wave sample stealing (kTolCapped: kLdsTab | kPark | kPack8 | kDefer | kSteal);
 // for any other depth (the reference's own unlimited recursion) the same with records packed by position and the pooled
 // stack, no stealing (kTolAny: kPackL in place of kPack8 | kSteal); each with and without the sample split of a launch's
-// last tiles (kSplit) — the class of every BASELINE Cornell configuration.  Never the default; bench.py reports it as a labelled row with its own
-// roofline fraction and the count of pixels that differ from the exact frame (tests/test_tolerance_gpu.py).
+// last tiles (kSplit) — the class of every BASELINE Cornell configuration.  Never what rtm_options.variant 0 chooses: a caller
+// asks for it by number.  bench.py's headline figure IS this row (bench.py --exact: the bit-exact kernel), labelled as such,
+// with its own roofline fraction and the count of pixels that differ from the exact frame (tests/test_tolerance_gpu.py).
 #define RTM_NS rtm_tol
 #define RTM_TOL 1
 #include <hip/hip_runtime.h>

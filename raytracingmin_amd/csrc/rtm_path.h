@@ -560,8 +560,17 @@ struct SceneView {
     // "+ emission" of a bounce level (src/Renderer.cpp:109) then adds +0 to a product that is never -0: an identity, bit for
     // bit, which the packed folds leave out (and with it the levels' emission reads).  The shipped Cornell box: the walls.
     unsigned fold_flags = 0u;
+    // Bit i: "a path that ENDS on object i may contribute" — all ones unless the host has proven kFoldZeroTermSkippable, and
+    // then set exactly for the objects whose emission row is not (+0, +0, +0); the identity row (a miss, index n <= 63) has no
+    // bit.  Under that flag the term of a path that ends on an object without a bit is emission x colorKD x ... =
+    // (+0, +0, +0) after the /SS/SS/S and the clamp too, and acc + (+0) == acc bit for bit (the accumulator is never -0 where
+    // it matters: render_tiles_kernel's path-end block), so the deferred-fold kernels do not queue such a path end.
+    unsigned long long emit_mask = ~0ull;
 };
 constexpr unsigned kFoldNoLevelEmission = 1u;
+// ... bit 2, kFoldZeroTermSkippable: kFoldNoLevelEmission holds, every colorKD of an object a path can bounce off is finite
+// (no 0 x inf) and the scene has at most 63 objects (SceneView::emit_mask has a bit for each)
+constexpr unsigned kFoldZeroTermSkippable = 4u;
 // ... and bit 1, kSceneCompact: every |centre| + radius is finite and at most 1e7 (the launcher adds the camera): what the
 // tolerance unit's light search roots ask for (seq_sqrt_batch)
 constexpr unsigned kSceneCompact = 2u;

@@ -48,6 +48,9 @@ struct RenderParams {
     // per-sample terms of waves 1..: one block of split_len rows per (tile, small wave), a row = 64 terms in the order
     // the wave FOLDED them ([3][64] doubles, whole lines from one store instruction) + 64 tags (owner lane, sample)
     unsigned char* __restrict__ contrib;
+    // ... and how many terms each small wave stored, [tile][small wave]: a path end that provably adds (+0, +0, +0) is not
+    // stored (SceneView::emit_mask), so the count is no longer split_len x the tile's valid pixels
+    unsigned* __restrict__ split_counts;
     // in-wave sample stealing (STEAL kernels, whole tiles): per tile a block of kStealHdrBytes (terms stored, every
     // pixel's final own-sample end) + 3 x 64 doubles (the accumulators) + steal_rows rows of kStealRowBytes (64 terms in
     // fold order + 64 four-byte tags (pixel lane, sample)); steal_finalize_kernel turns the block into pixels
@@ -242,6 +245,17 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, bool valid, i
             P.out8[o + c] = (v >= 0.0 && v < 256.0) ? (uint8_t)v : (uint8_t)0;
         }
     }
+}
+
+// Does a path that ended on object `term_id` (the identity row's index n for a miss) take an entry of the fold queue?  Not
+// where the host has proven that its term is (+0, +0, +0): SceneView::emit_mask (all ones without the proof; ids from 64 up
+// only occur then).  Skipping such an end is invisible because x + (+0) == x for every x but -0, and a -0 accumulator — only
+// a seeded pass could start from one: a caller's out64 holding -0 — is stored as 0.0 + acc = +0 by store_pixel whether +0 was
+// added to it or not, and gives t either way once a non-zero t is added.  That covers every entry point that seeds
+// (rtm_render_scene_samples, tile lists, the adaptive render's passes); the head wave's partial and a stealing tile's
+// accumulators reach store_pixel through the finalize kernels.
+__device__ __forceinline__ bool zero_term_queued(const SceneView& v, const unsigned term_id) {
+    return ((v.emit_mask >> (term_id & 63u)) & 1ull) != 0ull;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -872,16 +886,23 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             w_casts += (unsigned)__builtin_popcountll(m_live);
             w_draws += (unsigned)__builtin_popcountll(m_drew) + 2u * n_cont;
             w_bounces += n_cont;
+            // A path end whose terminal object has no bit in SceneView::emit_mask adds (+0, +0, +0) to an accumulator that is
+            // never -0 where a bit of the image depends on it (zero_term_queued): it takes no ring entry — no rank, no count,
+            // no tag, no fold, no store — and its lane goes straight on to its next sample.  The counters above have counted it.
+            const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
+            const bool queued = !cont && live && zero_term_queued(P.scene, term_id);
+            const unsigned long long m_queued = __builtin_amdgcn_ballot_w64(queued);
             if (!cont) {
-                if (live) {
-                    // queue this path end: ring position = tail + rank among the lanes ending now
-                    const unsigned long long ending = __builtin_amdgcn_ballot_w64(true);
-                    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(ending >> 32),
-                                                                   __builtin_amdgcn_mbcnt_lo((unsigned)ending, 0u));
+                if (queued) {
+                    // queue this path end: ring position = tail + rank among the lanes queueing now
+                    const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m_queued >> 32),
+                                                                   __builtin_amdgcn_mbcnt_lo((unsigned)m_queued, 0u));
                     const unsigned pos = (fq_tail + rank) & (kFoldRing - 1);
-                    const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
                     if constexpr (PACKL && kScatter && !SMALL) {
-                        // fq_pend: bits 0..7 the lane's path ends so far, 8..15 that count after its last DEEP path, 16: there was one
+                        // fq_pend: bits 0..7 the lane's QUEUED path ends so far, 8..15 that count after its last queued DEEP path, 16:
+                        // there was one.  (A deep path that is not queued leaves all of it alone: nobody will read its levels in
+                        // the pooled stack, so the lane keeps the stack it has — its next deep path overwrites them — and no
+                        // "deep entry waiting" state arises.)
                         const unsigned word = fq_pend[lane];
                         const unsigned count = word & 0xFFu, next = (count + 1u) & 0xFFu;
                         fq_in[pos] = uint4{(unsigned)recq, (unsigned)(recq >> 32),
@@ -905,7 +926,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                                            (unsigned)(stack.slot < 0 ? 0 : stack.slot)};
                         fq_in1[pos] = rec_w1[lane];
                     } else if constexpr (kScatter && !SMALL) {
-                        // (fold_pass: the folding lane adds the term to this lane's pixel when the count says it is its turn)
+                        // (fold_pass: the folding lane adds the term to this lane's pixel when the count says it is its turn.  The
+                        // count is of QUEUED path ends — fq_pend here, fq_done there —, so a pixel's additions keep the order of its
+                        // non-zero path ends; a zero one has no place in that order because it changes no bit)
                         const unsigned ends_so_far = fq_pend[lane];
                         fq_in[pos] = uint4{(unsigned)recq, (unsigned)(recq >> 32), term_id, (unsigned)lane | ((ends_so_far & 0xFFu) << 8)};
                         fq_pend[lane] = ends_so_far + 1u;
@@ -968,7 +991,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 recq = packed8_empty(scene_n);
                 rng = rng_open(pkey, n);
             }
-            const unsigned added = (unsigned)__builtin_popcountll(m_live & ~m_cont);
+            const unsigned added = (unsigned)__builtin_popcountll(m_queued);  // queued entries only
             if (added != 0u) {
                 fq_tail = (fq_tail + added) & (kFoldRing - 1);
                 fq_count += added;
@@ -977,6 +1000,12 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             }
         }
         while (fq_count > 0u) fold_pass(mode_tag);
+        if constexpr (SMALL) {
+            // how many terms split_finalize_kernel will find in this wave's rows (an absent (lane, sample) is nothing to add)
+            unsigned sf, stile;
+            split_wave(sf, stile);
+            if (lane == 0) P.split_counts[(size_t)stile * (P.split - 1u) + (sf - 1u)] = terms_out;
+        }
       };
       if constexpr (SPLIT) {
           if (n_first != P.sample_begin) trace(ModeSmall{});  // (a small wave's first sample is never the pass's first: wave 0 keeps at least one share)
@@ -1034,13 +1063,15 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             w_casts += (unsigned)__builtin_popcountll(m_busy);
             w_draws += (unsigned)__builtin_popcountll(m_drew) + 2u * n_cont;
             w_bounces += n_cont;
-            const bool ended = busy && !cont;
             const bool need = !busy || !cont;  // this lane wants a new sample
+            // (the main loop's rule: a path end that provably adds (+0, +0, +0) is not queued — an own sample keeps out of its
+            // pixel's count, a stolen one is not exported and steal_finalize_kernel finds nothing under its (pixel, sample))
+            const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
+            const bool ended = busy && !cont && zero_term_queued(P.scene, term_id);
+            const unsigned long long m_ended = __builtin_amdgcn_ballot_w64(ended);
             if (ended) {
-                const unsigned long long ending = __builtin_amdgcn_ballot_w64(true);
-                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(ending >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ending, 0u));
+                const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m_ended >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_ended, 0u));
                 const unsigned pos = (fq_tail + rank) & (kFoldRing - 1);
-                const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
                 const bool own = (cur >> 16) == (unsigned)lane;
                 if constexpr (kScatter) {
                     const unsigned ends_so_far = fq_pend[lane];  // (of this lane's OWN pixel)
@@ -1057,7 +1088,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 }
                 }
             }
-            const unsigned added = (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(ended));
+            const unsigned added = (unsigned)__builtin_popcountll(m_ended);  // queued entries only
             // (1) the lane's own next sample, if its pixel still has one that nobody took
             bool got = false;
             if (need && own_next < st_end[lane]) {
@@ -1272,35 +1303,46 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
 // scatters its rows into LDS by (sample, owner lane) — the tag — and waves 0..2 then add, each for ONE colour channel
 // (the three sums are independent), their pixel's terms in sample order.  LDS: split_len x 64 x 3 doubles (96 KB at
 // the 64 samples a small wave traces at most).
+// A small wave stores only the path ends it queued (SceneView::emit_mask): P.split_counts says how many, and a word per sample
+// behind the slots — bit l: "lane l's term of this sample is there" — says which; an absent one is nothing to add (its slot
+// holds whatever was there before and is not read).  The words are cleared per small wave: split_len x 8 bytes, not the slots.
 __global__ __launch_bounds__(256) void split_finalize_kernel(const RenderParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     double* slot = reinterpret_cast<double*>(lds_raw);  // [channel][sample][lane]
+    unsigned* present = reinterpret_cast<unsigned*>(slot + (size_t)P.split_len * 64u * 3u);  // [sample][2]
     const int tid = threadIdx.x, lane = tid & 63, chan = tid >> 6;
     const unsigned tile = frame_tile(P, P.split_first + blockIdx.x);  // blockIdx.x: index among the split tiles
     if (tile == ~0u) return;
     const int tx = tile % P.tiles_x, ty = tile / P.tiles_x;
     const int px = tx * 8 + (lane & 7), py = band_row(P, ty, lane >> 3);
     const bool valid = (px < P.W) && (py < P.row_end);
-    // terms a small wave of this tile has stored: one per valid pixel and sample of its range
-    const unsigned n_valid = (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(valid));
-    const unsigned n_terms = n_valid * P.split_len;
     const unsigned plane_sz = P.split_len * 64u;  // doubles per channel
     double acc = chan < 3 ? P.partial[(size_t)blockIdx.x * 192 + chan * 64 + lane] : 0.0;
     for (unsigned f = 1; f < P.split; ++f) {
         const unsigned char* rows = P.contrib + ((size_t)blockIdx.x * (P.split - 1u) + (f - 1u)) * P.split_len * kTermRowBytes;
+        // terms this small wave has stored: at most one per pixel and sample of its range (a count beyond that: a stale or
+        // foreign buffer, which must not turn into a fault)
+        unsigned n_terms = P.split_counts[(size_t)blockIdx.x * (P.split - 1u) + (f - 1u)];
+        n_terms = n_terms <= plane_sz ? n_terms : 0u;
+        for (unsigned m = (unsigned)tid; m < P.split_len * 2u; m += 256u) present[m] = 0u;
+        __syncthreads();
         for (unsigned e = (unsigned)tid; e < n_terms; e += 256u) {
             const unsigned char* row = rows + (size_t)(e >> 6) * kTermRowBytes;
             const double* v = reinterpret_cast<const double*>(row) + (e & 63u);
             const unsigned tag = reinterpret_cast<const unsigned short*>(row + 3 * 64 * sizeof(double))[e & 63u];
+            if ((tag >> 6) >= P.split_len) continue;  // (never, when the render kernel wrote the row)
             const unsigned at = (tag >> 6) * 64u + (tag & 63u);  // [sample][owner lane]
             slot[at] = v[0];
             slot[plane_sz + at] = v[64];
             slot[2 * plane_sz + at] = v[128];
+            atomicOr(&present[(tag >> 6) * 2u + ((tag >> 5) & 1u)], 1u << (tag & 31u));
         }
         __syncthreads();
         if (chan < 3) {
             const double* mine = slot + (size_t)chan * plane_sz + lane;
-            for (unsigned m = 0; m < P.split_len; ++m) acc = acc + mine[m * 64u];  // (an invalid pixel adds stale LDS: never stored)
+            const unsigned* bits = present + (lane >> 5);
+            for (unsigned m = 0; m < P.split_len; ++m)  // in sample order, the terms that are there
+                if ((bits[m * 2u] >> (lane & 31)) & 1u) acc = acc + mine[m * 64u];
         }
         __syncthreads();
     }
@@ -1313,7 +1355,8 @@ __global__ __launch_bounds__(256) void split_finalize_kernel(const RenderParams 
 // order of src/Renderer.cpp:241-242 — where `partial` holds the samples [0, end) the pixel's own lane traced and the terms
 // of [end, total) were traced by other lanes of the tile and lie, in fold order and tagged (pixel lane, sample), in the
 // tile's rows.  One wave per tile: an index of row positions by (sample, pixel) in LDS, then every lane walks its pixel's
-// stolen samples in order.  LDS: steal_depth x 64 two-byte entries.
+// stolen samples in order.  LDS: steal_depth x 64 two-byte entries, cleared to "absent" first: a stolen sample whose path
+// end provably adds (+0, +0, +0) was not exported (SceneView::emit_mask) and is nothing to add.
 __global__ __launch_bounds__(64) void steal_finalize_kernel(const RenderParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     unsigned short* idx = reinterpret_cast<unsigned short*>(lds_raw);  // [sample - floor][pixel lane] -> position in the rows
@@ -1337,6 +1380,8 @@ __global__ __launch_bounds__(64) void steal_finalize_kernel(const RenderParams P
         const unsigned total = P.sample_end;
         const unsigned floor_s = total > P.steal_depth ? total - P.steal_depth : 0u;
         const unsigned char* rows = blk + kStealHdrBytes + 3 * 64 * sizeof(double);
+        for (unsigned k = (unsigned)lane; k < P.steal_depth * 32u; k += 64u) reinterpret_cast<unsigned*>(idx)[k] = 0xFFFFFFFFu;
+        __syncthreads();
         for (unsigned e = (unsigned)lane; e < n_terms; e += 64u) {
             const unsigned tag = reinterpret_cast<const unsigned*>(rows + (size_t)(e >> 6) * kStealRowBytes + 3 * 64 * sizeof(double))[e & 63u];
             const unsigned ts = tag & 0xFFFFu, tv = (tag >> 16) & 63u;
@@ -1345,8 +1390,8 @@ __global__ __launch_bounds__(64) void steal_finalize_kernel(const RenderParams P
         __syncthreads();
         if (valid) {
             for (unsigned s = end_own; s < total; ++s) {
-                unsigned e = idx[(s - floor_s) * 64u + (unsigned)lane];
-                e = e < n_terms ? e : 0u;
+                const unsigned e = idx[(s - floor_s) * 64u + (unsigned)lane];
+                if (e >= n_terms) continue;  // absent (0xFFFF; a tile holds at most steal_rows x 64 < 65 535 terms)
                 const double* v = reinterpret_cast<const double*>(rows + (size_t)(e >> 6) * kStealRowBytes) + (e & 63u);
                 acc = acc + d3(v[0], v[64], v[128]);
             }
@@ -1364,7 +1409,7 @@ void launch_tiles(RenderParams P, unsigned grid, size_t pad, hipStream_t stream)
 }
 // after a split launch (kSplit): one block per split tile
 inline void launch_split_finalize(const RenderParams& P, hipStream_t stream) {
-    split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * 64 * 3 * sizeof(double), stream>>>(P);
+    split_finalize_kernel<<<P.n_tiles, 256, (size_t)P.split_len * (64 * 3 * sizeof(double) + 2 * sizeof(unsigned)), stream>>>(P);
 }
 // after a stealing launch (kSteal) of `grid` blocks: one block per whole tile
 inline void launch_steal_finalize(const RenderParams& P, unsigned grid, hipStream_t stream) {
