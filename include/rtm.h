@@ -398,6 +398,55 @@ size_t rtm_denoise_work_bytes(int32_t width, int32_t height);
 int rtm_denoise(const rtm_denoise_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
 
+/* ---- variance-guided denoiser: the spatial part of SVGF (Schied et al. 2017) on top of the filter above, for frames whose
+ * noise is uneven (adaptive frames, late progressive previews).  The colour weight of rtm_denoise, one global sigma_color,
+ * becomes a luminance weight relative to each pixel's own standard deviation, estimated from the frame itself and carried
+ * through the levels, so that converged pixels keep their shading.  Inputs as rtm_denoise.  Arithmetic in float; g_s(p,q)
+ * is rtm_denoise's geometry weight g(p,q) at step s (the object test, the +inf miss rules, w_z with sigma_depth s, w_n,
+ * g = 1 for q == p), h = {1/16, 1/4, 3/8, 1/4, 1/16}, lum(e) = 0.2126 e_R + 0.7152 e_G + 0.0722 e_B:
+ *   1 demodulate  as rtm_denoise: a_p, e0_p = c_p / a_p
+ *   2 variance    l = lum(e0); over the taps q = (x + dx, y + dy), dx, dy in -3..3 (unstepped), taps outside the frame
+ *                 skipped, the sums dy outer, dx inner: u = g_1(p,q), d_q = l_q - l_p, U = sum u (>= 1: the centre tap has
+ *                 u = 1, d = 0), m1 = sum u d_q / U, m2 = sum u d_q^2 / U, v0_p = max(0, m2 - m1 m1).  The shift by l_p is
+ *                 part of the contract: it keeps the subtraction from cancelling in float.  variance_out_dev (if non-null)
+ *                 receives v0, for K = 0 too.
+ *   3 iterate     for i = 0 .. K-1, step s = 2^i, l = lum(e(i)):
+ *                 v~_p = sum k[dx] k[dy] v(i)_q / sum k[dx] k[dy] over dx, dy in -1..1 (unstepped), in-frame taps only,
+ *                 k = {1/4, 1/2, 1/4}, no geometry weight;
+ *                 w_l(p,q) = sigma_lum > 0 ? exp(-|l_p - l_q| / (sigma_lum sqrt(v~_p) + 1e-4f)) : 1 (only v~_p enters, never
+ *                 v~_q); w(p,q) = h[dx] h[dy] g_s(p,q) w_l(p,q), w(p,p) = h[2]^2, over q = p + s (dx, dy), dx, dy in -2..2,
+ *                 taps outside the frame skipped, dy outer;
+ *                 e(i+1)_p = sum w e(i)_q / sum w;  v(i+1)_p = sum w^2 v(i)_q / (sum w)^2
+ *   4 remodulate  out_p = e(K)_p a_p
+ *   K = 0 copies color to out_f32 bit for bit.  out_u8 (if non-null) is rtm_quantise of (double)out_f32, bit for bit.
+ * exp, sqrt and the divisions may be the device's fast forms: against a float64 evaluation of the steps above every output
+ * component is within 1e-4 max(1, |ref|), and so is variance_out.  No atomics: the same inputs give the same bits on every
+ * call, on any stream.
+ * Defaults: RTM_DENOISE_VAR_DEFAULTS below (what Renderer.Render(denoise="variance") and rtm_cli --denoise-variance use;
+ * SVGF's sigma_lum and K with rtm_denoise's sigma_normal and sigma_depth): iterations 5, sigma_lum 4,
+ * sigma_normal 64, sigma_depth 0.05. */
+typedef struct rtm_denoise_var_params {
+    int32_t iterations; /* K, 0..10 */
+    float sigma_lum;    /* >= 0, finite; 0 switches the luminance term off */
+    float sigma_normal; /* as rtm_denoise_params */
+    float sigma_depth;  /* as rtm_denoise_params */
+} rtm_denoise_var_params;
+#define RTM_DENOISE_VAR_DEFAULTS {5, 4.0f, 64.0f, 0.05f} /* an initializer of rtm_denoise_var_params */
+/* Bytes of the work buffer rtm_denoise_variance needs for a frame: 56 per pixel (rtm_denoise's three planes of 16-byte
+ * records and two variance planes of one float); 0 for a non-positive size, SIZE_MAX when the size does not fit a size_t. */
+size_t rtm_denoise_variance_work_bytes(int32_t width, int32_t height);
+/* Filters `color_dev` into out_f32_dev and / or out_u8_dev and writes v0 to variance_out_dev (DEVICE, height x width
+ * floats); any of the three may be null, not all: with both colour outputs null the call only estimates the variance.  The
+ * caller owns every buffer; work_dev (DEVICE, 16-byte aligned, rtm_denoise_variance_work_bytes bytes) holds the intermediate
+ * planes, so the call allocates nothing and only ENQUEUES its launches (K + 2; for K = 0 one, or three with a variance
+ * output) on `stream` of `device`.  It keeps no per-(device, stream) state and needs no serialisation.  Everything
+ * rtm_denoise refuses (with "both outputs null" read as "all three outputs null"), and variance_out_dev equal to color_dev,
+ * to work_dev or to out_f32_dev: RTM_ERR_INVALID_ARGUMENT, before any device call.  Added after RTM_ABI_VERSION 5 without
+ * changing it: callers look the symbols up. */
+int rtm_denoise_variance(const rtm_denoise_var_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                         const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                         float* variance_out_dev, void* stream);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);

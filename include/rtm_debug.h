@@ -63,6 +63,13 @@ int rtm_debug_zero_term_facts(const rtm_sphere* spheres, size_t n, uint64_t fact
 /* isolated nearest-hit / shading loops timed with s_memtime (profiles/component_bench.py) */
 int rtm_debug_component_bench(int which, const rtm_sphere* spheres, size_t n, int reps, int blocks, int lds_pad,
                               double* cycles_per_rep);
+/* One form of rtm_denoise_variance's variance kernel alone (profiles/denoise_variance_pass.py, and the tests that hold the
+ * forms against each other): form 0 takes every tap from L2, 1 / 2 stage a tile of 64 x 4 / 64 x 8 pixels and its halo in
+ * LDS; the call ships one of them.  DEVICE buffers, unlike the hooks above: work_dev holds the records that a
+ * rtm_denoise_variance call with K = 0 and a variance output left there for the same frame, guides and sigmas (only the
+ * null-ness of the guide pointers is read); variance_out_dev receives v0.  Only enqueues on `stream`. */
+int rtm_debug_denoise_variance_kernel(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
+                                      const rtm_aov_buffers* guide_dev, void* work_dev, float* variance_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

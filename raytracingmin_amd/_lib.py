@@ -77,6 +77,10 @@ class rtm_denoise_params(C.Structure):  # include/rtm.h: rtm_denoise
     _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class rtm_denoise_var_params(C.Structure):  # include/rtm.h: rtm_denoise_variance
+    _fields_ = [("iterations", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 # every symbol include/rtm.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -109,6 +113,9 @@ SIGNATURES = {
     "rtm_denoise_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_denoise": (C.c_int, [_P(rtm_denoise_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_denoise_variance_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtm_denoise_variance": (C.c_int, [_P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),
@@ -155,6 +162,8 @@ DEBUG_SIGNATURES = {
     "rtm_debug_zero_term_facts": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtm_debug_grid_build": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rtm_debug_denoise_variance_kernel": (C.c_int, [C.c_int, _P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int,
+                                                    _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_debug_component_bench": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(C.c_double)]),
 }

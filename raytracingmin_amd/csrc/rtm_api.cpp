@@ -102,6 +102,13 @@ int rtm_denoise(const rtm_denoise_params* params, int32_t width, int32_t height,
                 const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
     RTM_GUARD(rtm::denoise(params, width, height, device, color_dev, guide_dev, work_dev, out_f32_dev, out_u8_dev, stream))
 }
+size_t rtm_denoise_variance_work_bytes(int32_t width, int32_t height) { return rtm::denoise_variance_work_bytes(width, height); }
+int rtm_denoise_variance(const rtm_denoise_var_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                         const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                         float* variance_out_dev, void* stream) {
+    RTM_GUARD(rtm::denoise_variance(params, width, height, device, color_dev, guide_dev, work_dev, out_f32_dev, out_u8_dev,
+                                    variance_out_dev, stream))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {
@@ -152,6 +159,10 @@ int rtm_debug_component_bench(int which, const rtm_sphere* sp, size_t n, int rep
 int rtm_debug_wf_nearest(int kind, const rtm_sphere* sp, size_t n, const double* org, const double* dir, size_t n_rays,
                          int32_t* out_id, double* out_t) {
     RTM_GUARD(rtm::wf_nearest_probe(kind, sp, n, org, dir, n_rays, out_id, out_t))
+}
+int rtm_debug_denoise_variance_kernel(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
+                                      const rtm_aov_buffers* guide_dev, void* work_dev, float* variance_out_dev, void* stream) {
+    RTM_GUARD(rtm::denoise_variance_kernel_probe(form, params, width, height, device, guide_dev, work_dev, variance_out_dev, stream))
 }
 int rtm_debug_selfcheck(int kind, unsigned long long* mismatches) { RTM_GUARD(rtm::selfcheck(kind, mismatches)) }
 int rtm_debug_grid_nearest(const rtm_sphere* sp, size_t n, const double* org, const double* dir, size_t n_rays,

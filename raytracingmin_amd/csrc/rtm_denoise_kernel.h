@@ -67,7 +67,8 @@ __global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_prepass_kernel(
 
 // Level i: e_out(p) = sum_q w(p, q) e_in(q) / sum_q w(p, q) over q = p + s (dx, dy), dx, dy in -2..2, taps outside the
 // frame skipped.  color_scale = 4^i / sigma_c^2 * log2(e), depth_scale = sigma_z * s.  LAST: out = e_out * a instead of
-// the record store.
+// the record store.  (The geometry weight below has a twin, dn_geometry of rtm_denoise_var_kernel.h, kept apart so that this
+// kernel's code does not move: a change to one belongs in the other.)
 template <bool LAST>
 __global__ __launch_bounds__(kDnTileX * kDnTileY) void denoise_level_kernel(
     const DenoiseFrame F, const int s, const float color_scale, const float depth_scale, const float4* __restrict__ rec_in,

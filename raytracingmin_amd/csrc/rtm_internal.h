@@ -47,6 +47,11 @@ int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options
 size_t denoise_work_bytes(int32_t width, int32_t height);
 int denoise(const rtm_denoise_params* params, int32_t width, int32_t height, int device, const float* color,
             const rtm_aov_buffers* guide, void* work, float* out32, uint8_t* out8, void* stream);
+size_t denoise_variance_work_bytes(int32_t width, int32_t height);
+int denoise_variance(const rtm_denoise_var_params* params, int32_t width, int32_t height, int device, const float* color,
+                     const rtm_aov_buffers* guide, void* work, float* out32, uint8_t* out8, float* var_out, void* stream);
+int denoise_variance_kernel_probe(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
+                                  const rtm_aov_buffers* guide, void* work, float* var_out, void* stream);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);

@@ -9,6 +9,7 @@
 //           [--passes N]                         (progressive: the frame's samples in N passes on one GPU, same image)
 //           [--aov]                              (first-hit feature buffers next to the image: STEM_depth/_normal/_albedo.pfm, .bmp)
 //           [--denoise]                          (the à-trous denoiser next to the image: STEM_denoised.bmp, .jpg)
+//           [--denoise-variance]                 (the variance-guided one: STEM_denoised_var.bmp, .jpg, STEM_variance.pfm)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -49,7 +50,10 @@ static void usage() {
         "--adaptive T [--adaptive-min M] : tile-adaptive sampling on one GPU (rtm_render_adaptive, threshold T, first pass\n"
         "             M samples, default 16); also writes STEM_spp.pfm, the samples each pixel traced\n"
         "--denoise : also write the frame denoised on one GPU (rtm_denoise at its default parameters, guided by the\n"
-        "            frame's first-hit feature buffers): STEM_denoised.bmp and STEM_denoised.jpg\n");
+        "            frame's first-hit feature buffers): STEM_denoised.bmp and STEM_denoised.jpg\n"
+        "--denoise-variance : also write the frame through the variance-guided denoiser on one GPU (rtm_denoise_variance at\n"
+        "            its default parameters; for frames whose noise is uneven, such as --adaptive's): STEM_denoised_var.bmp,\n"
+        "            STEM_denoised_var.jpg and STEM_variance.pfm, the per-pixel variance estimate\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -61,7 +65,7 @@ int main(int argc, char* argv[]) {
     std::string json_file = "settingData.json", stem = "result";
     int width = 0, height = 0, samples = 0, super_samples = 0, spp = 0;
     int mode = RTM_MODE_REPAIRED, max_bounces = -1, device = 0, gpus = 1, virtual_strips = 0, host_trig = 1, force_rccl = 0;
-    int passes = 0, aov = 0, denoise = 0, adaptive = 0, adaptive_min = 16;
+    int passes = 0, aov = 0, denoise = 0, denoise_variance = 0, adaptive = 0, adaptive_min = 16;
     float adaptive_threshold = 0.f;
     std::string dump_f32;
     unsigned long long seed = 0x5EED;
@@ -100,6 +104,7 @@ int main(int argc, char* argv[]) {
         else if (c == "--force-rccl") force_rccl = 1;
         else if (c == "--aov") aov = 1;
         else if (c == "--denoise") denoise = 1;
+        else if (c == "--denoise-variance") denoise_variance = 1;
         else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
         else if (c == "--seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 0);
         else if (c == "--out" && i + 1 < argc) stem = argv[++i];
@@ -128,6 +133,11 @@ int main(int argc, char* argv[]) {
     }
     if (denoise && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
         std::fprintf(stderr, "--denoise runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
+        return 2;
+    }
+    if (denoise_variance && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--denoise-variance runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or "
+                             "--force-rccl\n");
         return 2;
     }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
@@ -168,7 +178,7 @@ int main(int argc, char* argv[]) {
 
     const size_t vals = (size_t)st.width * st.height * 3;
     std::vector<uint8_t> rgb8(vals);
-    std::vector<float> rgb32(dump_f32.empty() && !denoise ? 0 : vals);
+    std::vector<float> rgb32(dump_f32.empty() && !denoise && !denoise_variance ? 0 : vals);
     rtm_stats stats;
     std::vector<uint32_t> tile_samples;
     if (adaptive) {
@@ -252,6 +262,16 @@ int main(int argc, char* argv[]) {
             return 1;
         }
         std::printf("denoise: %s_denoised.bmp, %s_denoised.jpg\n", stem.c_str(), stem.c_str());
+    }
+    if (denoise_variance) {
+        std::string err;
+        rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, rgb32.data(), stem, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "denoise-variance failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        std::printf("denoise-variance: %s_denoised_var.bmp, %s_denoised_var.jpg, %s_variance.pfm\n", stem.c_str(), stem.c_str(),
+                    stem.c_str());
     }
     return 0;
 }

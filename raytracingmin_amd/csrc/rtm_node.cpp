@@ -553,3 +553,72 @@ int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, s
     }
     return RTM_OK;
 }
+
+// --denoise-variance (rtm_node.h): as rtm_node_write_denoised with rtm_denoise_variance, plus the variance plane.
+int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
+                                     const float* f32_host, const std::string& stem, std::string& err) {
+    if (hipSetDevice(opt->device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(opt->device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    rtm_scene* scene = nullptr;
+    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
+    if (rc != RTM_OK) {
+        err = std::string("scene: ") + rtm_last_error_detail();
+        return rc;
+    }
+    const size_t pix = (size_t)st->width * st->height;
+    const size_t work_bytes = rtm_denoise_variance_work_bytes(st->width, st->height);
+    rtm_aov_buffers dev;
+    std::memset(&dev, 0, sizeof dev);
+    float *color = nullptr, *var = nullptr;
+    uint8_t* out8 = nullptr;
+    void* work = nullptr;
+    if (hipMalloc((void**)&dev.depth, pix * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&dev.normal, pix * 3 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&dev.albedo, pix * 3 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&dev.object, pix * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
+        hipMalloc((void**)&var, pix * sizeof(float)) != hipSuccess || hipMalloc(&work, work_bytes) != hipSuccess) {
+        err = "no device memory for the denoiser's buffers";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && hipMemcpy(color, f32_host, pix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        err = "copying the frame to the device failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        rc = rtm_render_aov(st, scene, opt, &dev, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    if (rc == RTM_OK) {
+        const rtm_denoise_var_params prm = RTM_DENOISE_VAR_DEFAULTS;
+        rc = rtm_denoise_variance(&prm, st->width, st->height, opt->device, color, &dev, work, nullptr, out8, var, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    std::vector<uint8_t> rgb8(pix * 3);
+    std::vector<float> variance(pix);
+    if (rc == RTM_OK && (hipMemcpy(rgb8.data(), out8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(variance.data(), var, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
+        err = "copying the denoised frame back failed";
+        rc = RTM_ERR_HIP;
+    }
+    (void)hipFree(dev.depth);
+    (void)hipFree(dev.normal);
+    (void)hipFree(dev.albedo);
+    (void)hipFree(dev.object);
+    (void)hipFree(color);
+    (void)hipFree(out8);
+    (void)hipFree(var);
+    (void)hipFree(work);
+    (void)rtm_scene_destroy(scene);
+    if (rc != RTM_OK) return rc;
+    const bool ok = rtm_write_jpg((stem + "_denoised_var.jpg").c_str(), st->width, st->height, 3, rgb8.data(), 60) == 1 &&
+                    rtm_write_bmp((stem + "_denoised_var.bmp").c_str(), st->width, st->height, 3, rgb8.data()) == 1 &&
+                    rtm_write_pfm((stem + "_variance.pfm").c_str(), st->width, st->height, 1, variance.data()) == 1;
+    if (!ok) {
+        err = "cannot write the variance-guided denoised files of " + stem;
+        return RTM_ERR_IO;
+    }
+    return RTM_OK;
+}

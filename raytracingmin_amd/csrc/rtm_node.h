@@ -32,3 +32,8 @@ int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t
 // and <stem>_denoised.bmp.
 int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
                             const float* f32_host, const std::string& stem, std::string& err);
+// The same frame through the variance-guided filter (rtm_denoise_variance at its default parameters, rtm_cli
+// --denoise-variance): <stem>_denoised_var.jpg (quality 60), <stem>_denoised_var.bmp and <stem>_variance.pfm, the per-pixel
+// variance estimate v0.
+int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
+                                     const float* f32_host, const std::string& stem, std::string& err);

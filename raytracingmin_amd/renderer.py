@@ -356,8 +356,12 @@ class Renderer:
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
         denoise=True also writes <fileName>_denoised.jpg (q=60) and _denoised.bmp: the frame's f32 filtered by denoise() at
         the default parameters, guided by its AOVs (write_denoised); the plain files and self.image do not change.
+        denoise="variance" writes instead <fileName>_denoised_var.jpg / .bmp and <fileName>_variance.pfm: the frame filtered
+        by denoise_variance() at its default parameters, and its per-pixel variance estimate (write_denoised_variance).
         adaptive=T renders tile-adaptively (Renderer.adaptive, threshold T, the default min_samples) and also writes
         <fileName>_spp.pfm, the per-pixel sample count (write_spp); the AOV and denoised files then come from that frame."""
+        if isinstance(denoise, str) and denoise != "variance":
+            raise ValueError(f'denoise is False, True or "variance", got {denoise!r}')
         if adaptive is not None:
             if passes > 1:
                 raise ValueError("adaptive and passes > 1 do not combine")
@@ -383,7 +387,9 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write {fileName}.jpg/.bmp")
         if aov:
             self.write_aov(fileName)
-        if denoise:
+        if denoise == "variance":
+            self.write_denoised_variance(fileName)
+        elif denoise:
             self.write_denoised(fileName)
         return rgb8
 
@@ -404,6 +410,25 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write {fileName}_denoised.jpg/.bmp")
         return rgb8
 
+    def write_denoised_variance(self, fileName):
+        """<fileName>_denoised_var.jpg (q=60), <fileName>_denoised_var.bmp and <fileName>_variance.pfm: self.image rounded to
+        float like out_f32, filtered by denoise_variance() at the default parameters with the frame's four AOVs as guides,
+        and the variance estimate v0 — what rtm_cli --denoise-variance writes.  Returns the (H, W, 3) uint8 pixels."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        out = denoise_variance(color, self.render_aov(), want=("u8", "var"))
+        rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
+        var = np.ascontiguousarray(out["var"].cpu().numpy())
+        L = _lib.lib()
+        H, W = self.data.height, self.data.width
+        ok = L.rtm_write_jpg(os.fsencode(fileName + "_denoised_var.jpg"), W, H, 3, rgb8.ctypes.data, 60) \
+            and L.rtm_write_bmp(os.fsencode(fileName + "_denoised_var.bmp"), W, H, 3, rgb8.ctypes.data) \
+            and L.rtm_write_pfm(os.fsencode(fileName + "_variance.pfm"), W, H, 1, var.ctypes.data)
+        if not ok:
+            raise _lib.RtmError(-3, f"could not write {fileName}_denoised_var.jpg/.bmp or {fileName}_variance.pfm")
+        return rgb8
+
 
 # include/rtm.h: RTM_DENOISE_DEFAULTS
 DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 16.0, "sigma_normal": 64.0, "sigma_depth": 0.05}
@@ -417,12 +442,34 @@ def denoise(color, aov=None, iterations=DENOISE_DEFAULTS["iterations"], sigma_co
     (H, W) int32), missing planes switch their terms off.  Returns {"f32": (H, W, 3) float32, "u8": (H, W, 3) uint8} for
     the names in `want`.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current
     stream) with a work buffer allocated here; nothing waits for it."""
+    return _denoise_call("rtm_denoise", _lib.rtm_denoise_params(int(iterations), float(sigma_color), float(sigma_normal),
+                                                               float(sigma_depth)), color, aov, want, ("f32", "u8"), stream)
+
+
+# include/rtm.h: RTM_DENOISE_VAR_DEFAULTS
+DENOISE_VAR_DEFAULTS = {"iterations": 5, "sigma_lum": 4.0, "sigma_normal": 64.0, "sigma_depth": 0.05}
+
+
+def denoise_variance(color, aov=None, iterations=DENOISE_VAR_DEFAULTS["iterations"], sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"],
+                     sigma_normal=DENOISE_VAR_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_VAR_DEFAULTS["sigma_depth"],
+                     want=("f32",), stream=None):
+    """The variance-guided à-trous denoiser (include/rtm.h: rtm_denoise_variance) on the device, for frames whose noise is
+    uneven: arguments and result as denoise(), with sigma_lum (relative to each pixel's own standard deviation) in place of
+    sigma_color, and "var" accepted in `want`: the (H, W) float32 variance estimate v0 of the demodulated luminance.  With
+    want=("var",) alone nothing is filtered."""
+    return _denoise_call("rtm_denoise_variance", _lib.rtm_denoise_var_params(int(iterations), float(sigma_lum), float(sigma_normal),
+                                                                            float(sigma_depth)), color, aov, want,
+                         ("f32", "u8", "var"), stream)
+
+
+def _denoise_call(entry, prm, color, aov, want, outputs, stream):
+    """denoise() and denoise_variance(): the checks of the tensors, the work buffer and outputs, and the library call."""
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError("denoise needs a HIP device; there is no CPU fallback")
-    unknown = set(want) - {"f32", "u8"}
+    unknown = set(want) - set(outputs)
     if unknown or not want:
-        raise ValueError(f"want names outputs among ('f32', 'u8'), got {tuple(want)}")
+        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
     if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
             and color.shape[2] == 3 and color.is_contiguous()):
         raise ValueError("color must be a contiguous (H, W, 3) float32 CUDA tensor")
@@ -450,17 +497,19 @@ def denoise(color, aov=None, iterations=DENOISE_DEFAULTS["iterations"], sigma_co
     else:
         s = torch.cuda.ExternalStream(int(stream), device=dev)
     L = _lib.lib()
-    prm = _lib.rtm_denoise_params(int(iterations), float(sigma_color), float(sigma_normal), float(sigma_depth))
     with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
-        work = torch.empty(max(1, L.rtm_denoise_work_bytes(W, H)), dtype=torch.uint8, device=dev)
+        work = torch.empty(max(1, getattr(L, entry + "_work_bytes")(W, H)), dtype=torch.uint8, device=dev)
         out = {}
         if "f32" in want:
             out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
         if "u8" in want:
             out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        if "var" in want:
+            out["var"] = torch.empty((H, W), dtype=torch.float32, device=dev)
     ptr = lambda k: out[k].data_ptr() if k in out else None
-    _lib.check(L.rtm_denoise(C.byref(prm), W, H, dev.index, color.data_ptr(), C.byref(guides), work.data_ptr(),
-                             ptr("f32"), ptr("u8"), C.c_void_p(s.cuda_stream)), "rtm_denoise")
+    tail = (ptr("var"),) if "var" in outputs else ()
+    _lib.check(getattr(L, entry)(C.byref(prm), W, H, dev.index, color.data_ptr(), C.byref(guides), work.data_ptr(),
+                                 ptr("f32"), ptr("u8"), *tail, C.c_void_p(s.cuda_stream)), entry)
     return out
 
 
