@@ -447,6 +447,67 @@ int rtm_denoise_variance(const rtm_denoise_var_params* params, int32_t width, in
                          const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev,
                          float* variance_out_dev, void* stream);
 
+/* ---- display transform: the last stage before an 8-bit file — exposure (fixed, or Reinhard's log-average key), a tone
+ * curve, the sRGB transfer function and an ordered-dither store.  Opt-in: rtm_quantise and the out_u8 of the renders and
+ * the denoisers stay the reference's bytes.
+ * Input: color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32; 4-byte alignment is enough).  Arithmetic in
+ * float unless stated, without contraction.  lum(c) = (0.2126 c_R + 0.7152 c_G) + 0.0722 c_B (the denoiser's weights).
+ *   1 statistics  over the whole frame.  A pixel COUNTS iff its three components are finite; Y_p = max(lum(c_p), 0); n the
+ *                 number of counting pixels; L_avg = exp((sum log(1e-4f + Y_p)) / n) (the logarithms float, their sum
+ *                 carried in DOUBLE in an order fixed by the frame size alone); L_max = max Y_p; n == 0: L_avg = L_max = 1.
+ *                 E = exp2(ev) (auto_exposure ? key / L_avg : 1).  stats_out_dev (nullable, DEVICE, one rtm_tonemap_stats)
+ *                 receives {L_avg, L_max, E, n}.  The statistics are skipped when nothing needs them: no auto exposure,
+ *                 not (REINHARD with white == 0) and no stats_out_dev.
+ *   2 map         per pixel, x = max(c E, 0) per channel, then
+ *                   CLAMP     t = x
+ *                   REINHARD  (extended, on luminance, chroma kept) Yx = lum(x), W = white > 0 ? white : E L_max;
+ *                             t = x ((1 + Yx / W^2) / (1 + Yx)) when Yx > 0 && W > 0, else t = x
+ *                   ACES      (Narkowicz's fit) per channel t = x (2.51 x + 0.03) / (x (2.43 x + 0.59) + 0.14)
+ *                 then t = min(max(t, 0), 1)
+ *   3 transfer    SRGB: t <= 0.0031308f ? 12.92f t : 1.055f t^(1/2.4) - 0.055f;  LINEAR: unchanged
+ *   4 non-finite  a pixel that does not count is (0, 0, 0) in both outputs
+ *   5 outputs     out_f32 = t.  out_u8 without dither is rtm_quantise of (double)out_f32, bit for bit; with dither it is
+ *                 (uint8_t)min(255.0f, floorf(255.0f t + (B(x & 7, y & 7) + 0.5f) / 64.0f)), B the 8 x 8 Bayer index
+ *                   B(x, y) = sum over i = 0..2 of (((x>>i) ^ (y>>i)) & 1) << (2(2-i)+1) | ((y>>i) & 1) << (2(2-i))
+ *                 (a permutation of 0..63 whose 2 x 2 core is [[0, 2], [3, 1]]): the reference's truncation becomes a store
+ *                 whose mean over an aligned 8 x 8 block is 255 t.
+ *   {CLAMP, LINEAR, auto_exposure 0, dither 0, ev 0} gives the u8 bytes rtm_quantise gives for the (finite) input.
+ * exp, log, exp2, pow and the divisions may be the device's fast forms: against a float64 evaluation of the steps above
+ * every out_f32 component and the three float statistics are within 1e-4 max(1, |ref|); pixels is exact; out_u8 is exact
+ * given the call's own out_f32.  No atomics: the same inputs give the same bits on every call, on any stream.
+ * work_dev: DEVICE, 256-byte aligned, rtm_tonemap_work_bytes = round256(16 ceil(width height / 4096)) + 256 bytes (one
+ * partial per 4096 pixels and the final statistics); 0 for a non-positive size, SIZE_MAX when the frame itself (12 bytes a
+ * pixel) does not fit a size_t.  Required even when the statistics are skipped.  The call allocates nothing, keeps no
+ * per-(device, stream) state, needs no serialisation and only ENQUEUES: three launches, one when the statistics are
+ * skipped, two when stats_out_dev is the only output.  out_f32_dev == color_dev (in place) is allowed: the statistics are
+ * read before the map, in stream order.  Null params, color_dev or work_dev, all three outputs null, a non-positive size,
+ * op or transfer out of range, auto_exposure or dither not 0 or 1, a NaN or infinite ev, key or white, |ev| > 32, key <= 0,
+ * white < 0, a misaligned work_dev, work_dev equal to any other buffer, stats_out_dev equal to color_dev or out_f32_dev, a
+ * negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.
+ * Defaults: RTM_TONEMAP_DEFAULTS below (what Renderer.Render(tonemap=True) and rtm_cli --display use).
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+enum { RTM_TONEMAP_CLAMP = 0, RTM_TONEMAP_REINHARD = 1, RTM_TONEMAP_ACES = 2 };
+enum { RTM_TRANSFER_LINEAR = 0, RTM_TRANSFER_SRGB = 1 };
+typedef struct rtm_tonemap_params {
+    int32_t op;            /* RTM_TONEMAP_*                                                       */
+    int32_t transfer;      /* RTM_TRANSFER_*                                                      */
+    int32_t auto_exposure; /* 0: E = 2^ev;  1: E = 2^ev * key / L_avg                             */
+    int32_t dither;        /* 0: u8 = rtm_quantise;  1: ordered 8x8 dither (above)                */
+    float ev;              /* finite, |ev| <= 32                                                  */
+    float key;             /* finite, > 0 (0.18: middle grey)                                     */
+    float white;           /* REINHARD only: finite, >= 0; 0 = the exposed frame maximum E*L_max  */
+} rtm_tonemap_params;
+#define RTM_TONEMAP_DEFAULTS {RTM_TONEMAP_ACES, RTM_TRANSFER_SRGB, 1, 1, 0.0f, 0.18f, 0.0f} /* of rtm_tonemap_params */
+typedef struct rtm_tonemap_stats {
+    float log_average;   /* L_avg */
+    float max_luminance; /* L_max */
+    float exposure;      /* E */
+    uint32_t pixels;     /* n */
+} rtm_tonemap_stats;
+size_t rtm_tonemap_work_bytes(int32_t width, int32_t height);
+int rtm_tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, rtm_tonemap_stats* stats_out_dev, void* stream);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);

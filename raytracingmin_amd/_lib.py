@@ -81,6 +81,19 @@ class rtm_denoise_var_params(C.Structure):  # include/rtm.h: rtm_denoise_varianc
     _fields_ = [("iterations", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+TONEMAP_OPS = {"clamp": 0, "reinhard": 1, "aces": 2}  # include/rtm.h: RTM_TONEMAP_*
+TRANSFERS = {"linear": 0, "srgb": 1}  # RTM_TRANSFER_*
+
+
+class rtm_tonemap_params(C.Structure):  # include/rtm.h: rtm_tonemap
+    _fields_ = [("op", C.c_int32), ("transfer", C.c_int32), ("auto_exposure", C.c_int32), ("dither", C.c_int32),
+                ("ev", C.c_float), ("key", C.c_float), ("white", C.c_float)]
+
+
+class rtm_tonemap_stats(C.Structure):  # what rtm_tonemap leaves in stats_out_dev
+    _fields_ = [("log_average", C.c_float), ("max_luminance", C.c_float), ("exposure", C.c_float), ("pixels", C.c_uint32)]
+
+
 # every symbol include/rtm.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -116,6 +129,9 @@ SIGNATURES = {
     "rtm_denoise_variance_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_denoise_variance": (C.c_int, [_P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_tonemap_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtm_tonemap": (C.c_int, [_P(rtm_tonemap_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),

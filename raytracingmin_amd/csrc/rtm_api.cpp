@@ -109,6 +109,11 @@ int rtm_denoise_variance(const rtm_denoise_var_params* params, int32_t width, in
     RTM_GUARD(rtm::denoise_variance(params, width, height, device, color_dev, guide_dev, work_dev, out_f32_dev, out_u8_dev,
                                     variance_out_dev, stream))
 }
+size_t rtm_tonemap_work_bytes(int32_t width, int32_t height) { return rtm::tonemap_work_bytes(width, height); }
+int rtm_tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, rtm_tonemap_stats* stats_out_dev, void* stream) {
+    RTM_GUARD(rtm::tonemap(params, width, height, device, color_dev, work_dev, out_f32_dev, out_u8_dev, stats_out_dev, stream))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {

@@ -52,6 +52,10 @@ int denoise_variance(const rtm_denoise_var_params* params, int32_t width, int32_
                      const rtm_aov_buffers* guide, void* work, float* out32, uint8_t* out8, float* var_out, void* stream);
 int denoise_variance_kernel_probe(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
                                   const rtm_aov_buffers* guide, void* work, float* var_out, void* stream);
+// display transform (rtm_tonemap.hip)
+size_t tonemap_work_bytes(int32_t width, int32_t height);
+int tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int device, const float* color, void* work,
+            float* out32, uint8_t* out8, rtm_tonemap_stats* stats_out, void* stream);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);

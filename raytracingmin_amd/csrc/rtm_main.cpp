@@ -10,6 +10,8 @@
 //           [--aov]                              (first-hit feature buffers next to the image: STEM_depth/_normal/_albedo.pfm, .bmp)
 //           [--denoise]                          (the à-trous denoiser next to the image: STEM_denoised.bmp, .jpg)
 //           [--denoise-variance]                 (the variance-guided one: STEM_denoised_var.bmp, .jpg, STEM_variance.pfm)
+//           [--display [clamp|reinhard|aces]] [--exposure auto|EV] [--linear] [--no-dither]
+//                                                (the display transform of the last stage: STEM_display.bmp, .jpg)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -53,7 +55,11 @@ static void usage() {
         "            frame's first-hit feature buffers): STEM_denoised.bmp and STEM_denoised.jpg\n"
         "--denoise-variance : also write the frame through the variance-guided denoiser on one GPU (rtm_denoise_variance at\n"
         "            its default parameters; for frames whose noise is uneven, such as --adaptive's): STEM_denoised_var.bmp,\n"
-        "            STEM_denoised_var.jpg and STEM_variance.pfm, the per-pixel variance estimate\n");
+        "            STEM_denoised_var.jpg and STEM_variance.pfm, the per-pixel variance estimate\n"
+        "--display [clamp|reinhard|aces] : also write the display transform (rtm_tonemap; default aces) of the last stage\n"
+        "            asked for on one GPU (the --denoise-variance frame, else the --denoise frame, else the frame itself):\n"
+        "            STEM_display.bmp and STEM_display.jpg.  --exposure auto|EV : Reinhard's log-average key 0.18 (default) or\n"
+        "            a fixed number of stops; --linear : no sRGB transfer function; --no-dither : the truncating 8-bit store\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -67,6 +73,8 @@ int main(int argc, char* argv[]) {
     int mode = RTM_MODE_REPAIRED, max_bounces = -1, device = 0, gpus = 1, virtual_strips = 0, host_trig = 1, force_rccl = 0;
     int passes = 0, aov = 0, denoise = 0, denoise_variance = 0, adaptive = 0, adaptive_min = 16;
     float adaptive_threshold = 0.f;
+    int display = 0;
+    rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
     std::string dump_f32;
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
@@ -105,6 +113,29 @@ int main(int argc, char* argv[]) {
         else if (c == "--aov") aov = 1;
         else if (c == "--denoise") denoise = 1;
         else if (c == "--denoise-variance") denoise_variance = 1;
+        else if (c == "--display") {
+            display = 1;
+            const std::string m = i + 1 < argc ? argv[i + 1] : "";
+            if (m == "clamp") display_prm.op = RTM_TONEMAP_CLAMP;
+            else if (m == "reinhard") display_prm.op = RTM_TONEMAP_REINHARD;
+            else if (m == "aces") display_prm.op = RTM_TONEMAP_ACES;
+            if (m == "clamp" || m == "reinhard" || m == "aces") ++i;  // anything else is the next option: the default curve
+        } else if (c == "--exposure" && i + 1 < argc) {
+            const std::string m = argv[++i];
+            char* end = nullptr;
+            const float ev = (float)std::strtod(m.c_str(), &end);  // (double first, as Python's float() then C float)
+            if (m == "auto") {
+                display_prm.auto_exposure = 1;
+                display_prm.ev = 0.0f;
+            } else if (end != m.c_str() && *end == '\0') {
+                display_prm.auto_exposure = 0;
+                display_prm.ev = ev;
+            } else {
+                std::fprintf(stderr, "--exposure takes auto or a number of stops, got %s\n", m.c_str());
+                return 2;
+            }
+        } else if (c == "--linear") display_prm.transfer = RTM_TRANSFER_LINEAR;
+        else if (c == "--no-dither") display_prm.dither = 0;
         else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
         else if (c == "--seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 0);
         else if (c == "--out" && i + 1 < argc) stem = argv[++i];
@@ -138,6 +169,10 @@ int main(int argc, char* argv[]) {
     if (denoise_variance && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
         std::fprintf(stderr, "--denoise-variance runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or "
                              "--force-rccl\n");
+        return 2;
+    }
+    if (display && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--display runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
         return 2;
     }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
@@ -178,7 +213,7 @@ int main(int argc, char* argv[]) {
 
     const size_t vals = (size_t)st.width * st.height * 3;
     std::vector<uint8_t> rgb8(vals);
-    std::vector<float> rgb32(dump_f32.empty() && !denoise && !denoise_variance ? 0 : vals);
+    std::vector<float> rgb32(dump_f32.empty() && !denoise && !denoise_variance && !display ? 0 : vals);
     rtm_stats stats;
     std::vector<uint32_t> tile_samples;
     if (adaptive) {
@@ -254,9 +289,11 @@ int main(int argc, char* argv[]) {
         std::printf("aov: %s_depth.pfm, %s_normal.pfm, %s_albedo.pfm, %s_normal.bmp, %s_albedo.bmp\n", stem.c_str(), stem.c_str(),
                     stem.c_str(), stem.c_str(), stem.c_str());
     }
+    std::vector<float> shown;  // the float frame of the last stage, when --display follows a denoiser
     if (denoise) {
         std::string err;
-        rc = rtm_node_write_denoised(&st, spheres.data(), n, &opt, rgb32.data(), stem, err);
+        rc = rtm_node_write_denoised(&st, spheres.data(), n, &opt, rgb32.data(), stem, err,
+                                     display && !denoise_variance ? &shown : nullptr);
         if (rc != RTM_OK) {
             std::fprintf(stderr, "denoise failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
             return 1;
@@ -265,13 +302,24 @@ int main(int argc, char* argv[]) {
     }
     if (denoise_variance) {
         std::string err;
-        rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, rgb32.data(), stem, err);
+        rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, rgb32.data(), stem, err, display ? &shown : nullptr);
         if (rc != RTM_OK) {
             std::fprintf(stderr, "denoise-variance failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
             return 1;
         }
         std::printf("denoise-variance: %s_denoised_var.bmp, %s_denoised_var.jpg, %s_variance.pfm\n", stem.c_str(), stem.c_str(),
                     stem.c_str());
+    }
+    if (display) {
+        std::string err;
+        rtm_tonemap_stats ts;
+        rc = rtm_node_write_display(&st, opt.device, &display_prm, shown.empty() ? rgb32.data() : shown.data(), stem, &ts, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",
+                    stem.c_str(), stem.c_str(), (double)ts.log_average, (double)ts.max_luminance, (double)ts.exposure, ts.pixels);
     }
     return 0;
 }

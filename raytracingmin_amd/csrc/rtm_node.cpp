@@ -491,7 +491,7 @@ int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t
 // --denoise (rtm_node.h): the frame's AOVs (rtm_render_aov), then rtm_denoise of its f32 at the default parameters on the
 // default stream, then the two files.
 int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
-                            const float* f32_host, const std::string& stem, std::string& err) {
+                            const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* f32_out) {
     if (hipSetDevice(opt->device) != hipSuccess) {
         err = "no HIP device " + std::to_string(opt->device);
         return RTM_ERR_NO_DEVICE;
@@ -506,7 +506,7 @@ int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, s
     const size_t work_bytes = rtm_denoise_work_bytes(st->width, st->height);
     rtm_aov_buffers dev;
     std::memset(&dev, 0, sizeof dev);
-    float* color = nullptr;
+    float *color = nullptr, *out32 = nullptr;
     uint8_t* out8 = nullptr;
     void* work = nullptr;
     if (hipMalloc((void**)&dev.depth, pix * sizeof(float)) != hipSuccess ||
@@ -514,7 +514,7 @@ int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, s
         hipMalloc((void**)&dev.albedo, pix * 3 * sizeof(float)) != hipSuccess ||
         hipMalloc((void**)&dev.object, pix * sizeof(int32_t)) != hipSuccess ||
         hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
-        hipMalloc(&work, work_bytes) != hipSuccess) {
+        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) || hipMalloc(&work, work_bytes) != hipSuccess) {
         err = "no device memory for the denoiser's buffers";
         rc = RTM_ERR_HIP;
     }
@@ -528,7 +528,7 @@ int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, s
     }
     if (rc == RTM_OK) {
         const rtm_denoise_params prm = RTM_DENOISE_DEFAULTS;
-        rc = rtm_denoise(&prm, st->width, st->height, opt->device, color, &dev, work, nullptr, out8, nullptr);
+        rc = rtm_denoise(&prm, st->width, st->height, opt->device, color, &dev, work, out32, out8, nullptr);
         if (rc != RTM_OK) err = rtm_last_error_detail();
     }
     std::vector<uint8_t> rgb8(pix * 3);
@@ -536,11 +536,19 @@ int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, s
         err = "copying the denoised frame back failed";
         rc = RTM_ERR_HIP;
     }
+    if (rc == RTM_OK && f32_out) {
+        f32_out->resize(pix * 3);
+        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            err = "copying the denoised frame back failed";
+            rc = RTM_ERR_HIP;
+        }
+    }
     (void)hipFree(dev.depth);
     (void)hipFree(dev.normal);
     (void)hipFree(dev.albedo);
     (void)hipFree(dev.object);
     (void)hipFree(color);
+    (void)hipFree(out32);
     (void)hipFree(out8);
     (void)hipFree(work);
     (void)rtm_scene_destroy(scene);
@@ -556,7 +564,8 @@ int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, s
 
 // --denoise-variance (rtm_node.h): as rtm_node_write_denoised with rtm_denoise_variance, plus the variance plane.
 int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
-                                     const float* f32_host, const std::string& stem, std::string& err) {
+                                     const float* f32_host, const std::string& stem, std::string& err,
+                                     std::vector<float>* f32_out) {
     if (hipSetDevice(opt->device) != hipSuccess) {
         err = "no HIP device " + std::to_string(opt->device);
         return RTM_ERR_NO_DEVICE;
@@ -571,7 +580,7 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
     const size_t work_bytes = rtm_denoise_variance_work_bytes(st->width, st->height);
     rtm_aov_buffers dev;
     std::memset(&dev, 0, sizeof dev);
-    float *color = nullptr, *var = nullptr;
+    float *color = nullptr, *var = nullptr, *out32 = nullptr;
     uint8_t* out8 = nullptr;
     void* work = nullptr;
     if (hipMalloc((void**)&dev.depth, pix * sizeof(float)) != hipSuccess ||
@@ -579,7 +588,8 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
         hipMalloc((void**)&dev.albedo, pix * 3 * sizeof(float)) != hipSuccess ||
         hipMalloc((void**)&dev.object, pix * sizeof(int32_t)) != hipSuccess ||
         hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
-        hipMalloc((void**)&var, pix * sizeof(float)) != hipSuccess || hipMalloc(&work, work_bytes) != hipSuccess) {
+        hipMalloc((void**)&var, pix * sizeof(float)) != hipSuccess ||
+        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) || hipMalloc(&work, work_bytes) != hipSuccess) {
         err = "no device memory for the denoiser's buffers";
         rc = RTM_ERR_HIP;
     }
@@ -593,7 +603,7 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
     }
     if (rc == RTM_OK) {
         const rtm_denoise_var_params prm = RTM_DENOISE_VAR_DEFAULTS;
-        rc = rtm_denoise_variance(&prm, st->width, st->height, opt->device, color, &dev, work, nullptr, out8, var, nullptr);
+        rc = rtm_denoise_variance(&prm, st->width, st->height, opt->device, color, &dev, work, out32, out8, var, nullptr);
         if (rc != RTM_OK) err = rtm_last_error_detail();
     }
     std::vector<uint8_t> rgb8(pix * 3);
@@ -603,11 +613,19 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
         err = "copying the denoised frame back failed";
         rc = RTM_ERR_HIP;
     }
+    if (rc == RTM_OK && f32_out) {
+        f32_out->resize(pix * 3);
+        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            err = "copying the denoised frame back failed";
+            rc = RTM_ERR_HIP;
+        }
+    }
     (void)hipFree(dev.depth);
     (void)hipFree(dev.normal);
     (void)hipFree(dev.albedo);
     (void)hipFree(dev.object);
     (void)hipFree(color);
+    (void)hipFree(out32);
     (void)hipFree(out8);
     (void)hipFree(var);
     (void)hipFree(work);
@@ -618,6 +636,56 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
                     rtm_write_pfm((stem + "_variance.pfm").c_str(), st->width, st->height, 1, variance.data()) == 1;
     if (!ok) {
         err = "cannot write the variance-guided denoised files of " + stem;
+        return RTM_ERR_IO;
+    }
+    return RTM_OK;
+}
+
+// --display (rtm_node.h): rtm_tonemap of the frame on the default stream, then the two files.
+int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* prm, const float* f32_host,
+                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err) {
+    if (hipSetDevice(device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    const size_t pix = (size_t)st->width * st->height;
+    const size_t work_bytes = rtm_tonemap_work_bytes(st->width, st->height);
+    float* color = nullptr;
+    uint8_t* out8 = nullptr;
+    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_tonemap asks of work_dev
+    rtm_tonemap_stats* stats_dev = nullptr;
+    int rc = RTM_OK;
+    if (hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
+        hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc((void**)&stats_dev, sizeof(rtm_tonemap_stats)) != hipSuccess) {
+        err = "no device memory for the display transform's buffers";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && hipMemcpy(color, f32_host, pix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        err = "copying the frame to the device failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        rc = rtm_tonemap(prm, st->width, st->height, device, color, work, nullptr, out8, stats_dev, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    std::vector<uint8_t> rgb8(pix * 3);
+    rtm_tonemap_stats got;
+    std::memset(&got, 0, sizeof got);
+    if (rc == RTM_OK && (hipMemcpy(rgb8.data(), out8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(&got, stats_dev, sizeof got, hipMemcpyDeviceToHost) != hipSuccess)) {
+        err = "copying the display frame back failed";
+        rc = RTM_ERR_HIP;
+    }
+    (void)hipFree(color);
+    (void)hipFree(out8);
+    (void)hipFree(work);
+    (void)hipFree(stats_dev);
+    if (rc != RTM_OK) return rc;
+    if (stats) *stats = got;
+    const bool ok = rtm_write_jpg((stem + "_display.jpg").c_str(), st->width, st->height, 3, rgb8.data(), 60) == 1 &&
+                    rtm_write_bmp((stem + "_display.bmp").c_str(), st->width, st->height, 3, rgb8.data()) == 1;
+    if (!ok) {
+        err = "cannot write the display files of " + stem;
         return RTM_ERR_IO;
     }
     return RTM_OK;

@@ -29,11 +29,18 @@ int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t
                        const std::string& stem, std::string& err);
 // The frame's f32 (HOST, height x width x 3) denoised on options->device at the default parameters (rtm_denoise guided by
 // the frame's rtm_render_aov planes, rtm_cli --denoise) and written next to the image: <stem>_denoised.jpg (quality 60)
-// and <stem>_denoised.bmp.
+// and <stem>_denoised.bmp.  f32_out (nullable) receives the filtered float frame, for a stage that follows (--display).
 int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
-                            const float* f32_host, const std::string& stem, std::string& err);
+                            const float* f32_host, const std::string& stem, std::string& err,
+                            std::vector<float>* f32_out = nullptr);
 // The same frame through the variance-guided filter (rtm_denoise_variance at its default parameters, rtm_cli
 // --denoise-variance): <stem>_denoised_var.jpg (quality 60), <stem>_denoised_var.bmp and <stem>_variance.pfm, the per-pixel
-// variance estimate v0.
+// variance estimate v0.  f32_out as rtm_node_write_denoised's.
 int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
-                                     const float* f32_host, const std::string& stem, std::string& err);
+                                     const float* f32_host, const std::string& stem, std::string& err,
+                                     std::vector<float>* f32_out = nullptr);
+// The display transform (rtm_tonemap, rtm_cli --display) of a float frame (HOST, height x width x 3) on device `device`,
+// written next to the image: <stem>_display.jpg (quality 60) and <stem>_display.bmp.  stats (nullable) receives the frame
+// statistics and the exposure that was applied.
+int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* params, const float* f32_host,
+                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err);

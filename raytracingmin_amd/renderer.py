@@ -350,7 +350,7 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None):
+    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -359,9 +359,22 @@ class Renderer:
         denoise="variance" writes instead <fileName>_denoised_var.jpg / .bmp and <fileName>_variance.pfm: the frame filtered
         by denoise_variance() at its default parameters, and its per-pixel variance estimate (write_denoised_variance).
         adaptive=T renders tile-adaptively (Renderer.adaptive, threshold T, the default min_samples) and also writes
-        <fileName>_spp.pfm, the per-pixel sample count (write_spp); the AOV and denoised files then come from that frame."""
+        <fileName>_spp.pfm, the per-pixel sample count (write_spp); the AOV and denoised files then come from that frame.
+        tonemap=True (or a dict of tonemap()'s parameters: op, transfer, exposure, key, white, dither) also writes
+        <fileName>_display.bmp and <fileName>_display.jpg (q=60): the display transform (write_display) of the last stage
+        asked for — the variance-denoised frame with denoise="variance", the denoised one with denoise=True, else the frame
+        itself.  The plain files and self.image do not change."""
         if isinstance(denoise, str) and denoise != "variance":
             raise ValueError(f'denoise is False, True or "variance", got {denoise!r}')
+        display = None
+        if tonemap is not False and tonemap is not None:
+            if tonemap is not True and not isinstance(tonemap, dict):
+                raise ValueError(f"tonemap is False, True or a dict of tonemap()'s parameters, got {tonemap!r}")
+            display = {} if tonemap is True else dict(tonemap)
+            unknown = set(display) - set(TONEMAP_DEFAULTS)
+            if unknown:
+                raise ValueError(f"tonemap's parameters are {tuple(TONEMAP_DEFAULTS)}, got {sorted(unknown)}")
+            _tonemap_params(**display)  # a bad parameter raises here, before anything is rendered
         if adaptive is not None:
             if passes > 1:
                 raise ValueError("adaptive and passes > 1 do not combine")
@@ -387,37 +400,61 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write {fileName}.jpg/.bmp")
         if aov:
             self.write_aov(fileName)
+        frame = None  # the f32 frame the display stage shows, when it is not self.image
         if denoise == "variance":
-            self.write_denoised_variance(fileName)
+            frame = self.write_denoised_variance(fileName, _keep=display is not None)
         elif denoise:
-            self.write_denoised(fileName)
+            frame = self.write_denoised(fileName, _keep=display is not None)
+        if display is not None:
+            self.write_display(fileName, frame=frame, **display)
         return rgb8
 
-    def write_denoised(self, fileName):
+    def write_display(self, fileName, frame=None, **params):
+        """<fileName>_display.bmp and <fileName>_display.jpg (q=60): the display transform tonemap(**params) (default: the
+        ACES curve at automatic exposure, sRGB, dithered) of `frame`, an (H, W, 3) float32 CUDA tensor, or of self.image
+        rounded to float like out_f32 — what rtm_cli --display writes.  Returns the (H, W, 3) uint8 pixels."""
+        import torch
+        _tonemap_params(**params)
+        if frame is None:
+            dev = torch.device("cuda", self.device)
+            frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        rgb8 = np.ascontiguousarray(tonemap(frame, want=("u8",), **params)["u8"].cpu().numpy())
+        L = _lib.lib()
+        H, W = self.data.height, self.data.width
+        ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_display.jpg"), W, H, 3, rgb8.ctypes.data, 60)
+        ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_display.bmp"), W, H, 3, rgb8.ctypes.data)
+        if not (ok_j and ok_b):
+            raise _lib.RtmError(-3, f"could not write {fileName}_display.jpg/.bmp")
+        return rgb8
+
+    def write_denoised(self, fileName, _keep=False):
         """<fileName>_denoised.jpg (q=60) and <fileName>_denoised.bmp: self.image (the frame just rendered) rounded to float
         like out_f32, filtered by denoise() at the default parameters with the frame's four AOVs as guides, quantised on
-        the device — what rtm_cli --denoise writes.  Returns the (H, W, 3) uint8 pixels."""
+        the device — what rtm_cli --denoise writes.  Returns the (H, W, 3) uint8 pixels (Render's _keep: the filtered float32
+        frame on the device instead, for the display stage; the files are the same)."""
         import torch
         dev = torch.device("cuda", self.device)
         color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
         guides = self.render_aov()
-        rgb8 = np.ascontiguousarray(denoise(color, guides, want=("u8",))["u8"].cpu().numpy())
+        out = denoise(color, guides, want=("u8", "f32") if _keep else ("u8",))
+        rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
         L = _lib.lib()
         H, W = self.data.height, self.data.width
         ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_denoised.jpg"), W, H, 3, rgb8.ctypes.data, 60)
         ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_denoised.bmp"), W, H, 3, rgb8.ctypes.data)
         if not (ok_j and ok_b):
             raise _lib.RtmError(-3, f"could not write {fileName}_denoised.jpg/.bmp")
-        return rgb8
+        return out["f32"] if _keep else rgb8
 
-    def write_denoised_variance(self, fileName):
+    def write_denoised_variance(self, fileName, _keep=False):
         """<fileName>_denoised_var.jpg (q=60), <fileName>_denoised_var.bmp and <fileName>_variance.pfm: self.image rounded to
         float like out_f32, filtered by denoise_variance() at the default parameters with the frame's four AOVs as guides,
-        and the variance estimate v0 — what rtm_cli --denoise-variance writes.  Returns the (H, W, 3) uint8 pixels."""
+        and the variance estimate v0 — what rtm_cli --denoise-variance writes.  Returns the (H, W, 3) uint8 pixels (Render's
+        _keep: as write_denoised)."""
         import torch
         dev = torch.device("cuda", self.device)
         color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
-        out = denoise_variance(color, self.render_aov(), want=("u8", "var"))
+        out = denoise_variance(color, self.render_aov(), want=("u8", "var", "f32") if _keep else ("u8", "var"))
         rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
         var = np.ascontiguousarray(out["var"].cpu().numpy())
         L = _lib.lib()
@@ -427,7 +464,7 @@ class Renderer:
             and L.rtm_write_pfm(os.fsencode(fileName + "_variance.pfm"), W, H, 1, var.ctypes.data)
         if not ok:
             raise _lib.RtmError(-3, f"could not write {fileName}_denoised_var.jpg/.bmp or {fileName}_variance.pfm")
-        return rgb8
+        return out["f32"] if _keep else rgb8
 
 
 # include/rtm.h: RTM_DENOISE_DEFAULTS
@@ -511,6 +548,95 @@ def _denoise_call(entry, prm, color, aov, want, outputs, stream):
     _lib.check(getattr(L, entry)(C.byref(prm), W, H, dev.index, color.data_ptr(), C.byref(guides), work.data_ptr(),
                                  ptr("f32"), ptr("u8"), *tail, C.c_void_p(s.cuda_stream)), entry)
     return out
+
+
+# include/rtm.h: RTM_TONEMAP_DEFAULTS (exposure "auto" is auto_exposure 1 at ev 0)
+TONEMAP_DEFAULTS = {"op": "aces", "transfer": "srgb", "exposure": "auto", "key": 0.18, "white": 0.0, "dither": True}
+
+
+def _tonemap_params(op=TONEMAP_DEFAULTS["op"], transfer=TONEMAP_DEFAULTS["transfer"], exposure=TONEMAP_DEFAULTS["exposure"],
+                    key=TONEMAP_DEFAULTS["key"], white=TONEMAP_DEFAULTS["white"], dither=TONEMAP_DEFAULTS["dither"]):
+    """tonemap()'s parameters as an rtm_tonemap_params; a ValueError names what the library would refuse.  No device use."""
+    if op not in _lib.TONEMAP_OPS:
+        raise ValueError(f"op is one of {tuple(_lib.TONEMAP_OPS)}, got {op!r}")
+    if transfer not in _lib.TRANSFERS:
+        raise ValueError(f"transfer is one of {tuple(_lib.TRANSFERS)}, got {transfer!r}")
+    auto = isinstance(exposure, str)
+    if auto and exposure != "auto":
+        raise ValueError(f'exposure is "auto" or a number of stops (EV), got {exposure!r}')
+    if not auto and isinstance(exposure, bool):
+        raise ValueError(f'exposure is "auto" or a number of stops (EV), got {exposure!r}')
+    ev = 0.0 if auto else float(exposure)
+    key, white = float(key), float(white)
+    if not (np.isfinite(ev) and abs(ev) <= 32.0):
+        raise ValueError(f"exposure must be finite and within +-32 stops, got {exposure!r}")
+    if not (np.isfinite(key) and key > 0.0):
+        raise ValueError(f"key must be finite and positive, got {key!r}")
+    if not (np.isfinite(white) and white >= 0.0):
+        raise ValueError(f"white must be finite and non-negative, got {white!r}")
+    if not isinstance(dither, (bool, np.bool_)) and dither not in (0, 1):
+        raise ValueError(f"dither is True or False, got {dither!r}")
+    return _lib.rtm_tonemap_params(_lib.TONEMAP_OPS[op], _lib.TRANSFERS[transfer], int(auto), int(bool(dither)), ev, key, white)
+
+
+def tonemap(color, op=TONEMAP_DEFAULTS["op"], transfer=TONEMAP_DEFAULTS["transfer"], exposure=TONEMAP_DEFAULTS["exposure"],
+            key=TONEMAP_DEFAULTS["key"], white=TONEMAP_DEFAULTS["white"], dither=TONEMAP_DEFAULTS["dither"], want=("u8",),
+            stream=None, out_f32=None):
+    """The display transform (include/rtm.h: rtm_tonemap) on the device.  `color` is an (H, W, 3) float32 torch CUDA tensor
+    (any 4-byte-aligned contiguous view).  op "clamp" | "reinhard" | "aces"; transfer "srgb" | "linear"; exposure "auto"
+    (Reinhard's log-average key: E = key / L_avg) or a number of stops EV (E = 2^EV); white: Reinhard's white point, 0 = the
+    exposed frame maximum; dither: the ordered 8 x 8 dither of the 8-bit store.  Returns a dict of the names in `want`:
+    "f32" (H, W, 3) float32, "u8" (H, W, 3) uint8, "stats" a 4-word int32 tensor holding the bits of rtm_tonemap_stats
+    (tonemap_stats() reads it on the host).  out_f32: the tensor to write "f32" into; `color` itself maps in place.
+    Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream) with a work buffer
+    allocated here; nothing waits for it and nothing is copied to the host."""
+    prm = _tonemap_params(op, transfer, exposure, key, white, dither)
+    outputs = ("f32", "u8", "stats")
+    unknown = set(want) - set(outputs)
+    if unknown or not want:
+        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("tonemap needs a HIP device; there is no CPU fallback")
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
+            and color.shape[2] == 3 and color.is_contiguous()):
+        raise ValueError("color must be a contiguous (H, W, 3) float32 CUDA tensor")
+    H, W = int(color.shape[0]), int(color.shape[1])
+    dev = color.device
+    if out_f32 is not None:
+        if "f32" not in want:
+            raise ValueError('out_f32 is given but "f32" is not in want')
+        if not (isinstance(out_f32, torch.Tensor) and out_f32.device == dev and out_f32.dtype == torch.float32
+                and tuple(out_f32.shape) == (H, W, 3) and out_f32.is_contiguous()):
+            raise ValueError(f"out_f32 must be a contiguous ({H}, {W}, 3) float32 tensor on {dev}")
+    if stream is None:
+        s = torch.cuda.current_stream(dev)
+    elif isinstance(stream, torch.cuda.Stream):
+        s = stream
+    else:
+        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    L = _lib.lib()
+    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
+        work = torch.empty(max(256, L.rtm_tonemap_work_bytes(W, H)), dtype=torch.uint8, device=dev)
+        out = {}
+        if "f32" in want:
+            out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if out_f32 is None else out_f32
+        if "u8" in want:
+            out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        if "stats" in want:
+            out["stats"] = torch.empty(4, dtype=torch.int32, device=dev)
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    _lib.check(L.rtm_tonemap(C.byref(prm), W, H, dev.index, color.data_ptr(), work.data_ptr(), ptr("f32"), ptr("u8"),
+                             ptr("stats"), C.c_void_p(s.cuda_stream)), "rtm_tonemap")
+    return out
+
+
+def tonemap_stats(words):
+    """tonemap()'s "stats" tensor as a dict {"log_average", "max_luminance", "exposure", "pixels"}; copies four words to the
+    host (synchronise the stream that wrote them first when it is not the current one)."""
+    raw = np.ascontiguousarray(words.cpu().numpy() if hasattr(words, "cpu") else words).view(np.uint32)
+    f = raw.view(np.float32)
+    return {"log_average": float(f[0]), "max_luminance": float(f[1]), "exposure": float(f[2]), "pixels": int(raw[3])}
 
 
 def plan_passes(n_samples, passes=None, samples_per_pass=None):
