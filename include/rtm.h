@@ -508,6 +508,65 @@ size_t rtm_tonemap_work_bytes(int32_t width, int32_t height);
 int rtm_tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, rtm_tonemap_stats* stats_out_dev, void* stream);
 
+/* ---- AOV-guided upsampling: a frame traced at 1/f of the resolution in each axis, brought to full size by a joint
+ * bilateral upsample (Kopf et al. 2007) steered by the full-resolution first-hit planes, with the albedo demodulated so that
+ * material colour comes back at full resolution.  The AOVs have no random draws and cost one cheap kernel at any size; the
+ * path-traced colour needs f^2 fewer paths.
+ * Inputs: the low frame is w x h, the output W x H with W = f w, H = f h.  color_low (DEVICE, h x w x 3 floats,
+ * RGB-interleaved like out_f32); guide_low in the rtm_aov_buffers layout at w x h and guide_high in the same layout at W x H
+ * (rows = the frame's height, no bands).  A plane (depth, normal, albedo, object) is GIVEN iff it is non-null in both guide
+ * structs; either struct pointer may be null (no planes at all), and then both must be.  Depths are positive or +inf, as
+ * rtm_render_aov writes them.  Arithmetic in float:
+ *   1 taps        in integers.  For the output column x: num = 2x + 1 - f, X0 = floor(num / 2f) (floor division: a negative
+ *                 num rounds down), r = num - 2f X0 in [0, 2f), t_x = r / (2f); rows alike.  (X0 + t_x is the pixel centre
+ *                 (x + 0.5) / f - 0.5 in low-resolution pixel coordinates.)  The taps are the low pixels
+ *                 q = (X0 + dx, Y0 + dy), dx, dy in -1..2; taps outside the low frame are skipped (not clamped); the sums run
+ *                 dy outer, dx inner.  The tap nearest to the pixel centre is always inside the frame.
+ *   2 spatial     h_x[dx] = exp(-(dx - t_x)^2 / (2 sigma_spatial^2)); it depends only on x mod f, so there are 4f values
+ *                 per axis: computed in double on the host, rounded to float, one table for both axes.
+ *                 h(p,q) = h_x[dx] h_y[dy].
+ *   3 geometry    g(p,q), rtm_denoise's weight with step s = f; p the full-resolution pixel with the high guides, q the
+ *                 low tap with the low guides:
+ *                   object given and obj_p != obj_q: 0
+ *                   else, depth given: both depths +inf (two misses): 1, the terms below skipped; exactly one +inf: 0;
+ *                         otherwise w_z = sigma_depth > 0 ? exp(-|z_p - z_q| / (sigma_depth f max(z_p, z_q))) : 1
+ *                   w_n = (normal given && sigma_normal > 0) ? max(0, n_p . n_q)^sigma_normal : 1;  g = w_z w_n
+ *                 There is no centre-tap case: no tap coincides with p.
+ *   4 combine     w(p,q) = h(p,q) (g(p,q) + 1e-6f): a continuous fallback, no threshold.  a_q,k = albedo_q,k > 1e-3f ?
+ *                 albedo_q,k : 1.0f from the LOW albedo (1.0f when albedo is not given), e_q = c_q / a_q per channel;
+ *                 e^_p = sum_q w e_q / sum_q w;  out_p = e^_p A_p, A built the same way from the HIGH albedo.
+ *                 A full-resolution pixel whose object no tap saw (a thin feature) gets the spatial average of its taps;
+ *                 a pixel whose nearest tap carries its object with g = 1 takes, at the default sigma_spatial, under 1e-5
+ *                 of its value from across an edge (DESIGN.md has the bound).  sum w > 0 always: never a division by zero.
+ *   out_u8 (if non-null) is rtm_quantise of (double)out_f32, bit for bit.
+ * exp, pow and the divisions may be the device's fast forms: against a float64 evaluation of the steps above every output
+ * component is within 1e-4 max(1, |ref|).  No atomics: the same inputs give the same bits on every call, on any stream.
+ * Defaults: RTM_UPSAMPLE_DEFAULTS below (what Renderer.preview and rtm_cli --preview use; the sigma_spatial sweep on the
+ * Cornell box: DESIGN.md): factor 2, sigma_spatial 0.5, sigma_normal 64, sigma_depth 0.05. */
+typedef struct rtm_upsample_params {
+    int32_t factor;       /* f, 2..8: the full frame is (f w) x (f h) */
+    float sigma_spatial;  /* finite, 0.25..4, in low-resolution pixels */
+    float sigma_normal;   /* as rtm_denoise_params */
+    float sigma_depth;    /* as rtm_denoise_params */
+} rtm_upsample_params;
+#define RTM_UPSAMPLE_DEFAULTS {2, 0.5f, 64.0f, 0.05f} /* an initializer of rtm_upsample_params */
+/* Bytes of the work buffer rtm_upsample needs for a low frame: 32 per low pixel (two 16-byte records, (e.xyz, object bits)
+ * and (n.xyz, z), packed by a prepass like the denoiser's); 0 for a non-positive size, SIZE_MAX when the full frame at
+ * f = 8 (12 x 64 bytes per low pixel) does not fit a size_t. */
+size_t rtm_upsample_work_bytes(int32_t low_width, int32_t low_height);
+/* Upsamples `color_low_dev` into out_f32_dev and / or out_u8_dev (DEVICE, (f h) x (f w) x 3; either may be null, not
+ * both).  The caller owns every buffer; work_dev (DEVICE, 16-byte aligned, rtm_upsample_work_bytes bytes) holds the packed
+ * low records, so the call allocates nothing and only ENQUEUES its two launches (the low-resolution prepass and the
+ * upsample) on `stream` of `device`.  It keeps no per-(device, stream) state and needs no serialisation: calls on different
+ * streams with different work buffers run side by side.  Null params, color_low_dev or work_dev, both outputs null, a
+ * non-positive size, factor outside 2..8, sigma_spatial outside [0.25, 4] or not finite, a negative, NaN or infinite
+ * sigma_normal or sigma_depth, a plane (or a guide struct) given at one resolution only, a misaligned work_dev, work_dev or
+ * color_low_dev equal to an output, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  Added after
+ * RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+int rtm_upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device,
+                 const float* color_low_dev, const rtm_aov_buffers* guide_low_dev, const rtm_aov_buffers* guide_high_dev,
+                 void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);

@@ -81,6 +81,10 @@ class rtm_denoise_var_params(C.Structure):  # include/rtm.h: rtm_denoise_varianc
     _fields_ = [("iterations", C.c_int32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class rtm_upsample_params(C.Structure):  # include/rtm.h: rtm_upsample
+    _fields_ = [("factor", C.c_int32), ("sigma_spatial", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
 TONEMAP_OPS = {"clamp": 0, "reinhard": 1, "aces": 2}  # include/rtm.h: RTM_TONEMAP_*
 TRANSFERS = {"linear": 0, "srgb": 1}  # RTM_TRANSFER_*
 
@@ -132,6 +136,9 @@ SIGNATURES = {
     "rtm_tonemap_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_tonemap": (C.c_int, [_P(rtm_tonemap_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_upsample_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtm_upsample": (C.c_int, [_P(rtm_upsample_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
+                               _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),

@@ -114,6 +114,13 @@ int rtm_tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height,
                 void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, rtm_tonemap_stats* stats_out_dev, void* stream) {
     RTM_GUARD(rtm::tonemap(params, width, height, device, color_dev, work_dev, out_f32_dev, out_u8_dev, stats_out_dev, stream))
 }
+size_t rtm_upsample_work_bytes(int32_t low_width, int32_t low_height) { return rtm::upsample_work_bytes(low_width, low_height); }
+int rtm_upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device,
+                 const float* color_low_dev, const rtm_aov_buffers* guide_low_dev, const rtm_aov_buffers* guide_high_dev,
+                 void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
+    RTM_GUARD(rtm::upsample(params, low_width, low_height, device, color_low_dev, guide_low_dev, guide_high_dev, work_dev,
+                            out_f32_dev, out_u8_dev, stream))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {

@@ -56,6 +56,11 @@ int denoise_variance_kernel_probe(int form, const rtm_denoise_var_params* params
 size_t tonemap_work_bytes(int32_t width, int32_t height);
 int tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int device, const float* color, void* work,
             float* out32, uint8_t* out8, rtm_tonemap_stats* stats_out, void* stream);
+// AOV-guided upsampling (rtm_upsample.hip)
+size_t upsample_work_bytes(int32_t low_width, int32_t low_height);
+int upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device, const float* color_low,
+             const rtm_aov_buffers* guide_low, const rtm_aov_buffers* guide_high, void* work, float* out32, uint8_t* out8,
+             void* stream);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);

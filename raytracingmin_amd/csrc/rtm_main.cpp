@@ -12,6 +12,8 @@
 //           [--denoise-variance]                 (the variance-guided one: STEM_denoised_var.bmp, .jpg, STEM_variance.pfm)
 //           [--display [clamp|reinhard|aces]] [--exposure auto|EV] [--linear] [--no-dither]
 //                                                (the display transform of the last stage: STEM_display.bmp, .jpg)
+//           [--preview F [--preview-only]]       (the frame traced at 1/F of the resolution per axis, denoised there and upsampled
+//                                                by the first-hit feature buffers: STEM_preview.bmp, .jpg; -only: no full render)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -59,7 +61,12 @@ static void usage() {
         "--display [clamp|reinhard|aces] : also write the display transform (rtm_tonemap; default aces) of the last stage\n"
         "            asked for on one GPU (the --denoise-variance frame, else the --denoise frame, else the frame itself):\n"
         "            STEM_display.bmp and STEM_display.jpg.  --exposure auto|EV : Reinhard's log-average key 0.18 (default) or\n"
-        "            a fixed number of stops; --linear : no sRGB transfer function; --no-dither : the truncating 8-bit store\n");
+        "            a fixed number of stops; --linear : no sRGB transfer function; --no-dither : the truncating 8-bit store\n"
+        "--preview F [--preview-only] : also write a fast preview on one GPU: the scene traced at width / F x height / F (F in\n"
+        "            2..8, dividing both; F^2 fewer paths), denoised there (rtm_denoise at its defaults) and brought to full size\n"
+        "            by rtm_upsample, guided by the first-hit feature buffers at both resolutions: STEM_preview.bmp and\n"
+        "            STEM_preview.jpg (with --display also STEM_preview_display.bmp, .jpg).  --preview-only : skip the full\n"
+        "            render; STEM.bmp and STEM.jpg are not written\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -73,7 +80,7 @@ int main(int argc, char* argv[]) {
     int mode = RTM_MODE_REPAIRED, max_bounces = -1, device = 0, gpus = 1, virtual_strips = 0, host_trig = 1, force_rccl = 0;
     int passes = 0, aov = 0, denoise = 0, denoise_variance = 0, adaptive = 0, adaptive_min = 16;
     float adaptive_threshold = 0.f;
-    int display = 0;
+    int display = 0, preview = 0, preview_only = 0;
     rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
     std::string dump_f32;
     unsigned long long seed = 0x5EED;
@@ -111,6 +118,8 @@ int main(int argc, char* argv[]) {
         else if (c == "--device-trig") host_trig = 0;
         else if (c == "--force-rccl") force_rccl = 1;
         else if (c == "--aov") aov = 1;
+        else if (c == "--preview") next_int(preview);
+        else if (c == "--preview-only") preview_only = 1;
         else if (c == "--denoise") denoise = 1;
         else if (c == "--denoise-variance") denoise_variance = 1;
         else if (c == "--display") {
@@ -175,6 +184,27 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "--display runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
         return 2;
     }
+    if (preview_only && preview == 0) {
+        std::fprintf(stderr, "--preview-only requires --preview F\n");
+        return 2;
+    }
+    if (preview != 0 && (preview < 2 || preview > 8)) {
+        std::fprintf(stderr, "--preview takes a factor in 2..8, got %d\n", preview);
+        return 2;
+    }
+    if (preview && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--preview runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
+        return 2;
+    }
+    if (preview_only && (adaptive || passes > 0)) {
+        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --adaptive or --passes\n");
+        return 2;
+    }
+    if (preview_only && (denoise || denoise_variance || !dump_f32.empty())) {
+        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --denoise, --denoise-variance or "
+                             "--dump-f32\n");
+        return 2;
+    }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
         std::printf("saving the sample scene json file: %s\n", json_file.c_str());
         if (rtm_scene_save_sample_json(json_file.c_str()) != RTM_OK) return 1;
@@ -210,6 +240,42 @@ int main(int argc, char* argv[]) {
     opt.row_begin = 0;
     opt.row_end = st.height;
     opt.device = device;
+
+    if (preview && (st.width % preview != 0 || st.height % preview != 0)) {
+        std::fprintf(stderr, "--preview %d does not divide the %d x %d frame\n", preview, st.width, st.height);
+        return 2;
+    }
+    if (preview) {  // STEM_preview.bmp / .jpg, and their display transform
+        std::string err;
+        std::vector<float> shown;
+        rtm_stats ps;
+        rc = rtm_node_write_preview(&st, spheres.data(), n, &opt, preview, stem, err, display ? &shown : nullptr, &ps);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "preview failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        std::printf("preview: %s_preview.bmp, %s_preview.jpg (%d x %d traced, %llu samples, kernel %.3f ms)\n", stem.c_str(),
+                    stem.c_str(), st.width / preview, st.height / preview, (unsigned long long)ps.samples, ps.kernel_ms);
+        if (display) {
+            rtm_tonemap_stats ts;
+            rc = rtm_node_write_display(&st, opt.device, &display_prm, shown.data(), stem + "_preview", &ts, err);
+            if (rc != RTM_OK) {
+                std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+                return 1;
+            }
+            std::printf("display: %s_preview_display.bmp, %s_preview_display.jpg\n", stem.c_str(), stem.c_str());
+        }
+        if (preview_only) {
+            if (aov) {
+                rc = rtm_node_write_aov(&st, spheres.data(), n, &opt, stem, err);
+                if (rc != RTM_OK) {
+                    std::fprintf(stderr, "aov failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+                    return 1;
+                }
+            }
+            return 0;
+        }
+    }
 
     const size_t vals = (size_t)st.width * st.height * 3;
     std::vector<uint8_t> rgb8(vals);

@@ -690,3 +690,97 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
     }
     return RTM_OK;
 }
+
+// --preview (rtm_node.h): the low render, its AOVs and rtm_denoise, the full AOVs, rtm_upsample, all on the default stream,
+// then the two files.
+int rtm_node_write_preview(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int factor,
+                           const std::string& stem, std::string& err, std::vector<float>* f32_out, rtm_stats* stats) {
+    if (factor < 2 || factor > 8 || st->width % factor != 0 || st->height % factor != 0) {
+        err = "--preview " + std::to_string(factor) + ": a factor in 2..8 that divides the width and the height";
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (hipSetDevice(opt->device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(opt->device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    rtm_scene* scene = nullptr;
+    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
+    if (rc != RTM_OK) {
+        err = std::string("scene: ") + rtm_last_error_detail();
+        return rc;
+    }
+    rtm_settings lo_st = *st;
+    lo_st.width = st->width / factor;
+    lo_st.height = st->height / factor;
+    rtm_options lo_opt = *opt;
+    lo_opt.row_begin = 0;
+    lo_opt.row_end = lo_st.height;
+    const size_t lo_pix = (size_t)lo_st.width * lo_st.height, pix = (size_t)st->width * st->height;
+    rtm_aov_buffers lo, hi;
+    std::memset(&lo, 0, sizeof lo);
+    std::memset(&hi, 0, sizeof hi);
+    float *color = nullptr, *den = nullptr, *out32 = nullptr;
+    uint8_t* out8 = nullptr;
+    void *dn_work = nullptr, *up_work = nullptr;
+    auto planes = [](rtm_aov_buffers& b, size_t p) {
+        return hipMalloc((void**)&b.depth, p * sizeof(float)) == hipSuccess && hipMalloc((void**)&b.normal, p * 3 * sizeof(float)) == hipSuccess &&
+               hipMalloc((void**)&b.albedo, p * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&b.object, p * sizeof(int32_t)) == hipSuccess;
+    };
+    if (!planes(lo, lo_pix) || !planes(hi, pix) || hipMalloc((void**)&color, lo_pix * 3 * sizeof(float)) != hipSuccess ||
+        hipMalloc((void**)&den, lo_pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
+        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) ||
+        hipMalloc(&dn_work, rtm_denoise_work_bytes(lo_st.width, lo_st.height)) != hipSuccess ||
+        hipMalloc(&up_work, rtm_upsample_work_bytes(lo_st.width, lo_st.height)) != hipSuccess) {
+        err = "no device memory for the preview's buffers";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        rc = rtm_render_scene(&lo_st, scene, &lo_opt, nullptr, color, nullptr, nullptr, stats);
+        if (rc == RTM_OK) rc = rtm_render_aov(&lo_st, scene, &lo_opt, &lo, nullptr);
+        if (rc == RTM_OK) {
+            const rtm_denoise_params prm = RTM_DENOISE_DEFAULTS;
+            rc = rtm_denoise(&prm, lo_st.width, lo_st.height, opt->device, color, &lo, dn_work, den, nullptr, nullptr);
+        }
+        if (rc == RTM_OK) rc = rtm_render_aov(st, scene, opt, &hi, nullptr);
+        if (rc == RTM_OK) {
+            rtm_upsample_params prm = RTM_UPSAMPLE_DEFAULTS;
+            prm.factor = factor;
+            rc = rtm_upsample(&prm, lo_st.width, lo_st.height, opt->device, den, &lo, &hi, up_work, out32, out8, nullptr);
+        }
+        if (rc == RTM_OK) rc = rtm_stream_status(opt->device, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    std::vector<uint8_t> rgb8(pix * 3);
+    if (rc == RTM_OK && hipMemcpy(rgb8.data(), out8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess) {
+        err = "copying the preview back failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && f32_out) {
+        f32_out->resize(pix * 3);
+        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            err = "copying the preview back failed";
+            rc = RTM_ERR_HIP;
+        }
+    }
+    for (rtm_aov_buffers* b : {&lo, &hi}) {
+        (void)hipFree(b->depth);
+        (void)hipFree(b->normal);
+        (void)hipFree(b->albedo);
+        (void)hipFree(b->object);
+    }
+    (void)hipFree(color);
+    (void)hipFree(den);
+    (void)hipFree(out32);
+    (void)hipFree(out8);
+    (void)hipFree(dn_work);
+    (void)hipFree(up_work);
+    (void)rtm_scene_destroy(scene);
+    if (rc != RTM_OK) return rc;
+    const bool ok = rtm_write_jpg((stem + "_preview.jpg").c_str(), st->width, st->height, 3, rgb8.data(), 60) == 1 &&
+                    rtm_write_bmp((stem + "_preview.bmp").c_str(), st->width, st->height, 3, rgb8.data()) == 1;
+    if (!ok) {
+        err = "cannot write the preview files of " + stem;
+        return RTM_ERR_IO;
+    }
+    return RTM_OK;
+}

@@ -44,3 +44,12 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
 // statistics and the exposure that was applied.
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* params, const float* f32_host,
                            const std::string& stem, rtm_tonemap_stats* stats, std::string& err);
+// The preview of the frame on options->device (rtm_cli --preview F): the scene traced at (width / factor) x (height / factor)
+// with the same camera, samples, seed and mode, denoised there at the default parameters (rtm_denoise guided by the low
+// rtm_render_aov planes) and brought to full size by rtm_upsample at its default sigmas, guided by the AOVs at both
+// resolutions; written next to the image: <stem>_preview.jpg (quality 60) and <stem>_preview.bmp.  factor must divide the
+// width and the height.  f32_out (nullable) receives the float frame, for a stage that follows (--display); stats
+// (nullable) the low render's.
+int rtm_node_write_preview(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options, int factor,
+                           const std::string& stem, std::string& err, std::vector<float>* f32_out = nullptr,
+                           rtm_stats* stats = nullptr);

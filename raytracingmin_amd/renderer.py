@@ -324,6 +324,70 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write the AOV files of {fileName}")
         return planes
 
+    # ---- low-resolution preview at full size (rtm_upsample) -----------------------------------
+    def preview(self, factor=2, denoise=True, want=("f32",), stream=None):
+        """The frame traced at (width / factor) x (height / factor) — same camera, samples, super-samples, seed and mode, so
+        factor^2 fewer paths — and brought to full size by upsample() at its default sigmas, guided by the first-hit AOVs at
+        both resolutions.  On one stream: the low render, the low AOVs, denoise() at its defaults on the low frame (unless
+        denoise=False), the full AOVs, the upsample.  Returns upsample()'s dict ("f32" / "u8" (H, W, 3) CUDA tensors);
+        nothing waits for the stream.  factor is 2..8 and must divide both width and height (ValueError)."""
+        f = int(factor)
+        H, W = int(self.data.height), int(self.data.width)
+        if not 2 <= f <= 8:
+            raise ValueError(f"factor must be in 2..8, got {factor!r}")
+        if W % f or H % f:
+            raise ValueError(f"factor {f} does not divide the {W}x{H} frame")
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        dev = torch.device("cuda", self.device)
+        if stream is None:
+            s = torch.cuda.current_stream(dev)
+        elif isinstance(stream, torch.cuda.Stream):
+            s = stream
+        else:
+            s = torch.cuda.ExternalStream(int(stream), device=dev)
+        w, h = W // f, H // f
+        st = self.data.settings_c()
+        st.width, st.height = w, h
+        opt = self._options(0, h)
+        L = _lib.lib()
+        shapes = {"depth": ((h, w), torch.float32), "normal": ((h, w, 3), torch.float32),
+                  "albedo": ((h, w, 3), torch.float32), "object": ((h, w), torch.int32)}
+        with torch.cuda.stream(s):  # allocated on the stream that uses them; render_aov and the filters take the current stream
+            color = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+            aov_low = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
+            bufs = _lib.rtm_aov_buffers()
+            for k, v in aov_low.items():
+                setattr(bufs, k, v.data_ptr())
+            hip_stream = C.c_void_p(s.cuda_stream)
+            _lib.check(L.rtm_render_scene(C.byref(st), self._scene_handle(), C.byref(opt), None, C.c_void_p(color.data_ptr()),
+                                          None, hip_stream, None), "rtm_render_scene")
+            _lib.check(L.rtm_render_aov(C.byref(st), self._scene_handle(), C.byref(opt), C.byref(bufs), hip_stream),
+                       "rtm_render_aov")
+            if denoise:
+                d = DENOISE_DEFAULTS  # (the module's denoise(): this method's flag has its name)
+                prm = _lib.rtm_denoise_params(d["iterations"], d["sigma_color"], d["sigma_normal"], d["sigma_depth"])
+                color = _denoise_call("rtm_denoise", prm, color, aov_low, ("f32",), ("f32", "u8"), None)["f32"]
+            return upsample(color, aov_low, self.render_aov(), factor=f, want=want)
+
+    def write_preview(self, fileName, factor=2, _keep=False):
+        """<fileName>_preview.jpg (q=60) and <fileName>_preview.bmp: preview(factor), denoised at the low resolution,
+        quantised on the device — what rtm_cli --preview writes.  Returns the (H, W, 3) uint8 pixels (Render's _keep: the
+        float32 frame on the device instead, for the display stage; the files are the same)."""
+        import torch
+        out = self.preview(factor, want=("u8", "f32") if _keep else ("u8",))
+        torch.cuda.synchronize(self.device)
+        self.stream_status()
+        rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
+        L = _lib.lib()
+        H, W = self.data.height, self.data.width
+        ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_preview.jpg"), W, H, 3, rgb8.ctypes.data, 60)
+        ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_preview.bmp"), W, H, 3, rgb8.ctypes.data)
+        if not (ok_j and ok_b):
+            raise _lib.RtmError(-3, f"could not write {fileName}_preview.jpg/.bmp")
+        return out["f32"] if _keep else rgb8
+
     # ---- host-buffer render (the blocking C entry point) ------------------------------------
     def render_rows(self, row_begin=0, row_end=None, want=("f64",), band=None):
         row_end = self.data.height if row_end is None else row_end
@@ -350,7 +414,7 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False):
+    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -363,7 +427,15 @@ class Renderer:
         tonemap=True (or a dict of tonemap()'s parameters: op, transfer, exposure, key, white, dither) also writes
         <fileName>_display.bmp and <fileName>_display.jpg (q=60): the display transform (write_display) of the last stage
         asked for — the variance-denoised frame with denoise="variance", the denoised one with denoise=True, else the frame
-        itself.  The plain files and self.image do not change."""
+        itself.  The plain files and self.image do not change.
+        preview=F also writes <fileName>_preview.bmp and <fileName>_preview.jpg (q=60): the frame traced at 1 / F of the
+        resolution in each axis, denoised there and upsampled by the AOVs (write_preview); with tonemap, the display transform
+        of the preview as well, as <fileName>_preview_display.bmp / .jpg.  F must divide the width and the height."""
+        if preview is not None:
+            f = int(preview)
+            if not 2 <= f <= 8 or self.data.width % f or self.data.height % f:
+                raise ValueError(f"preview is a factor in 2..8 that divides the {self.data.width}x{self.data.height} frame, "
+                                 f"got {preview!r}")
         if isinstance(denoise, str) and denoise != "variance":
             raise ValueError(f'denoise is False, True or "variance", got {denoise!r}')
         display = None
@@ -407,6 +479,10 @@ class Renderer:
             frame = self.write_denoised(fileName, _keep=display is not None)
         if display is not None:
             self.write_display(fileName, frame=frame, **display)
+        if preview is not None:
+            shown = self.write_preview(fileName, int(preview), _keep=display is not None)
+            if display is not None:
+                self.write_display(fileName + "_preview", frame=shown, **display)
         return rgb8
 
     def write_display(self, fileName, frame=None, **params):
@@ -547,6 +623,73 @@ def _denoise_call(entry, prm, color, aov, want, outputs, stream):
     tail = (ptr("var"),) if "var" in outputs else ()
     _lib.check(getattr(L, entry)(C.byref(prm), W, H, dev.index, color.data_ptr(), C.byref(guides), work.data_ptr(),
                                  ptr("f32"), ptr("u8"), *tail, C.c_void_p(s.cuda_stream)), entry)
+    return out
+
+
+# include/rtm.h: RTM_UPSAMPLE_DEFAULTS
+UPSAMPLE_DEFAULTS = {"factor": 2, "sigma_spatial": 0.5, "sigma_normal": 64.0, "sigma_depth": 0.05}
+
+
+def upsample(color_low, aov_low=None, aov_high=None, factor=UPSAMPLE_DEFAULTS["factor"],
+             sigma_spatial=UPSAMPLE_DEFAULTS["sigma_spatial"], sigma_normal=UPSAMPLE_DEFAULTS["sigma_normal"],
+             sigma_depth=UPSAMPLE_DEFAULTS["sigma_depth"], want=("f32",), stream=None):
+    """The AOV-guided upsampler (include/rtm.h: rtm_upsample) on the device.  `color_low` is an (h, w, 3) float32 torch CUDA
+    tensor; `aov_low` / `aov_high` are dicts like Renderer.render_aov returns, at (h, w) and at (factor h, factor w); a plane
+    guides the filter when both hold it, and a plane in one of them only is a ValueError.  Returns {"f32": (H, W, 3) float32,
+    "u8": (H, W, 3) uint8} for the names in `want`.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle;
+    default: the current stream) with a work buffer allocated here; nothing waits for it."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("upsample needs a HIP device; there is no CPU fallback")
+    outputs = ("f32", "u8")
+    unknown = set(want) - set(outputs)
+    if unknown or not want:
+        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+    if not (isinstance(color_low, torch.Tensor) and color_low.is_cuda and color_low.dtype == torch.float32
+            and color_low.dim() == 3 and color_low.shape[2] == 3 and color_low.is_contiguous()):
+        raise ValueError("color_low must be a contiguous (h, w, 3) float32 CUDA tensor")
+    f = int(factor)
+    h, w = int(color_low.shape[0]), int(color_low.shape[1])
+    H, W = f * h, f * w
+    dev = color_low.device
+    aov_low = {k: v for k, v in (aov_low or {}).items() if v is not None}
+    aov_high = {k: v for k, v in (aov_high or {}).items() if v is not None}
+    planes = ("depth", "normal", "albedo", "object")
+    unknown = (set(aov_low) | set(aov_high)) - set(planes)
+    if unknown:
+        raise ValueError(f"unknown AOV plane(s) {sorted(unknown)}; the planes are {planes}")
+    if set(aov_low) != set(aov_high):
+        raise ValueError(f"plane(s) {sorted(set(aov_low) ^ set(aov_high))} are given at one resolution only")
+    guides = []
+    for aov, (rows, cols) in ((aov_low, (h, w)), (aov_high, (H, W))):
+        layout = {"depth": ((rows, cols), torch.float32), "normal": ((rows, cols, 3), torch.float32),
+                  "albedo": ((rows, cols, 3), torch.float32), "object": ((rows, cols), torch.int32)}
+        g = _lib.rtm_aov_buffers()
+        for k, v in aov.items():
+            shape, dtype = layout[k]
+            if not (isinstance(v, torch.Tensor) and v.device == dev and v.dtype == dtype and tuple(v.shape) == shape
+                    and v.is_contiguous()):
+                raise ValueError(f"the {rows}x{cols} plane {k!r} must be a contiguous {shape} {dtype} tensor on {dev}")
+            setattr(g, k, v.data_ptr())
+        guides.append(g)
+    if stream is None:
+        s = torch.cuda.current_stream(dev)
+    elif isinstance(stream, torch.cuda.Stream):
+        s = stream
+    else:
+        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    L = _lib.lib()
+    prm = _lib.rtm_upsample_params(f, float(sigma_spatial), float(sigma_normal), float(sigma_depth))
+    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
+        work = torch.empty(max(16, L.rtm_upsample_work_bytes(w, h)), dtype=torch.uint8, device=dev)
+        out = {}
+        if "f32" in want:
+            out["f32"] = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev)
+        if "u8" in want:
+            out["u8"] = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.uint8, device=dev)
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    _lib.check(L.rtm_upsample(C.byref(prm), w, h, dev.index, color_low.data_ptr(), C.byref(guides[0]), C.byref(guides[1]),
+                              work.data_ptr(), ptr("f32"), ptr("u8"), C.c_void_p(s.cuda_stream)), "rtm_upsample")
     return out
 
 
