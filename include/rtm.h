@@ -567,6 +567,74 @@ int rtm_upsample(const rtm_upsample_params* params, int32_t low_width, int32_t l
                  const float* color_low_dev, const rtm_aov_buffers* guide_low_dev, const rtm_aov_buffers* guide_high_dev,
                  void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
 
+/* ---- frame comparison: how far a frame is from a reference, measured where both frames are — maximum error, the count of
+ * pixels outside a tolerance, MSE / PSNR, relative MSE, SSIM and a per-pixel error map, in one pass with nothing copied to
+ * the host.
+ * Inputs: `a` is the frame under test, `b` the reference: DEVICE buffers of height x width x 3, RGB-interleaved like out_f32
+ * (RTM_COMPARE_F32) or out_f64 (RTM_COMPARE_F64), both of the params' dtype; alignment is only the element's own, 4 or 8
+ * bytes.  Every input value is widened to double exactly and all arithmetic is in double (one ulp at 1.0 between two out_f64
+ * frames is seen and counted).  FMA contraction is allowed; the exact fields below do not depend on it.
+ *   1 counting    a pixel COUNTS iff its six components (three of a, three of b) are finite.  pixels = n, the number of
+ *                 counting pixels; nonfinite = width height - n; nonfinite_mismatch = the non-counting pixels that have a
+ *                 component c where neither (a_c and b_c are both NaN) nor (a_c == b_c) holds: two frames with "the same
+ *                 NaNs" (and the same infinities) report 0.
+ *   2 error       per counting pixel d_c = |a_c - b_c|, D_p = max(max(d_R, d_G), d_B).  max_abs = max D_p (0 when n = 0);
+ *                 (argmax_x, argmax_y) = the lowest row-major pixel index that attains max_abs ((-1, -1) when n = 0);
+ *                 outside = #{p : D_p > tolerance}, a strict inequality: with tolerance 0 the number of differing pixels.
+ *   3 mse         mse = sum_p ((d_R^2 + d_G^2) + d_B^2) / (3 n) (0 when n = 0); psnr = 10 log10(peak^2 / mse) when mse > 0,
+ *                 else +inf.
+ *   4 rel_mse     rel_mse = sum_p sum_c d_c^2 / (b_c^2 + rel_epsilon) / (3 n) (0 when n = 0): not symmetric in a and b.
+ *   5 ssim        (Wang et al. 2004, on luminance) l = (0.2126 R + 0.7152 G) + 0.0722 B for a counting pixel and 0 IN BOTH
+ *                 IMAGES at a non-counting one (the display transform's rule).  Window g[k] = exp(-k^2 / 4.5), k = -5..5
+ *                 (sigma 1.5 over 11 x 11); only in-frame taps are used, renormalised: the tap (dx, dy) of pixel (x, y) has
+ *                 weight g[dx] g[dy] / (G_x G_y), G_x the sum of g over the in-frame dx and G_y likewise — separable at the
+ *                 border too, and defined for every frame size including 1 x 1.  With E[.] that weighted mean:
+ *                 mu_a = E[l_a], mu_b = E[l_b], var_a = E[l_a^2] - mu_a^2, var_b likewise, cov = E[l_a l_b] - mu_a mu_b;
+ *                 C1 = (0.01 peak)^2, C2 = (0.03 peak)^2;
+ *                 S_p = ((2 mu_a mu_b + C1)(2 cov + C2)) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2));
+ *                 ssim = the mean of S_p over all width height pixels.
+ *   6 map         map_out_dev (nullable, DEVICE, height x width floats): RTM_COMPARE_MAP_ABS (float)D_p, NaN at a
+ *                 non-counting pixel; RTM_COMPARE_MAP_SSIM (float)S_p.
+ * Sums are taken in an order fixed by the frame size alone; no atomics: the same inputs give the same bits on every call, on
+ * any stream, and at any alignment of the frames.  Against a float64 evaluation of the steps above: pixels, outside,
+ * nonfinite, nonfinite_mismatch, max_abs, argmax_x, argmax_y and the MAP_ABS map are exact; mse, rel_mse and psnr are within
+ * 1e-9 relative (psnr: both +inf, or within 1e-9 relative); ssim within 1e-9 absolute; the MAP_SSIM map within 1e-7 absolute
+ * (1e-9 plus the float rounding).
+ * work_dev: DEVICE, 256-byte aligned, rtm_compare_work_bytes = round256(48 tiles) + 256 bytes, tiles = ceil(width / 32)
+ * ceil(height / 32): one 48-byte partial per 32 x 32 tile of pixels and the final record, nothing else (SSIM's moments stay on
+ * the chip).  That is at most 256 bytes per 1024 pixels plus 512 for every frame whose sides are both 32 or more and for
+ * every frame of one tile; a frame thinner than a tile pays its 48 bytes per started tile.  0 for a non-positive size,
+ * SIZE_MAX when the frame itself (24 bytes a pixel) does not fit a size_t.
+ * The call allocates nothing, keeps no per-(device, stream) state, needs no serialisation and only ENQUEUES two launches on
+ * `stream` of `device`: one block per tile, then a one-block fold of the partials that writes the record; one launch when
+ * result_out_dev is null (a map alone needs no fold, and the ABS map alone no window).  a_dev == b_dev is allowed.
+ * Null params, a_dev, b_dev or work_dev, both outputs null, a non-positive size, dtype or map out of range, a negative, NaN or
+ * infinite tolerance, peak or rel_epsilon not finite and > 0, a frame pointer, an output or work_dev misaligned (the
+ * element's 4 or 8 bytes, 8 for the record, 4 for the map, 256 for work_dev), work_dev or either output equal to a_dev or
+ * b_dev, map_out_dev equal to work_dev or to result_out_dev, result_out_dev equal to work_dev, a negative device:
+ * RTM_ERR_INVALID_ARGUMENT, before any device call.  A frame too large for one launch (2^31 pixels or more):
+ * RTM_ERR_UNSUPPORTED, as rtm_tonemap.
+ * Defaults: RTM_COMPARE_DEFAULTS below (the headline's tolerance 1e-4, peak 1, rel_epsilon 1e-2; what rtm_cli --compare uses).
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+enum { RTM_COMPARE_F32 = 0, RTM_COMPARE_F64 = 1 };
+enum { RTM_COMPARE_MAP_ABS = 0, RTM_COMPARE_MAP_SSIM = 1 };
+typedef struct rtm_compare_params {
+    int32_t dtype;       /* RTM_COMPARE_F*: the element type of BOTH frames                     */
+    int32_t map;         /* RTM_COMPARE_MAP_*: what map_out_dev receives                        */
+    double tolerance;    /* >= 0, finite: outside counts D_p > tolerance                        */
+    double peak;         /* > 0, finite: PSNR's peak and SSIM's dynamic range L                 */
+    double rel_epsilon;  /* > 0, finite: rel_mse's denominator offset                           */
+} rtm_compare_params;
+#define RTM_COMPARE_DEFAULTS {RTM_COMPARE_F32, RTM_COMPARE_MAP_ABS, 1e-4, 1.0, 1e-2} /* an initializer of rtm_compare_params */
+typedef struct rtm_compare_result { /* 80 bytes, no padding */
+    double max_abs, mse, psnr, rel_mse, ssim;
+    uint64_t pixels, outside, nonfinite, nonfinite_mismatch;
+    int32_t argmax_x, argmax_y;
+} rtm_compare_result;
+size_t rtm_compare_work_bytes(int32_t width, int32_t height);
+int rtm_compare(const rtm_compare_params* params, int32_t width, int32_t height, int device, const void* a_dev,
+                const void* b_dev, void* work_dev, rtm_compare_result* result_out_dev, float* map_out_dev, void* stream);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);
@@ -655,6 +723,13 @@ int rtm_write_jpg(const char* filename, int w, int h, int comp, const void* data
  * bottom-up; data is HOST, rows top-down like the writers above.  1 on success, 0 on failure.  Added after
  * RTM_ABI_VERSION 5 (callers look the symbol up). */
 int rtm_write_pfm(const char* filename, int w, int h, int comp /* 1 or 3 */, const float* data);
+/* Reads a file rtm_write_pfm wrote, bit for bit: *w, *h and *comp (1 or 3) receive the header's values; data (HOST,
+ * nullable) receives the rows top-down, as the writer was given them, when capacity (in floats) is at least w h comp.  A
+ * null data with capacity 0 only queries the size (the samples are still checked to be all there).  Only little-endian
+ * files (a negative scale) are read.  1 on success; 0, with nothing promised about data, for a file that cannot be opened, a
+ * malformed header (magic, a non-positive or overflowing size, a scale that is no number or 0), a big-endian file, a
+ * truncated file or a capacity that is too small.  Added after RTM_ABI_VERSION 5 (callers look the symbol up). */
+int rtm_read_pfm(const char* filename, int* w, int* h, int* comp, float* data, size_t capacity);
 
 #ifdef __cplusplus
 }

@@ -98,6 +98,21 @@ class rtm_tonemap_stats(C.Structure):  # what rtm_tonemap leaves in stats_out_de
     _fields_ = [("log_average", C.c_float), ("max_luminance", C.c_float), ("exposure", C.c_float), ("pixels", C.c_uint32)]
 
 
+COMPARE_DTYPES = {"float32": 0, "float64": 1}  # include/rtm.h: RTM_COMPARE_F32, RTM_COMPARE_F64
+COMPARE_MAPS = {"abs": 0, "ssim": 1}  # RTM_COMPARE_MAP_*
+
+
+class rtm_compare_params(C.Structure):  # include/rtm.h: rtm_compare
+    _fields_ = [("dtype", C.c_int32), ("map", C.c_int32), ("tolerance", C.c_double), ("peak", C.c_double),
+                ("rel_epsilon", C.c_double)]
+
+
+class rtm_compare_result(C.Structure):  # what rtm_compare leaves in result_out_dev: 80 bytes, no padding
+    _fields_ = [("max_abs", C.c_double), ("mse", C.c_double), ("psnr", C.c_double), ("rel_mse", C.c_double),
+                ("ssim", C.c_double), ("pixels", C.c_uint64), ("outside", C.c_uint64), ("nonfinite", C.c_uint64),
+                ("nonfinite_mismatch", C.c_uint64), ("argmax_x", C.c_int32), ("argmax_y", C.c_int32)]
+
+
 # every symbol include/rtm.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -139,6 +154,9 @@ SIGNATURES = {
     "rtm_upsample_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_upsample": (C.c_int, [_P(rtm_upsample_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
                                _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_compare_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtm_compare": (C.c_int, [_P(rtm_compare_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),
@@ -171,6 +189,7 @@ SIGNATURES = {
     "rtm_write_bmp": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rtm_write_jpg": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "rtm_write_pfm": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "rtm_read_pfm": (C.c_int, [C.c_char_p, _P(C.c_int), _P(C.c_int), _P(C.c_int), C.c_void_p, C.c_size_t]),
 }
 # test and diagnostic hooks: include/rtm_debug.h (not part of the drop-in boundary)
 DEBUG_SIGNATURES = {

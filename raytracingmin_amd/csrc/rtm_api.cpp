@@ -121,6 +121,11 @@ int rtm_upsample(const rtm_upsample_params* params, int32_t low_width, int32_t l
     RTM_GUARD(rtm::upsample(params, low_width, low_height, device, color_low_dev, guide_low_dev, guide_high_dev, work_dev,
                             out_f32_dev, out_u8_dev, stream))
 }
+size_t rtm_compare_work_bytes(int32_t width, int32_t height) { return rtm::compare_work_bytes(width, height); }
+int rtm_compare(const rtm_compare_params* params, int32_t width, int32_t height, int device, const void* a_dev,
+                const void* b_dev, void* work_dev, rtm_compare_result* result_out_dev, float* map_out_dev, void* stream) {
+    RTM_GUARD(rtm::compare(params, width, height, device, a_dev, b_dev, work_dev, result_out_dev, map_out_dev, stream))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {
@@ -223,6 +228,13 @@ int rtm_write_jpg(const char* filename, int w, int h, int comp, const void* data
 int rtm_write_pfm(const char* filename, int w, int h, int comp, const float* data) {
     try {
         return rtm::write_pfm(filename, w, h, comp, data);
+    } catch (...) {
+        return 0;
+    }
+}
+int rtm_read_pfm(const char* filename, int* w, int* h, int* comp, float* data, size_t capacity) {
+    try {
+        return rtm::read_pfm(filename, w, h, comp, data, capacity);
     } catch (...) {
         return 0;
     }

@@ -4,8 +4,11 @@
 // signatures (int return, 1 = success): a 24-bit bottom-up BGR BMP with stb's 54-byte header, and a
 // baseline JFIF JPEG (standard Annex-K tables scaled by quality, 4:2:0 at quality <= 90 like
 // stb's encoder).
+#include <cerrno>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -68,6 +71,54 @@ int write_pfm(const char* filename, int w, int h, int comp, const float* data) {
         }
     }
     return out.ok() ? 1 : 0;
+}
+
+// The reader of the files write_pfm writes (and of any little-endian PFM): the header's three whitespace-separated fields —
+// magic, "w h", scale — end with exactly one whitespace byte; the rows come bottom-up and go back top-down.
+int read_pfm(const char* filename, int* w, int* h, int* comp, float* data, size_t capacity) {
+    if (!filename || !w || !h || !comp || (!data && capacity)) return 0;
+    FILE* f = std::fopen(filename, "rb");
+    if (!f) return 0;
+    struct Closer {
+        FILE* f;
+        ~Closer() { std::fclose(f); }
+    } closer{f};
+    char magic[4] = {0, 0, 0, 0}, size_text[2][32], scale_text[64];
+    if (std::fscanf(f, "%3s", magic) != 1 || magic[0] != 'P' || (magic[1] != 'F' && magic[1] != 'f') || magic[2] != '\0') return 0;
+    if (std::fscanf(f, "%31s %31s", size_text[0], size_text[1]) != 2) return 0;
+    long size[2];
+    char* end = nullptr;
+    for (int i = 0; i < 2; ++i) {
+        errno = 0;
+        size[i] = std::strtol(size_text[i], &end, 10);
+        if (end == size_text[i] || *end != '\0' || errno != 0 || size[i] <= 0 || size[i] > INT32_MAX) return 0;
+    }
+    const int fw = (int)size[0], fh = (int)size[1];
+    if (std::fscanf(f, "%63s", scale_text) != 1) return 0;
+    const double scale = std::strtod(scale_text, &end);
+    if (end == scale_text || *end != '\0' || !(scale < 0.0) || !std::isfinite(scale)) return 0;  // positive: big-endian samples
+    const int sep = std::fgetc(f);
+    if (sep != '\n' && sep != ' ' && sep != '\t' && sep != '\r') return 0;
+    const int fc = magic[1] == 'F' ? 3 : 1;
+    const size_t row = (size_t)fw * (size_t)fc;
+    if ((size_t)fh > SIZE_MAX / sizeof(float) / row) return 0;
+    const size_t n = row * (size_t)fh;
+    *w = fw;
+    *h = fh;
+    *comp = fc;
+    if (data && capacity < n) return 0;
+    std::vector<uint8_t> line(row * 4);
+    for (int y = fh - 1; y >= 0; --y) {
+        if (std::fread(line.data(), 1, line.size(), f) != line.size()) return 0;  // truncated
+        if (!data) continue;
+        float* out = data + (size_t)y * row;
+        for (size_t i = 0; i < row; ++i) {
+            const uint32_t bits = (uint32_t)line[4 * i] | (uint32_t)line[4 * i + 1] << 8 | (uint32_t)line[4 * i + 2] << 16 |
+                                  (uint32_t)line[4 * i + 3] << 24;
+            std::memcpy(&out[i], &bits, sizeof bits);
+        }
+    }
+    return 1;
 }
 
 // stbi_write_bmp layout for comp = 3: "BM", file size, 0, 0, data offset 54; BITMAPINFOHEADER

@@ -61,6 +61,10 @@ size_t upsample_work_bytes(int32_t low_width, int32_t low_height);
 int upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device, const float* color_low,
              const rtm_aov_buffers* guide_low, const rtm_aov_buffers* guide_high, void* work, float* out32, uint8_t* out8,
              void* stream);
+// frame comparison (rtm_compare.hip)
+size_t compare_work_bytes(int32_t width, int32_t height);
+int compare(const rtm_compare_params* params, int32_t width, int32_t height, int device, const void* a, const void* b, void* work,
+            rtm_compare_result* result_out, float* map_out, void* stream);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);
@@ -108,5 +112,6 @@ int quantise(const double* image, size_t n_values, uint8_t* out);
 int write_bmp(const char* filename, int w, int h, int comp, const void* data);
 int write_jpg(const char* filename, int w, int h, int comp, const void* data, int quality);
 int write_pfm(const char* filename, int w, int h, int comp, const float* data);
+int read_pfm(const char* filename, int* w, int* h, int* comp, float* data, size_t capacity);
 
 }  // namespace rtm

@@ -14,6 +14,8 @@
 //                                                (the display transform of the last stage: STEM_display.bmp, .jpg)
 //           [--preview F [--preview-only]]       (the frame traced at 1/F of the resolution per axis, denoised there and upsampled
 //                                                by the first-hit feature buffers: STEM_preview.bmp, .jpg; -only: no full render)
+//           [--pfm]                              (the float frame of the last stage: STEM.pfm)
+//           [--compare REF.pfm]                  (that frame against a reference on the device: one line "compare: {...}")
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -31,6 +33,15 @@ static bool file_exists(const std::string& p) {
     FILE* f = std::fopen(p.c_str(), "rb");
     if (f) std::fclose(f);
     return f != nullptr;
+}
+
+// a double as JSON: the shortest text that reads back to the same bits; Infinity / NaN as Python's json module writes them
+static std::string json_number(double v) {
+    if (std::isnan(v)) return "NaN";
+    if (std::isinf(v)) return v > 0 ? "Infinity" : "-Infinity";
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
 }
 
 static void usage() {
@@ -66,7 +77,12 @@ static void usage() {
         "            2..8, dividing both; F^2 fewer paths), denoised there (rtm_denoise at its defaults) and brought to full size\n"
         "            by rtm_upsample, guided by the first-hit feature buffers at both resolutions: STEM_preview.bmp and\n"
         "            STEM_preview.jpg (with --display also STEM_preview_display.bmp, .jpg).  --preview-only : skip the full\n"
-        "            render; STEM.bmp and STEM.jpg are not written\n");
+        "            render; STEM.bmp and STEM.jpg are not written\n"
+        "--pfm : also write STEM.pfm, the float frame of the last stage asked for (the --denoise-variance frame, else the\n"
+        "        --denoise frame, else the frame itself), bit for bit\n"
+        "--compare REF.pfm : compare that same frame with the 3-channel float map REF.pfm (the reference) on the device\n"
+        "        (rtm_compare at its default parameters: tolerance 1e-4, peak 1, rel_epsilon 1e-2) and print one line\n"
+        "        'compare: {...}', the record's fields as JSON; a file that cannot be read or has another size: exit status 1\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -82,7 +98,8 @@ int main(int argc, char* argv[]) {
     float adaptive_threshold = 0.f;
     int display = 0, preview = 0, preview_only = 0;
     rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
-    std::string dump_f32;
+    int pfm = 0;
+    std::string dump_f32, compare_ref;
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
         const std::string c = argv[i];
@@ -145,6 +162,8 @@ int main(int argc, char* argv[]) {
             }
         } else if (c == "--linear") display_prm.transfer = RTM_TRANSFER_LINEAR;
         else if (c == "--no-dither") display_prm.dither = 0;
+        else if (c == "--pfm") pfm = 1;
+        else if (c == "--compare" && i + 1 < argc) compare_ref = argv[++i];
         else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
         else if (c == "--seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 0);
         else if (c == "--out" && i + 1 < argc) stem = argv[++i];
@@ -205,6 +224,10 @@ int main(int argc, char* argv[]) {
                              "--dump-f32\n");
         return 2;
     }
+    if (preview_only && (pfm || !compare_ref.empty())) {
+        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --pfm or --compare\n");
+        return 2;
+    }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
         std::printf("saving the sample scene json file: %s\n", json_file.c_str());
         if (rtm_scene_save_sample_json(json_file.c_str()) != RTM_OK) return 1;
@@ -245,6 +268,25 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "--preview %d does not divide the %d x %d frame\n", preview, st.width, st.height);
         return 2;
     }
+    std::vector<float> reference;  // --compare: read before anything is rendered, so that a bad file costs no render
+    if (!compare_ref.empty()) {
+        int rw = 0, rh = 0, rcomp = 0;
+        if (rtm_read_pfm(compare_ref.c_str(), &rw, &rh, &rcomp, nullptr, 0) != 1) {
+            std::fprintf(stderr, "--compare: cannot read %s as a little-endian float map\n", compare_ref.c_str());
+            return 1;
+        }
+        if (rw != st.width || rh != st.height || rcomp != 3) {
+            std::fprintf(stderr, "--compare: %s is %d x %d x %d, the frame is %d x %d x 3\n", compare_ref.c_str(), rw, rh, rcomp,
+                         st.width, st.height);
+            return 1;
+        }
+        reference.resize((size_t)rw * rh * 3);
+        if (rtm_read_pfm(compare_ref.c_str(), &rw, &rh, &rcomp, reference.data(), reference.size()) != 1) {
+            std::fprintf(stderr, "--compare: cannot read %s as a little-endian float map\n", compare_ref.c_str());
+            return 1;
+        }
+    }
+    const bool want_last = display || pfm || !compare_ref.empty();  // a later stage takes the float frame of the last one
     if (preview) {  // STEM_preview.bmp / .jpg, and their display transform
         std::string err;
         std::vector<float> shown;
@@ -279,7 +321,7 @@ int main(int argc, char* argv[]) {
 
     const size_t vals = (size_t)st.width * st.height * 3;
     std::vector<uint8_t> rgb8(vals);
-    std::vector<float> rgb32(dump_f32.empty() && !denoise && !denoise_variance && !display ? 0 : vals);
+    std::vector<float> rgb32(dump_f32.empty() && !denoise && !denoise_variance && !want_last ? 0 : vals);
     rtm_stats stats;
     std::vector<uint32_t> tile_samples;
     if (adaptive) {
@@ -355,11 +397,11 @@ int main(int argc, char* argv[]) {
         std::printf("aov: %s_depth.pfm, %s_normal.pfm, %s_albedo.pfm, %s_normal.bmp, %s_albedo.bmp\n", stem.c_str(), stem.c_str(),
                     stem.c_str(), stem.c_str(), stem.c_str());
     }
-    std::vector<float> shown;  // the float frame of the last stage, when --display follows a denoiser
+    std::vector<float> shown;  // the float frame of the last stage, when --display, --pfm or --compare follows a denoiser
     if (denoise) {
         std::string err;
         rc = rtm_node_write_denoised(&st, spheres.data(), n, &opt, rgb32.data(), stem, err,
-                                     display && !denoise_variance ? &shown : nullptr);
+                                     want_last && !denoise_variance ? &shown : nullptr);
         if (rc != RTM_OK) {
             std::fprintf(stderr, "denoise failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
             return 1;
@@ -368,7 +410,7 @@ int main(int argc, char* argv[]) {
     }
     if (denoise_variance) {
         std::string err;
-        rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, rgb32.data(), stem, err, display ? &shown : nullptr);
+        rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, rgb32.data(), stem, err, want_last ? &shown : nullptr);
         if (rc != RTM_OK) {
             std::fprintf(stderr, "denoise-variance failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
             return 1;
@@ -386,6 +428,29 @@ int main(int argc, char* argv[]) {
         }
         std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",
                     stem.c_str(), stem.c_str(), (double)ts.log_average, (double)ts.max_luminance, (double)ts.exposure, ts.pixels);
+    }
+    const float* last = shown.empty() ? rgb32.data() : shown.data();
+    if (pfm) {
+        if (rtm_write_pfm((stem + ".pfm").c_str(), st.width, st.height, 3, last) != 1) {
+            std::fprintf(stderr, "cannot write %s.pfm\n", stem.c_str());
+            return 1;
+        }
+        std::printf("pfm: %s.pfm\n", stem.c_str());
+    }
+    if (!compare_ref.empty()) {
+        std::string err;
+        rtm_compare_result cr;
+        rc = rtm_node_compare(&st, opt.device, last, reference.data(), &cr, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "compare failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        std::printf("compare: {\"max_abs\": %s, \"mse\": %s, \"psnr\": %s, \"rel_mse\": %s, \"ssim\": %s, \"pixels\": %llu, "
+                    "\"outside\": %llu, \"nonfinite\": %llu, \"nonfinite_mismatch\": %llu, \"argmax_x\": %d, \"argmax_y\": %d}\n",
+                    json_number(cr.max_abs).c_str(), json_number(cr.mse).c_str(), json_number(cr.psnr).c_str(),
+                    json_number(cr.rel_mse).c_str(), json_number(cr.ssim).c_str(), (unsigned long long)cr.pixels,
+                    (unsigned long long)cr.outside, (unsigned long long)cr.nonfinite, (unsigned long long)cr.nonfinite_mismatch,
+                    cr.argmax_x, cr.argmax_y);
     }
     return 0;
 }

@@ -691,6 +691,45 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
     return RTM_OK;
 }
 
+// --compare (rtm_node.h): rtm_compare of the two frames on the default stream.
+int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host, const float* reference_host,
+                     rtm_compare_result* result, std::string& err) {
+    if (hipSetDevice(device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    const size_t bytes = (size_t)st->width * st->height * 3 * sizeof(float);
+    const size_t work_bytes = rtm_compare_work_bytes(st->width, st->height);
+    float *a = nullptr, *b = nullptr;
+    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_compare asks of work_dev
+    rtm_compare_result* result_dev = nullptr;
+    int rc = RTM_OK;
+    if (hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess ||
+        hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc((void**)&result_dev, sizeof(rtm_compare_result)) != hipSuccess) {
+        err = "no device memory for the comparison's buffers";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && (hipMemcpy(a, frame_host, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                         hipMemcpy(b, reference_host, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+        err = "copying the frames to the device failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        const rtm_compare_params prm = RTM_COMPARE_DEFAULTS;
+        rc = rtm_compare(&prm, st->width, st->height, device, a, b, work, result_dev, nullptr, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    if (rc == RTM_OK && hipMemcpy(result, result_dev, sizeof *result, hipMemcpyDeviceToHost) != hipSuccess) {
+        err = "copying the comparison's record back failed";
+        rc = RTM_ERR_HIP;
+    }
+    (void)hipFree(a);
+    (void)hipFree(b);
+    (void)hipFree(work);
+    (void)hipFree(result_dev);
+    return rc;
+}
+
 // --preview (rtm_node.h): the low render, its AOVs and rtm_denoise, the full AOVs, rtm_upsample, all on the default stream,
 // then the two files.
 int rtm_node_write_preview(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int factor,

@@ -44,6 +44,10 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
 // statistics and the exposure that was applied.
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* params, const float* f32_host,
                            const std::string& stem, rtm_tonemap_stats* stats, std::string& err);
+// Two float frames (HOST, height x width x 3; `frame` under test, `reference`) compared on device `device` (rtm_compare at its
+// default parameters, rtm_cli --compare): both are copied to the device, one call on the default stream, the record copied back.
+int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host, const float* reference_host,
+                     rtm_compare_result* result, std::string& err);
 // The preview of the frame on options->device (rtm_cli --preview F): the scene traced at (width / factor) x (height / factor)
 // with the same camera, samples, seed and mode, denoised there at the default parameters (rtm_denoise guided by the low
 // rtm_render_aov planes) and brought to full size by rtm_upsample at its default sigmas, guided by the AOVs at both

@@ -114,6 +114,22 @@ class Renderer:
             o.band_count, o.band_index = int(band[0]), int(band[1])
         return o
 
+    def compare(self, reference, frame=None, **params):
+        """compare() of a frame of this renderer against `reference`, decoded: a dict of rtm_compare_result's fields.
+        frame=None: the last rendered image (self.image, float64); else an (H, W, 3) array or tensor.  `reference` is an
+        (H, W, 3) array or tensor; both go to this renderer's device, and a float64 frame is rounded to float32 when the
+        reference is float32 (what out_f32 holds).  params: compare()'s tolerance, peak, rel_epsilon."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        to_dev = lambda v: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(dev).contiguous()
+        ref = to_dev(reference)
+        got = to_dev(self.image if frame is None else frame)
+        if got.dtype == torch.float64 and ref.dtype == torch.float32:
+            got = got.to(torch.float32)
+        out = compare(got, ref, want=("result",), **params)
+        torch.cuda.current_stream(dev).synchronize()
+        return compare_result(out["result"])
+
     # ---- device-resident render: outputs are torch tensors on the GPU ------------------------
     def render_rows_device(self, row_begin=0, row_end=None, want=("f32",), stats=True,
                            stream=None, band=None):
@@ -780,6 +796,89 @@ def tonemap_stats(words):
     raw = np.ascontiguousarray(words.cpu().numpy() if hasattr(words, "cpu") else words).view(np.uint32)
     f = raw.view(np.float32)
     return {"log_average": float(f[0]), "max_luminance": float(f[1]), "exposure": float(f[2]), "pixels": int(raw[3])}
+
+
+# include/rtm.h: RTM_COMPARE_DEFAULTS (the dtype comes from the tensors)
+COMPARE_DEFAULTS = {"tolerance": 1e-4, "peak": 1.0, "rel_epsilon": 1e-2, "map": "abs"}
+
+
+def _compare_params(dtype, tolerance=COMPARE_DEFAULTS["tolerance"], peak=COMPARE_DEFAULTS["peak"],
+                    rel_epsilon=COMPARE_DEFAULTS["rel_epsilon"], map=COMPARE_DEFAULTS["map"]):
+    """compare()'s parameters as an rtm_compare_params; a ValueError names what the library would refuse.  No device use."""
+    if map not in _lib.COMPARE_MAPS:
+        raise ValueError(f"map is one of {tuple(_lib.COMPARE_MAPS)}, got {map!r}")
+    tolerance, peak, rel_epsilon = float(tolerance), float(peak), float(rel_epsilon)
+    if not (np.isfinite(tolerance) and tolerance >= 0.0):
+        raise ValueError(f"tolerance must be finite and non-negative, got {tolerance!r}")
+    if not (np.isfinite(peak) and peak > 0.0):
+        raise ValueError(f"peak must be finite and positive, got {peak!r}")
+    if not (np.isfinite(rel_epsilon) and rel_epsilon > 0.0):
+        raise ValueError(f"rel_epsilon must be finite and positive, got {rel_epsilon!r}")
+    return _lib.rtm_compare_params(_lib.COMPARE_DTYPES[dtype], _lib.COMPARE_MAPS[map], tolerance, peak, rel_epsilon)
+
+
+def compare(a, b, tolerance=COMPARE_DEFAULTS["tolerance"], peak=COMPARE_DEFAULTS["peak"],
+            rel_epsilon=COMPARE_DEFAULTS["rel_epsilon"], map=COMPARE_DEFAULTS["map"], want=("result",), stream=None):
+    """Frame comparison (include/rtm.h: rtm_compare) on the device: `a` is the frame under test, `b` the reference, both
+    contiguous (H, W, 3) torch CUDA tensors of the same shape, device and dtype, float32 or float64 (the dtype the library
+    is told comes from the tensors).  tolerance: `outside` counts the pixels whose largest component error exceeds it; peak:
+    PSNR's peak and SSIM's dynamic range; rel_epsilon: the offset of rel_mse's denominator; map "abs" | "ssim": what the
+    "map" output holds.  Returns a dict of the names in `want`: "result" a 20-word int32 tensor holding the bits of
+    rtm_compare_result (compare_result() reads it on the host), "map" an (H, W) float32 tensor.  A shape or dtype mismatch
+    raises before the library is called.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the
+    current stream) with a work buffer allocated here; nothing waits for it and nothing is copied to the host."""
+    outputs = ("result", "map")
+    unknown = set(want) - set(outputs)
+    if unknown or not want:
+        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+    shape_a, shape_b = tuple(getattr(a, "shape", ())), tuple(getattr(b, "shape", ()))
+    if len(shape_a) != 3 or shape_a[2] != 3 or shape_a[0] < 1 or shape_a[1] < 1:
+        raise ValueError(f"a must be an (H, W, 3) frame, got shape {shape_a}")
+    if shape_a != shape_b:
+        raise ValueError(f"a and b must have the same shape, got {shape_a} and {shape_b}")
+    dtype_a, dtype_b = str(a.dtype).split(".")[-1], str(b.dtype).split(".")[-1]
+    if dtype_a != dtype_b:
+        raise ValueError(f"a and b must have the same dtype, got {dtype_a} and {dtype_b}")
+    if dtype_a not in _lib.COMPARE_DTYPES:
+        raise ValueError(f"frames are float32 or float64, got {dtype_a}")
+    prm = _compare_params(dtype_a, tolerance, peak, rel_epsilon, map)
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("compare needs a HIP device; there is no CPU fallback")
+    for name, v in (("a", a), ("b", b)):
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous CUDA tensor")
+    if a.device != b.device:
+        raise ValueError(f"a and b must be on one device, got {a.device} and {b.device}")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    dev = a.device
+    if stream is None:
+        s = torch.cuda.current_stream(dev)
+    elif isinstance(stream, torch.cuda.Stream):
+        s = stream
+    else:
+        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    L = _lib.lib()
+    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
+        work = torch.empty(max(256, L.rtm_compare_work_bytes(W, H)), dtype=torch.uint8, device=dev)
+        out = {}
+        if "result" in want:
+            out["result"] = torch.empty(C.sizeof(_lib.rtm_compare_result) // 4, dtype=torch.int32, device=dev)
+        if "map" in want:
+            out["map"] = torch.empty((H, W), dtype=torch.float32, device=dev)
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    _lib.check(L.rtm_compare(C.byref(prm), W, H, dev.index, a.data_ptr(), b.data_ptr(), work.data_ptr(), ptr("result"),
+                             ptr("map"), C.c_void_p(s.cuda_stream)), "rtm_compare")
+    return out
+
+
+def compare_result(words):
+    """compare()'s "result" tensor as a dict of rtm_compare_result's fields; copies the record's 20 words to the host
+    (synchronise the stream that wrote them first when it is not the current one)."""
+    raw = np.ascontiguousarray(words.cpu().numpy() if hasattr(words, "cpu") else words).view(np.uint8)
+    rec = _lib.rtm_compare_result.from_buffer_copy(raw.tobytes())
+    floats = ("max_abs", "mse", "psnr", "rel_mse", "ssim")
+    return {name: (float(getattr(rec, name)) if name in floats else int(getattr(rec, name))) for name, _ in rec._fields_}
 
 
 def plan_passes(n_samples, passes=None, samples_per_pass=None):
