@@ -635,6 +635,92 @@ size_t rtm_compare_work_bytes(int32_t width, int32_t height);
 int rtm_compare(const rtm_compare_params* params, int32_t width, int32_t height, int device, const void* a_dev,
                 const void* b_dev, void* work_dev, rtm_compare_result* result_out_dev, float* map_out_dev, void* stream);
 
+/* ---- perceptual frame difference (LDR FLIP, Andersson et al. 2020, "A Difference Evaluator for Alternating Images"): which
+ * of two wrong frames LOOKS closer to a reference, where rtm_compare answers whether two frames are the same.  Contrast
+ * sensitivity filtering in an opponent colour space, a perceptually uniform colour distance and an edge / point feature term
+ * give one error map in [0, 1] and pooled statistics, on the device.  This text is the definition; its constants are the
+ * paper's and its published program's as known here, and no figure has been compared with that program.
+ * Inputs: `a` is the frame under test, `b` the reference: DEVICE buffers of height x width x 3 floats, RGB-interleaved like
+ * out_f32, 4-byte aligned, DISPLAY-REFERRED: params.transfer says how they are encoded, RTM_TRANSFER_SRGB as rtm_tonemap
+ * writes them by default, RTM_TRANSFER_LINEAR already linear.  Every value is widened to double exactly and all arithmetic
+ * is in double; FMA contraction is allowed.  ppd = params.pixels_per_degree, finite, in [8, 128]; the default is a 0.7 m wide
+ * 3840-pixel monitor viewed from 0.7 m, 0.7 * 3840 / 0.7 * pi / 180 = 67.02...
+ *   1 counting    a pixel COUNTS iff its six components are finite.  A non-counting pixel is (0, 0, 0) in BOTH frames for
+ *                 everything below (its neighbours see black), its map value is NaN and it is excluded from the pooled
+ *                 statistics.  pixels = n, the number of counting pixels; nonfinite = width height - n.
+ *   2 to linear   each component clamped to [0, 1]; for SRGB then c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4).
+ *   3 opponent    XYZ = M rgb, M's rows (10135552, 8788810, 4435075) / 24577794, (2613072, 8788810, 887015) / 12288897,
+ *                 (1425312, 8788810, 70074185) / 73733382, each entry one double division, a row applied as
+ *                 (m0 r + m1 g) + m2 b; (Xn, Yn, Zn) = M (1, 1, 1) = (m0 + m1) + m2 per row.  With x = X / Xn, y = Y / Yn,
+ *                 z = Z / Zn:  Y = 116 y - 16,  Cx = 500 (x - y),  Cz = 200 (y - z).
+ *   4 CSF         e_b(k) = exp(-pi^2 (k / ppd)^2 / b), k = -r..r, r = ceil(3 sqrt(0.04 / (2 pi^2)) ppd) (10 at the default,
+ *                 2..18 over the range).  Y is filtered with e_0.0047(dx) e_0.0047(dy), Cx with e_0.0053(dx) e_0.0053(dy), Cz
+ *                 with A1 e_0.04(dx) e_0.04(dy) + A2 e_0.025(dx) e_0.025(dy), A1 = 34.1 sqrt(pi / 0.04), A2 = 13.5 sqrt(pi /
+ *                 0.025); each 2-D filter is divided by its own sum over the (2r+1)^2 grid.  As 1-D tables used in both axes:
+ *                 t_Y(k) = e_0.0047(k) / sum e_0.0047, t_Cx likewise, and for Cz the two parts t_1(k) = sqrt(A1 / S) e_0.04(k),
+ *                 t_2(k) = sqrt(A2 / S) e_0.025(k) with S = A1 (sum e_0.04)^2 + A2 (sum e_0.025)^2, filtered Cz = the sum of
+ *                 the two separable results.  A tap outside the frame takes the NEAREST IN-FRAME pixel (coordinates clamped:
+ *                 replicate padding).  That is the published definition and it DIFFERS from the skip-and-renormalise rule of
+ *                 this library's other filters (rtm_compare's SSIM window, the denoisers).  A separable filter is evaluated
+ *                 horizontal pass first, taps in ascending offset; the tables are computed in double on the host.
+ *   5 colour      filtered (Y, Cx, Cz) back to linear RGB: y = (Y + 16) / 116, x = Cx / 500 + y, z = y - Cz / 200, times
+ *                 (Xn, Yn, Zn), then M^-1 (inverted in double on the host), clamped to [0, 1]; to CIELAB with the same white:
+ *                 f(t) = t > (6/29)^3 ? cbrt(t) : t / (3 (6/29)^2) + 4/29 on M rgb / white, L = 116 f(y) - 16,
+ *                 a = 500 (f(x) - f(y)), b = 200 (f(y) - f(z)); Hunt adjustment (L, 0.01 L a, 0.01 L b); HyAB distance
+ *                 |dL| + sqrt(da^2 + db^2) between the two frames; c = HyAB^0.7; cmax = the same power of the HyAB distance
+ *                 between the Hunt-adjusted Lab of linear (0, 1, 0) and of linear (0, 0, 1), computed on the host (41.276...);
+ *                 dEc = c < 0.4 cmax ? (0.95 / (0.4 cmax)) c : 0.95 + (c - 0.4 cmax) / (cmax - 0.4 cmax) 0.05.
+ *   6 feature     on the UNFILTERED y = (Y + 16) / 116 of each frame: sigma = 0.5 0.082 ppd, rf = ceil(3 sigma) (9 at the
+ *                 default, 1..16 over the range), g(k) = exp(-k^2 / (2 sigma^2)), d(k) = -k g(k) (edge), p(k) = (k^2 / sigma^2
+ *                 - 1) g(k) (point).  Of each 2-D filter d(dx) g(dy) and p(dx) g(dy) the positive weights are divided by their
+ *                 sum and the negative ones by the magnitude of theirs; the sign depends on dx alone, so as 1-D tables:
+ *                 g'(k) = g(k) / sum g;  d'(k) = d(k) / sum_{k<0} d(k) (d is odd: one divisor serves both signs);
+ *                 p'(k) = p(k) / sum_{p>0} p where p(k) > 0, p(k) / |sum_{p<0} p| where p(k) < 0.  ex = d'(dx) g'(dy),
+ *                 ey = g'(dx) d'(dy), px = p'(dx) g'(dy), py = g'(dx) p'(dy), replicate padding, horizontal pass first.  Per
+ *                 frame |edge| = sqrt(ex^2 + ey^2), |point| = sqrt(px^2 + py^2);
+ *                 dEf = sqrt(max(| |edge_b| - |edge_a| |, | |point_b| - |point_a| |) / sqrt(2)).
+ *   7 combine     dE_p = dEc^(1 - dEf), with pow(0, .) = 0.  map_out_dev (nullable, DEVICE, height x width floats) receives
+ *                 (float)dE_p, NaN at a non-counting pixel.  Identical inputs give dE_p = +0 exactly at every counting pixel.
+ *   8 pooled      rtm_flip_result (1072 bytes, no padding): mean = the mean of dE_p over the counting pixels (0 when n = 0);
+ *                 max, with (argmax_x, argmax_y) the lowest row-major pixel index that attains it (0 and (-1, -1) when n = 0);
+ *                 min (0 when n = 0); pixels, nonfinite as in step 1; hist[256] = counts of counting pixels, bin =
+ *                 min(255, (int)(m * 256.0f)) with m the pixel's FLOAT map value: exact given the call's own map, the way
+ *                 rtm_tonemap's out_u8 is exact given its own out_f32, and computed whether or not the map is stored.
+ * Sums are taken in an order fixed by the frame size alone and the only atomics add integers (the histogram): the same inputs
+ * give the same bits on every call, on any stream.  Against a float64 evaluation of the steps above: pixels, nonfinite and
+ * where the map is NaN are exact; mean, min and max are within 1e-9 absolute, the map within 1e-9 plus its float rounding
+ * (2^-25 = 3e-8); argmax is the evaluation's wherever its two largest values differ by more than 2e-9.  (The bound is max(1e-9,
+ * 100 D), D = 9.3e-14 the largest disagreement of two float64 evaluation orders, separable and direct 2-D: DESIGN.md.)
+ * work_dev: DEVICE, 256-byte aligned, rtm_flip_work_bytes = round256(112 width height) + round256(32 tiles) + 1024 bytes,
+ * tiles = ceil(width / 64) ceil(height / 16): the seven horizontally filtered planes of each frame as doubles (they do not
+ * fit the chip: a tile with the halo of the largest tables would need 3.2 times a CU's LDS), one 32-byte partial per tile
+ * and the histogram.  0 for a non-positive size, SIZE_MAX when that sum does not fit a size_t.
+ * The call allocates nothing, keeps no per-(device, stream) state, needs no serialisation and only ENQUEUES three launches on
+ * `stream` of `device`: the horizontal pass (one block per 256 pixels of a row), the vertical pass with steps 5-8 (one block
+ * per tile) and a one-block fold that writes the record; two launches when result_out_dev is null.  a_dev == b_dev is
+ * allowed.  Null params, a_dev, b_dev or work_dev, both outputs null, a non-positive size, transfer out of range,
+ * pixels_per_degree NaN, infinite or outside [8, 128], a frame pointer, an output or work_dev misaligned (4 bytes for the
+ * frames and the map, 8 for the record, 256 for work_dev), work_dev or either output equal to a_dev or b_dev, map_out_dev
+ * equal to work_dev or to result_out_dev, result_out_dev equal to work_dev, a negative device: RTM_ERR_INVALID_ARGUMENT,
+ * before any device call.  A frame of 2^31 pixels or more: RTM_ERR_UNSUPPORTED.
+ * Defaults: RTM_FLIP_DEFAULTS below (what rtm_cli --flip uses).
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+typedef struct rtm_flip_params { /* 16 bytes */
+    int32_t transfer;         /* RTM_TRANSFER_*: how BOTH frames are encoded                    */
+    double pixels_per_degree; /* finite, in [8, 128]                                            */
+} rtm_flip_params;
+#define RTM_FLIP_DEFAULT_PPD (0.7 * 3840.0 / 0.7 * 3.14159265358979323846 / 180.0)
+#define RTM_FLIP_DEFAULTS {RTM_TRANSFER_SRGB, RTM_FLIP_DEFAULT_PPD} /* an initializer of rtm_flip_params */
+typedef struct rtm_flip_result { /* 1072 bytes, no padding */
+    double mean, max, min;
+    uint64_t pixels, nonfinite;
+    int32_t argmax_x, argmax_y;
+    uint32_t hist[256];
+} rtm_flip_result;
+size_t rtm_flip_work_bytes(int32_t width, int32_t height);
+int rtm_flip(const rtm_flip_params* params, int32_t width, int32_t height, int device, const float* a_dev,
+             const float* b_dev, void* work_dev, rtm_flip_result* result_out_dev, float* map_out_dev, void* stream);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);

@@ -113,6 +113,15 @@ class rtm_compare_result(C.Structure):  # what rtm_compare leaves in result_out_
                 ("nonfinite_mismatch", C.c_uint64), ("argmax_x", C.c_int32), ("argmax_y", C.c_int32)]
 
 
+class rtm_flip_params(C.Structure):  # include/rtm.h: rtm_flip (16 bytes: four bytes of padding after transfer)
+    _fields_ = [("transfer", C.c_int32), ("pixels_per_degree", C.c_double)]
+
+
+class rtm_flip_result(C.Structure):  # what rtm_flip leaves in result_out_dev: 1072 bytes, no padding
+    _fields_ = [("mean", C.c_double), ("max", C.c_double), ("min", C.c_double), ("pixels", C.c_uint64),
+                ("nonfinite", C.c_uint64), ("argmax_x", C.c_int32), ("argmax_y", C.c_int32), ("hist", C.c_uint32 * 256)]
+
+
 # every symbol include/rtm.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -157,6 +166,9 @@ SIGNATURES = {
     "rtm_compare_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_compare": (C.c_int, [_P(rtm_compare_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_flip_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "rtm_flip": (C.c_int, [_P(rtm_flip_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),

@@ -126,6 +126,11 @@ int rtm_compare(const rtm_compare_params* params, int32_t width, int32_t height,
                 const void* b_dev, void* work_dev, rtm_compare_result* result_out_dev, float* map_out_dev, void* stream) {
     RTM_GUARD(rtm::compare(params, width, height, device, a_dev, b_dev, work_dev, result_out_dev, map_out_dev, stream))
 }
+size_t rtm_flip_work_bytes(int32_t width, int32_t height) { return rtm::flip_work_bytes(width, height); }
+int rtm_flip(const rtm_flip_params* params, int32_t width, int32_t height, int device, const float* a_dev, const float* b_dev,
+             void* work_dev, rtm_flip_result* result_out_dev, float* map_out_dev, void* stream) {
+    RTM_GUARD(rtm::flip(params, width, height, device, a_dev, b_dev, work_dev, result_out_dev, map_out_dev, stream))
+}
 int rtm_render_device(const rtm_settings* settings, const rtm_sphere* spheres, size_t n_spheres,
                       int spheres_on_device, const rtm_options* options, double* out_f64_dev,
                       float* out_f32_dev, uint8_t* out_u8_dev, void* stream, rtm_stats* stats) {

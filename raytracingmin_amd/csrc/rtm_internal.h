@@ -65,6 +65,10 @@ int upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_h
 size_t compare_work_bytes(int32_t width, int32_t height);
 int compare(const rtm_compare_params* params, int32_t width, int32_t height, int device, const void* a, const void* b, void* work,
             rtm_compare_result* result_out, float* map_out, void* stream);
+// perceptual frame difference (rtm_flip.hip)
+size_t flip_work_bytes(int32_t width, int32_t height);
+int flip(const rtm_flip_params* params, int32_t width, int32_t height, int device, const float* a, const float* b, void* work,
+         rtm_flip_result* result_out, float* map_out, void* stream);
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int spheres_on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8, void* stream,
                   rtm_stats* stats);

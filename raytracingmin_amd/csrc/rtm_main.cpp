@@ -16,6 +16,11 @@
 //                                                by the first-hit feature buffers: STEM_preview.bmp, .jpg; -only: no full render)
 //           [--pfm]                              (the float frame of the last stage: STEM.pfm)
 //           [--compare REF.pfm]                  (that frame against a reference on the device: one line "compare: {...}")
+//           [--display-pfm]                      (with --display: the display transform's float frame, STEM_display.pfm)
+//           [--flip REF.pfm [--flip-ppd X] [--flip-map]]
+//                                                (the perceptual difference of the display frame, or without --display of the
+//                                                last stage's frame taken as linear, from a reference of the same kind: one
+//                                                line "flip: {...}"; -map: STEM_flip.pfm)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
@@ -82,7 +87,16 @@ static void usage() {
         "        --denoise frame, else the frame itself), bit for bit\n"
         "--compare REF.pfm : compare that same frame with the 3-channel float map REF.pfm (the reference) on the device\n"
         "        (rtm_compare at its default parameters: tolerance 1e-4, peak 1, rel_epsilon 1e-2) and print one line\n"
-        "        'compare: {...}', the record's fields as JSON; a file that cannot be read or has another size: exit status 1\n");
+        "        'compare: {...}', the record's fields as JSON; a file that cannot be read or has another size: exit status 1\n"
+        "--display-pfm : with --display, also write STEM_display.pfm, the display transform's float frame (sRGB-encoded, or\n"
+        "        linear with --linear), bit for bit: what --display --flip takes as its reference\n"
+        "--flip REF.pfm [--flip-ppd X] [--flip-map] : the perceptual difference (rtm_flip, LDR FLIP) between the frame and the\n"
+        "        3-channel float map REF.pfm (the reference) on the device.  With --display the frame is the display transform's\n"
+        "        float frame (sRGB, or linear with --linear) and REF.pfm a --display-pfm file; without it the float frame of the\n"
+        "        last stage, taken as linear and clamped to [0, 1], and REF.pfm a --pfm file.  --flip-ppd X : pixels per degree\n"
+        "        in [8, 128] (default 67.02: a 0.7 m wide 4K monitor at 0.7 m).  Prints one line 'flip: {...}', the record\n"
+        "        without its histogram plus the weighted median, as JSON; --flip-map : also write STEM_flip.pfm, the error map\n"
+        "        in [0, 1]; a file that cannot be read or has another size: exit status 1\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -99,7 +113,9 @@ int main(int argc, char* argv[]) {
     int display = 0, preview = 0, preview_only = 0;
     rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
     int pfm = 0;
-    std::string dump_f32, compare_ref;
+    std::string dump_f32, compare_ref, flip_ref;
+    int display_pfm = 0, flip_map = 0, flip_ppd_given = 0;
+    rtm_flip_params flip_prm = RTM_FLIP_DEFAULTS;
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
         const std::string c = argv[i];
@@ -164,7 +180,19 @@ int main(int argc, char* argv[]) {
         else if (c == "--no-dither") display_prm.dither = 0;
         else if (c == "--pfm") pfm = 1;
         else if (c == "--compare" && i + 1 < argc) compare_ref = argv[++i];
-        else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
+        else if (c == "--display-pfm") display_pfm = 1;
+        else if (c == "--flip" && i + 1 < argc) flip_ref = argv[++i];
+        else if (c == "--flip-map") flip_map = 1;
+        else if (c == "--flip-ppd" && i + 1 < argc) {
+            const std::string m = argv[++i];
+            char* end = nullptr;
+            flip_prm.pixels_per_degree = std::strtod(m.c_str(), &end);
+            flip_ppd_given = 1;
+            if (end == m.c_str() || *end != '\0' || !(flip_prm.pixels_per_degree >= 8.0 && flip_prm.pixels_per_degree <= 128.0)) {
+                std::fprintf(stderr, "--flip-ppd takes a number of pixels per degree in [8, 128], got %s\n", m.c_str());
+                return 2;
+            }
+        } else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
         else if (c == "--seed" && i + 1 < argc) seed = std::strtoull(argv[++i], nullptr, 0);
         else if (c == "--out" && i + 1 < argc) stem = argv[++i];
         else if (c == "--mode" && i + 1 < argc) {
@@ -228,6 +256,19 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --pfm or --compare\n");
         return 2;
     }
+    if (preview_only && !flip_ref.empty()) {
+        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --flip\n");
+        return 2;
+    }
+    if (display_pfm && (!display || preview_only)) {
+        std::fprintf(stderr, "--display-pfm writes the display transform's float frame of the full render: it requires --display and "
+                             "does not combine with --preview-only\n");
+        return 2;
+    }
+    if ((flip_map || flip_ppd_given) && flip_ref.empty()) {
+        std::fprintf(stderr, "--flip-map and --flip-ppd require --flip REF.pfm\n");
+        return 2;
+    }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
         std::printf("saving the sample scene json file: %s\n", json_file.c_str());
         if (rtm_scene_save_sample_json(json_file.c_str()) != RTM_OK) return 1;
@@ -286,7 +327,26 @@ int main(int argc, char* argv[]) {
             return 1;
         }
     }
-    const bool want_last = display || pfm || !compare_ref.empty();  // a later stage takes the float frame of the last one
+    std::vector<float> flip_reference;  // --flip: likewise
+    if (!flip_ref.empty()) {
+        int rw = 0, rh = 0, rcomp = 0;
+        if (rtm_read_pfm(flip_ref.c_str(), &rw, &rh, &rcomp, nullptr, 0) != 1) {
+            std::fprintf(stderr, "--flip: cannot read %s as a little-endian float map\n", flip_ref.c_str());
+            return 1;
+        }
+        if (rw != st.width || rh != st.height || rcomp != 3) {
+            std::fprintf(stderr, "--flip: %s is %d x %d x %d, the frame is %d x %d x 3\n", flip_ref.c_str(), rw, rh, rcomp, st.width,
+                         st.height);
+            return 1;
+        }
+        flip_reference.resize((size_t)rw * rh * 3);
+        if (rtm_read_pfm(flip_ref.c_str(), &rw, &rh, &rcomp, flip_reference.data(), flip_reference.size()) != 1) {
+            std::fprintf(stderr, "--flip: cannot read %s as a little-endian float map\n", flip_ref.c_str());
+            return 1;
+        }
+    }
+    // a later stage takes the float frame of the last one
+    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty();
     if (preview) {  // STEM_preview.bmp / .jpg, and their display transform
         std::string err;
         std::vector<float> shown;
@@ -418,16 +478,25 @@ int main(int argc, char* argv[]) {
         std::printf("denoise-variance: %s_denoised_var.bmp, %s_denoised_var.jpg, %s_variance.pfm\n", stem.c_str(), stem.c_str(),
                     stem.c_str());
     }
+    std::vector<float> displayed;  // the display transform's float frame, when --display-pfm or --flip follows --display
     if (display) {
         std::string err;
         rtm_tonemap_stats ts;
-        rc = rtm_node_write_display(&st, opt.device, &display_prm, shown.empty() ? rgb32.data() : shown.data(), stem, &ts, err);
+        rc = rtm_node_write_display(&st, opt.device, &display_prm, shown.empty() ? rgb32.data() : shown.data(), stem, &ts, err,
+                                    display_pfm || !flip_ref.empty() ? &displayed : nullptr);
         if (rc != RTM_OK) {
             std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
             return 1;
         }
         std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",
                     stem.c_str(), stem.c_str(), (double)ts.log_average, (double)ts.max_luminance, (double)ts.exposure, ts.pixels);
+    }
+    if (display_pfm) {
+        if (rtm_write_pfm((stem + "_display.pfm").c_str(), st.width, st.height, 3, displayed.data()) != 1) {
+            std::fprintf(stderr, "cannot write %s_display.pfm\n", stem.c_str());
+            return 1;
+        }
+        std::printf("display-pfm: %s_display.pfm\n", stem.c_str());
     }
     const float* last = shown.empty() ? rgb32.data() : shown.data();
     if (pfm) {
@@ -451,6 +520,43 @@ int main(int argc, char* argv[]) {
                     json_number(cr.rel_mse).c_str(), json_number(cr.ssim).c_str(), (unsigned long long)cr.pixels,
                     (unsigned long long)cr.outside, (unsigned long long)cr.nonfinite, (unsigned long long)cr.nonfinite_mismatch,
                     cr.argmax_x, cr.argmax_y);
+    }
+    if (!flip_ref.empty()) {
+        std::string err;
+        rtm_flip_result fr;
+        std::vector<float> fmap;
+        if (display)
+            flip_prm.transfer = display_prm.transfer;  // the display frame's own encoding
+        else
+            flip_prm.transfer = RTM_TRANSFER_LINEAR;  // the last stage's frame, taken as linear
+        rc = rtm_node_flip(&st, opt.device, &flip_prm, display ? displayed.data() : last, flip_reference.data(), &fr,
+                           flip_map ? &fmap : nullptr, err);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "flip failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        // the weighted median as the published tool pools it: bin i weighs its count times its centre (i + 0.5) / 256; the
+        // centre of the first bin at which the running weight reaches half of the total (bin resolution, 1/256)
+        double run[256], total = 0.0, median = 0.0;
+        for (int i = 0; i < 256; ++i) run[i] = total += (double)fr.hist[i] * (((double)i + 0.5) / 256.0);
+        if (total > 0.0)
+            for (int i = 0; i < 256; ++i)
+                if (run[i] >= 0.5 * total) {
+                    median = ((double)i + 0.5) / 256.0;
+                    break;
+                }
+        std::printf("flip: {\"mean\": %s, \"max\": %s, \"min\": %s, \"pixels\": %llu, \"nonfinite\": %llu, \"argmax_x\": %d, "
+                    "\"argmax_y\": %d, \"weighted_median\": %s}\n",
+                    json_number(fr.mean).c_str(), json_number(fr.max).c_str(), json_number(fr.min).c_str(),
+                    (unsigned long long)fr.pixels, (unsigned long long)fr.nonfinite, fr.argmax_x, fr.argmax_y,
+                    json_number(median).c_str());
+        if (flip_map) {
+            if (rtm_write_pfm((stem + "_flip.pfm").c_str(), st.width, st.height, 1, fmap.data()) != 1) {
+                std::fprintf(stderr, "cannot write %s_flip.pfm\n", stem.c_str());
+                return 1;
+            }
+            std::printf("flip-map: %s_flip.pfm\n", stem.c_str());
+        }
     }
     return 0;
 }

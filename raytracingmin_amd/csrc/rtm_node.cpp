@@ -643,7 +643,7 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
 
 // --display (rtm_node.h): rtm_tonemap of the frame on the default stream, then the two files.
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* prm, const float* f32_host,
-                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err) {
+                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err, std::vector<float>* f32_out) {
     if (hipSetDevice(device) != hipSuccess) {
         err = "no HIP device " + std::to_string(device);
         return RTM_ERR_NO_DEVICE;
@@ -651,11 +651,13 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
     const size_t pix = (size_t)st->width * st->height;
     const size_t work_bytes = rtm_tonemap_work_bytes(st->width, st->height);
     float* color = nullptr;
+    float* out32 = nullptr;  // only when f32_out is asked for
     uint8_t* out8 = nullptr;
     void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_tonemap asks of work_dev
     rtm_tonemap_stats* stats_dev = nullptr;
     int rc = RTM_OK;
     if (hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
+        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) ||
         hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc((void**)&stats_dev, sizeof(rtm_tonemap_stats)) != hipSuccess) {
         err = "no device memory for the display transform's buffers";
         rc = RTM_ERR_HIP;
@@ -665,7 +667,7 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
         rc = RTM_ERR_HIP;
     }
     if (rc == RTM_OK) {
-        rc = rtm_tonemap(prm, st->width, st->height, device, color, work, nullptr, out8, stats_dev, nullptr);
+        rc = rtm_tonemap(prm, st->width, st->height, device, color, work, out32, out8, stats_dev, nullptr);
         if (rc != RTM_OK) err = rtm_last_error_detail();
     }
     std::vector<uint8_t> rgb8(pix * 3);
@@ -676,7 +678,15 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
         err = "copying the display frame back failed";
         rc = RTM_ERR_HIP;
     }
+    if (rc == RTM_OK && f32_out) {
+        f32_out->resize(pix * 3);
+        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            err = "copying the display frame back failed";
+            rc = RTM_ERR_HIP;
+        }
+    }
     (void)hipFree(color);
+    (void)hipFree(out32);
     (void)hipFree(out8);
     (void)hipFree(work);
     (void)hipFree(stats_dev);
@@ -725,6 +735,54 @@ int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host
     }
     (void)hipFree(a);
     (void)hipFree(b);
+    (void)hipFree(work);
+    (void)hipFree(result_dev);
+    return rc;
+}
+
+// --flip (rtm_node.h): rtm_flip of the two frames on the default stream.
+int rtm_node_flip(const rtm_settings* st, int device, const rtm_flip_params* prm, const float* frame_host,
+                  const float* reference_host, rtm_flip_result* result, std::vector<float>* map_out, std::string& err) {
+    if (hipSetDevice(device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    const size_t pix = (size_t)st->width * st->height;
+    const size_t bytes = pix * 3 * sizeof(float);
+    const size_t work_bytes = rtm_flip_work_bytes(st->width, st->height);
+    float *a = nullptr, *b = nullptr, *map_dev = nullptr;
+    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_flip asks of work_dev
+    rtm_flip_result* result_dev = nullptr;
+    int rc = RTM_OK;
+    if (work_bytes == SIZE_MAX || hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess ||
+        hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc((void**)&result_dev, sizeof(rtm_flip_result)) != hipSuccess ||
+        (map_out && hipMalloc((void**)&map_dev, pix * sizeof(float)) != hipSuccess)) {
+        err = "no device memory for the perceptual difference's buffers";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && (hipMemcpy(a, frame_host, bytes, hipMemcpyHostToDevice) != hipSuccess ||
+                         hipMemcpy(b, reference_host, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+        err = "copying the frames to the device failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        rc = rtm_flip(prm, st->width, st->height, device, a, b, work, result_dev, map_dev, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    if (rc == RTM_OK && hipMemcpy(result, result_dev, sizeof *result, hipMemcpyDeviceToHost) != hipSuccess) {
+        err = "copying the perceptual difference's record back failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && map_out) {
+        map_out->resize(pix);
+        if (hipMemcpy(map_out->data(), map_dev, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+            err = "copying the perceptual difference's map back failed";
+            rc = RTM_ERR_HIP;
+        }
+    }
+    (void)hipFree(a);
+    (void)hipFree(b);
+    (void)hipFree(map_dev);
     (void)hipFree(work);
     (void)hipFree(result_dev);
     return rc;

@@ -41,13 +41,20 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
                                      std::vector<float>* f32_out = nullptr);
 // The display transform (rtm_tonemap, rtm_cli --display) of a float frame (HOST, height x width x 3) on device `device`,
 // written next to the image: <stem>_display.jpg (quality 60) and <stem>_display.bmp.  stats (nullable) receives the frame
-// statistics and the exposure that was applied.
+// statistics and the exposure that was applied; f32_out (nullable) the transform's float frame (rtm_tonemap's out_f32), for a
+// stage that follows (--flip, --display-pfm).
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* params, const float* f32_host,
-                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err);
+                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err,
+                           std::vector<float>* f32_out = nullptr);
 // Two float frames (HOST, height x width x 3; `frame` under test, `reference`) compared on device `device` (rtm_compare at its
 // default parameters, rtm_cli --compare): both are copied to the device, one call on the default stream, the record copied back.
 int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host, const float* reference_host,
                      rtm_compare_result* result, std::string& err);
+// The perceptual difference of two display-referred float frames (HOST, height x width x 3; `frame` under test, `reference`)
+// on device `device` (rtm_flip, rtm_cli --flip): both are copied to the device, one call on the default stream, the record
+// copied back; map_out (nullable) receives the height x width error map.
+int rtm_node_flip(const rtm_settings* st, int device, const rtm_flip_params* params, const float* frame_host,
+                  const float* reference_host, rtm_flip_result* result, std::vector<float>* map_out, std::string& err);
 // The preview of the frame on options->device (rtm_cli --preview F): the scene traced at (width / factor) x (height / factor)
 // with the same camera, samples, seed and mode, denoised there at the default parameters (rtm_denoise guided by the low
 // rtm_render_aov planes) and brought to full size by rtm_upsample at its default sigmas, guided by the AOVs at both

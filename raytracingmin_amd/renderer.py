@@ -130,6 +130,18 @@ class Renderer:
         torch.cuda.current_stream(dev).synchronize()
         return compare_result(out["result"])
 
+    def flip(self, reference, frame=None, **params):
+        """flip() of a frame of this renderer against `reference`, decoded: flip_result()'s dict.  frame=None: the last
+        rendered image (self.image); else an (H, W, 3) array or tensor.  Both are DISPLAY-REFERRED frames (pass
+        transfer="linear" for frames that are linear; values outside [0, 1] are clamped), go to this renderer's device and
+        are rounded to float32.  params: flip()'s transfer, pixels_per_degree."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        to_dev = lambda v: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))).to(dev).to(torch.float32).contiguous()
+        out = flip(to_dev(self.image if frame is None else frame), to_dev(reference), want=("result",), **params)
+        torch.cuda.current_stream(dev).synchronize()
+        return flip_result(out["result"])
+
     # ---- device-resident render: outputs are torch tensors on the GPU ------------------------
     def render_rows_device(self, row_begin=0, row_end=None, want=("f32",), stats=True,
                            stream=None, band=None):
@@ -879,6 +891,98 @@ def compare_result(words):
     rec = _lib.rtm_compare_result.from_buffer_copy(raw.tobytes())
     floats = ("max_abs", "mse", "psnr", "rel_mse", "ssim")
     return {name: (float(getattr(rec, name)) if name in floats else int(getattr(rec, name))) for name, _ in rec._fields_}
+
+
+# include/rtm.h: RTM_FLIP_DEFAULTS (a 0.7 m wide 3840-pixel monitor viewed from 0.7 m)
+FLIP_DEFAULTS = {"transfer": "srgb", "pixels_per_degree": 0.7 * 3840.0 / 0.7 * 3.14159265358979323846 / 180.0}
+
+
+def _flip_params(transfer=FLIP_DEFAULTS["transfer"], pixels_per_degree=FLIP_DEFAULTS["pixels_per_degree"]):
+    """flip()'s parameters as an rtm_flip_params; a ValueError names what the library would refuse.  No device use."""
+    if transfer not in _lib.TRANSFERS:
+        raise ValueError(f"transfer is one of {tuple(_lib.TRANSFERS)}, got {transfer!r}")
+    pixels_per_degree = float(pixels_per_degree)
+    if not (np.isfinite(pixels_per_degree) and 8.0 <= pixels_per_degree <= 128.0):
+        raise ValueError(f"pixels_per_degree must be finite and in [8, 128], got {pixels_per_degree!r}")
+    return _lib.rtm_flip_params(_lib.TRANSFERS[transfer], pixels_per_degree)
+
+
+def flip(a, b, transfer=FLIP_DEFAULTS["transfer"], pixels_per_degree=FLIP_DEFAULTS["pixels_per_degree"], want=("result",),
+         stream=None):
+    """Perceptual frame difference (include/rtm.h: rtm_flip, LDR FLIP) on the device: `a` is the frame under test, `b` the
+    reference, both contiguous (H, W, 3) float32 torch CUDA tensors of the same shape and device, DISPLAY-REFERRED (what
+    tonemap()'s "f32" holds).  transfer "srgb" | "linear": how both are encoded; pixels_per_degree in [8, 128]: the viewing
+    condition.  Returns a dict of the names in `want`: "result" a 268-word int32 tensor holding the bits of rtm_flip_result
+    (flip_result() reads it on the host), "map" an (H, W) float32 tensor in [0, 1], NaN where a pixel has a non-finite
+    component.  A shape or dtype mismatch raises before the library is called.  Enqueued on `stream` (a torch.cuda.Stream or
+    a raw hipStream_t handle; default: the current stream) with a work buffer allocated here (112 bytes a pixel); nothing
+    waits for it and nothing is copied to the host."""
+    outputs = ("result", "map")
+    unknown = set(want) - set(outputs)
+    if unknown or not want:
+        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+    shape_a, shape_b = tuple(getattr(a, "shape", ())), tuple(getattr(b, "shape", ()))
+    if len(shape_a) != 3 or shape_a[2] != 3 or shape_a[0] < 1 or shape_a[1] < 1:
+        raise ValueError(f"a must be an (H, W, 3) frame, got shape {shape_a}")
+    if shape_a != shape_b:
+        raise ValueError(f"a and b must have the same shape, got {shape_a} and {shape_b}")
+    for name, v in (("a", a), ("b", b)):
+        if str(v.dtype).split(".")[-1] != "float32":
+            raise ValueError(f"{name} must be float32, got {v.dtype}")
+    prm = _flip_params(transfer, pixels_per_degree)
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("flip needs a HIP device; there is no CPU fallback")
+    for name, v in (("a", a), ("b", b)):
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous CUDA tensor")
+    if a.device != b.device:
+        raise ValueError(f"a and b must be on one device, got {a.device} and {b.device}")
+    H, W = int(a.shape[0]), int(a.shape[1])
+    dev = a.device
+    if stream is None:
+        s = torch.cuda.current_stream(dev)
+    elif isinstance(stream, torch.cuda.Stream):
+        s = stream
+    else:
+        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    L = _lib.lib()
+    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
+        work = torch.empty(max(256, L.rtm_flip_work_bytes(W, H)), dtype=torch.uint8, device=dev)
+        out = {}
+        if "result" in want:
+            out["result"] = torch.empty(C.sizeof(_lib.rtm_flip_result) // 4, dtype=torch.int32, device=dev)
+        if "map" in want:
+            out["map"] = torch.empty((H, W), dtype=torch.float32, device=dev)
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    _lib.check(L.rtm_flip(C.byref(prm), W, H, dev.index, a.data_ptr(), b.data_ptr(), work.data_ptr(), ptr("result"),
+                          ptr("map"), C.c_void_p(s.cuda_stream)), "rtm_flip")
+    return out
+
+
+def _flip_weighted_quantile(hist, q):
+    """The published tool's pooling of the histogram: bin i weighs its count times its centre value (i + 0.5) / 256; the
+    quantile is the centre of the first bin at which the running weight reaches q of the total (0 for an empty histogram)."""
+    centres = (np.arange(256) + 0.5) / 256.0
+    run = np.cumsum(np.asarray(hist, np.float64) * centres)  # bin by bin, in ascending order
+    if run[-1] <= 0:
+        return 0.0
+    return float(centres[int(np.searchsorted(run, q * run[-1], side="left"))])
+
+
+def flip_result(words):
+    """flip()'s "result" tensor as a dict of rtm_flip_result's fields ("hist" a list of 256 counts) plus
+    "weighted_median", "weighted_first_quartile" and "weighted_third_quartile", derived here from the histogram with each
+    bin weighted by its centre value, as the published tool pools: they have the bins' resolution, 1/256.  Copies the
+    record's 268 words to the host (synchronise the stream that wrote them first when it is not the current one)."""
+    raw = np.ascontiguousarray(words.cpu().numpy() if hasattr(words, "cpu") else words).view(np.uint8)
+    rec = _lib.rtm_flip_result.from_buffer_copy(raw.tobytes())
+    out = {"mean": float(rec.mean), "max": float(rec.max), "min": float(rec.min), "pixels": int(rec.pixels),
+           "nonfinite": int(rec.nonfinite), "argmax_x": int(rec.argmax_x), "argmax_y": int(rec.argmax_y), "hist": list(rec.hist)}
+    out["weighted_median"] = _flip_weighted_quantile(out["hist"], 0.5)
+    out["weighted_first_quartile"] = _flip_weighted_quantile(out["hist"], 0.25)
+    out["weighted_third_quartile"] = _flip_weighted_quantile(out["hist"], 0.75)
+    return out
 
 
 def plan_passes(n_samples, passes=None, samples_per_pass=None):
