@@ -352,6 +352,60 @@ typedef struct rtm_aov_buffers {
 int rtm_render_aov(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options,
                    const rtm_aov_buffers* out_dev, void* stream);
 
+/* ---- coverage AOVs of a frame: alpha, ranked id / coverage layers (Cryptomatte-style), a matte, "over" a background ----
+ * rtm_render_aov's object plane is one hard choice per pixel; these planes say which objects cover a pixel and by how much.
+ * Sub-pixels, rays and hits are exactly rtm_render_aov's: sx = 1..SS outer, sy = 1..SS inner, the primary direction of
+ * src/Renderer.cpp:227-232 (the render kernels' bits), the nearest-hit loop of :58-73 (hit needs t < dis && t > 0, the lowest
+ * index wins ties; spheres and the build-defined plane).  Nothing is random, so every value is exact.  Per pixel:
+ *   counts    c_i = the number of the SS^2 sub-pixels whose first hit is object i;  m = the number that miss
+ *   alpha     (float)((double)(SS^2 - m) / (double)SS^2)
+ *   ranking   the objects with c_i > 0 by c_i descending, ties by i ascending; misses are never ranked
+ *   layer l   (0-based) of a pixel with D distinct objects: id = i_l, coverage = (float)((double)c_{i_l} / (double)SS^2) for
+ *             l < D;  id = -1, coverage = +0.0f for l >= D
+ * Objects beyond `layers` are dropped: alpha - (sum of the coverages) tells how much.  Layers are PLANAR: plane l of id and of
+ * coverage is rank l of every pixel.  Any plane pointer may be null; only the non-null ones are written. */
+typedef struct rtm_matte_buffers {
+    int32_t* id;       /* DEVICE, layers x rows x width (planar: plane l is rank l) */
+    float*   coverage; /* DEVICE, layers x rows x width                             */
+    float*   alpha;    /* DEVICE, rows x width                                      */
+} rtm_matte_buffers;
+/* The coverage AOVs of the rows [row_begin, row_end): rows, bands, variants (0, 1 and 17 as rtm_render_aov serves them; any
+ * other: RTM_ERR_UNSUPPORTED), the serialisation per (device, stream) and the recording of the scene's use are
+ * rtm_render_aov's.  Only ENQUEUES one kernel on `stream`, allocates nothing and needs no work buffer; seed, max_bounces and
+ * the mode flags are ignored.  layers outside 1..8, all three planes null, null settings, options or out_dev, bad rows or
+ * bands, a bad mode: RTM_ERR_INVALID_ARGUMENT.  super_samples > 8: RTM_ERR_UNSUPPORTED (a block keeps the SS^2 ids of its 64
+ * pixels in LDS: 8^2 ids x 64 lanes x 4 B = 16 KiB is the limit).  Both are checked before the scene pointer is looked at; a
+ * null scene is RTM_ERR_INVALID_ARGUMENT after that; all before any device call.
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+int rtm_render_mattes(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options, int32_t layers,
+                      const rtm_matte_buffers* out_dev, void* stream);
+#define RTM_MATTE_DEFAULT_LAYERS 4 /* what rtm_cli --matte-layers and the Python package default to */
+/* The antialiased matte of a set of objects from a frame's layers (width x height pixels, rows = height, no bands):
+ *   matte_p = (float)min(1.0, sum over the layers l ascending with id_{l,p} >= 0 in the list of (double)coverage_{l,p})
+ * the sum taken in double from +0.0: exact given the layers.  ids_dev: a DEVICE list of n_ids ids, unsorted; duplicates are
+ * harmless, a negative entry selects nothing.  Keeps no state, allocates nothing, ENQUEUES one launch on `stream` of `device`.
+ * layers outside 1..8, n_ids outside 1..64, a null pointer, a non-positive size, a pointer that is not 4-byte aligned,
+ * matte_out_dev equal to an input, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A frame of 2^31
+ * pixels or more: RTM_ERR_UNSUPPORTED. */
+int rtm_matte(int32_t width, int32_t height, int32_t layers, int device, const int32_t* layer_id_dev,
+              const float* layer_coverage_dev, const int32_t* ids_dev, int32_t n_ids, float* matte_out_dev, void* stream);
+/* A traced frame "over" a background, premultiplied: the frame already holds zero for the fraction of a pixel that missed
+ * (a primary ray that misses returns vec3(), src/Renderer.cpp:116).  color (DEVICE, height x width x 3 floats, RGB-interleaved
+ * like out_f32), alpha (height x width, as rtm_render_mattes writes it), background_dev (nullable, height x width x 3).  Per
+ * channel, in float, without contraction:
+ *   t = 1.0f - alpha_p;   out = color + t * B      B = the background pixel where background_dev is given, else
+ *                                                      params->background
+ * out_u8 (if non-null) is rtm_quantise of (double)out_f32, bit for bit.  out_f32_dev == color_dev is allowed.  Keeps no
+ * state, allocates nothing, ENQUEUES one launch.  Null params, color_dev or alpha_dev, both outputs null, a NaN or infinite
+ * constant background, a non-positive size, a float pointer that is not 4-byte aligned, an output equal to alpha_dev or
+ * background_dev, out_u8_dev equal to color_dev, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A
+ * frame of 2^31 pixels or more: RTM_ERR_UNSUPPORTED, as rtm_tonemap. */
+typedef struct rtm_composite_params {
+    float background[3]; /* finite; used where background_dev is null */
+} rtm_composite_params;
+int rtm_composite(const rtm_composite_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                  const float* alpha_dev, const float* background_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
+
 /* ---- denoiser: an edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) guided by the AOVs above, with the albedo
  * demodulated (SVGF-style) and no temporal part ----
  * Inputs: a frame of width x height pixels; color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32); the

@@ -70,6 +70,15 @@ int rtm_debug_component_bench(int which, const rtm_sphere* spheres, size_t n, in
  * null-ness of the guide pointers is read); variance_out_dev receives v0.  Only enqueues on `stream`. */
 int rtm_debug_denoise_variance_kernel(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
                                       const rtm_aov_buffers* guide_dev, void* work_dev, float* variance_out_dev, void* stream);
+/* rtm_render_mattes' ranking alone (csrc/rtm_matte_kernel.h: matte_rank) on caller-given id lists, so that ties, truncation
+ * and lists of 64 distinct ids can be pinned without rays.  DEVICE buffers: ids_dev holds n_pixels lists of SS^2 ids each
+ * (pixel-major), any negative id is a miss; a small kernel loads 64 pixels' lists into the render kernel's LDS layout and calls
+ * the same function.  Outputs are planar, layers x n_pixels (id, coverage) and n_pixels (alpha); each may be null, not all.
+ * Only enqueues on `stream`; n_pixels == 0 enqueues nothing.  layers outside 1..8, a non-positive super_samples, null ids_dev,
+ * every output null, a misaligned pointer, a negative device: RTM_ERR_INVALID_ARGUMENT; super_samples > 8:
+ * RTM_ERR_UNSUPPORTED; both before any device call. */
+int rtm_debug_matte_rank(int32_t super_samples, int32_t layers, int device, const int32_t* ids_dev, size_t n_pixels,
+                         int32_t* id_out_dev, float* coverage_out_dev, float* alpha_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

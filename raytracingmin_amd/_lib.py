@@ -69,6 +69,14 @@ class rtm_aov_buffers(C.Structure):  # DEVICE pointers, any may be null (include
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("object", C.c_void_p)]
 
 
+class rtm_matte_buffers(C.Structure):  # DEVICE pointers, any may be null but not all (include/rtm.h: rtm_render_mattes)
+    _fields_ = [("id", C.c_void_p), ("coverage", C.c_void_p), ("alpha", C.c_void_p)]
+
+
+class rtm_composite_params(C.Structure):  # include/rtm.h: rtm_composite
+    _fields_ = [("background", C.c_float * 3)]
+
+
 class rtm_adaptive_params(C.Structure):  # include/rtm.h: rtm_render_adaptive
     _fields_ = [("min_samples", C.c_uint32), ("threshold", C.c_float)]
 
@@ -151,6 +159,11 @@ SIGNATURES = {
     "rtm_render_adaptive": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), _P(rtm_adaptive_params), C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _P(rtm_stats)]),
     "rtm_render_aov": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), _P(rtm_aov_buffers), C.c_void_p]),
+    "rtm_render_mattes": (C.c_int, [_P(rtm_settings), C.c_void_p, _P(rtm_options), C.c_int32, _P(rtm_matte_buffers), C.c_void_p]),
+    "rtm_matte": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                            C.c_void_p]),
+    "rtm_composite": (C.c_int, [_P(rtm_composite_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_denoise_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_denoise": (C.c_int, [_P(rtm_denoise_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -218,6 +231,8 @@ DEBUG_SIGNATURES = {
                                        C.c_size_t, C.c_void_p, C.c_size_t]),
     "rtm_debug_denoise_variance_kernel": (C.c_int, [C.c_int, _P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int,
                                                     _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_debug_matte_rank": (C.c_int, [C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "rtm_debug_component_bench": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(C.c_double)]),
 }

@@ -21,8 +21,11 @@ struct SceneGlobalObjects : SceneGlobal {
 };
 
 enum { kAovChunked = 0, kAovGeneral = 1, kAovGrid = 2 };
-__host__ __device__ inline size_t aov_lds_bytes(int search) {
-    return search == kAovGrid ? GridWalk<MathFast, SceneGlobal>::queue_bytes(64) : 0;
+// Dynamic LDS of a block of aov_kernel, and of matte_kernel (rtm_matte_kernel.h) at matte_ss = SS: the grid walk's queue,
+// then the 64 lanes' SS^2 object ids; aov_lds_bytes(search) is therefore where the id lists start
+__host__ __device__ inline size_t aov_lds_bytes(int search, int matte_ss = 0) {
+    return (search == kAovGrid ? GridWalk<MathFast, SceneGlobal>::queue_bytes(64) : 0) +
+           (size_t)matte_ss * (size_t)matte_ss * 64 * sizeof(int);
 }
 
 // depth / object: the centre sub-pixel c = (SS + 1) / 2 in both axes; normal / albedo: the sums over the SS^2 sub-pixels in

@@ -97,6 +97,18 @@ int rtm_render_aov(const rtm_settings* settings, const rtm_scene* scene, const r
                    const rtm_aov_buffers* out_dev, void* stream) {
     RTM_GUARD(rtm::render_aov(settings, scene, options, out_dev, stream))
 }
+int rtm_render_mattes(const rtm_settings* settings, const rtm_scene* scene, const rtm_options* options, int32_t layers,
+                      const rtm_matte_buffers* out_dev, void* stream) {
+    RTM_GUARD(rtm::render_mattes(settings, scene, options, layers, out_dev, stream))
+}
+int rtm_matte(int32_t width, int32_t height, int32_t layers, int device, const int32_t* layer_id_dev,
+              const float* layer_coverage_dev, const int32_t* ids_dev, int32_t n_ids, float* matte_out_dev, void* stream) {
+    RTM_GUARD(rtm::matte(width, height, layers, device, layer_id_dev, layer_coverage_dev, ids_dev, n_ids, matte_out_dev, stream))
+}
+int rtm_composite(const rtm_composite_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                  const float* alpha_dev, const float* background_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
+    RTM_GUARD(rtm::composite(params, width, height, device, color_dev, alpha_dev, background_dev, out_f32_dev, out_u8_dev, stream))
+}
 size_t rtm_denoise_work_bytes(int32_t width, int32_t height) { return rtm::denoise_work_bytes(width, height); }
 int rtm_denoise(const rtm_denoise_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 const rtm_aov_buffers* guide_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
@@ -185,6 +197,11 @@ int rtm_debug_wf_nearest(int kind, const rtm_sphere* sp, size_t n, const double*
 int rtm_debug_denoise_variance_kernel(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
                                       const rtm_aov_buffers* guide_dev, void* work_dev, float* variance_out_dev, void* stream) {
     RTM_GUARD(rtm::denoise_variance_kernel_probe(form, params, width, height, device, guide_dev, work_dev, variance_out_dev, stream))
+}
+int rtm_debug_matte_rank(int32_t super_samples, int32_t layers, int device, const int32_t* ids_dev, size_t n_pixels,
+                         int32_t* id_out_dev, float* coverage_out_dev, float* alpha_out_dev, void* stream) {
+    RTM_GUARD(rtm::matte_rank_probe(super_samples, layers, device, ids_dev, n_pixels, id_out_dev, coverage_out_dev, alpha_out_dev,
+                                    stream))
 }
 int rtm_debug_selfcheck(int kind, unsigned long long* mismatches) { RTM_GUARD(rtm::selfcheck(kind, mismatches)) }
 int rtm_debug_grid_nearest(const rtm_sphere* sp, size_t n, const double* org, const double* dir, size_t n_rays,

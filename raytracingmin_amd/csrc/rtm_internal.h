@@ -43,6 +43,15 @@ int render_adaptive(const rtm_settings* st, const rtm_scene* scene, const rtm_op
                     rtm_stats* stats);
 int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const rtm_aov_buffers* out,
                void* stream);
+int render_mattes(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, int32_t layers,
+                  const rtm_matte_buffers* out, void* stream);
+// coverage AOVs (rtm_matte.hip): the ranking hook; the matte of a set of ids; "over" a background
+int matte_rank_probe(int32_t super_samples, int32_t layers, int device, const int32_t* ids, size_t n_pixels, int32_t* id_out,
+                     float* coverage_out, float* alpha_out, void* stream);
+int matte(int32_t width, int32_t height, int32_t layers, int device, const int32_t* layer_id, const float* layer_coverage,
+          const int32_t* ids, int32_t n_ids, float* matte_out, void* stream);
+int composite(const rtm_composite_params* params, int32_t width, int32_t height, int device, const float* color,
+              const float* alpha, const float* background, float* out32, uint8_t* out8, void* stream);
 // denoiser (rtm_denoise.hip)
 size_t denoise_work_bytes(int32_t width, int32_t height);
 int denoise(const rtm_denoise_params* params, int32_t width, int32_t height, int device, const float* color,

@@ -8,6 +8,7 @@
 //   rtm_wavefront.h      the large-scene pipeline (BASELINE configs[4])
 //   rtm_fp32.h           the separately labelled single-precision row
 //   rtm_seam_kernels.h   per-ray / per-call seams, probes, self-checks, the fp64 peak kernel
+//   rtm_matte.hip        the coverage AOVs' kernels (rtm_matte_kernel.h) and launches, included at the end of this file
 //   this file            scene lifetime (flattening, upload, deferred release), per-(device, stream) contexts and scratch,
 //                        variant selection, the sample-split plan, launches, the blocking conveniences, the test hooks
 // Shape of the render kernel: DESIGN.md §4.  No MFMA: there is no dense contraction on this path.  fp64 throughout,
@@ -2494,6 +2495,82 @@ int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options
     return RTM_OK;
 }
 
+// rtm_render_mattes: the coverage AOVs of the call's rows.  render_aov's checks, variants and serialisation; what is the
+// call's own (layers, the plane set, the super-sample cap) is refused before the scene pointer is looked at.  The kernel
+// and its launch are in rtm_matte.hip (launch_matte), included at the end of this file.
+static int launch_matte(const RenderParams& P, int search, bool planes, unsigned tiles, size_t lds, int32_t layers, size_t plane,
+                        const rtm_matte_buffers& out, hipStream_t stream);
+int render_mattes(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, int32_t layers,
+                  const rtm_matte_buffers* out, void* stream_v) {
+    if (!out) {
+        set_last_error("out_dev: the buffer set is null");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (!opt) {
+        set_last_error("null argument");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (layers < 1 || layers > 8) {
+        set_last_error("layers = " + std::to_string(layers) + ": outside 1..8");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (!out->id && !out->coverage && !out->alpha) {
+        set_last_error("out_dev: every plane is null");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    rtm_options o = *opt;
+    o.max_bounces = -1;  // (no paths are traced: the depth cap does not apply)
+    int rc = validate(st, nullptr, 0, &o);
+    if (rc != RTM_OK) return rc;
+    if (st->super_samples > 8) {
+        set_last_error("rtm_render_mattes serves superSamples up to 8 (the id lists of a block: 16 KiB of LDS)");
+        return RTM_ERR_UNSUPPORTED;
+    }
+    if (!scene) {
+        set_last_error("null scene");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    if (scene->device != opt->device) {
+        set_last_error("the scene lives on another device than rtm_options.device");
+        return RTM_ERR_INVALID_ARGUMENT;
+    }
+    std::shared_lock<std::shared_mutex> gate(g_gate);
+    reap_scenes(false);
+    const void* grid = grid_for(scene, st, opt);
+    int search;
+    if (opt->variant == kVariantAuto) {
+        search = grid != nullptr ? kAovGrid : kAovChunked;  // the grid exactly where a render would take it
+    } else if (opt->variant == kVariantRef) {
+        search = kAovGeneral;
+    } else if (opt->variant == kVariantGrid) {
+        if (grid == nullptr) {
+            set_last_error("variant 17 (uniform grid): this scene has no grid");
+            return RTM_ERR_UNSUPPORTED;
+        }
+        search = kAovGrid;
+    } else {
+        set_last_error("rtm_render_mattes serves variants 0, 1 and 17");
+        return RTM_ERR_UNSUPPORTED;
+    }
+    const int rows = output_rows(opt);
+    if (rows == 0) return RTM_OK;
+    RTM_HIP_CHECK(hipSetDevice(opt->device));
+    const hipStream_t stream = (hipStream_t)stream_v;
+    StreamCtx& ctx = *get_ctx(opt->device, stream);
+    std::lock_guard<std::mutex> lock(ctx.mu);
+    RenderParams P;
+    std::memset(&P, 0, sizeof P);
+    fill_render_params(P, st, opt, SamplePass{});
+    P.scene = scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
+                         scene->has_planes ? scene->plane.as<double>() : nullptr, grid, scene->surf.as<double>(), scene->axis_pat,
+                         scene->fold_flags, scene->emit_mask);
+    const unsigned tiles = (unsigned)P.tiles_x * (unsigned)((rows + 7) / 8);
+    rc = launch_matte(P, search, scene->has_planes, tiles, aov_lds_bytes(search, st->super_samples), layers,
+                      (size_t)rows * (size_t)st->width, *out, stream);
+    note_scene_use(scene, stream);
+    return rc;
+}
+
 int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int on_device,
                   const rtm_options* opt, double* out64, float* out32, uint8_t* out8,
                   void* stream_v, rtm_stats* stats) {
@@ -3034,3 +3111,6 @@ int device_count(int* count) {
 }
 
 }  // namespace rtm
+
+// the coverage AOVs' kernels and launches: part of this translation unit (rtm_matte.hip says why)
+#include "rtm_matte.hip"

@@ -21,9 +21,14 @@
 //                                                (the perceptual difference of the display frame, or without --display of the
 //                                                last stage's frame taken as linear, from a reference of the same kind: one
 //                                                line "flip: {...}"; -map: STEM_flip.pfm)
+//           [--alpha] [--matte ID[,ID...] [--matte-layers K]] [--background R,G,B]
+//                                                (coverage AOVs on one GPU: STEM_alpha.pfm; the antialiased matte of the listed
+//                                                objects, STEM_matte.pfm, .bmp; the last stage's frame over a constant
+//                                                background, STEM_over.bmp, .jpg, with --display also STEM_over_display.*)
 //
 // Flow of the reference: pick the JSON (default settingData.json), create the sample JSON when it
 // does not exist, load, render, write <stem>.jpg (quality 60) and <stem>.bmp with stem "result".
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -96,7 +101,17 @@ static void usage() {
         "        last stage, taken as linear and clamped to [0, 1], and REF.pfm a --pfm file.  --flip-ppd X : pixels per degree\n"
         "        in [8, 128] (default 67.02: a 0.7 m wide 4K monitor at 0.7 m).  Prints one line 'flip: {...}', the record\n"
         "        without its histogram plus the weighted median, as JSON; --flip-map : also write STEM_flip.pfm, the error map\n"
-        "        in [0, 1]; a file that cannot be read or has another size: exit status 1\n");
+        "        in [0, 1]; a file that cannot be read or has another size: exit status 1\n"
+        "--alpha : also write STEM_alpha.pfm on one GPU (rtm_render_mattes): per pixel the fraction of its superSamples^2\n"
+        "        sub-pixels whose primary ray hits anything (superSamples up to 8)\n"
+        "--matte ID[,ID...] [--matte-layers K] : also write the antialiased matte of the listed objects (1..64 indices into the\n"
+        "        scene's object list; rtm_matte over K ranked id / coverage layers, K in 1..8, default 4): STEM_matte.pfm and a\n"
+        "        grey STEM_matte.bmp\n"
+        "--background R,G,B : also write the frame of the last stage asked for over that constant colour (rtm_composite with\n"
+        "        the alpha plane: frame + (1 - alpha) * colour): STEM_over.bmp and STEM_over.jpg; with --display also its display\n"
+        "        transform, STEM_over_display.bmp and STEM_over_display.jpg\n"
+        "        These three need the full render (not with --preview-only) and superSamples up to 8; --matte-layers requires\n"
+        "        --matte\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -116,6 +131,9 @@ int main(int argc, char* argv[]) {
     std::string dump_f32, compare_ref, flip_ref;
     int display_pfm = 0, flip_map = 0, flip_ppd_given = 0;
     rtm_flip_params flip_prm = RTM_FLIP_DEFAULTS;
+    int alpha = 0, matte_layers = RTM_MATTE_DEFAULT_LAYERS, matte_layers_given = 0, background = 0;
+    std::vector<int32_t> matte_ids;
+    rtm_composite_params composite_prm = {{0.0f, 0.0f, 0.0f}};
     unsigned long long seed = 0x5EED;
     for (int i = 1; i < argc; ++i) {
         const std::string c = argv[i];
@@ -190,6 +208,41 @@ int main(int argc, char* argv[]) {
             flip_ppd_given = 1;
             if (end == m.c_str() || *end != '\0' || !(flip_prm.pixels_per_degree >= 8.0 && flip_prm.pixels_per_degree <= 128.0)) {
                 std::fprintf(stderr, "--flip-ppd takes a number of pixels per degree in [8, 128], got %s\n", m.c_str());
+                return 2;
+            }
+        } else if (c == "--alpha") alpha = 1;
+        else if (c == "--matte" || c == "--background" || c == "--matte-layers") {
+            // a comma-separated list of numbers, all of it: 1..64 object indices, three finite colour components, or K in 1..8
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            std::vector<double> v;
+            bool ok = !m.empty();
+            for (size_t at = 0; ok && at <= m.size();) {
+                const size_t comma = std::min(m.find(',', at), m.size());
+                const std::string item = m.substr(at, comma - at);
+                char* end = nullptr;
+                const double d = std::strtod(item.c_str(), &end);
+                ok = !item.empty() && end == item.c_str() + item.size() && std::isfinite(d);
+                v.push_back(d);
+                at = comma + 1;
+            }
+            if (c == "--matte") {
+                ok = ok && v.size() <= 64;
+                for (size_t k = 0; ok && k < v.size(); ++k) ok = v[k] == std::floor(v[k]) && v[k] >= -2147483648.0 && v[k] <= 2147483647.0;
+                if (ok) matte_ids.assign(v.begin(), v.end());
+            } else if (c == "--background") {
+                ok = ok && v.size() == 3;
+                for (size_t k = 0; ok && k < 3; ++k) ok = std::isfinite(composite_prm.background[k] = (float)v[k]);
+                background = 1;
+            } else {
+                ok = ok && v.size() == 1 && v[0] == std::floor(v[0]) && v[0] >= 1.0 && v[0] <= 8.0;
+                if (ok) matte_layers = (int)v[0];
+                matte_layers_given = 1;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "%s takes %s, got %s\n", c.c_str(),
+                             c == "--matte" ? "1..64 comma-separated object indices" : c == "--background" ? "three finite numbers R,G,B"
+                                                                                                         : "a number of layers in 1..8",
+                             m.c_str());
                 return 2;
             }
         } else if (c == "--dump-f32" && i + 1 < argc) dump_f32 = argv[++i];
@@ -269,6 +322,20 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "--flip-map and --flip-ppd require --flip REF.pfm\n");
         return 2;
     }
+    const bool mattes = alpha || !matte_ids.empty() || background;
+    if (mattes && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
+        std::fprintf(stderr, "--alpha, --matte and --background run on one GPU: they do not combine with --gpus > 1, --virtual-strips or "
+                             "--force-rccl\n");
+        return 2;
+    }
+    if (mattes && preview_only) {
+        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --alpha, --matte or --background\n");
+        return 2;
+    }
+    if (matte_layers_given && matte_ids.empty()) {
+        std::fprintf(stderr, "--matte-layers requires --matte ID[,ID...]\n");
+        return 2;
+    }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
         std::printf("saving the sample scene json file: %s\n", json_file.c_str());
         if (rtm_scene_save_sample_json(json_file.c_str()) != RTM_OK) return 1;
@@ -305,6 +372,10 @@ int main(int argc, char* argv[]) {
     opt.row_end = st.height;
     opt.device = device;
 
+    if (mattes && st.super_samples > 8) {  // rtm_render_mattes' limit, known before anything is rendered
+        std::fprintf(stderr, "--alpha, --matte and --background serve superSamples up to 8, got %d\n", st.super_samples);
+        return 2;
+    }
     if (preview && (st.width % preview != 0 || st.height % preview != 0)) {
         std::fprintf(stderr, "--preview %d does not divide the %d x %d frame\n", preview, st.width, st.height);
         return 2;
@@ -346,7 +417,7 @@ int main(int argc, char* argv[]) {
         }
     }
     // a later stage takes the float frame of the last one
-    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty();
+    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background;
     if (preview) {  // STEM_preview.bmp / .jpg, and their display transform
         std::string err;
         std::vector<float> shown;
@@ -520,6 +591,29 @@ int main(int argc, char* argv[]) {
                     json_number(cr.rel_mse).c_str(), json_number(cr.ssim).c_str(), (unsigned long long)cr.pixels,
                     (unsigned long long)cr.outside, (unsigned long long)cr.nonfinite, (unsigned long long)cr.nonfinite_mismatch,
                     cr.argmax_x, cr.argmax_y);
+    }
+    if (mattes) {
+        std::string err;
+        std::vector<float> over;
+        rc = rtm_node_write_mattes(&st, spheres.data(), n, &opt, alpha != 0, matte_layers, matte_ids, background ? &composite_prm : nullptr,
+                                   background ? last : nullptr, stem, err, background && display ? &over : nullptr);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "mattes failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+            return 1;
+        }
+        if (alpha) std::printf("alpha: %s_alpha.pfm\n", stem.c_str());
+        if (!matte_ids.empty())
+            std::printf("matte: %s_matte.pfm, %s_matte.bmp (%d ids, %d layers)\n", stem.c_str(), stem.c_str(), (int)matte_ids.size(), matte_layers);
+        if (background) std::printf("background: %s_over.bmp, %s_over.jpg\n", stem.c_str(), stem.c_str());
+        if (background && display) {
+            rtm_tonemap_stats ts;
+            rc = rtm_node_write_display(&st, opt.device, &display_prm, over.data(), stem + "_over", &ts, err);
+            if (rc != RTM_OK) {
+                std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
+                return 1;
+            }
+            std::printf("display: %s_over_display.bmp, %s_over_display.jpg\n", stem.c_str(), stem.c_str());
+        }
     }
     if (!flip_ref.empty()) {
         std::string err;

@@ -488,6 +488,89 @@ int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t
     return RTM_OK;
 }
 
+// --alpha / --matte / --background (rtm_node.h): one rtm_render_mattes of the frame on the default stream (the layers only
+// when a matte is asked for), then rtm_matte and rtm_composite behind it, then the files.
+int rtm_node_write_mattes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, bool want_alpha,
+                          int layers, const std::vector<int32_t>& ids, const rtm_composite_params* background,
+                          const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* over_out) {
+    if (hipSetDevice(opt->device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(opt->device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    rtm_scene* scene = nullptr;
+    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
+    if (rc != RTM_OK) {
+        err = std::string("scene: ") + rtm_last_error_detail();
+        return rc;
+    }
+    const size_t pix = (size_t)st->width * st->height;
+    const bool want_matte = !ids.empty();
+    rtm_matte_buffers dev;
+    std::memset(&dev, 0, sizeof dev);
+    int32_t* sel = nullptr;
+    float* matte = nullptr;
+    float* color = nullptr;  // the frame, composited in place
+    uint8_t* over8 = nullptr;
+    if (hipMalloc((void**)&dev.alpha, pix * sizeof(float)) != hipSuccess ||
+        (want_matte && (hipMalloc((void**)&dev.id, pix * layers * sizeof(int32_t)) != hipSuccess ||
+                        hipMalloc((void**)&dev.coverage, pix * layers * sizeof(float)) != hipSuccess ||
+                        hipMalloc((void**)&sel, ids.size() * sizeof(int32_t)) != hipSuccess ||
+                        hipMalloc((void**)&matte, pix * sizeof(float)) != hipSuccess)) ||
+        (background && (hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess ||
+                        hipMalloc((void**)&over8, pix * 3) != hipSuccess))) {
+        err = "no device memory for the coverage planes";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && ((want_matte && hipMemcpy(sel, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) ||
+                         (background && hipMemcpy(color, f32_host, pix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))) {
+        err = "copying the id list or the frame to the device failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) rc = rtm_render_mattes(st, scene, opt, layers, &dev, nullptr);
+    if (rc == RTM_OK && want_matte)
+        rc = rtm_matte(st->width, st->height, layers, opt->device, dev.id, dev.coverage, sel, (int32_t)ids.size(), matte, nullptr);
+    if (rc == RTM_OK && background)
+        rc = rtm_composite(background, st->width, st->height, opt->device, color, dev.alpha, nullptr, color, over8, nullptr);
+    if (rc != RTM_OK && err.empty()) err = rtm_last_error_detail();
+    std::vector<float> alpha_h(pix), matte_h(want_matte ? pix : 0), over_h(background && over_out ? pix * 3 : 0);
+    std::vector<uint8_t> over8_h(background ? pix * 3 : 0);
+    if (rc == RTM_OK &&
+        (hipMemcpy(alpha_h.data(), dev.alpha, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
+         (want_matte && hipMemcpy(matte_h.data(), matte, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
+         (background && hipMemcpy(over8_h.data(), over8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess) ||
+         (!over_h.empty() && hipMemcpy(over_h.data(), color, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
+        err = "copying the coverage planes back failed";
+        rc = RTM_ERR_HIP;
+    }
+    (void)hipFree(dev.alpha);
+    (void)hipFree(dev.id);
+    (void)hipFree(dev.coverage);
+    (void)hipFree(sel);
+    (void)hipFree(matte);
+    (void)hipFree(color);
+    (void)hipFree(over8);
+    (void)rtm_scene_destroy(scene);
+    if (rc != RTM_OK) return rc;
+    const int w = st->width, h = st->height;
+    bool ok = !want_alpha || rtm_write_pfm((stem + "_alpha.pfm").c_str(), w, h, 1, alpha_h.data()) == 1;
+    if (want_matte) {
+        std::vector<double> v(pix * 3);
+        std::vector<uint8_t> grey(pix * 3);
+        for (size_t i = 0; i < v.size(); ++i) v[i] = (double)matte_h[i / 3];
+        ok = ok && rtm_write_pfm((stem + "_matte.pfm").c_str(), w, h, 1, matte_h.data()) == 1 &&
+             rtm_quantise(v.data(), v.size(), grey.data()) == RTM_OK && rtm_write_bmp((stem + "_matte.bmp").c_str(), w, h, 3, grey.data()) == 1;
+    }
+    if (background)
+        ok = ok && rtm_write_bmp((stem + "_over.bmp").c_str(), w, h, 3, over8_h.data()) == 1 &&
+             rtm_write_jpg((stem + "_over.jpg").c_str(), w, h, 3, over8_h.data(), 60) == 1;
+    if (!ok) {
+        err = "cannot write the matte files of " + stem;
+        return RTM_ERR_IO;
+    }
+    if (over_out) *over_out = std::move(over_h);
+    return RTM_OK;
+}
+
 // --denoise (rtm_node.h): the frame's AOVs (rtm_render_aov), then rtm_denoise of its f32 at the default parameters on the
 // default stream, then the two files.
 int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,

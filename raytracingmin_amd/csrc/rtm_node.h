@@ -27,6 +27,14 @@ int rtm_node_render_adaptive(const rtm_settings* st, const rtm_object* objects, 
 // 0.5 n + 0.5) and <stem>_albedo.bmp (the quantised albedo).
 int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options,
                        const std::string& stem, std::string& err);
+// The coverage AOVs of the whole frame on options->device (rtm_render_mattes, rtm_cli --alpha / --matte / --background),
+// written next to the image: with want_alpha <stem>_alpha.pfm; with ids (1..64 of them) <stem>_matte.pfm, rtm_matte of those
+// objects over `layers` ranked layers, and a grey <stem>_matte.bmp; with background, <stem>_over.bmp and <stem>_over.jpg
+// (quality 60), rtm_composite of f32_host (HOST, height x width x 3: the frame of the last stage) over that colour, and in
+// *over_out (nullable) its float frame.
+int rtm_node_write_mattes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* options, bool want_alpha,
+                          int layers, const std::vector<int32_t>& ids, const rtm_composite_params* background,
+                          const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* over_out);
 // The frame's f32 (HOST, height x width x 3) denoised on options->device at the default parameters (rtm_denoise guided by
 // the frame's rtm_render_aov planes, rtm_cli --denoise) and written next to the image: <stem>_denoised.jpg (quality 60)
 // and <stem>_denoised.bmp.  f32_out (nullable) receives the filtered float frame, for a stage that follows (--display).

@@ -352,6 +352,79 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write the AOV files of {fileName}")
         return planes
 
+    # ---- coverage AOVs (rtm_render_mattes) ----------------------------------------------------
+    MATTE_PLANES = ("id", "coverage", "alpha")
+
+    def render_mattes(self, layers=4, row_begin=0, row_end=None, band=None, want=MATTE_PLANES, stream=None):
+        """The coverage AOVs of rows [row_begin, row_end) as torch CUDA tensors: "id" (layers, rows, W) int32 and "coverage"
+        (layers, rows, W) float32 — plane l holds the object of rank l behind every pixel (-1: none) and the fraction of the
+        pixel's SS^2 sub-pixels it covers, most first — and "alpha" (rows, W) float32, the fraction that hit anything
+        (include/rtm.h: rtm_render_mattes).  layers is 1..8; only the planes named in `want` are allocated and written.
+        Enqueued on `stream` (default: the current stream); nothing waits for it."""
+        layers = _matte_layers(layers)
+        unknown = set(want) - set(self.MATTE_PLANES)
+        if unknown or not want:
+            raise ValueError(f"want names planes among {self.MATTE_PLANES}, got {tuple(want)}")
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        row_end = self.data.height if row_end is None else row_end
+        opt = self._options(row_begin, row_end, band)
+        rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
+        dev = torch.device("cuda", self.device)
+        shapes = {"id": ((layers, rows, W), torch.int32), "coverage": ((layers, rows, W), torch.float32),
+                  "alpha": ((rows, W), torch.float32)}
+        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in self.MATTE_PLANES if k in want}
+        if rows == 0:
+            return out
+        bufs = _lib.rtm_matte_buffers()
+        for k, v in out.items():
+            setattr(bufs, k, v.data_ptr())
+        st = self.data.settings_c()
+        hip_stream = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
+        _lib.check(_lib.lib().rtm_render_mattes(C.byref(st), self._scene_handle(), C.byref(opt), layers, C.byref(bufs),
+                                                C.c_void_p(hip_stream)), "rtm_render_mattes")
+        return out
+
+    def write_mattes(self, fileName, layers=4, ids=None, background=None, frame=None):
+        """<fileName>_alpha.pfm: the frame's alpha plane (render_mattes).  With ids (1..64 object indices): <fileName>_matte.pfm,
+        the antialiased matte() of those objects cut from `layers` ranked layers, and a grey <fileName>_matte.bmp.  With
+        background (a colour or an (H, W, 3) float32 CUDA tensor): <fileName>_over.bmp and <fileName>_over.jpg (q=60), the
+        frame composite()d over it — `frame` an (H, W, 3) float32 CUDA tensor, default self.image rounded to float like
+        out_f32.  What rtm_cli --alpha / --matte / --background write.  Returns a dict: "alpha" and "matte" as (H, W) float32
+        arrays, "over" the composited (H, W, 3) float32 frame on the device."""
+        layers, ids, background = _matte_args(layers, ids, background)
+        import torch
+        dev = torch.device("cuda", self.device)
+        H, W = self.data.height, self.data.width
+        L = _lib.lib()
+        planes = self.render_mattes(layers, want=self.MATTE_PLANES if ids is not None else ("alpha",))
+        res = {}
+        if ids is not None:
+            m = matte(planes["id"], planes["coverage"], ids)
+        if background is not None:
+            if frame is None:
+                frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+            over = composite(frame, planes["alpha"], background, want=("f32", "u8"))
+        torch.cuda.synchronize(self.device)
+        res["alpha"] = np.ascontiguousarray(planes["alpha"].cpu().numpy())
+        ok = L.rtm_write_pfm(os.fsencode(fileName + "_alpha.pfm"), W, H, 1, res["alpha"].ctypes.data) == 1
+        if ids is not None:
+            res["matte"] = np.ascontiguousarray(m.cpu().numpy())
+            grey = np.ascontiguousarray(np.repeat(res["matte"].astype(np.float64)[..., None], 3, axis=2))
+            rgb8 = np.zeros(grey.shape, dtype=np.uint8)
+            _lib.check(L.rtm_quantise(grey.ctypes.data, grey.size, rgb8.ctypes.data), "rtm_quantise")
+            ok = ok and L.rtm_write_pfm(os.fsencode(fileName + "_matte.pfm"), W, H, 1, res["matte"].ctypes.data) == 1 \
+                and L.rtm_write_bmp(os.fsencode(fileName + "_matte.bmp"), W, H, 3, rgb8.ctypes.data) == 1
+        if background is not None:
+            res["over"] = over["f32"]
+            rgb8 = np.ascontiguousarray(over["u8"].cpu().numpy())
+            ok = ok and L.rtm_write_bmp(os.fsencode(fileName + "_over.bmp"), W, H, 3, rgb8.ctypes.data) == 1 \
+                and L.rtm_write_jpg(os.fsencode(fileName + "_over.jpg"), W, H, 3, rgb8.ctypes.data, 60) == 1
+        if not ok:
+            raise _lib.RtmError(-3, f"could not write the matte files of {fileName}")
+        return res
+
     # ---- low-resolution preview at full size (rtm_upsample) -----------------------------------
     def preview(self, factor=2, denoise=True, want=("f32",), stream=None):
         """The frame traced at (width / factor) x (height / factor) — same camera, samples, super-samples, seed and mode, so
@@ -442,7 +515,7 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None):
+    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -458,7 +531,21 @@ class Renderer:
         itself.  The plain files and self.image do not change.
         preview=F also writes <fileName>_preview.bmp and <fileName>_preview.jpg (q=60): the frame traced at 1 / F of the
         resolution in each axis, denoised there and upsampled by the AOVs (write_preview); with tonemap, the display transform
-        of the preview as well, as <fileName>_preview_display.bmp / .jpg.  F must divide the width and the height."""
+        of the preview as well, as <fileName>_preview_display.bmp / .jpg.  F must divide the width and the height.
+        mattes=True (or a dict of write_mattes' parameters: layers, ids, background) also writes <fileName>_alpha.pfm, with ids
+        <fileName>_matte.pfm / .bmp, and with background <fileName>_over.bmp / .jpg: the last stage asked for (plain, denoised,
+        variance-denoised) over that background; with tonemap, its display transform as well, as <fileName>_over_display.bmp /
+        .jpg.  A bad value raises ValueError before anything is rendered; the other files and self.image do not change."""
+        matte_prm = None
+        if mattes is not None and mattes is not False:
+            if mattes is not True and not isinstance(mattes, dict):
+                raise ValueError(f"mattes is None, True or a dict of write_mattes' parameters, got {mattes!r}")
+            matte_prm = {} if mattes is True else dict(mattes)
+            unknown = set(matte_prm) - {"layers", "ids", "background"}
+            if unknown:
+                raise ValueError(f"mattes' parameters are ('layers', 'ids', 'background'), got {sorted(unknown)}")
+            _matte_args(matte_prm.get("layers", MATTE_DEFAULTS["layers"]), matte_prm.get("ids"), matte_prm.get("background"),
+                        frame_shape=(self.data.height, self.data.width))
         if preview is not None:
             f = int(preview)
             if not 2 <= f <= 8 or self.data.width % f or self.data.height % f:
@@ -501,12 +588,17 @@ class Renderer:
         if aov:
             self.write_aov(fileName)
         frame = None  # the f32 frame the display stage shows, when it is not self.image
+        keep = display is not None or (matte_prm is not None and matte_prm.get("background") is not None)
         if denoise == "variance":
-            frame = self.write_denoised_variance(fileName, _keep=display is not None)
+            frame = self.write_denoised_variance(fileName, _keep=keep)
         elif denoise:
-            frame = self.write_denoised(fileName, _keep=display is not None)
+            frame = self.write_denoised(fileName, _keep=keep)
         if display is not None:
             self.write_display(fileName, frame=frame, **display)
+        if matte_prm is not None:
+            over = self.write_mattes(fileName, frame=frame, **matte_prm).get("over")
+            if over is not None and display is not None:
+                self.write_display(fileName + "_over", frame=over, **display)
         if preview is not None:
             shown = self.write_preview(fileName, int(preview), _keep=display is not None)
             if display is not None:
@@ -722,6 +814,140 @@ def upsample(color_low, aov_low=None, aov_high=None, factor=UPSAMPLE_DEFAULTS["f
 
 
 # include/rtm.h: RTM_TONEMAP_DEFAULTS (exposure "auto" is auto_exposure 1 at ev 0)
+# include/rtm.h: RTM_MATTE_DEFAULT_LAYERS
+MATTE_DEFAULTS = {"layers": 4}
+
+
+def _matte_layers(layers):
+    if isinstance(layers, bool) or not isinstance(layers, (int, np.integer)) or not 1 <= int(layers) <= 8:
+        raise ValueError(f"layers is an integer in 1..8, got {layers!r}")
+    return int(layers)
+
+
+def _matte_ids(ids):
+    """matte()'s id list as a tuple of 1..64 ints that fit an int32; a ValueError otherwise.  No device use."""
+    try:
+        ids = tuple(ids)
+    except TypeError:
+        raise ValueError(f"ids is a list of 1..64 object indices, got {ids!r}") from None
+    if not 1 <= len(ids) <= 64:
+        raise ValueError(f"ids is a list of 1..64 object indices, got {len(ids)} of them")
+    for i in ids:
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not -2 ** 31 <= int(i) < 2 ** 31:
+            raise ValueError(f"ids holds integers that fit an int32, got {i!r}")
+    return tuple(int(i) for i in ids)
+
+
+def _matte_background(background, frame_shape=None):
+    """composite()'s background: a colour as a tuple of three finite floats, or the (H, W, 3) float32 CUDA tensor itself; a
+    ValueError otherwise.  No device use."""
+    if hasattr(background, "is_cuda"):
+        import torch
+        if not (background.is_cuda and background.dtype == torch.float32 and background.dim() == 3 and background.shape[2] == 3
+                and background.is_contiguous()):
+            raise ValueError("background must be a colour or a contiguous (H, W, 3) float32 CUDA tensor")
+        if frame_shape is not None and tuple(background.shape[:2]) != tuple(frame_shape):
+            raise ValueError(f"background is {tuple(background.shape[:2])}, the frame {tuple(frame_shape)}")
+        return background
+    try:
+        rgb = tuple(float(v) for v in background)
+    except (TypeError, ValueError):
+        raise ValueError(f"background is a colour (three numbers) or an (H, W, 3) float32 CUDA tensor, got {background!r}") from None
+    if len(rgb) != 3 or not all(np.isfinite(v) for v in rgb):
+        raise ValueError(f"background is a colour of three finite numbers, got {background!r}")
+    return rgb
+
+
+def _matte_args(layers=MATTE_DEFAULTS["layers"], ids=None, background=None, frame_shape=None):
+    """Renderer.write_mattes' parameters, checked: (layers, ids or None, background or None).  No device use."""
+    return (_matte_layers(layers), None if ids is None else _matte_ids(ids),
+            None if background is None else _matte_background(background, frame_shape))
+
+
+def _stream_of(stream, dev):
+    import torch
+    if stream is None:
+        return torch.cuda.current_stream(dev)
+    return stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+
+
+def matte(layer_id, layer_coverage, ids, stream=None):
+    """The antialiased matte of a set of objects (include/rtm.h: rtm_matte) on the device.  layer_id (L, H, W) int32 and
+    layer_coverage (L, H, W) float32 are Renderer.render_mattes' "id" and "coverage" of a whole frame, L in 1..8; ids a list
+    of 1..64 object indices (unsorted, duplicates harmless, a negative entry selects nothing) or an int32 CUDA tensor of them.
+    Returns the (H, W) float32 matte: per pixel the summed coverage of the listed objects, at most 1.  Enqueued on `stream` (a
+    torch.cuda.Stream or a raw hipStream_t handle; default: the current stream); nothing waits for it."""
+    on_device = hasattr(ids, "is_cuda")
+    if not on_device:
+        ids = _matte_ids(ids)
+    import torch
+    if not (isinstance(layer_id, torch.Tensor) and layer_id.is_cuda and layer_id.dtype == torch.int32 and layer_id.dim() == 3
+            and layer_id.is_contiguous() and 1 <= layer_id.shape[0] <= 8):
+        raise ValueError("layer_id must be a contiguous (L, H, W) int32 CUDA tensor, L in 1..8")
+    if not (isinstance(layer_coverage, torch.Tensor) and layer_coverage.device == layer_id.device and layer_coverage.dtype == torch.float32
+            and layer_coverage.shape == layer_id.shape and layer_coverage.is_contiguous()):
+        raise ValueError("layer_coverage must be a contiguous float32 tensor of layer_id's shape on its device")
+    dev = layer_id.device
+    if on_device and not (ids.device == dev and ids.dtype == torch.int32 and ids.dim() == 1 and 1 <= ids.numel() <= 64
+                          and ids.is_contiguous()):
+        raise ValueError("ids on the device must be a contiguous int32 vector of 1..64 entries on layer_id's device")
+    layers, H, W = (int(v) for v in layer_id.shape)
+    if H == 0 or W == 0:
+        raise ValueError("the frame is empty")
+    s = _stream_of(stream, dev)
+    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
+        sel = ids if on_device else torch.tensor(ids, dtype=torch.int32, device=dev)
+        out = torch.empty((H, W), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().rtm_matte(W, H, layers, dev.index, layer_id.data_ptr(), layer_coverage.data_ptr(), sel.data_ptr(),
+                                    int(sel.numel()), out.data_ptr(), C.c_void_p(s.cuda_stream)), "rtm_matte")
+    return out
+
+
+def composite(color, alpha, background=(0, 0, 0), want=("f32",), stream=None, out_f32=None):
+    """A traced frame over a background (include/rtm.h: rtm_composite) on the device: out = color + (1 - alpha) * background per
+    channel in float; the frame already holds zero for the part of a pixel that missed.  color (H, W, 3) float32 and alpha
+    (H, W) float32 CUDA tensors (Renderer.render_mattes' "alpha"); background a colour or an (H, W, 3) float32 CUDA tensor.
+    Returns a dict of the names in `want`: "f32" (H, W, 3) float32, "u8" (H, W, 3) uint8 (rtm_quantise of it).  out_f32: the
+    tensor to write "f32" into; `color` itself composites in place.  Enqueued on `stream` (a torch.cuda.Stream or a raw
+    hipStream_t handle; default: the current stream); nothing waits for it."""
+    background = _matte_background(background)
+    outputs = ("f32", "u8")
+    unknown = set(want) - set(outputs)
+    if unknown or not want:
+        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+    import torch
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
+            and color.shape[2] == 3 and color.is_contiguous() and color.numel() > 0):
+        raise ValueError("color must be a contiguous, non-empty (H, W, 3) float32 CUDA tensor")
+    H, W = int(color.shape[0]), int(color.shape[1])
+    dev = color.device
+    if not (isinstance(alpha, torch.Tensor) and alpha.device == dev and alpha.dtype == torch.float32
+            and tuple(alpha.shape) == (H, W) and alpha.is_contiguous()):
+        raise ValueError(f"alpha must be a contiguous ({H}, {W}) float32 tensor on {dev}")
+    image = isinstance(background, torch.Tensor)
+    if image and not (background.device == dev and tuple(background.shape) == (H, W, 3)):
+        raise ValueError(f"a background image must be ({H}, {W}, 3) on {dev}")
+    if out_f32 is not None:
+        if "f32" not in want:
+            raise ValueError('out_f32 is given but "f32" is not in want')
+        if not (isinstance(out_f32, torch.Tensor) and out_f32.device == dev and out_f32.dtype == torch.float32
+                and tuple(out_f32.shape) == (H, W, 3) and out_f32.is_contiguous()):
+            raise ValueError(f"out_f32 must be a contiguous ({H}, {W}, 3) float32 tensor on {dev}")
+    s = _stream_of(stream, dev)
+    with torch.cuda.stream(s):
+        out = {}
+        if "f32" in want:
+            out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if out_f32 is None else out_f32
+        if "u8" in want:
+            out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    prm = _lib.rtm_composite_params((C.c_float * 3)(*((0.0, 0.0, 0.0) if image else background)))
+    ptr = lambda k: out[k].data_ptr() if k in out else None
+    _lib.check(_lib.lib().rtm_composite(C.byref(prm), W, H, dev.index, color.data_ptr(), alpha.data_ptr(),
+                                        background.data_ptr() if image else None, ptr("f32"), ptr("u8"),
+                                        C.c_void_p(s.cuda_stream)), "rtm_composite")
+    return out
+
+
 TONEMAP_DEFAULTS = {"op": "aces", "transfer": "srgb", "exposure": "auto", "key": 0.18, "white": 0.0, "dither": True}
 
 
