@@ -118,6 +118,13 @@ __device__ __forceinline__ double sel_f64_mask(unsigned long long m, double a, d
     return __hiloint2double((int)hi, (int)lo);
 }
 
+// x + 1 for the lanes of the wave mask m, x elsewhere: the mask is the carry-in of one add (a select and an add otherwise)
+__device__ __forceinline__ uint32_t add_lane_bit(uint32_t x, unsigned long long m) {
+    uint32_t r;
+    asm("v_addc_co_u32_e64 %0, vcc, 0, %1, %2" : "=v"(r) : "v"(x), "s"(m) : "vcc");
+    return r;
+}
+
 // k ? index : old for a small non-negative index: as an inline constant of the VOP3 encoding when the
 // compiler knows it (the unrolled tail chunk of a scene under 8 spheres), else from a register.
 __device__ __forceinline__ int sel_index_mask(unsigned long long m, int index, int old) {

@@ -1693,6 +1693,9 @@ __device__ __forceinline__ bool path_shade(const Scene& sc, const int id, const 
     return path_shade_with(m, sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, pc, push);
 }
 
+// stream_after_end = false: the caller opens the lane's next stream whenever a path ends (the deferred-fold render loops), so
+// the stream is not moved past an ended path's draws — an update nobody reads, which the compiler cannot see through the
+// lanes' regions (one 64-bit multiply-add and the draw count's moves per trip).
 // Speculative form: the whole shading block with MathSpec (one basic block), then ONE check; if any
 // lane's operand was outside MathSpec's exact range the block is re-run with the compiler's math
 // from the same inputs (path_shade_core leaves them alone).  The hit record is pushed once, after the
@@ -1701,7 +1704,7 @@ template <class Scene, typename PushFn>
 __device__ __forceinline__ bool path_shade_spec(const Scene& sc, const int id, const double dis, const int mode,
                                                 const int max_bounces, D3& org, D3& dir, int& depth,
                                                 RngStream& rng, D3& term, PathCounters& pc, PushFn push,
-                                                const ShadeLds lds = ShadeLds()) {
+                                                const ShadeLds lds = ShadeLds(), const bool stream_after_end = true) {
     ShadeOut o;
     typename std::conditional<Scene::kPlanes, MathSpecZ, MathSpec>::type m;  // plane normals have exact zeros: see MathSpecT
     m.set_lds(lds);
@@ -1720,7 +1723,7 @@ __device__ __forceinline__ bool path_shade_spec(const Scene& sc, const int id, c
         org = o.org;
         dir = o.dir;
         rng.ctr = o.ctr;
-    } else {
+    } else if (stream_after_end) {
         rng.ctr += (unsigned)o.draws * 0x9E3779B9u;
     }
     return cont;
@@ -1735,7 +1738,8 @@ __device__ __forceinline__ bool path_shade_spec(const Scene& sc, const int id, c
 template <class Scene, typename PushFn, typename FixFn>
 __device__ __forceinline__ bool path_shade_spec_fix(const Scene& sc, int& id, double& dis, const int mode, const int max_bounces,
                                                     D3& org, D3& dir, int& depth, RngStream& rng, D3& term, PathCounters& pc,
-                                                    PushFn push, const ShadeLds lds, const bool flagged, FixFn fix) {
+                                                    PushFn push, const ShadeLds lds, const bool flagged, FixFn fix,
+                                                    const bool stream_after_end = true) {
     ShadeOut o;
     typename std::conditional<Scene::kPlanes, MathSpecZ, MathSpec>::type m;
     m.set_lds(lds);
@@ -1755,24 +1759,26 @@ __device__ __forceinline__ bool path_shade_spec_fix(const Scene& sc, int& id, do
         org = o.org;
         dir = o.dir;
         rng.ctr = o.ctr;
-    } else {
+    } else if (stream_after_end) {
         rng.ctr += (unsigned)o.draws * 0x9E3779B9u;
     }
     return cont;
 }
 #endif
 
-// One PathTracing invocation: nearest-hit loop + shading.
+// One PathTracing invocation: nearest-hit loop + shading.  (stream_after_end = false is honoured by the speculative form
+// alone, M = MathFast — the only policy the deferred-fold loops run; path_shade<M> always moves the stream past an ended
+// path's draws, which is what a caller gets when it says nothing.)
 template <class M, int UNROLL, class Scene, typename PushFn>
 __device__ __forceinline__ bool path_step(const Scene& sc, const int mode, const int max_bounces,
                                           D3& org, D3& dir, int& depth, RngStream& rng, D3& term,
                                           PathCounters& pc, PushFn push, const ShadeLds lds = ShadeLds(),
-                                          int* hit_id = nullptr) {
+                                          int* hit_id = nullptr, const bool stream_after_end = true) {
     double dis;
     const int id = nearest_hit<M, UNROLL>(sc, org, dir, dis);
     if (hit_id) *hit_id = id;
     if constexpr (std::is_same<M, MathFast>::value)
-        return path_shade_spec(sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, pc, push, lds);
+        return path_shade_spec(sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, pc, push, lds, stream_after_end);
     else
         return path_shade<M>(sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, pc, push);
 }

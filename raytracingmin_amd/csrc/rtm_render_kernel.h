@@ -247,15 +247,22 @@ __device__ __forceinline__ void store_pixel(const RenderParams& P, bool valid, i
     }
 }
 
-// Does a path that ended on object `term_id` (the identity row's index n for a miss) take an entry of the fold queue?  Not
+// Does a path that ended on object `hit_id` (-1: a miss, the identity row) take an entry of the fold queue?  Not
 // where the host has proven that its term is (+0, +0, +0): SceneView::emit_mask (all ones without the proof; ids from 64 up
 // only occur then).  Skipping such an end is invisible because x + (+0) == x for every x but -0, and a -0 accumulator — only
 // a seeded pass could start from one: a caller's out64 holding -0 — is stored as 0.0 + acc = +0 by store_pixel whether +0 was
 // added to it or not, and gives t either way once a non-zero t is added.  That covers every entry point that seeds
 // (rtm_render_scene_samples, tile lists, the adaptive render's passes); the head wave's partial and a stealing tile's
 // accumulators reach store_pixel through the finalize kernels.
-__device__ __forceinline__ bool zero_term_queued(const SceneView& v, const unsigned term_id) {
-    return ((v.emit_mask >> (term_id & 63u)) & 1ull) != 0ull;
+// Two vector instructions (round 6; eight before): the mask is bit-reversed (scalar), so that shifting it LEFT by the id brings
+// the object's bit to the sign bit, and the test is one signed compare that yields the lane mask.  The raw hit id serves
+// as it is: a 64-bit shift takes its low six bits, so a miss (-1) asks for bit 63 — never set under the proof (at most 63
+// objects: bits 0..62), set without it, which is the identity row's answer in both cases; ids from 64 up only meet all ones.
+__device__ __forceinline__ bool zero_term_queued(const SceneView& v, const int hit_id) {
+    const unsigned long long reversed = __builtin_bitreverse64(v.emit_mask);
+    int hi = (int)((reversed << ((unsigned)hit_id & 63u)) >> 32);
+    asm("" : "+v"(hi));  // (opaque: the compare is of the high word alone, not a 64-bit one)
+    return hi < 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -533,6 +540,13 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     unsigned n = valid ? n_first : n_end;  // sample index ((sx-1)*SS + (sy-1))*S + s
     int left_in_sub = P.S - (int)(n_first % (unsigned)P.S);  // samples left before the sub-pixel changes
     const int sub_first = (int)(n_first / (unsigned)P.S);
+    // The deferred-fold loops' running sub-pixel index (round 6): a lane's own samples go up by one, so the sub-pixel it moves
+    // on to when left_in_sub reaches zero is the next one — no n / S per move.  Right for any first sample (a pass or a small
+    // wave that starts inside a sub-pixel: left_in_sub above is what is left of THAT one).  It advances for LIVE lanes only: a
+    // lane past its range keeps tracing dummies with n at n_end and the index at n_end / S, a lane outside the frame stays at
+    // its wave's first sub-pixel — both within what prim_prepass_kernel wrote for this pass (the pass's sub-pixels and the next
+    // one); the direction table's other entries are never read.
+    [[maybe_unused]] int sub_cur = sub_first;
     if constexpr (kPrimFix) {
         const unsigned tile_id = (SPLIT && blockIdx.x >= P.split_first) ? P.split_first + (blockIdx.x - P.split_first) % P.n_tiles
                                                                          : blockIdx.x;
@@ -871,15 +885,17 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                                                const int id_ref = nearest_hit_exactfp(sc, org, dir, dis_ref);
                                                id_fix = flagged ? id_ref : id_fix;
                                                dis_fix = flagged ? dis_ref : dis_fix;
-                                           });
+                                           }, /*stream_after_end=*/false);  // (a path end reopens the lane's stream below)
             } else
 #endif
             cont = path_step<M, UNROLL>(sc, mode, P.max_bounces, org, dir, depth, rng, term, unused, push,
-                                        shade_lds, &hit_id);
+                                        shade_lds, &hit_id, /*stream_after_end=*/false);
             if (PACKL && cont && stack.overflow) cont = false;  // records exhausted: the call fails loudly
             // counters (src/Renderer.cpp has none; rtm_stats): one cast per live lane, one draw for the RR test of a
             // hit below the depth cap, two more and a bounce when the path continues
-            const unsigned long long m_cont = __builtin_amdgcn_ballot_w64(cont) & m_live;
+            // (lane masks from compares, combined as scalars: a ballot of a bool that is no compare goes through a VGPR and
+            // back.  A path that continued is one whose depth went up — but for a PACKL lane that was stopped just above)
+            const unsigned long long m_cont = (PACKL ? __builtin_amdgcn_ballot_w64(cont) : __builtin_amdgcn_ballot_w64(depth != depth_before)) & m_live;
             unsigned long long m_drew = __builtin_amdgcn_ballot_w64(hit_id >= 0) & m_live;
             if (P.max_bounces >= 0) m_drew &= ~__builtin_amdgcn_ballot_w64(depth_before >= P.max_bounces);
             const unsigned n_cont = (unsigned)__builtin_popcountll(m_cont);
@@ -889,12 +905,13 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             // A path end whose terminal object has no bit in SceneView::emit_mask adds (+0, +0, +0) to an accumulator that is
             // never -0 where a bit of the image depends on it (zero_term_queued): it takes no ring entry — no rank, no count,
             // no tag, no fold, no store — and its lane goes straight on to its next sample.  The counters above have counted it.
-            const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
-            const bool queued = !cont && live && zero_term_queued(P.scene, term_id);
-            const unsigned long long m_queued = __builtin_amdgcn_ballot_w64(queued);
+            const bool emits = zero_term_queued(P.scene, hit_id);
+            const bool queued = !cont && live && emits;
+            const unsigned long long m_queued = m_live & ~m_cont & __builtin_amdgcn_ballot_w64(emits);
             if (!cont) {
                 if (queued) {
                     // queue this path end: ring position = tail + rank among the lanes queueing now
+                    const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
                     const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m_queued >> 32),
                                                                    __builtin_amdgcn_mbcnt_lo((unsigned)m_queued, 0u));
                     const unsigned pos = (fq_tail + rank) & (kFoldRing - 1);
@@ -971,10 +988,11 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 }
                 // next sample of this pixel (src/Renderer.cpp:236-239); a lane past its range stays at n_end, so that
                 // "n - pending" remains the sample index of its queued path ends (fold_pass, SPLIT)
-                n += live ? 1u : 0u;
+                n = add_lane_bit(n, m_live);
                 if (--left_in_sub == 0) {
                     left_in_sub = P.S;
-                    const int sub = (int)(n / (unsigned)P.S);
+                    // (== n / S for a lane in its range: n has just become a multiple of S; a lane past it stays where it is)
+                    const int sub = sub_cur = (int)add_lane_bit((uint32_t)sub_cur, m_live);
                     int px, py;
                     pixel_xy(px, py);
                     if constexpr (kPrimDirs) pdir = primary_of((unsigned)lane, px, py, (unsigned)sub);
@@ -1052,11 +1070,12 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                                                const int id_ref = nearest_hit_exactfp(sc, org, dir, dis_ref);
                                                id_fix = flagged ? id_ref : id_fix;
                                                dis_fix = flagged ? dis_ref : dis_fix;
-                                           });
+                                           }, /*stream_after_end=*/false);  // (a path end reopens the lane's stream below)
             } else
 #endif
-            cont = path_step<M, UNROLL>(sc, mode, P.max_bounces, org, dir, depth, rng, term, unused, push, shade_lds, &hit_id);
-            const unsigned long long m_cont = __builtin_amdgcn_ballot_w64(cont) & m_busy;
+            cont = path_step<M, UNROLL>(sc, mode, P.max_bounces, org, dir, depth, rng, term, unused, push, shade_lds, &hit_id,
+                                        /*stream_after_end=*/false);
+            const unsigned long long m_cont = __builtin_amdgcn_ballot_w64(depth != depth_before) & m_busy;  // (the main loop's rule)
             unsigned long long m_drew = __builtin_amdgcn_ballot_w64(hit_id >= 0) & m_busy;
             if (P.max_bounces >= 0) m_drew &= ~__builtin_amdgcn_ballot_w64(depth_before >= P.max_bounces);
             const unsigned n_cont = (unsigned)__builtin_popcountll(m_cont);
@@ -1066,10 +1085,11 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             const bool need = !busy || !cont;  // this lane wants a new sample
             // (the main loop's rule: a path end that provably adds (+0, +0, +0) is not queued — an own sample keeps out of its
             // pixel's count, a stolen one is not exported and steal_finalize_kernel finds nothing under its (pixel, sample))
-            const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
-            const bool ended = busy && !cont && zero_term_queued(P.scene, term_id);
-            const unsigned long long m_ended = __builtin_amdgcn_ballot_w64(ended);
+            const bool emits = zero_term_queued(P.scene, hit_id);
+            const bool ended = busy && !cont && emits;
+            const unsigned long long m_ended = m_busy & ~m_cont & __builtin_amdgcn_ballot_w64(emits);
             if (ended) {
+                const unsigned term_id = (unsigned)(hit_id < 0 ? scene_n : hit_id);
                 const unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(m_ended >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_ended, 0u));
                 const unsigned pos = (fq_tail + rank) & (kFoldRing - 1);
                 const bool own = (cur >> 16) == (unsigned)lane;
@@ -1098,7 +1118,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 got = true;
                 if (--left_in_sub == 0) {
                     left_in_sub = P.S;
-                    const int sub = (int)((cur & 0xFFFFu) / (unsigned)P.S);
+                    const int sub = ++sub_cur;  // (own samples — always within the pass here — go up by one as in the main loop)
                     int px, py;
                     pixel_xy(px, py);
                     if constexpr (kPrimDirs) pdir = primary_of((unsigned)lane, px, py, (unsigned)sub);
