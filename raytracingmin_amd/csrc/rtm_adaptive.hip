@@ -8,27 +8,13 @@
 #include <string>
 
 #include "rtm_adaptive_kernel.h"
-#include "rtm_internal.h"
+#include "rtm_host.h"
 
 namespace rtm {
 
 namespace {
 constexpr size_t kAlign = 256;
 size_t round_up(size_t b) { return (b + kAlign - 1) / kAlign * kAlign; }
-
-int invalid(const char* what) {
-    set_last_error(what);
-    return RTM_ERR_INVALID_ARGUMENT;
-}
-
-#define RTM_AD_CHECK(call)                                                       \
-    do {                                                                         \
-        const hipError_t e_ = (call);                                            \
-        if (e_ != hipSuccess) {                                                  \
-            set_last_error(std::string(#call ": ") + hipGetErrorString(e_));     \
-            return RTM_ERR_HIP;                                                  \
-        }                                                                        \
-    } while (0)
 
 // The work buffer: [snapshot: 24 bytes per pixel of the call's rows][list A][list B][flags][counts], each part 256-aligned.
 struct Work {
@@ -80,7 +66,7 @@ int render_adaptive(const rtm_settings* st, const rtm_scene* scene, const rtm_op
     if (!work) return invalid("work_dev: null");
     if (prm->min_samples == 0u) return invalid("params.min_samples is 0");
     if (!std::isfinite(prm->threshold)) return invalid("params.threshold is NaN or infinite");
-    if (((uintptr_t)work & (kAlign - 1)) != 0) return invalid("work_dev is not 256-byte aligned");
+    if (!aligned256(work)) return invalid("work_dev is not 256-byte aligned");
     if (!st || !opt) return invalid("null settings or options");
     if (!scene) return invalid("null scene");
     const uint64_t ss = st->super_samples > 0 ? (uint64_t)st->super_samples : 0u, s1 = st->samples > 0 ? (uint64_t)st->samples : 0u;
@@ -95,23 +81,23 @@ int render_adaptive(const rtm_settings* st, const rtm_scene* scene, const rtm_op
     const size_t pixels = (size_t)st->width * (size_t)rows;
     const Work w = carve(work, pixels, n_tiles);
     const hipStream_t stream = (hipStream_t)stream_v;
-    RTM_AD_CHECK(hipSetDevice(opt->device));
+    RTM_HIP_CHECK(hipSetDevice(opt->device));
 
     // pass 0: [0, b_0) of every tile, through the list path.  Only the work buffer is written before it: a variant that
     // refuses lists refuses there, before any of the caller's outputs (tile_samples included) is touched.
     const unsigned begin_blocks = (n_tiles + 255u) / 256u;
     adaptive_begin_kernel<<<begin_blocks, 256, 0, stream>>>(w.list[0], nullptr, n_tiles, b0);
-    RTM_AD_CHECK(hipGetLastError());
+    RTM_HIP_CHECK(hipGetLastError());
     rtm_stats s;
     int rc = render_scene_tiles(st, scene, opt, 0u, b0, w.list[0], n_tiles, accum, out32, out8, stream_v, stats ? &s : nullptr);
     if (rc != RTM_OK) return rc;
     if (stats) add_stats(stats, s);
     if (tile_samples) {
         adaptive_begin_kernel<<<begin_blocks, 256, 0, stream>>>(w.list[0], tile_samples, n_tiles, b0);
-        RTM_AD_CHECK(hipGetLastError());
+        RTM_HIP_CHECK(hipGetLastError());
     }
     if ((uint64_t)b0 == total) return RTM_OK;
-    RTM_AD_CHECK(hipMemcpyAsync(w.snap, accum, pixels * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    RTM_HIP_CHECK(hipMemcpyAsync(w.snap, accum, pixels * 3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
 
     hipEvent_t ev[2] = {nullptr, nullptr};
     struct Events {
@@ -122,7 +108,7 @@ int render_adaptive(const rtm_settings* st, const rtm_scene* scene, const rtm_op
         }
     } guard{ev};
     if (stats)
-        for (auto& e : ev) RTM_AD_CHECK(hipEventCreate(&e));
+        for (auto& e : ev) RTM_HIP_CHECK(hipEventCreate(&e));
 
     unsigned n_active = n_tiles, cur = 0;
     uint64_t a = b0;
@@ -133,7 +119,7 @@ int render_adaptive(const rtm_settings* st, const rtm_scene* scene, const rtm_op
         if (rc != RTM_OK) return rc;
         if (stats) {
             add_stats(stats, s);
-            RTM_AD_CHECK(hipEventRecord(ev[0], stream));
+            RTM_HIP_CHECK(hipEventRecord(ev[0], stream));
         }
         AdaptiveCheck A;
         A.acc = accum;
@@ -152,14 +138,14 @@ int render_adaptive(const rtm_settings* st, const rtm_scene* scene, const rtm_op
         A.threshold = (double)prm->threshold;
         adaptive_check_kernel<<<n_active, 64, 0, stream>>>(A);
         adaptive_compact_kernel<<<1, kCompactThreads, 0, stream>>>(w.flags, w.list[cur], n_active, w.list[cur ^ 1u], w.count);
-        RTM_AD_CHECK(hipGetLastError());
-        if (stats) RTM_AD_CHECK(hipEventRecord(ev[1], stream));
+        RTM_HIP_CHECK(hipGetLastError());
+        if (stats) RTM_HIP_CHECK(hipEventRecord(ev[1], stream));
         unsigned next = 0;
-        RTM_AD_CHECK(hipMemcpyAsync(&next, w.count, sizeof next, hipMemcpyDeviceToHost, stream));
-        RTM_AD_CHECK(hipStreamSynchronize(stream));
+        RTM_HIP_CHECK(hipMemcpyAsync(&next, w.count, sizeof next, hipMemcpyDeviceToHost, stream));
+        RTM_HIP_CHECK(hipStreamSynchronize(stream));
         if (stats) {
             float ms = 0.f;
-            RTM_AD_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            RTM_HIP_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
             stats->kernel_ms += ms;
         }
         n_active = next;

@@ -6,18 +6,13 @@
 #include <cstdint>
 #include <string>
 
-#include "rtm_internal.h"
+#include "rtm_host.h"
 #include "rtm_compare_kernel.h"
 
 namespace rtm {
 
 namespace {
 constexpr size_t kCmpAlign = 256;  // work_dev's alignment and the size of its last part
-
-int invalid(const char* what) {
-    set_last_error(what);
-    return RTM_ERR_INVALID_ARGUMENT;
-}
 
 size_t cmp_tiles_x(int32_t width) { return ((size_t)width + kCmpTile - 1) / kCmpTile; }
 size_t cmp_tiles(int32_t width, int32_t height) { return cmp_tiles_x(width) * (((size_t)height + kCmpTile - 1) / kCmpTile); }
@@ -69,7 +64,7 @@ int compare(const rtm_compare_params* prm, int32_t width, int32_t height, int de
     if (!std::isfinite(prm->rel_epsilon) || !(prm->rel_epsilon > 0.0)) return invalid("rel_epsilon is not finite and positive");
     const uintptr_t elem = prm->dtype == RTM_COMPARE_F64 ? sizeof(double) : sizeof(float);
     if (((uintptr_t)a & (elem - 1)) != 0 || ((uintptr_t)b & (elem - 1)) != 0) return invalid("a frame pointer is not aligned to its element");
-    if (((uintptr_t)work & (kCmpAlign - 1)) != 0) return invalid("work_dev is not 256-byte aligned");
+    if (!aligned256(work)) return invalid("work_dev is not 256-byte aligned");
     if (((uintptr_t)result_out & 7) != 0 || ((uintptr_t)map_out & 3) != 0) return invalid("an output pointer is not aligned to its element");
     if (work == a || work == b || (const void*)result_out == a || (const void*)result_out == b ||
         (map_out && ((const void*)map_out == a || (const void*)map_out == b)))
@@ -79,15 +74,9 @@ int compare(const rtm_compare_params* prm, int32_t width, int32_t height, int de
     if ((void*)result_out == work) return invalid("result_out_dev aliases work_dev");
     if (device < 0) return invalid("negative device");
     const size_t pix = (size_t)width * (size_t)height;
-    if (pix > SIZE_MAX / (3 * sizeof(double)) || pix > 0x7FFFFFFFu) {  // the partials index pixels in 32 bits
-        set_last_error("frame too large for one launch of the comparison");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
+    if (pix > SIZE_MAX / (3 * sizeof(double)) || pix > 0x7FFFFFFFu)  // the partials index pixels in 32 bits
+        return unsupported("frame too large for one launch of the comparison");
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     const hipStream_t stream = (hipStream_t)stream_v;
     CmpArgs args;
     for (int i = 0; i <= kCmpRadius; ++i) args.g[i] = std::exp(-(double)(i * i) / 4.5);
@@ -108,12 +97,7 @@ int compare(const rtm_compare_params* prm, int32_t width, int32_t height, int de
     if (result_out)
         compare_final_kernel<<<1, kCmpBlock, 0, stream>>>(args, partials, (uint32_t)tiles,
                                                           (rtm_compare_result*)((char*)work + cmp_partial_bytes(tiles)), result_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("compare kernel launch: ") + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
+    return launched("compare");
 }
 
 }  // namespace rtm

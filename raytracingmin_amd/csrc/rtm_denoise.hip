@@ -11,7 +11,7 @@
 
 #include "rtm_denoise_kernel.h"
 #include "rtm_denoise_var_kernel.h"
-#include "rtm_internal.h"
+#include "rtm_host.h"
 
 namespace rtm {
 
@@ -19,10 +19,6 @@ namespace {
 constexpr size_t kDnRecord = sizeof(float4);  // 16 B
 constexpr size_t kDnPlanes = 3;               // colour records ping and pong, geometry records
 
-int invalid(const char* what) {
-    set_last_error(what);
-    return RTM_ERR_INVALID_ARGUMENT;
-}
 }  // namespace
 
 // Three planes of width x height 16-byte records: [0] colour ping, [1] colour pong, [2] (n, z).  SIZE_MAX when that does
@@ -49,15 +45,9 @@ int denoise(const rtm_denoise_params* prm, int32_t width, int32_t height, int de
     if (device < 0) return invalid("negative device");
     const size_t pix = (size_t)width * (size_t)height;
     const size_t tiles_x = ((size_t)width + kDnTileX - 1) / kDnTileX, tiles = tiles_x * (((size_t)height + kDnTileY - 1) / kDnTileY);
-    if (tiles > 0x7FFFFFFFu / (kDnTileX * kDnTileY)) {
-        set_last_error("frame too large for one launch of the denoiser");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
+    if (tiles > 0x7FFFFFFFu / (kDnTileX * kDnTileY))
+        return unsupported("frame too large for one launch of the denoiser");
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     const hipStream_t stream = (hipStream_t)stream_v;
     const rtm_aov_buffers g = guide ? *guide : rtm_aov_buffers{nullptr, nullptr, nullptr, nullptr};
     if (prm->iterations == 0) {
@@ -94,12 +84,7 @@ int denoise(const rtm_denoise_params* prm, int32_t width, int32_t height, int de
                                                                        nullptr, g.albedo, out32, out8);
         }
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("denoise kernel launch: ") + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
+    return launched("denoise");
 }
 
 // ---- the variance-guided filter --------------------------------------------------------------------------------------
@@ -127,10 +112,8 @@ int dv_plan(int32_t iterations, const float (&sigmas)[3], int32_t width, int32_t
     if (device < 0) return invalid("negative device");
     P.pix = (size_t)width * (size_t)height;
     const size_t tiles_x = ((size_t)width + kDnTileX - 1) / kDnTileX, tiles = tiles_x * (((size_t)height + kDnTileY - 1) / kDnTileY);
-    if (tiles > 0x7FFFFFFFu / (kDnTileX * kDnTileY)) {
-        set_last_error("frame too large for one launch of the denoiser");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (tiles > 0x7FFFFFFFu / (kDnTileX * kDnTileY))
+        return unsupported("frame too large for one launch of the denoiser");
     P.grid = (unsigned)tiles;
     P.F.W = width;
     P.F.H = height;
@@ -160,15 +143,6 @@ void dv_launch_variance(int form, const DvPlan& P, float sigma_depth, float* v_o
     else
         denoise_variance_kernel<2><<<tall, block, 0, stream>>>(P.F, P.F.tiles_x, sigma_depth, P.rec[0], P.rec_g, v_out, var_out);
 }
-
-int dv_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string(what) + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
-}
 }  // namespace
 
 // rtm_denoise's 48 bytes per pixel and two variance planes of one float each.  SIZE_MAX when that does not fit a size_t.
@@ -192,11 +166,7 @@ int denoise_variance(const rtm_denoise_var_params* prm, int32_t width, int32_t h
     const float sigmas[3] = {prm->sigma_lum, prm->sigma_normal, prm->sigma_depth};
     const int rc = dv_plan(prm->iterations, sigmas, width, height, device, g, work, P);
     if (rc != RTM_OK) return rc;
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     const hipStream_t stream = (hipStream_t)stream_v;
     const unsigned block = kDnTileX * kDnTileY;
     const int K = (out32 || out8) ? prm->iterations : 0;  // a variance-only call filters nothing
@@ -220,7 +190,7 @@ int denoise_variance(const rtm_denoise_var_params* prm, int32_t width, int32_t h
             denoise_level_var_kernel<true><<<P.grid, block, 0, stream>>>(P.F, s, prm->sigma_lum, depth_scale, P.rec[i & 1], P.rec_g,
                                                                          P.v[i & 1], nullptr, nullptr, g.albedo, out32, out8);
     }
-    return dv_launched("denoise_variance kernel launch: ");
+    return launched("denoise_variance");
 }
 
 // rtm_debug_denoise_variance_kernel (include/rtm_debug.h): one form of the variance kernel alone, on the records a
@@ -235,13 +205,9 @@ int denoise_variance_kernel_probe(int form, const rtm_denoise_var_params* prm, i
     const float sigmas[3] = {prm->sigma_lum, prm->sigma_normal, prm->sigma_depth};
     const int rc = dv_plan(prm->iterations, sigmas, width, height, device, g, work, P);
     if (rc != RTM_OK) return rc;
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     dv_launch_variance(form, P, prm->sigma_depth, nullptr, var_out, (hipStream_t)stream_v);
-    return dv_launched("denoise_variance kernel launch: ");
+    return launched("denoise_variance");
 }
 
 }  // namespace rtm

@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <string>
 
-#include "rtm_internal.h"
+#include "rtm_host.h"
 #include "rtm_flip_kernel.h"
 
 namespace rtm {
@@ -15,11 +15,6 @@ namespace rtm {
 namespace {
 constexpr size_t kFlipAlign = 256;  // work_dev's alignment and the granule of its parts
 constexpr double kPi = 3.14159265358979323846;
-
-int invalid(const char* what) {
-    set_last_error(what);
-    return RTM_ERR_INVALID_ARGUMENT;
-}
 
 size_t round_up(size_t v) { return (v + kFlipAlign - 1) / kFlipAlign * kFlipAlign; }
 size_t flip_tiles_x(int32_t width) { return ((size_t)width + kFlipTileW - 1) / kFlipTileW; }
@@ -133,7 +128,7 @@ int flip(const rtm_flip_params* prm, int32_t width, int32_t height, int device, 
     if (!std::isfinite(prm->pixels_per_degree) || prm->pixels_per_degree < 8.0 || prm->pixels_per_degree > 128.0)
         return invalid("pixels_per_degree is NaN, infinite or outside [8, 128]");
     if (((uintptr_t)a & 3) != 0 || ((uintptr_t)b & 3) != 0) return invalid("a frame pointer is not aligned to its element");
-    if (((uintptr_t)work & (kFlipAlign - 1)) != 0) return invalid("work_dev is not 256-byte aligned");
+    if (!aligned256(work)) return invalid("work_dev is not 256-byte aligned");
     if (((uintptr_t)result_out & 7) != 0 || ((uintptr_t)map_out & 3) != 0) return invalid("an output pointer is not aligned to its element");
     if (work == (const void*)a || work == (const void*)b || (const void*)result_out == (const void*)a ||
         (const void*)result_out == (const void*)b || (map_out && (map_out == a || map_out == b)))
@@ -143,15 +138,9 @@ int flip(const rtm_flip_params* prm, int32_t width, int32_t height, int device, 
     if ((void*)result_out == work) return invalid("result_out_dev aliases work_dev");
     if (device < 0) return invalid("negative device");
     const size_t pix = (size_t)width * (size_t)height;
-    if (pix > 0x7FFFFFFFu || flip_work_bytes(width, height) == SIZE_MAX) {  // the partials index pixels in 32 bits
-        set_last_error("frame too large for one launch of the perceptual difference");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
+    if (pix > 0x7FFFFFFFu || flip_work_bytes(width, height) == SIZE_MAX)  // the partials index pixels in 32 bits
+        return unsupported("frame too large for one launch of the perceptual difference");
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     const hipStream_t stream = (hipStream_t)stream_v;
     FlipArgs args;
     flip_constants(prm->pixels_per_degree, prm->transfer, args);
@@ -171,12 +160,7 @@ int flip(const rtm_flip_params* prm, int32_t width, int32_t height, int device, 
     else
         flip_cols_kernel<false, true><<<(unsigned)tiles, kFlipBlock, 0, stream>>>(args, a, b, planes, nullptr, nullptr, map_out);
     if (result_out) flip_final_kernel<<<1, kFlipBlock, 0, stream>>>(args, partials, (uint32_t)tiles, hist, result_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("flip kernel launch: ") + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
+    return launched("flip");
 }
 
 }  // namespace rtm

@@ -34,7 +34,7 @@
 
 #include "../../include/rtm.h"
 #include "rtm_device.h"
-#include "rtm_internal.h"
+#include "rtm_host.h"
 #include "rtm_path.h"
 
 #include "rtm_render_kernel.h"
@@ -54,16 +54,6 @@ constexpr int kModeFlags = RTM_MODE_HOST_TRIG | RTM_MODE_COUNT_TESTS | RTM_MODE_
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
 const char* last_error() { return g_last_error.c_str(); }
-
-#define RTM_HIP_CHECK(expr)                                                               \
-    do {                                                                                  \
-        hipError_t e__ = (expr);                                                          \
-        if (e__ != hipSuccess) {                                                          \
-            (void)hipGetLastError(); /* do not leave a sticky error for the host app */  \
-            set_last_error(std::string(#expr) + ": " + hipGetErrorString(e__));           \
-            return RTM_ERR_HIP;                                                           \
-        }                                                                                 \
-    } while (0)
 
 // src/Ray.h / src/Renderer.cpp:202-208 on the host, same operation order as the device code
 namespace host {
@@ -373,6 +363,11 @@ static SceneView scene_view(const double* geom, const double* mat, const double*
     }
     return v;
 }
+// A scene object as a render reads it.  `grid`: grid_for's answer for the call, or null for a render that takes no grid.
+static SceneView view_of(const rtm_scene& sc, const void* grid) {
+    return scene_view(sc.geom.as<double>(), sc.mat.as<double>(), sc.aux.as<double>(), sc.n,
+                      sc.has_planes ? sc.plane.as<double>() : nullptr, grid, sc.surf.as<double>(), sc.axis_pat, sc.fold_flags, sc.emit_mask);
+}
 
 // ---- uniform grid of a large scene (rtm_path.h: GridHeader, GridWalk — where the pads are derived) ------------------
 // Built on the host from the flattened geometry rows (cx, cy, cz, float r*r) when a scene OBJECT is created: 25 ms for
@@ -559,10 +554,7 @@ int grid_build_host(const rtm_sphere* sp, size_t n, uint64_t* info, double* pads
     std::vector<double> hg, hm;
     flatten_scene(sp, n, hg, hm);
     GridBuild B;
-    if (!make_grid(hg.data(), n, B, pads)) {
-        set_last_error("this scene gets no grid");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (!make_grid(hg.data(), n, B, pads)) return unsupported("this scene gets no grid");
     const size_t cells = B.cell_start.size() - 1;
     info[0] = cells;
     info[1] = B.refs;
@@ -724,10 +716,7 @@ static int scene_build_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n,
 }
 
 int scene_create(const rtm_sphere* sp, size_t n, int on_device, int device, rtm_scene** out) {
-    if (!out || (!sp && n) || n > 0x7FFFFFFFull) {
-        set_last_error("null argument or scene too large");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!out || (!sp && n) || n > 0x7FFFFFFFull) return invalid("null argument or scene too large");
     *out = nullptr;
     std::unique_ptr<rtm_scene> sc(new rtm_scene);
     const int rc = on_device ? scene_build_device(*sc, sp, n, device) : scene_build_host(*sc, sp, n, device);
@@ -751,19 +740,14 @@ static void plane_row(const rtm_object& o, double row[16]) {
 }
 
 int scene_create_objects(const rtm_object* objs, size_t n, int device, rtm_scene** out) {
-    if (!out || (!objs && n) || n > 0x7FFFFFFFull) {
-        set_last_error("null argument or scene too large");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!out || (!objs && n) || n > 0x7FFFFFFFull) return invalid("null argument or scene too large");
     *out = nullptr;
     std::vector<rtm_sphere> view(n ? n : 1);
     std::vector<double> rows(n * 16, 0.0);
     bool any_plane = false;
     for (size_t i = 0; i < n; ++i) {
-        if (objs[i].type != RTM_OBJECT_SPHERE && objs[i].type != RTM_OBJECT_PLANE) {
-            set_last_error("unknown object type (1 = sphere, 2 = plane)");
-            return RTM_ERR_INVALID_SCENE;
-        }
+        if (objs[i].type != RTM_OBJECT_SPHERE && objs[i].type != RTM_OBJECT_PLANE)
+            return fail(RTM_ERR_INVALID_SCENE, "unknown object type (1 = sphere, 2 = plane)");
         std::memset(&view[i], 0, sizeof view[i]);
         for (int k = 0; k < 3; ++k) {
             view[i].center[k] = objs[i].position[k];
@@ -801,10 +785,7 @@ int scene_create_objects(const rtm_object* objs, size_t n, int device, rtm_scene
 
 int intersect_objects_batch(const rtm_object* objs, const double* org, const double* dir, size_t n, int mode,
                             int32_t* out_hit, double* out_t, double* out_normal) {
-    if (!objs || !org || !dir || !out_hit || !out_t || !out_normal) {
-        set_last_error("null argument");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!objs || !org || !dir || !out_hit || !out_t || !out_normal) return invalid("null argument");
     if (n == 0) return RTM_OK;
     int device = 0;
     RTM_HIP_CHECK(hipGetDevice(&device));
@@ -994,10 +975,8 @@ static int ensure_trig_fix(int device, const uint32_t** out) {
             }
         });
     for (auto& th : pool) th.join();
-    if (out_of_range.load() != 0) {
-        set_last_error("host and device sin/cos differ by more than one ulp somewhere: RTM_MODE_HOST_TRIG unavailable");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (out_of_range.load() != 0)
+        return unsupported("host and device sin/cos differ by more than one ulp somewhere: RTM_MODE_HOST_TRIG unavailable");
     DevMem d_table;
     const int rc = d_table.alloc((size_t)words * 4);
     if (rc != RTM_OK) return rc;
@@ -1024,39 +1003,21 @@ int output_rows(const rtm_options* opt) {
 }
 
 static int validate(const rtm_settings* st, const rtm_sphere* sp, size_t n, const rtm_options* opt) {
-    if (!st || !opt || (!sp && n)) {
-        set_last_error("null argument");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (st->width <= 0 || st->height <= 0 || st->samples <= 0 || st->super_samples <= 0) {
-        set_last_error("width, height, samples and superSamples must be positive");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (opt->row_begin < 0 || opt->row_end > st->height || opt->row_begin > opt->row_end) {
-        set_last_error("row range outside the image");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (opt->band_count < 0 || (opt->band_count > 1 && (opt->band_index < 0 || opt->band_index >= opt->band_count))) {
-        set_last_error("band_index outside [0, band_count)");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if ((opt->mode & ~kModeFlags) != RTM_MODE_LITERAL && (opt->mode & ~kModeFlags) != RTM_MODE_REPAIRED) {
-        set_last_error("unknown mode");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!st || !opt || (!sp && n)) return invalid("null argument");
+    if (st->width <= 0 || st->height <= 0 || st->samples <= 0 || st->super_samples <= 0)
+        return invalid("width, height, samples and superSamples must be positive");
+    if (opt->row_begin < 0 || opt->row_end > st->height || opt->row_begin > opt->row_end)
+        return invalid("row range outside the image");
+    if (opt->band_count < 0 || (opt->band_count > 1 && (opt->band_index < 0 || opt->band_index >= opt->band_count)))
+        return invalid("band_index outside [0, band_count)");
+    if ((opt->mode & ~kModeFlags) != RTM_MODE_LITERAL && (opt->mode & ~kModeFlags) != RTM_MODE_REPAIRED)
+        return invalid("unknown mode");
     if ((uint64_t)st->super_samples * st->super_samples * st->samples > 0xFFFFFFFFull ||
-        (uint64_t)st->width * st->height > 0xFFFFFFFFull || n > 0x7FFFFFFFull) {
-        set_last_error("image, sample or scene count exceeds 32-bit indexing");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    if (opt->max_bounces > 16 + kPoolLevels) {
-        set_last_error("max_bounces exceeds the hit-record capacity (976); use -1 for unlimited");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    if (opt->variant < 0 || opt->variant >= num_variants()) {
-        set_last_error("unknown kernel variant");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+        (uint64_t)st->width * st->height > 0xFFFFFFFFull || n > 0x7FFFFFFFull)
+        return unsupported("image, sample or scene count exceeds 32-bit indexing");
+    if (opt->max_bounces > 16 + kPoolLevels)
+        return unsupported("max_bounces exceeds the hit-record capacity (976); use -1 for unlimited");
+    if (opt->variant < 0 || opt->variant >= num_variants()) return invalid("unknown kernel variant");
     return RTM_OK;
 }
 
@@ -1662,10 +1623,7 @@ static int run_wavefront_impl(const RenderParams& P, int rows, StreamCtx& ctx, b
     S.part_t = (double*)take((size_t)(kWfMaxParts - 1) * kWfPartSlots * 8);
     S.part_id = (int*)take((size_t)(kWfMaxParts - 1) * kWfPartSlots * 4);
     S.part_slots = kWfPartSlots;
-    if (!P.scene.geom32) {
-        set_last_error("scene without rejection-test data");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!P.scene.geom32) return invalid("scene without rejection-test data");
     const unsigned grid = (unsigned)((N + 255) / 256);
     wf_init_kernel<<<grid, 256, 0, stream>>>(P, S);  // also sets n_active = {npix, 0}
     RTM_HIP_CHECK(hipGetLastError());
@@ -1701,10 +1659,7 @@ static int run_wavefront_impl(const RenderParams& P, int rows, StreamCtx& ctx, b
     const unsigned long long max_trips = (unsigned long long)pass_len * (unsigned long long)(S.levels + 1) + 8;
     unsigned long long trip = 0;
     for (unsigned long long b = 0;; ++b) {
-        if (trip > max_trips + 64) {
-            set_last_error("wavefront loop did not terminate");
-            return RTM_ERR_HIP;
-        }
+        if (trip > max_trips + 64) return fail(RTM_ERR_HIP, "wavefront loop did not terminate");
         // short trips (few spheres or few rays): eight per batch, so that the host's lag of one batch hides the
         // read-back; long trips: one
         const int batch = ((unsigned long long)na * (unsigned long long)P.scene.n < 2000000000ull) ? 8 : 1;
@@ -1759,8 +1714,7 @@ static int take_stream_status(StreamCtx& ctx, bool wait) {
     RTM_HIP_CHECK(hipMemsetAsync(ctx.sticky + 3, 0, sizeof(unsigned long long), ctx.stream));
     RTM_HIP_CHECK(hipStreamSynchronize(ctx.stream));
     *ctx.flag_host = 0ull;
-    set_last_error(std::string("an earlier render on this stream was truncated: ") + kOverflowText);
-    return RTM_ERR_UNSUPPORTED;
+    return unsupported(std::string("an earlier render on this stream was truncated: ") + kOverflowText);
 }
 
 // rtm_stream_release: the (device, stream) context goes — after the stream's queued work, which may still use its buffers.
@@ -1896,21 +1850,14 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     // 16 waves per CU); global-memory tables up to 511 (the tables no longer cost occupancy); from 512
     // spheres the wavefront pipeline with its rejection test wins over the monolithic kernel
     plan.force_split = variant == kVariantSplit;
-    if (variant < 0 || variant >= num_variants() || variant_retired(variant)) {
-        set_last_error(variant >= 0 && variant < num_variants() ? std::string("variant ") + std::to_string(variant) + ": " + kVariantNames[variant]
-                                                                : std::string("no such variant"));
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (variant < 0 || variant >= num_variants() || variant_retired(variant))
+        return unsupported(variant >= 0 && variant < num_variants() ? std::string("variant ") + std::to_string(variant) + ": " + kVariantNames[variant]
+                                                                    : std::string("no such variant"));
     if (opt->mode & RTM_MODE_SURFACE_SAMPLE) {
         // the integrator switch: png::SurfaeSample through its own general kernel (rtm_surface.h), whatever the scene's size
-        if (variant != kVariantAuto && variant != kVariantSurface) {
-            set_last_error("RTM_MODE_SURFACE_SAMPLE is served by its own kernel: variant 0 (or 19)");
-            return RTM_ERR_UNSUPPORTED;
-        }
-        if (view.surf == nullptr || n == 0) {
-            set_last_error("RTM_MODE_SURFACE_SAMPLE needs a scene with at least one object");
-            return RTM_ERR_UNSUPPORTED;
-        }
+        if (variant != kVariantAuto && variant != kVariantSurface)
+            return unsupported("RTM_MODE_SURFACE_SAMPLE is served by its own kernel: variant 0 (or 19)");
+        if (view.surf == nullptr || n == 0) return unsupported("RTM_MODE_SURFACE_SAMPLE needs a scene with at least one object");
         if (needs_pool(P)) {
             P.pool_slots = 65536u;
             plan.bytes[kScratchPool] = (size_t)P.pool_slots * kPoolLevels * sizeof(uint2) + 64;
@@ -1918,46 +1865,33 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
         plan.variant = kVariantSurface;
         return RTM_OK;
     }
-    if (variant == kVariantSurface) {
-        set_last_error("variant 19 is chosen by RTM_MODE_SURFACE_SAMPLE in rtm_options.mode");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    if (!whole_frame && (variant == kVariantStamped || variant == kVariantPrimaryReuse || variant == kVariantFp32)) {
-        set_last_error(std::string("variant ") + std::to_string(variant) + " renders whole frames only: sample range [0, " +
-                       std::to_string(P.total_samples) + ")");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    if (pass.tiles && (variant == kVariantStamped || variant == kVariantPrimaryReuse || variant == kVariantFp32)) {
-        set_last_error(std::string("variant ") + std::to_string(variant) + " renders whole frames only: no tile lists");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (variant == kVariantSurface) return unsupported("variant 19 is chosen by RTM_MODE_SURFACE_SAMPLE in rtm_options.mode");
+    if (!whole_frame && (variant == kVariantStamped || variant == kVariantPrimaryReuse || variant == kVariantFp32))
+        return unsupported(std::string("variant ") + std::to_string(variant) + " renders whole frames only: sample range [0, " +
+                           std::to_string(P.total_samples) + ")");
+    if (pass.tiles && (variant == kVariantStamped || variant == kVariantPrimaryReuse || variant == kVariantFp32))
+        return unsupported(std::string("variant ") + std::to_string(variant) + " renders whole frames only: no tile lists");
     if (variant == kVariantAuto)
         variant = n <= (size_t)kAutoLdsTableSpheres ? kVariantFastLds :
                   view.grid != nullptr ? kVariantGrid :  // (grid_for: the scene has one and the camera is within its reach)
                   n < 256 ? kVariantGlobalDefer :
                   n < (size_t)kAutoWavefrontSpheres ? kVariantFastGlobal : kVariantWavefrontRejectF32;
-    if (pass.tiles && variant == kVariantWavefrontRejectF32) {
+    if (pass.tiles && variant == kVariantWavefrontRejectF32)
         // the pipeline's path state is indexed by pixel of the call's rows: it renders whole rows only
-        set_last_error("variant 12 (wavefront pipeline, also variant 0's choice from 512 spheres without a grid) does not "
-                       "render tile lists");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    if (variant == kVariantGrid && view.grid == nullptr) {
-        set_last_error("variant 17 (uniform grid) serves scenes of 64 gridded spheres or more held by an rtm_scene "
-                       "(rtm_scene_create*, rtm_render_rows*) or made per call from a device array; this scene has no grid");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    else if (variant == kVariantSplit)
+        return unsupported("variant 12 (wavefront pipeline, also variant 0's choice from 512 spheres without a grid) does not "
+                           "render tile lists");
+    if (variant == kVariantGrid && view.grid == nullptr)
+        return unsupported("variant 17 (uniform grid) serves scenes of 64 gridded spheres or more held by an rtm_scene "
+                           "(rtm_scene_create*, rtm_render_rows*) or made per call from a device array; this scene has no grid");
+    if (variant == kVariantSplit)
         variant = kVariantFastLds;
     // variant 18, the labelled tolerance row (rtm_kernels_tol.hip): planned exactly like the default kernel of small scenes —
     // sample split of the last tiles, in-wave sample stealing — and launched from the other translation unit
     const bool tol = variant == kVariantTol;
     plan.tol = tol;
     if (tol) {
-        if (!(n >= 1 && n <= (size_t)kAutoLdsTableSpheres && view.plane == nullptr && P.sample_end < 65536u)) {
-            set_last_error("variant 18 (fp64 tolerance row) serves all-sphere scenes of 1..24 spheres with fewer than 65 536 samples per pixel");
-            return RTM_ERR_UNSUPPORTED;
-        }
+        if (!(n >= 1 && n <= (size_t)kAutoLdsTableSpheres && view.plane == nullptr && P.sample_end < 65536u))
+            return unsupported("variant 18 (fp64 tolerance row) serves all-sphere scenes of 1..24 spheres with fewer than 65 536 samples per pixel");
         variant = kVariantFastLds;
     }
     if (view.plane != nullptr && variant != kVariantGrid) {
@@ -1965,10 +1899,8 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
         // grid kernel scenes that have a grid (planes are tested by every ray, next to the spheres that span the scene), the
         // per-object loop with the compiler's math (variant 1) any size; the other kernels know spheres only
         if (opt->variant != kVariantAuto && opt->variant != kVariantRef && opt->variant != kVariantFastLds &&
-            opt->variant != kVariantSplit) {
-            set_last_error("scenes that hold planes are rendered by variants 0 (auto), 1 (per-object loop), 2, 9 and 17");
-            return RTM_ERR_UNSUPPORTED;
-        }
+            opt->variant != kVariantSplit)
+            return unsupported("scenes that hold planes are rendered by variants 0 (auto), 1 (per-object loop), 2, 9 and 17");
         if (opt->variant == kVariantRef || n >= 256)
             variant = kVariantRef;
         else
@@ -1977,15 +1909,11 @@ static int plan_render(const rtm_settings* st, const SceneView& view, size_t n, 
     // beyond what their records / tables hold, the packed-record and the stamped kernels hand over to the global-table one
     if ((variant == kVariantStamped && n > (size_t)kLdsTableMaxSpheres) || (variant == kVariantGlobalDefer && n >= 256))
         variant = kVariantFastGlobal;
-    if (variant == kVariantFp32 && !(n >= 1 && n <= 256 && P.mode == RTM_MODE_REPAIRED)) {
-        set_last_error("variant 16 (fp32 fast row) serves repaired-mode scenes of 1..256 spheres");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (variant == kVariantFp32 && !(n >= 1 && n <= 256 && P.mode == RTM_MODE_REPAIRED))
+        return unsupported("variant 16 (fp32 fast row) serves repaired-mode scenes of 1..256 spheres");
     if (variant == kVariantPrimaryReuse &&
-        !(n >= 1 && n <= (size_t)kAutoLdsTableSpheres && P.max_bounces >= 0 && P.max_bounces <= 8)) {
-        set_last_error("variant 15 (primary-hit reuse) serves scenes of 1..24 spheres with 0 <= max_bounces <= 8");
-        return RTM_ERR_UNSUPPORTED;
-    }
+        !(n >= 1 && n <= (size_t)kAutoLdsTableSpheres && P.max_bounces >= 0 && P.max_bounces <= 8))
+        return unsupported("variant 15 (primary-hit reuse) serves scenes of 1..24 spheres with 0 <= max_bounces <= 8");
     // the sample split rides on the packed-record kernels (explicit variant 2 never splits)
     if (n < 256 && (opt->variant == kVariantAuto || plan.force_split || tol) &&
         (variant == kVariantFastLds || variant == kVariantGlobalDefer)) {
@@ -2093,10 +2021,7 @@ static int run_grid(RenderParams& P, unsigned tiles, StreamCtx& ctx, const Rende
     for (;;) {
         if (scratch_acquire(ctx, kScratchTerms, chunk * per_tile, &ws) == RTM_OK) break;
         (void)hipGetLastError();
-        if (chunk <= 64) {
-            set_last_error("no device memory for the grid kernel's term buffer");
-            return RTM_ERR_HIP;
-        }
+        if (chunk <= 64) return fail(RTM_ERR_HIP, "no device memory for the grid kernel's term buffer");
         chunk = (chunk + 1) / 2;
     }
     P.contrib = static_cast<unsigned char*>(ws);
@@ -2299,10 +2224,7 @@ static int render_view(const rtm_settings* st, const SceneView& view, size_t n, 
     // Intersect calls (src/Renderer.cpp:66) the render made: every object for every cast in the exhaustive kernels; counted
     // by the grid kernel when RTM_MODE_COUNT_TESTS asks for its counting instantiation (0: not counted)
     stats->object_tests = variant == kVariantGrid ? (plan.count_tests ? c[4] : 0ull) : c[0] * (uint64_t)n;
-    if (c[3]) {
-        set_last_error(kOverflowText);
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (c[3]) return unsupported(kOverflowText);
     return RTM_OK;
 }
 
@@ -2322,16 +2244,12 @@ static const void* grid_for(const rtm_scene* sc, const rtm_settings* st, const r
 // touching the device's memory.  out[0] total, out[1] per-sample terms (sample split / grid kernel), out[2] pooled hit
 // records, out[3] the exhaustive pipeline's path state, out[4] stolen samples' rows, out[5] the pre-pass's table.
 int scratch_bytes(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint64_t out[6]) {
-    if (!scene || !out) {
-        set_last_error("null argument");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!scene || !out) return invalid("null argument");
     int rc = validate(st, nullptr, 0, opt);
     if (rc != RTM_OK) return rc;
     RenderParams P;
     RenderPlan plan;
-    const SceneView view = scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
-                                      scene->has_planes ? scene->plane.as<double>() : nullptr, grid_for(scene, st, opt), scene->surf.as<double>(), scene->axis_pat, scene->fold_flags, scene->emit_mask);
+    const SceneView view = view_of(*scene, grid_for(scene, st, opt));
     for (int k = 0; k < 6; ++k) out[k] = 0;
     if (output_rows(opt) == 0) return RTM_OK;
     rc = plan_render(st, view, scene->n, opt, P, plan);
@@ -2348,22 +2266,15 @@ int scratch_bytes(const rtm_settings* st, const rtm_scene* scene, const rtm_opti
 // rtm_render_scene is the pass [0, N) of rtm_render_scene_samples: one path
 static int render_scene_pass(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const SamplePass& pass,
                              double* out64, float* out32, uint8_t* out8, void* stream_v, rtm_stats* stats) {
-    if (!scene) {
-        set_last_error("null scene");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!scene) return invalid("null scene");
     int rc = validate(st, nullptr, 0, opt);
     if (rc == RTM_OK && scene->n > 0x7FFFFFFFull) rc = RTM_ERR_UNSUPPORTED;
     if (rc != RTM_OK) return rc;
-    if (scene->device != opt->device) {
-        set_last_error("the scene lives on another device than rtm_options.device");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (scene->device != opt->device) return invalid("the scene lives on another device than rtm_options.device");
     std::shared_lock<std::shared_mutex> gate(g_gate);
     reap_scenes(false);
-    rc = render_view(st, scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
-                                    scene->has_planes ? scene->plane.as<double>() : nullptr, grid_for(scene, st, opt), scene->surf.as<double>(), scene->axis_pat, scene->fold_flags, scene->emit_mask),
-                     scene->n, opt, out64, out32, out8, (hipStream_t)stream_v, stats, pass);
+    rc = render_view(st, view_of(*scene, grid_for(scene, st, opt)), scene->n, opt, out64, out32, out8, (hipStream_t)stream_v, stats,
+                     pass);
     note_scene_use(scene, (hipStream_t)stream_v);  // also after a failure: part of the work may have been queued
     return rc;
 }
@@ -2379,30 +2290,18 @@ int render_scene(const rtm_settings* st, const rtm_scene* scene, const rtm_optio
 static int render_range(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, uint32_t sample_begin,
                         uint32_t sample_end, bool list, const uint32_t* tiles, uint32_t n_tiles, double* accum, float* out32,
                         uint8_t* out8, void* stream_v, rtm_stats* stats) {
-    if (!accum) {
-        set_last_error("accum_f64_dev: the pixel accumulator is null");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (sample_begin > sample_end) {
-        set_last_error("sample range [" + std::to_string(sample_begin) + ", " + std::to_string(sample_end) +
+    if (!accum) return invalid("accum_f64_dev: the pixel accumulator is null");
+    if (sample_begin > sample_end)
+        return invalid("sample range [" + std::to_string(sample_begin) + ", " + std::to_string(sample_end) +
                        "): sample_begin > sample_end");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (!st) {
-        set_last_error("null settings");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!st) return invalid("null settings");
     const uint64_t ss = st->super_samples > 0 ? (uint64_t)st->super_samples : 0u, s1 = st->samples > 0 ? (uint64_t)st->samples : 0u;
     const uint64_t total = ss * ss * s1;  // N (validate() rejects non-positive sizes below)
-    if (sample_end > total) {
-        set_last_error("sample range [" + std::to_string(sample_begin) + ", " + std::to_string(sample_end) +
+    if (sample_end > total)
+        return invalid("sample range [" + std::to_string(sample_begin) + ", " + std::to_string(sample_end) +
                        "): sample_end > N = superSamples^2 x samples = " + std::to_string(total));
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (list && tiles == nullptr && n_tiles != 0u) {
-        set_last_error("tiles_dev: the tile list is null and n_tiles = " + std::to_string(n_tiles));
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (list && tiles == nullptr && n_tiles != 0u)
+        return invalid("tiles_dev: the tile list is null and n_tiles = " + std::to_string(n_tiles));
     if (sample_begin == sample_end || (list && n_tiles == 0u)) {  // nothing to trace: nothing is enqueued
         if (stats) std::memset(stats, 0, sizeof *stats);
         return RTM_OK;
@@ -2422,77 +2321,76 @@ int render_scene_tiles(const rtm_settings* st, const rtm_scene* scene, const rtm
     return render_range(st, scene, opt, sample_begin, sample_end, true, tiles, n_tiles, accum, out32, out8, stream_v, stats);
 }
 
+// ---- rtm_render_aov and rtm_render_mattes: one launch over the first hits of the call's rows ---------------------------
+// validate() for a call that traces no paths: the depth cap does not apply
+static int validate_first_hit(const rtm_settings* st, const rtm_options* opt) {
+    rtm_options o = *opt;
+    o.max_bounces = -1;
+    return validate(st, nullptr, 0, &o);
+}
+
+// What both entries do once their own arguments have passed, in this order: the scene and its device are checked, the
+// variant picks the search (kAov*), and, where there is something to launch, the device is set, the (device, stream)
+// context is locked and P is planned.  rows == 0 afterwards: nothing to launch (RTM_OK).  The locks live as long as this.
+struct FirstHitCall {
+    std::shared_lock<std::shared_mutex> gate;
+    std::unique_lock<std::mutex> ctx_lock;
+    int search = kAovChunked, rows = 0;
+    unsigned tiles = 0;
+    RenderParams P;
+};
+static int begin_first_hit(const char* entry, const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, bool any_output,
+                           hipStream_t stream, FirstHitCall& C) {
+    if (!scene) return invalid("null scene");
+    if (scene->device != opt->device) return invalid("the scene lives on another device than rtm_options.device");
+    C.gate = std::shared_lock<std::shared_mutex>(g_gate);
+    reap_scenes(false);
+    const void* grid = grid_for(scene, st, opt);
+    if (opt->variant == kVariantAuto) {
+        C.search = grid != nullptr ? kAovGrid : kAovChunked;  // the grid exactly where a render would take it
+    } else if (opt->variant == kVariantRef) {
+        C.search = kAovGeneral;
+    } else if (opt->variant == kVariantGrid) {
+        if (grid == nullptr) return unsupported("variant 17 (uniform grid): this scene has no grid");
+        C.search = kAovGrid;
+    } else {
+        return unsupported(std::string(entry) + " serves variants 0, 1 and 17");
+    }
+    C.rows = any_output ? output_rows(opt) : 0;
+    if (C.rows == 0) return RTM_OK;
+    RTM_HIP_CHECK(hipSetDevice(opt->device));
+    C.ctx_lock = std::unique_lock<std::mutex>(get_ctx(opt->device, stream)->mu);
+    std::memset(&C.P, 0, sizeof C.P);
+    fill_render_params(C.P, st, opt, SamplePass{});
+    C.P.scene = view_of(*scene, grid);
+    C.tiles = (unsigned)C.P.tiles_x * (unsigned)((C.rows + 7) / 8);
+    return RTM_OK;
+}
+
 // rtm_render_aov: the first-hit feature buffers of the call's rows (rtm_aov_kernel.h).  Every argument is checked before
 // anything touches the device; then the call only enqueues one launch, serialised with the other calls on (device, stream).
 int render_aov(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, const rtm_aov_buffers* out,
                void* stream_v) {
-    if (!out) {
-        set_last_error("out_dev: the buffer set is null");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (!opt) {
-        set_last_error("null argument");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    rtm_options o = *opt;
-    o.max_bounces = -1;  // (no paths are traced: the depth cap does not apply)
-    int rc = validate(st, nullptr, 0, &o);
+    if (!out) return invalid("out_dev: the buffer set is null");
+    if (!opt) return invalid("null argument");
+    int rc = validate_first_hit(st, opt);
     if (rc != RTM_OK) return rc;
-    if (!scene) {
-        set_last_error("null scene");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (scene->device != opt->device) {
-        set_last_error("the scene lives on another device than rtm_options.device");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    std::shared_lock<std::shared_mutex> gate(g_gate);
-    reap_scenes(false);
-    const void* grid = grid_for(scene, st, opt);
-    int search;
-    if (opt->variant == kVariantAuto) {
-        search = grid != nullptr ? kAovGrid : kAovChunked;  // the grid exactly where a render would take it
-    } else if (opt->variant == kVariantRef) {
-        search = kAovGeneral;
-    } else if (opt->variant == kVariantGrid) {
-        if (grid == nullptr) {
-            set_last_error("variant 17 (uniform grid): this scene has no grid");
-            return RTM_ERR_UNSUPPORTED;
-        }
-        search = kAovGrid;
-    } else {
-        set_last_error("rtm_render_aov serves variants 0, 1 and 17");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const int rows = output_rows(opt);
-    if (rows == 0 || (!out->depth && !out->normal && !out->albedo && !out->object)) return RTM_OK;
-    RTM_HIP_CHECK(hipSetDevice(opt->device));
     const hipStream_t stream = (hipStream_t)stream_v;
-    StreamCtx& ctx = *get_ctx(opt->device, stream);
-    std::lock_guard<std::mutex> lock(ctx.mu);
-    RenderParams P;
-    std::memset(&P, 0, sizeof P);
-    fill_render_params(P, st, opt, SamplePass{});
-    P.scene = scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
-                         scene->has_planes ? scene->plane.as<double>() : nullptr, grid, scene->surf.as<double>(), scene->axis_pat,
-                         scene->fold_flags, scene->emit_mask);
-    const unsigned tiles = (unsigned)P.tiles_x * (unsigned)((rows + 7) / 8);
-    const size_t lds = aov_lds_bytes(search);
-    if (search == kAovGrid)
-        aov_kernel<kAovGrid, SceneGlobal><<<tiles, 64, lds, stream>>>(P, *out);
-    else if (search == kAovGeneral)
-        aov_kernel<kAovGeneral, SceneGlobal><<<tiles, 64, lds, stream>>>(P, *out);
+    FirstHitCall C;
+    rc = begin_first_hit("rtm_render_aov", st, scene, opt, out->depth || out->normal || out->albedo || out->object, stream, C);
+    if (rc != RTM_OK || C.rows == 0) return rc;
+    const size_t lds = aov_lds_bytes(C.search);
+    if (C.search == kAovGrid)
+        aov_kernel<kAovGrid, SceneGlobal><<<C.tiles, 64, lds, stream>>>(C.P, *out);
+    else if (C.search == kAovGeneral)
+        aov_kernel<kAovGeneral, SceneGlobal><<<C.tiles, 64, lds, stream>>>(C.P, *out);
     else if (scene->has_planes)
-        aov_kernel<kAovChunked, SceneGlobalObjects><<<tiles, 64, lds, stream>>>(P, *out);
+        aov_kernel<kAovChunked, SceneGlobalObjects><<<C.tiles, 64, lds, stream>>>(C.P, *out);
     else
-        aov_kernel<kAovChunked, SceneGlobal><<<tiles, 64, lds, stream>>>(P, *out);
-    const hipError_t e = hipGetLastError();
+        aov_kernel<kAovChunked, SceneGlobal><<<C.tiles, 64, lds, stream>>>(C.P, *out);
+    rc = launched("AOV");
     note_scene_use(scene, stream);
-    if (e != hipSuccess) {
-        set_last_error(std::string("AOV kernel launch: ") + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
+    return rc;
 }
 
 // rtm_render_mattes: the coverage AOVs of the call's rows.  render_aov's checks, variants and serialisation; what is the
@@ -2502,71 +2400,20 @@ static int launch_matte(const RenderParams& P, int search, bool planes, unsigned
                         const rtm_matte_buffers& out, hipStream_t stream);
 int render_mattes(const rtm_settings* st, const rtm_scene* scene, const rtm_options* opt, int32_t layers,
                   const rtm_matte_buffers* out, void* stream_v) {
-    if (!out) {
-        set_last_error("out_dev: the buffer set is null");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (!opt) {
-        set_last_error("null argument");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (layers < 1 || layers > 8) {
-        set_last_error("layers = " + std::to_string(layers) + ": outside 1..8");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (!out->id && !out->coverage && !out->alpha) {
-        set_last_error("out_dev: every plane is null");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    rtm_options o = *opt;
-    o.max_bounces = -1;  // (no paths are traced: the depth cap does not apply)
-    int rc = validate(st, nullptr, 0, &o);
+    if (!out) return invalid("out_dev: the buffer set is null");
+    if (!opt) return invalid("null argument");
+    if (layers < 1 || layers > 8) return invalid("layers = " + std::to_string(layers) + ": outside 1..8");
+    if (!out->id && !out->coverage && !out->alpha) return invalid("out_dev: every plane is null");
+    int rc = validate_first_hit(st, opt);
     if (rc != RTM_OK) return rc;
-    if (st->super_samples > 8) {
-        set_last_error("rtm_render_mattes serves superSamples up to 8 (the id lists of a block: 16 KiB of LDS)");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    if (!scene) {
-        set_last_error("null scene");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (scene->device != opt->device) {
-        set_last_error("the scene lives on another device than rtm_options.device");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    std::shared_lock<std::shared_mutex> gate(g_gate);
-    reap_scenes(false);
-    const void* grid = grid_for(scene, st, opt);
-    int search;
-    if (opt->variant == kVariantAuto) {
-        search = grid != nullptr ? kAovGrid : kAovChunked;  // the grid exactly where a render would take it
-    } else if (opt->variant == kVariantRef) {
-        search = kAovGeneral;
-    } else if (opt->variant == kVariantGrid) {
-        if (grid == nullptr) {
-            set_last_error("variant 17 (uniform grid): this scene has no grid");
-            return RTM_ERR_UNSUPPORTED;
-        }
-        search = kAovGrid;
-    } else {
-        set_last_error("rtm_render_mattes serves variants 0, 1 and 17");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const int rows = output_rows(opt);
-    if (rows == 0) return RTM_OK;
-    RTM_HIP_CHECK(hipSetDevice(opt->device));
+    if (st->super_samples > 8)
+        return unsupported("rtm_render_mattes serves superSamples up to 8 (the id lists of a block: 16 KiB of LDS)");
     const hipStream_t stream = (hipStream_t)stream_v;
-    StreamCtx& ctx = *get_ctx(opt->device, stream);
-    std::lock_guard<std::mutex> lock(ctx.mu);
-    RenderParams P;
-    std::memset(&P, 0, sizeof P);
-    fill_render_params(P, st, opt, SamplePass{});
-    P.scene = scene_view(scene->geom.as<double>(), scene->mat.as<double>(), scene->aux.as<double>(), scene->n,
-                         scene->has_planes ? scene->plane.as<double>() : nullptr, grid, scene->surf.as<double>(), scene->axis_pat,
-                         scene->fold_flags, scene->emit_mask);
-    const unsigned tiles = (unsigned)P.tiles_x * (unsigned)((rows + 7) / 8);
-    rc = launch_matte(P, search, scene->has_planes, tiles, aov_lds_bytes(search, st->super_samples), layers,
-                      (size_t)rows * (size_t)st->width, *out, stream);
+    FirstHitCall C;
+    rc = begin_first_hit("rtm_render_mattes", st, scene, opt, true, stream, C);
+    if (rc != RTM_OK || C.rows == 0) return rc;
+    rc = launch_matte(C.P, C.search, scene->has_planes, C.tiles, aov_lds_bytes(C.search, st->super_samples), layers,
+                      (size_t)C.rows * (size_t)st->width, *out, stream);
     note_scene_use(scene, stream);
     return rc;
 }
@@ -2583,8 +2430,7 @@ int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int on
         std::shared_ptr<rtm_scene> sc;
         rc = cached_scene(sp, n, opt->device, &sc);
         if (rc != RTM_OK) return rc;
-        rc = render_view(st, scene_view(sc->geom.as<double>(), sc->mat.as<double>(), sc->aux.as<double>(), n, nullptr, grid_for(sc.get(), st, opt), sc->surf.as<double>(), sc->axis_pat, sc->fold_flags, sc->emit_mask),
-                         n, opt, out64, out32, out8, stream, stats);
+        rc = render_view(st, view_of(*sc, grid_for(sc.get(), st, opt)), n, opt, out64, out32, out8, stream, stats);
         note_scene_use(sc.get(), stream);  // an eviction while this render is queued parks the tables instead of waiting
         return rc;
     }
@@ -2597,8 +2443,7 @@ int render_device(const rtm_settings* st, const rtm_sphere* sp, size_t n, int on
         std::shared_ptr<rtm_scene> sc;
         rc = cached_device_scene(sp, n, opt->device, stream, &sc);
         if (rc != RTM_OK) return rc;
-        rc = render_view(st, scene_view(sc->geom.as<double>(), sc->mat.as<double>(), sc->aux.as<double>(), n, nullptr, grid_for(sc.get(), st, opt), sc->surf.as<double>(), sc->axis_pat, sc->fold_flags, sc->emit_mask),
-                         n, opt, out64, out32, out8, stream, stats);
+        rc = render_view(st, view_of(*sc, grid_for(sc.get(), st, opt)), n, opt, out64, out32, out8, stream, stats);
         note_scene_use(sc.get(), stream);
         return rc;
     }
@@ -2685,14 +2530,9 @@ static SurfaceConsts surface_consts() {
 // rtm_surface_sample_batch: png::SurfaeSample (depth 0 entry) for a batch of rays; ray i draws from stream (seed, i, 0)
 int surface_sample_batch(const rtm_sphere* sp, size_t n, const rtm_options* opt, const double* org, const double* dir,
                          size_t n_rays, double* out, uint32_t* out_draws, uint32_t* out_casts) {
-    if (!opt || !sp || !n || !org || !dir || !out) {
-        set_last_error("null argument or empty scene");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if ((opt->mode & ~kModeFlags) != RTM_MODE_LITERAL && (opt->mode & ~kModeFlags) != RTM_MODE_REPAIRED) {
-        set_last_error("unknown mode");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!opt || !sp || !n || !org || !dir || !out) return invalid("null argument or empty scene");
+    if ((opt->mode & ~kModeFlags) != RTM_MODE_LITERAL && (opt->mode & ~kModeFlags) != RTM_MODE_REPAIRED)
+        return invalid("unknown mode");
     if (n_rays == 0) return RTM_OK;
     rtm_scene ds;
     int rc = scene_build_host(ds, sp, n, opt->device, false);
@@ -2729,28 +2569,18 @@ int surface_sample_batch(const rtm_sphere* sp, size_t n, const rtm_options* opt,
     RTM_HIP_CHECK(hipMemcpy(out, d_out.p, vb, hipMemcpyDeviceToHost));
     if (out_draws) RTM_HIP_CHECK(hipMemcpy(out_draws, d_draws.p, n_rays * 4, hipMemcpyDeviceToHost));
     if (out_casts) RTM_HIP_CHECK(hipMemcpy(out_casts, d_casts.p, n_rays * 4, hipMemcpyDeviceToHost));
-    if (c[3]) {
-        set_last_error("a SurfaeSample recursion ran deeper than SURF_MAX_DEPTH");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (c[3]) return unsupported("a SurfaeSample recursion ran deeper than SURF_MAX_DEPTH");
     return RTM_OK;
 }
 
 int path_trace_batch(const rtm_sphere* sp, size_t n, const rtm_options* opt, const double* org,
                      const double* dir, size_t n_rays, double* out, uint32_t* out_draws,
                      uint32_t* out_casts) {
-    if (!opt || (!sp && n) || !org || !dir || !out) {
-        set_last_error("null argument");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (opt->band_count < 0 || (opt->band_count > 1 && (opt->band_index < 0 || opt->band_index >= opt->band_count))) {
-        set_last_error("band_index outside [0, band_count)");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if ((opt->mode & ~kModeFlags) != RTM_MODE_LITERAL && (opt->mode & ~kModeFlags) != RTM_MODE_REPAIRED) {
-        set_last_error("unknown mode");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!opt || (!sp && n) || !org || !dir || !out) return invalid("null argument");
+    if (opt->band_count < 0 || (opt->band_count > 1 && (opt->band_index < 0 || opt->band_index >= opt->band_count)))
+        return invalid("band_index outside [0, band_count)");
+    if ((opt->mode & ~kModeFlags) != RTM_MODE_LITERAL && (opt->mode & ~kModeFlags) != RTM_MODE_REPAIRED)
+        return invalid("unknown mode");
     if (n_rays == 0) return RTM_OK;
     rtm_scene ds;
     int rc = scene_build_host(ds, sp, n, opt->device);
@@ -2815,19 +2645,13 @@ int path_trace_batch(const rtm_sphere* sp, size_t n, const rtm_options* opt, con
     RTM_HIP_CHECK(hipMemcpy(out, d_out.p, vb, hipMemcpyDeviceToHost));
     if (out_draws) RTM_HIP_CHECK(hipMemcpy(out_draws, d_draws.p, n_rays * 4, hipMemcpyDeviceToHost));
     if (out_casts) RTM_HIP_CHECK(hipMemcpy(out_casts, d_casts.p, n_rays * 4, hipMemcpyDeviceToHost));
-    if (c[3]) {
-        set_last_error("a path ran deeper than RAY_MAX_DEPTH");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (c[3]) return unsupported("a path ran deeper than RAY_MAX_DEPTH");
     return RTM_OK;
 }
 
 int intersect_batch(const rtm_sphere* sp, const double* org, const double* dir, size_t n, int mode,
                     int32_t* out_hit, double* out_t, double* out_normal) {
-    if (!sp || !org || !dir || !out_hit || !out_t || !out_normal) {
-        set_last_error("null argument");
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
+    if (!sp || !org || !dir || !out_hit || !out_t || !out_normal) return invalid("null argument");
     if (n == 0) return RTM_OK;
     int device = 0;
     RTM_HIP_CHECK(hipGetDevice(&device));
@@ -3016,11 +2840,9 @@ int grid_nearest_probe(const rtm_sphere* sp, size_t n, const double* org, const 
     rtm_scene ds;
     int rc = scene_build_host(ds, sp, n, device);
     if (rc != RTM_OK) return rc;
-    if (!ds.grid.p) {
-        set_last_error("this scene gets no grid (fewer than 64 gridded spheres, non-finite geometry, or too many spheres "
-                       "that span the scene)");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (!ds.grid.p)
+        return unsupported("this scene gets no grid (fewer than 64 gridded spheres, non-finite geometry, or too many spheres "
+                           "that span the scene)");
     if (info) {
         GridHeader H;
         RTM_HIP_CHECK(hipMemcpy(&H, ds.grid.p, sizeof H, hipMemcpyDeviceToHost));
@@ -3103,8 +2925,7 @@ int device_count(int* count) {
     hipError_t e = hipGetDeviceCount(&c);
     if (e != hipSuccess || c <= 0) {
         if (count) *count = 0;
-        set_last_error(std::string("no HIP device: ") + hipGetErrorString(e));
-        return RTM_ERR_NO_DEVICE;
+        return fail(RTM_ERR_NO_DEVICE, std::string("no HIP device: ") + hipGetErrorString(e));
     }
     if (count) *count = c;
     return RTM_OK;

@@ -8,31 +8,7 @@
 namespace rtm {
 
 namespace {
-int invalid(const char* what) {
-    set_last_error(what);
-    return RTM_ERR_INVALID_ARGUMENT;
-}
-
 bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
-
-int launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string(what) + " kernel launch: " + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
-}
-
-int set_device(int device) {
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        (void)hipGetLastError();
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
-}
 }  // namespace
 
 // rtm_render_mattes' launch for the planned P; search = kAov*, lds = aov_lds_bytes(search, P.SS).  The caller (render_mattes)
@@ -59,17 +35,11 @@ int matte_rank_probe(int32_t super_samples, int32_t layers, int device, const in
     if (misaligned4(ids) || misaligned4(id_out) || misaligned4(coverage_out) || misaligned4(alpha_out))
         return invalid("a buffer is not 4-byte aligned");
     if (device < 0) return invalid("negative device");
-    if (super_samples > kMatteMaxSS) {
-        set_last_error("the ranking serves superSamples up to 8 (the id lists of a block: 16 KiB of LDS)");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    if (n_pixels > 0x7FFFFFFFull) {
-        set_last_error("2^31 pixels or more");
-        return RTM_ERR_UNSUPPORTED;
-    }
+    if (super_samples > kMatteMaxSS)
+        return unsupported("the ranking serves superSamples up to 8 (the id lists of a block: 16 KiB of LDS)");
+    if (n_pixels > 0x7FFFFFFFull) return unsupported("2^31 pixels or more");
     if (n_pixels == 0) return RTM_OK;
-    const int rc = set_device(device);
-    if (rc != RTM_OK) return rc;
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     const rtm_matte_buffers out{id_out, coverage_out, alpha_out};
     matte_rank_kernel<<<(unsigned)((n_pixels + 63) / 64), 64, aov_lds_bytes(kAovChunked, super_samples), (hipStream_t)stream_v>>>(
         super_samples * super_samples, layers, ids, n_pixels, out);
@@ -89,12 +59,8 @@ int matte(int32_t width, int32_t height, int32_t layers, int device, const int32
         return invalid("matte_out_dev is one of the inputs");
     if (device < 0) return invalid("negative device");
     const size_t pix = (size_t)width * (size_t)height;
-    if (pix > 0x7FFFFFFFull) {
-        set_last_error("a frame of 2^31 pixels or more");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const int rc = set_device(device);
-    if (rc != RTM_OK) return rc;
+    if (pix > 0x7FFFFFFFull) return unsupported("a frame of 2^31 pixels or more");
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     matte_extract_kernel<<<(unsigned)((pix + 255) / 256), 256, 0, (hipStream_t)stream_v>>>(pix, layers, layer_id, layer_coverage, ids,
                                                                                          n_ids, matte_out);
     return launched("matte extract");
@@ -115,12 +81,8 @@ int composite(const rtm_composite_params* prm, int32_t width, int32_t height, in
     if ((const void*)out8 == (const void*)color) return invalid("out_u8_dev is color_dev");
     if (device < 0) return invalid("negative device");
     const size_t pix = (size_t)width * (size_t)height;
-    if (pix > 0x7FFFFFFFull) {
-        set_last_error("a frame of 2^31 pixels or more");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const int rc = set_device(device);
-    if (rc != RTM_OK) return rc;
+    if (pix > 0x7FFFFFFFull) return unsupported("a frame of 2^31 pixels or more");
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     composite_kernel<<<(unsigned)((pix + 255) / 256), 256, 0, (hipStream_t)stream_v>>>(
         pix, color, alpha, background, prm->background[0], prm->background[1], prm->background[2], out32, out8);
     return launched("composite");

@@ -6,7 +6,7 @@
 #include <cstdint>
 #include <string>
 
-#include "rtm_internal.h"
+#include "rtm_host.h"
 #include "rtm_tonemap_kernel.h"
 
 namespace rtm {
@@ -14,11 +14,6 @@ namespace rtm {
 namespace {
 constexpr size_t kTmAlign = 256;      // work_dev's alignment and the size of its last part
 constexpr size_t kTmPixelBytes = 12;  // the frame: three floats a pixel
-
-int invalid(const char* what) {
-    set_last_error(what);
-    return RTM_ERR_INVALID_ARGUMENT;
-}
 
 size_t tm_blocks(size_t pix) { return (pix + kTmBlockPixels - 1) / kTmBlockPixels; }
 size_t tm_partial_bytes(size_t pix) { return (tm_blocks(pix) * sizeof(TmPartial) + kTmAlign - 1) / kTmAlign * kTmAlign; }
@@ -65,7 +60,7 @@ int tonemap(const rtm_tonemap_params* prm, int32_t width, int32_t height, int de
     if (std::fabs(prm->ev) > 32.0f) return invalid("|ev| > 32");
     if (!(prm->key > 0.0f)) return invalid("key <= 0");
     if (prm->white < 0.0f) return invalid("white < 0");
-    if (((uintptr_t)work & (kTmAlign - 1)) != 0) return invalid("work_dev is not 256-byte aligned");
+    if (!aligned256(work)) return invalid("work_dev is not 256-byte aligned");
     if (work == (const void*)color || work == (void*)out32 || work == (void*)out8 || work == (void*)stats_out)
         return invalid("work_dev aliases another buffer");
     if (stats_out && ((const void*)stats_out == (const void*)color || (void*)stats_out == (void*)out32))
@@ -73,15 +68,9 @@ int tonemap(const rtm_tonemap_params* prm, int32_t width, int32_t height, int de
     if (device < 0) return invalid("negative device");
     const size_t pix = (size_t)width * (size_t)height;
     const size_t tiles_x = ((size_t)width + kTmTileX - 1) / kTmTileX, tiles = tiles_x * (((size_t)height + kTmTileY - 1) / kTmTileY);
-    if (pix > SIZE_MAX / kTmPixelBytes || tiles > 0x7FFFFFFFu / (kTmTileX * kTmTileY)) {
-        set_last_error("frame too large for one launch of the display transform");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
+    if (pix > SIZE_MAX / kTmPixelBytes || tiles > 0x7FFFFFFFu / (kTmTileX * kTmTileY))
+        return unsupported("frame too large for one launch of the display transform");
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     const hipStream_t stream = (hipStream_t)stream_v;
     const float e_scale = std::exp2(prm->ev);
     const bool reinhard_auto_white = prm->op == RTM_TONEMAP_REINHARD && prm->white == 0.0f;
@@ -101,12 +90,7 @@ int tonemap(const rtm_tonemap_params* prm, int32_t width, int32_t height, int de
     if (out32 || out8)
         tm_map_kernel(prm->op, prm->transfer, prm->dither)<<<(unsigned)tiles, kTmTileX * kTmTileY, 0, stream>>>(
             width, height, (int)tiles_x, color, fin, e_scale, prm->white, out32, out8);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("tonemap kernel launch: ") + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
+    return launched("tonemap");
 }
 
 }  // namespace rtm

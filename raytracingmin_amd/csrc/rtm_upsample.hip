@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <string>
 
-#include "rtm_internal.h"
+#include "rtm_host.h"
 #include "rtm_upsample_kernel.h"
 
 namespace rtm {
@@ -16,11 +16,6 @@ namespace {
 constexpr size_t kUpRecord = sizeof(float4);  // 16 B
 constexpr size_t kUpPlanes = 2;               // (e, object bits) and (n, z) per low pixel
 constexpr size_t kUpFullPixelBytes = 12 * (size_t)kUpMaxFactor * kUpMaxFactor;  // the full frame at f = 8, per low pixel
-
-int invalid(const char* what) {
-    set_last_error(what);
-    return RTM_ERR_INVALID_ARGUMENT;
-}
 
 using UpKernel = void (*)(UpsampleFrame, const float4*, const float4*, const float*, const float*, const float*, const int32_t*,
                           float*, uint8_t*);
@@ -73,15 +68,9 @@ int upsample(const rtm_upsample_params* prm, int32_t low_width, int32_t low_heig
     const int64_t W = (int64_t)f * low_width, H = (int64_t)f * low_height;
     const size_t pix = (size_t)low_width * (size_t)low_height;
     const size_t tiles_x = ((size_t)W + kUpTileX - 1) / kUpTileX, tiles = tiles_x * (((size_t)H + kUpTileY - 1) / kUpTileY);
-    if (W > INT32_MAX || H > INT32_MAX || pix > SIZE_MAX / kUpFullPixelBytes || tiles > 0x7FFFFFFFu / (kUpTileX * kUpTileY)) {
-        set_last_error("frame too large for one launch of the upsampler");
-        return RTM_ERR_UNSUPPORTED;
-    }
-    const hipError_t se = hipSetDevice(device);
-    if (se != hipSuccess) {
-        set_last_error(std::string("hipSetDevice: ") + hipGetErrorString(se));
-        return RTM_ERR_HIP;
-    }
+    if (W > INT32_MAX || H > INT32_MAX || pix > SIZE_MAX / kUpFullPixelBytes || tiles > 0x7FFFFFFFu / (kUpTileX * kUpTileY))
+        return unsupported("frame too large for one launch of the upsampler");
+    if (const int rc = use_device(device); rc != RTM_OK) return rc;
     const hipStream_t stream = (hipStream_t)stream_v;
     UpsampleFrame U;
     U.w = low_width;
@@ -108,12 +97,7 @@ int upsample(const rtm_upsample_params* prm, int32_t low_width, int32_t low_heig
     upsample_pack_kernel<<<low_tiles, block, 0, stream>>>(U, color_low, lo.depth, lo.normal, lo.albedo, lo.object, rec_e, rec_g);
     U.tiles_x = (int)tiles_x;
     up_kernel(f)<<<(unsigned)tiles, block, 0, stream>>>(U, rec_e, rec_g, hi.depth, hi.normal, hi.albedo, hi.object, out32, out8);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error(std::string("upsample kernel launch: ") + hipGetErrorString(e));
-        return RTM_ERR_HIP;
-    }
-    return RTM_OK;
+    return launched("upsample");
 }
 
 }  // namespace rtm

@@ -149,8 +149,7 @@ class Renderer:
         band=(count, index) renders only every count-th 8-row band of the range, stored back to back
         (include/rtm.h, rtm_options.band_count)."""
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        _need_device("Renderer")
         row_end = self.data.height if row_end is None else row_end
         opt = self._options(row_begin, row_end, band)
         rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
@@ -183,8 +182,7 @@ class Renderer:
         holds.  Returns (dict, stats): "f64" is `accum` itself; "f32" / "u8" are the frame's views after the last pass and
         a preview (accum x N / sample_end) before it."""
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        _need_device("Renderer")
         row_end = self.data.height if row_end is None else row_end
         opt = self._options(row_begin, row_end, band)
         rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
@@ -234,8 +232,7 @@ class Renderer:
         indices): their pixels get the pass's accumulator and f32 / u8 views; every other pixel of `accum` and of the
         tensors in `out` (reused when given, so that unlisted tiles keep what they held) is neither read nor written."""
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        _need_device("Renderer")
         row_end = self.data.height if row_end is None else row_end
         opt = self._options(row_begin, row_end, band)
         rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
@@ -268,8 +265,7 @@ class Renderer:
         render_samples_device's ("f64" is the accumulator), tile_samples a (tiles_y, tiles_x) int64 CUDA tensor of the
         samples each tile traced.  Tile t equals rtm_render_scene_samples [0, tile_samples[t]) bit for bit.  Blocks."""
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        _need_device("Renderer")
         row_end = self.data.height if row_end is None else row_end
         opt = self._options(row_begin, row_end, band)
         L = _lib.lib()
@@ -310,18 +306,13 @@ class Renderer:
         "albedo" (rows, W, 3) float32, "object" (rows, W) int32 (include/rtm.h: rtm_render_aov).  Only the planes named in
         `want` are allocated and computed.  Enqueued on `stream` (default: the current stream); nothing waits for it."""
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
-        unknown = set(want) - set(self.AOV_PLANES)
-        if unknown:
-            raise ValueError(f"unknown AOV plane(s) {sorted(unknown)}; the planes are {self.AOV_PLANES}")
+        _need_device("Renderer")
+        _check_planes(want)
         row_end = self.data.height if row_end is None else row_end
         opt = self._options(row_begin, row_end, band)
         rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
         dev = torch.device("cuda", self.device)
-        shapes = {"depth": ((rows, W), torch.float32), "normal": ((rows, W, 3), torch.float32),
-                  "albedo": ((rows, W, 3), torch.float32), "object": ((rows, W), torch.int32)}
-        out = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in self.AOV_PLANES if k in want}
+        out = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in _aov_layout(rows, W).items() if k in want}
         bufs = _lib.rtm_aov_buffers()
         for k, v in out.items():
             setattr(bufs, k, v.data_ptr() if rows > 0 else None)
@@ -366,8 +357,7 @@ class Renderer:
         if unknown or not want:
             raise ValueError(f"want names planes among {self.MATTE_PLANES}, got {tuple(want)}")
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        _need_device("Renderer")
         row_end = self.data.height if row_end is None else row_end
         opt = self._options(row_begin, row_end, band)
         rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
@@ -439,28 +429,18 @@ class Renderer:
         if W % f or H % f:
             raise ValueError(f"factor {f} does not divide the {W}x{H} frame")
         import torch
-        if not torch.cuda.is_available():
-            raise RuntimeError("Renderer needs a HIP device; there is no CPU fallback")
+        _need_device("Renderer")
         dev = torch.device("cuda", self.device)
-        if stream is None:
-            s = torch.cuda.current_stream(dev)
-        elif isinstance(stream, torch.cuda.Stream):
-            s = stream
-        else:
-            s = torch.cuda.ExternalStream(int(stream), device=dev)
+        s = _stream_of(stream, dev)
         w, h = W // f, H // f
         st = self.data.settings_c()
         st.width, st.height = w, h
         opt = self._options(0, h)
         L = _lib.lib()
-        shapes = {"depth": ((h, w), torch.float32), "normal": ((h, w, 3), torch.float32),
-                  "albedo": ((h, w, 3), torch.float32), "object": ((h, w), torch.int32)}
         with torch.cuda.stream(s):  # allocated on the stream that uses them; render_aov and the filters take the current stream
             color = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-            aov_low = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in shapes.items()}
-            bufs = _lib.rtm_aov_buffers()
-            for k, v in aov_low.items():
-                setattr(bufs, k, v.data_ptr())
+            aov_low = {k: torch.empty(shape, dtype=dt, device=dev) for k, (shape, dt) in _aov_layout(h, w).items()}
+            bufs = _aov_buffers(aov_low, h, w, dev, "aov[{k!r}]")
             hip_stream = C.c_void_p(s.cuda_stream)
             _lib.check(L.rtm_render_scene(C.byref(st), self._scene_handle(), C.byref(opt), None, C.c_void_p(color.data_ptr()),
                                           None, hip_stream, None), "rtm_render_scene")
@@ -663,6 +643,111 @@ class Renderer:
         return out["f32"] if _keep else rgb8
 
 
+# ---- what the stage wrappers below do alike: one helper per step ----------------------------------
+def _need_device(who):
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{who} needs a HIP device; there is no CPU fallback")
+
+
+def _check_want(want, outputs):
+    unknown = set(want) - set(outputs)
+    if unknown or not want:
+        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+
+
+def _stream_of(stream, dev):
+    """A torch stream for `stream`: a torch.cuda.Stream, a raw hipStream_t handle, or None for the current stream of `dev`."""
+    import torch
+    if stream is None:
+        return torch.cuda.current_stream(dev)
+    return stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
+
+
+def _frame_size(color, name, dims="(H, W, 3)", non_empty=False):
+    """(H, W) of `color`, which must be a contiguous (H, W, 3) float32 CUDA tensor; the ValueError names it as the caller does."""
+    import torch
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
+            and color.shape[2] == 3 and color.is_contiguous() and (color.numel() > 0 or not non_empty)):
+        raise ValueError(f"{name} must be a contiguous{', non-empty' if non_empty else ''} {dims} float32 CUDA tensor")
+    return int(color.shape[0]), int(color.shape[1])
+
+
+def _aov_layout(rows, cols):
+    """Renderer.render_aov's planes at rows x cols: name -> (shape, dtype), in Renderer.AOV_PLANES' order."""
+    import torch
+    return {"depth": ((rows, cols), torch.float32), "normal": ((rows, cols, 3), torch.float32),
+            "albedo": ((rows, cols, 3), torch.float32), "object": ((rows, cols), torch.int32)}
+
+
+def _check_planes(names):
+    unknown = set(names) - set(Renderer.AOV_PLANES)
+    if unknown:
+        raise ValueError(f"unknown AOV plane(s) {sorted(unknown)}; the planes are {Renderer.AOV_PLANES}")
+
+
+def _aov_buffers(aov, rows, cols, dev, label):
+    """An rtm_aov_buffers of the dict's planes (a None entry: no plane), each a contiguous tensor of _aov_layout(rows, cols)
+    on `dev`.  `label` names plane k in the ValueError: a format string over k, rows and cols."""
+    import torch
+    layout = _aov_layout(rows, cols)
+    bufs = _lib.rtm_aov_buffers()
+    for k, v in aov.items():
+        if v is None:
+            continue
+        shape, dtype = layout[k]
+        if not (isinstance(v, torch.Tensor) and v.device == dev and v.dtype == dtype and tuple(v.shape) == shape
+                and v.is_contiguous()):
+            raise ValueError(f"{label.format(k=k, rows=rows, cols=cols)} must be a contiguous {shape} {dtype} tensor on {dev}")
+        setattr(bufs, k, v.data_ptr())
+    return bufs
+
+
+def _stage_tensors(s, dev, want, outputs, work_bytes=0, out_f32=None):
+    """The work buffer of `work_bytes` (0: none) and, of `outputs` (name -> (shape, dtype)), the tensors named in `want`,
+    allocated under stream `s`, the stream that uses them: the caching allocator then orders any reuse.  out_f32: the
+    caller's tensor for "f32".  Returns (out, ptr): the outputs' dict, and ptr(name) -> data pointer or None, which also
+    knows "work"."""
+    import torch
+    with torch.cuda.stream(s):
+        held = {"work": torch.empty(work_bytes, dtype=torch.uint8, device=dev) if work_bytes else None}
+        out = {k: out_f32 if k == "f32" and out_f32 is not None else torch.empty(shape, dtype=dt, device=dev)
+               for k, (shape, dt) in outputs.items() if k in want}
+    held.update(out)
+    return out, lambda k: held[k].data_ptr() if held.get(k) is not None else None
+
+
+def _check_out_f32(out_f32, want, H, W, dev):
+    import torch
+    if out_f32 is None:
+        return
+    if "f32" not in want:
+        raise ValueError('out_f32 is given but "f32" is not in want')
+    if not (isinstance(out_f32, torch.Tensor) and out_f32.device == dev and out_f32.dtype == torch.float32
+            and tuple(out_f32.shape) == (H, W, 3) and out_f32.is_contiguous()):
+        raise ValueError(f"out_f32 must be a contiguous ({H}, {W}, 3) float32 tensor on {dev}")
+
+
+def _pair_shape(a, b):
+    """compare() and flip(): a and b are (H, W, 3) frames of one shape (any array type: no device use)."""
+    shape_a, shape_b = tuple(getattr(a, "shape", ())), tuple(getattr(b, "shape", ()))
+    if len(shape_a) != 3 or shape_a[2] != 3 or shape_a[0] < 1 or shape_a[1] < 1:
+        raise ValueError(f"a must be an (H, W, 3) frame, got shape {shape_a}")
+    if shape_a != shape_b:
+        raise ValueError(f"a and b must have the same shape, got {shape_a} and {shape_b}")
+
+
+def _pair_device(a, b):
+    """compare() and flip(): a and b are contiguous CUDA tensors on one device; returns (H, W, device)."""
+    import torch
+    for name, v in (("a", a), ("b", b)):
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous CUDA tensor")
+    if a.device != b.device:
+        raise ValueError(f"a and b must be on one device, got {a.device} and {b.device}")
+    return int(a.shape[0]), int(a.shape[1]), a.device
+
+
 # include/rtm.h: RTM_DENOISE_DEFAULTS
 DENOISE_DEFAULTS = {"iterations": 4, "sigma_color": 16.0, "sigma_normal": 64.0, "sigma_depth": 0.05}
 
@@ -698,50 +783,19 @@ def denoise_variance(color, aov=None, iterations=DENOISE_VAR_DEFAULTS["iteration
 def _denoise_call(entry, prm, color, aov, want, outputs, stream):
     """denoise() and denoise_variance(): the checks of the tensors, the work buffer and outputs, and the library call."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("denoise needs a HIP device; there is no CPU fallback")
-    unknown = set(want) - set(outputs)
-    if unknown or not want:
-        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
-    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
-            and color.shape[2] == 3 and color.is_contiguous()):
-        raise ValueError("color must be a contiguous (H, W, 3) float32 CUDA tensor")
-    H, W = int(color.shape[0]), int(color.shape[1])
+    _need_device("denoise")
+    _check_want(want, outputs)
+    H, W = _frame_size(color, "color")
     dev = color.device
     aov = {} if aov is None else aov
-    layout = {"depth": ((H, W), torch.float32), "normal": ((H, W, 3), torch.float32),
-              "albedo": ((H, W, 3), torch.float32), "object": ((H, W), torch.int32)}
-    unknown = set(aov) - set(layout)
-    if unknown:
-        raise ValueError(f"unknown AOV plane(s) {sorted(unknown)}; the planes are {tuple(layout)}")
-    guides = _lib.rtm_aov_buffers()
-    for k, v in aov.items():
-        shape, dtype = layout[k]
-        if v is None:
-            continue
-        if not (isinstance(v, torch.Tensor) and v.device == dev and v.dtype == dtype and tuple(v.shape) == shape
-                and v.is_contiguous()):
-            raise ValueError(f"aov[{k!r}] must be a contiguous {shape} {dtype} tensor on {dev}")
-        setattr(guides, k, v.data_ptr())
-    if stream is None:
-        s = torch.cuda.current_stream(dev)
-    elif isinstance(stream, torch.cuda.Stream):
-        s = stream
-    else:
-        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    _check_planes(aov)
+    guides = _aov_buffers(aov, H, W, dev, "aov[{k!r}]")
+    s = _stream_of(stream, dev)
     L = _lib.lib()
-    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
-        work = torch.empty(max(1, getattr(L, entry + "_work_bytes")(W, H)), dtype=torch.uint8, device=dev)
-        out = {}
-        if "f32" in want:
-            out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-        if "u8" in want:
-            out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-        if "var" in want:
-            out["var"] = torch.empty((H, W), dtype=torch.float32, device=dev)
-    ptr = lambda k: out[k].data_ptr() if k in out else None
+    specs = {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8), "var": ((H, W), torch.float32)}
+    out, ptr = _stage_tensors(s, dev, want, specs, max(1, getattr(L, entry + "_work_bytes")(W, H)))
     tail = (ptr("var"),) if "var" in outputs else ()
-    _lib.check(getattr(L, entry)(C.byref(prm), W, H, dev.index, color.data_ptr(), C.byref(guides), work.data_ptr(),
+    _lib.check(getattr(L, entry)(C.byref(prm), W, H, dev.index, color.data_ptr(), C.byref(guides), ptr("work"),
                                  ptr("f32"), ptr("u8"), *tail, C.c_void_p(s.cuda_stream)), entry)
     return out
 
@@ -759,57 +813,27 @@ def upsample(color_low, aov_low=None, aov_high=None, factor=UPSAMPLE_DEFAULTS["f
     "u8": (H, W, 3) uint8} for the names in `want`.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle;
     default: the current stream) with a work buffer allocated here; nothing waits for it."""
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("upsample needs a HIP device; there is no CPU fallback")
-    outputs = ("f32", "u8")
-    unknown = set(want) - set(outputs)
-    if unknown or not want:
-        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
-    if not (isinstance(color_low, torch.Tensor) and color_low.is_cuda and color_low.dtype == torch.float32
-            and color_low.dim() == 3 and color_low.shape[2] == 3 and color_low.is_contiguous()):
-        raise ValueError("color_low must be a contiguous (h, w, 3) float32 CUDA tensor")
+    _need_device("upsample")
+    _check_want(want, ("f32", "u8"))
+    h, w = _frame_size(color_low, "color_low", "(h, w, 3)")
     f = int(factor)
-    h, w = int(color_low.shape[0]), int(color_low.shape[1])
     H, W = f * h, f * w
     dev = color_low.device
     aov_low = {k: v for k, v in (aov_low or {}).items() if v is not None}
     aov_high = {k: v for k, v in (aov_high or {}).items() if v is not None}
-    planes = ("depth", "normal", "albedo", "object")
-    unknown = (set(aov_low) | set(aov_high)) - set(planes)
-    if unknown:
-        raise ValueError(f"unknown AOV plane(s) {sorted(unknown)}; the planes are {planes}")
+    _check_planes(set(aov_low) | set(aov_high))
     if set(aov_low) != set(aov_high):
         raise ValueError(f"plane(s) {sorted(set(aov_low) ^ set(aov_high))} are given at one resolution only")
-    guides = []
-    for aov, (rows, cols) in ((aov_low, (h, w)), (aov_high, (H, W))):
-        layout = {"depth": ((rows, cols), torch.float32), "normal": ((rows, cols, 3), torch.float32),
-                  "albedo": ((rows, cols, 3), torch.float32), "object": ((rows, cols), torch.int32)}
-        g = _lib.rtm_aov_buffers()
-        for k, v in aov.items():
-            shape, dtype = layout[k]
-            if not (isinstance(v, torch.Tensor) and v.device == dev and v.dtype == dtype and tuple(v.shape) == shape
-                    and v.is_contiguous()):
-                raise ValueError(f"the {rows}x{cols} plane {k!r} must be a contiguous {shape} {dtype} tensor on {dev}")
-            setattr(g, k, v.data_ptr())
-        guides.append(g)
-    if stream is None:
-        s = torch.cuda.current_stream(dev)
-    elif isinstance(stream, torch.cuda.Stream):
-        s = stream
-    else:
-        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    guides = [_aov_buffers(aov, rows, cols, dev, "the {rows}x{cols} plane {k!r}")
+              for aov, (rows, cols) in ((aov_low, (h, w)), (aov_high, (H, W)))]
+    s = _stream_of(stream, dev)
     L = _lib.lib()
     prm = _lib.rtm_upsample_params(f, float(sigma_spatial), float(sigma_normal), float(sigma_depth))
-    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
-        work = torch.empty(max(16, L.rtm_upsample_work_bytes(w, h)), dtype=torch.uint8, device=dev)
-        out = {}
-        if "f32" in want:
-            out["f32"] = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.float32, device=dev)
-        if "u8" in want:
-            out["u8"] = torch.empty((max(H, 0), max(W, 0), 3), dtype=torch.uint8, device=dev)
-    ptr = lambda k: out[k].data_ptr() if k in out else None
+    full = (max(H, 0), max(W, 0), 3)
+    out, ptr = _stage_tensors(s, dev, want, {"f32": (full, torch.float32), "u8": (full, torch.uint8)},
+                              max(16, L.rtm_upsample_work_bytes(w, h)))
     _lib.check(L.rtm_upsample(C.byref(prm), w, h, dev.index, color_low.data_ptr(), C.byref(guides[0]), C.byref(guides[1]),
-                              work.data_ptr(), ptr("f32"), ptr("u8"), C.c_void_p(s.cuda_stream)), "rtm_upsample")
+                              ptr("work"), ptr("f32"), ptr("u8"), C.c_void_p(s.cuda_stream)), "rtm_upsample")
     return out
 
 
@@ -864,13 +888,6 @@ def _matte_args(layers=MATTE_DEFAULTS["layers"], ids=None, background=None, fram
             None if background is None else _matte_background(background, frame_shape))
 
 
-def _stream_of(stream, dev):
-    import torch
-    if stream is None:
-        return torch.cuda.current_stream(dev)
-    return stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=dev)
-
-
 def matte(layer_id, layer_coverage, ids, stream=None):
     """The antialiased matte of a set of objects (include/rtm.h: rtm_matte) on the device.  layer_id (L, H, W) int32 and
     layer_coverage (L, H, W) float32 are Renderer.render_mattes' "id" and "coverage" of a whole frame, L in 1..8; ids a list
@@ -911,15 +928,9 @@ def composite(color, alpha, background=(0, 0, 0), want=("f32",), stream=None, ou
     tensor to write "f32" into; `color` itself composites in place.  Enqueued on `stream` (a torch.cuda.Stream or a raw
     hipStream_t handle; default: the current stream); nothing waits for it."""
     background = _matte_background(background)
-    outputs = ("f32", "u8")
-    unknown = set(want) - set(outputs)
-    if unknown or not want:
-        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+    _check_want(want, ("f32", "u8"))
     import torch
-    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
-            and color.shape[2] == 3 and color.is_contiguous() and color.numel() > 0):
-        raise ValueError("color must be a contiguous, non-empty (H, W, 3) float32 CUDA tensor")
-    H, W = int(color.shape[0]), int(color.shape[1])
+    H, W = _frame_size(color, "color", non_empty=True)
     dev = color.device
     if not (isinstance(alpha, torch.Tensor) and alpha.device == dev and alpha.dtype == torch.float32
             and tuple(alpha.shape) == (H, W) and alpha.is_contiguous()):
@@ -927,21 +938,10 @@ def composite(color, alpha, background=(0, 0, 0), want=("f32",), stream=None, ou
     image = isinstance(background, torch.Tensor)
     if image and not (background.device == dev and tuple(background.shape) == (H, W, 3)):
         raise ValueError(f"a background image must be ({H}, {W}, 3) on {dev}")
-    if out_f32 is not None:
-        if "f32" not in want:
-            raise ValueError('out_f32 is given but "f32" is not in want')
-        if not (isinstance(out_f32, torch.Tensor) and out_f32.device == dev and out_f32.dtype == torch.float32
-                and tuple(out_f32.shape) == (H, W, 3) and out_f32.is_contiguous()):
-            raise ValueError(f"out_f32 must be a contiguous ({H}, {W}, 3) float32 tensor on {dev}")
+    _check_out_f32(out_f32, want, H, W, dev)
     s = _stream_of(stream, dev)
-    with torch.cuda.stream(s):
-        out = {}
-        if "f32" in want:
-            out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if out_f32 is None else out_f32
-        if "u8" in want:
-            out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+    out, ptr = _stage_tensors(s, dev, want, {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8)}, out_f32=out_f32)
     prm = _lib.rtm_composite_params((C.c_float * 3)(*((0.0, 0.0, 0.0) if image else background)))
-    ptr = lambda k: out[k].data_ptr() if k in out else None
     _lib.check(_lib.lib().rtm_composite(C.byref(prm), W, H, dev.index, color.data_ptr(), alpha.data_ptr(),
                                         background.data_ptr() if image else None, ptr("f32"), ptr("u8"),
                                         C.c_void_p(s.cuda_stream)), "rtm_composite")
@@ -988,42 +988,17 @@ def tonemap(color, op=TONEMAP_DEFAULTS["op"], transfer=TONEMAP_DEFAULTS["transfe
     Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream) with a work buffer
     allocated here; nothing waits for it and nothing is copied to the host."""
     prm = _tonemap_params(op, transfer, exposure, key, white, dither)
-    outputs = ("f32", "u8", "stats")
-    unknown = set(want) - set(outputs)
-    if unknown or not want:
-        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
+    _check_want(want, ("f32", "u8", "stats"))
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("tonemap needs a HIP device; there is no CPU fallback")
-    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.dim() == 3
-            and color.shape[2] == 3 and color.is_contiguous()):
-        raise ValueError("color must be a contiguous (H, W, 3) float32 CUDA tensor")
-    H, W = int(color.shape[0]), int(color.shape[1])
+    _need_device("tonemap")
+    H, W = _frame_size(color, "color")
     dev = color.device
-    if out_f32 is not None:
-        if "f32" not in want:
-            raise ValueError('out_f32 is given but "f32" is not in want')
-        if not (isinstance(out_f32, torch.Tensor) and out_f32.device == dev and out_f32.dtype == torch.float32
-                and tuple(out_f32.shape) == (H, W, 3) and out_f32.is_contiguous()):
-            raise ValueError(f"out_f32 must be a contiguous ({H}, {W}, 3) float32 tensor on {dev}")
-    if stream is None:
-        s = torch.cuda.current_stream(dev)
-    elif isinstance(stream, torch.cuda.Stream):
-        s = stream
-    else:
-        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    _check_out_f32(out_f32, want, H, W, dev)
+    s = _stream_of(stream, dev)
     L = _lib.lib()
-    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
-        work = torch.empty(max(256, L.rtm_tonemap_work_bytes(W, H)), dtype=torch.uint8, device=dev)
-        out = {}
-        if "f32" in want:
-            out["f32"] = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if out_f32 is None else out_f32
-        if "u8" in want:
-            out["u8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
-        if "stats" in want:
-            out["stats"] = torch.empty(4, dtype=torch.int32, device=dev)
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    _lib.check(L.rtm_tonemap(C.byref(prm), W, H, dev.index, color.data_ptr(), work.data_ptr(), ptr("f32"), ptr("u8"),
+    specs = {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8), "stats": (4, torch.int32)}
+    out, ptr = _stage_tensors(s, dev, want, specs, max(256, L.rtm_tonemap_work_bytes(W, H)), out_f32=out_f32)
+    _lib.check(L.rtm_tonemap(C.byref(prm), W, H, dev.index, color.data_ptr(), ptr("work"), ptr("f32"), ptr("u8"),
                              ptr("stats"), C.c_void_p(s.cuda_stream)), "rtm_tonemap")
     return out
 
@@ -1065,15 +1040,8 @@ def compare(a, b, tolerance=COMPARE_DEFAULTS["tolerance"], peak=COMPARE_DEFAULTS
     rtm_compare_result (compare_result() reads it on the host), "map" an (H, W) float32 tensor.  A shape or dtype mismatch
     raises before the library is called.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the
     current stream) with a work buffer allocated here; nothing waits for it and nothing is copied to the host."""
-    outputs = ("result", "map")
-    unknown = set(want) - set(outputs)
-    if unknown or not want:
-        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
-    shape_a, shape_b = tuple(getattr(a, "shape", ())), tuple(getattr(b, "shape", ()))
-    if len(shape_a) != 3 or shape_a[2] != 3 or shape_a[0] < 1 or shape_a[1] < 1:
-        raise ValueError(f"a must be an (H, W, 3) frame, got shape {shape_a}")
-    if shape_a != shape_b:
-        raise ValueError(f"a and b must have the same shape, got {shape_a} and {shape_b}")
+    _check_want(want, ("result", "map"))
+    _pair_shape(a, b)
     dtype_a, dtype_b = str(a.dtype).split(".")[-1], str(b.dtype).split(".")[-1]
     if dtype_a != dtype_b:
         raise ValueError(f"a and b must have the same dtype, got {dtype_a} and {dtype_b}")
@@ -1081,31 +1049,13 @@ def compare(a, b, tolerance=COMPARE_DEFAULTS["tolerance"], peak=COMPARE_DEFAULTS
         raise ValueError(f"frames are float32 or float64, got {dtype_a}")
     prm = _compare_params(dtype_a, tolerance, peak, rel_epsilon, map)
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("compare needs a HIP device; there is no CPU fallback")
-    for name, v in (("a", a), ("b", b)):
-        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous CUDA tensor")
-    if a.device != b.device:
-        raise ValueError(f"a and b must be on one device, got {a.device} and {b.device}")
-    H, W = int(a.shape[0]), int(a.shape[1])
-    dev = a.device
-    if stream is None:
-        s = torch.cuda.current_stream(dev)
-    elif isinstance(stream, torch.cuda.Stream):
-        s = stream
-    else:
-        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    _need_device("compare")
+    H, W, dev = _pair_device(a, b)
+    s = _stream_of(stream, dev)
     L = _lib.lib()
-    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
-        work = torch.empty(max(256, L.rtm_compare_work_bytes(W, H)), dtype=torch.uint8, device=dev)
-        out = {}
-        if "result" in want:
-            out["result"] = torch.empty(C.sizeof(_lib.rtm_compare_result) // 4, dtype=torch.int32, device=dev)
-        if "map" in want:
-            out["map"] = torch.empty((H, W), dtype=torch.float32, device=dev)
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    _lib.check(L.rtm_compare(C.byref(prm), W, H, dev.index, a.data_ptr(), b.data_ptr(), work.data_ptr(), ptr("result"),
+    specs = {"result": (C.sizeof(_lib.rtm_compare_result) // 4, torch.int32), "map": ((H, W), torch.float32)}
+    out, ptr = _stage_tensors(s, dev, want, specs, max(256, L.rtm_compare_work_bytes(W, H)))
+    _lib.check(L.rtm_compare(C.byref(prm), W, H, dev.index, a.data_ptr(), b.data_ptr(), ptr("work"), ptr("result"),
                              ptr("map"), C.c_void_p(s.cuda_stream)), "rtm_compare")
     return out
 
@@ -1143,45 +1093,20 @@ def flip(a, b, transfer=FLIP_DEFAULTS["transfer"], pixels_per_degree=FLIP_DEFAUL
     component.  A shape or dtype mismatch raises before the library is called.  Enqueued on `stream` (a torch.cuda.Stream or
     a raw hipStream_t handle; default: the current stream) with a work buffer allocated here (112 bytes a pixel); nothing
     waits for it and nothing is copied to the host."""
-    outputs = ("result", "map")
-    unknown = set(want) - set(outputs)
-    if unknown or not want:
-        raise ValueError(f"want names outputs among {outputs}, got {tuple(want)}")
-    shape_a, shape_b = tuple(getattr(a, "shape", ())), tuple(getattr(b, "shape", ()))
-    if len(shape_a) != 3 or shape_a[2] != 3 or shape_a[0] < 1 or shape_a[1] < 1:
-        raise ValueError(f"a must be an (H, W, 3) frame, got shape {shape_a}")
-    if shape_a != shape_b:
-        raise ValueError(f"a and b must have the same shape, got {shape_a} and {shape_b}")
+    _check_want(want, ("result", "map"))
+    _pair_shape(a, b)
     for name, v in (("a", a), ("b", b)):
         if str(v.dtype).split(".")[-1] != "float32":
             raise ValueError(f"{name} must be float32, got {v.dtype}")
     prm = _flip_params(transfer, pixels_per_degree)
     import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("flip needs a HIP device; there is no CPU fallback")
-    for name, v in (("a", a), ("b", b)):
-        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous CUDA tensor")
-    if a.device != b.device:
-        raise ValueError(f"a and b must be on one device, got {a.device} and {b.device}")
-    H, W = int(a.shape[0]), int(a.shape[1])
-    dev = a.device
-    if stream is None:
-        s = torch.cuda.current_stream(dev)
-    elif isinstance(stream, torch.cuda.Stream):
-        s = stream
-    else:
-        s = torch.cuda.ExternalStream(int(stream), device=dev)
+    _need_device("flip")
+    H, W, dev = _pair_device(a, b)
+    s = _stream_of(stream, dev)
     L = _lib.lib()
-    with torch.cuda.stream(s):  # allocated on the stream that uses them: the caching allocator then orders any reuse
-        work = torch.empty(max(256, L.rtm_flip_work_bytes(W, H)), dtype=torch.uint8, device=dev)
-        out = {}
-        if "result" in want:
-            out["result"] = torch.empty(C.sizeof(_lib.rtm_flip_result) // 4, dtype=torch.int32, device=dev)
-        if "map" in want:
-            out["map"] = torch.empty((H, W), dtype=torch.float32, device=dev)
-    ptr = lambda k: out[k].data_ptr() if k in out else None
-    _lib.check(L.rtm_flip(C.byref(prm), W, H, dev.index, a.data_ptr(), b.data_ptr(), work.data_ptr(), ptr("result"),
+    specs = {"result": (C.sizeof(_lib.rtm_flip_result) // 4, torch.int32), "map": ((H, W), torch.float32)}
+    out, ptr = _stage_tensors(s, dev, want, specs, max(256, L.rtm_flip_work_bytes(W, H)))
+    _lib.check(L.rtm_flip(C.byref(prm), W, H, dev.index, a.data_ptr(), b.data_ptr(), ptr("work"), ptr("result"),
                           ptr("map"), C.c_void_p(s.cuda_stream)), "rtm_flip")
     return out
 
