@@ -16,9 +16,13 @@ extern "C" {
 #endif
 
 /* device sqrt / sqrtf / division / sin / cos and the exact-fast forms on caller data; `op` as in
- * math_probe_kernel (csrc/rtm_seam_kernels.h); ops 32..41: the tolerance row's arithmetic — one-ulp square root, division and
+ * math_probe_kernel (csrc/rtm_seam_kernels.h); ops 32..44: the tolerance row's arithmetic — one-ulp square root, division and
  * reciprocal, a contracted multiply-add, its sin / cos, the unfused fold step (csrc/rtm_kernels_tol.hip) */
 int rtm_debug_math_probe(int op, const double* a, const double* b, size_t n, double* out);
+/* The tolerance row's sin / cos table as the HOST builds it for every device (no device is touched; runs in the CPU test
+ * suite): out[2 i], out[2 i + 1] = sin, cos of i 2 pi / entries, evaluated in long double and rounded to double once.  The
+ * row itself uses entries = 16384 (ops 42 / 43 of rtm_debug_math_probe run its sequence; 44: the shading block's unit root). */
+int rtm_debug_trig_table(int entries, double* out);
 /* exhaustive device self-checks; *mismatches = number of failing inputs (kind 0: fast sqrtf) */
 int rtm_debug_selfcheck(int kind, unsigned long long* mismatches);
 /* nearest hit for caller-given rays: kind 1 the reference's loop as written (src/Renderer.cpp:58-73, the compiler's

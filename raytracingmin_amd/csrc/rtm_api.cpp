@@ -203,6 +203,7 @@ int rtm_debug_matte_rank(int32_t super_samples, int32_t layers, int device, cons
     RTM_GUARD(rtm::matte_rank_probe(super_samples, layers, device, ids_dev, n_pixels, id_out_dev, coverage_out_dev, alpha_out_dev,
                                     stream))
 }
+int rtm_debug_trig_table(int entries, double* out) { RTM_GUARD(rtm::trig_table_host(entries, out)) }
 int rtm_debug_selfcheck(int kind, unsigned long long* mismatches) { RTM_GUARD(rtm::selfcheck(kind, mismatches)) }
 int rtm_debug_grid_nearest(const rtm_sphere* sp, size_t n, const double* org, const double* dir, size_t n_rays,
                            int32_t* out_id, double* out_t, uint32_t* out_tests, uint32_t* out_steps, uint64_t* info) {

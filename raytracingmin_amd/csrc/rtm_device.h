@@ -186,6 +186,9 @@ struct TrigFromRegs {
 struct ShadeLds {
     const double* trig = nullptr;
     const double* unit = nullptr;
+#if RTM_TOL
+    const double2* tab = nullptr;  // not LDS: the device's sin / cos table points (sincos_turn24_tab_load; RenderParams::trig_tab)
+#endif
     __device__ __forceinline__ ShadeLds() {}
     __device__ __forceinline__ ShadeLds(const double* t, bool with_unit = false) : trig(t), unit(with_unit && t ? t + kTrigConstCount : nullptr) {}
 };
@@ -243,6 +246,8 @@ __device__ __forceinline__ void sincos_small(const double x, double& sn, double&
     sincos_small_k(TrigFromRegs{}, x, sn, cs);
 }
 #if RTM_TOL
+// (Until round 7 the shading block's sequence; it now runs sincos_turn24_tab_load / _apply below, and this one stays for probe
+// ops 39 / 40 of rtm_debug_math_probe and their test.)
 // The tolerance unit's sin / cos of r1 = 2 pi (m 2^-24), m the draw's 24-bit integer (src/Renderer.cpp:88,93-94), without the
 // Cody-Waite reduction: the quadrant and the offset from it are EXACT in the draw's own units — q = rint(m 2^-22),
 // f = m 2^-22 - q in [-1/2, 1/2] — so the reduced argument is one rounded product f (pi/2) (relative error 2^-53; the
@@ -278,6 +283,35 @@ __device__ __forceinline__ void sincos_turn24_k(const K& k, const double m24, do
     const double co = sel_f64(odd, -sinv, cosv);
     sn = __hiloint2double(__double2hiint(so) ^ flip, __double2loint(so));
     cs = __hiloint2double(__double2hiint(co) ^ flip, __double2loint(co));
+}
+// What the shading block runs since round 7: the angle split EXACTLY, in the draw's own units, into a table point and a
+// remainder — x = m 2^-10, k = rint(x) in 0 .. 16384, fl = x - k (|fl| < 1/2 and never 0: m is odd) —, the sine and cosine
+// of the point k 2 pi / 16384 from a table (kTrigTabEntries x (sin, cos), built on the host in long double and rounded
+// once: rtm_kernels_tol.hip, trig_tab_fill; one 16-byte gather from 256 KB that stay in L2), those of the remainder
+// r = fl 2 pi / 16384, |r| <= 1.92e-4, from two series terms (r^5 / 120 <= 2.2e-21 and r^6 / 720 <= 7e-26 are dropped), and
+// the angle-sum formulas.  No quadrant logic, no polynomial constants from LDS; within 3e-16 of the sine and cosine of
+// 2 pi m 2^-24 over all 2^23 draws (tests/test_shade_trig_gpu.py).  Two halves, like trig_fix_load / trig_fix_apply: the
+// gather is issued where the draw is made and its result consumed where the sine is needed, a block of arithmetic later.
+constexpr int kTrigTabEntries = 16384;
+struct TrigTabWord {
+    double s, c;  // sin and cos of the table point
+    double fl;    // the remainder, in table steps
+};
+__device__ __forceinline__ TrigTabWord sincos_turn24_tab_load(const double2* __restrict__ tab, const double m24) {
+    const double x = m24 * 0x1p-10;
+    const double k = __builtin_rint(x);
+    unsigned off = ((unsigned)(int)k & (unsigned)(kTrigTabEntries - 1)) * (unsigned)sizeof(double2);
+    asm volatile("" : "+v"(off));  // (opaque, like primary_of's column: nothing of the lane's address is formed outside the trip)
+    const double2 e = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(tab) + off);
+    return TrigTabWord{e.x, e.y, x - k};
+}
+__device__ __forceinline__ void sincos_turn24_tab_apply(const TrigTabWord w, double& sn, double& cs) {
+    const double r = w.fl * (6.283185307179586 / kTrigTabEntries);
+    const double t = r * r;
+    const double cr = __builtin_fma(t, __builtin_fma(t, 1.0 / 24.0, -0.5), 1.0);
+    const double sr = __builtin_fma(r * t, -1.0 / 6.0, r);
+    sn = __builtin_fma(w.c, sr, w.s * cr);
+    cs = __builtin_fma(-w.s, sr, w.c * cr);
 }
 #endif
 

@@ -1462,6 +1462,7 @@ int release_scratch(int device) {
             }
         }
     }
+    release_trig_tab(device);  // the tolerance row's sin / cos table (rtm_kernels_tol.hip)
     {
         std::lock_guard<std::mutex> lock(g_scene_cache.mu);
         auto& e = g_scene_cache.entries;

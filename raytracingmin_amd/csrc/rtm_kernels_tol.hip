@@ -7,8 +7,10 @@
 // float islands of src/Ray.h:67-72, src/SettingData.h:14-16 and src/SettingData.cpp:200,208, the same order of the
 // additions into Renderer::image) a second time, into namespace rtm_tol, with
 //   * FMA contraction allowed (-ffp-contract=fast-honor-pragmas), and
-//   * division and square root to about one ulp (RTM_TOL: rtm_path.h, seq_rcp / seq_quot / seq_sqrt), sin / cos as the
-//     device evaluates them (within one ulp of the host libm's; RTM_MODE_HOST_TRIG has no effect on this row);
+//   * division and square root to about one ulp (RTM_TOL: rtm_path.h, seq_rcp / seq_quot / seq_sqrt; the shading block's two
+//     unit-range roots and, in compact scenes, the search's without the residual step: 2^-45), the sine and cosine of a
+//     draw's angle 2 pi m 2^-24 from a table of 16 384 points (host long double, rounded once) and two series terms,
+//     within 3e-16 of the true values (rtm_device.h: sincos_turn24_tab_load; RTM_MODE_HOST_TRIG has no effect on this row);
 //   * the fold L = colorKD * L + emission (src/Renderer.cpp:109) kept unfused (rtm_device.h: fold_step), so that a
 //     sample's value stays a function of its path's hit ids alone: the image differs from the exact kernel's only where
 //     a last-bit difference in a distance or a direction changes WHICH sphere a ray hits.
@@ -26,6 +28,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <vector>
 
 #include "rtm_internal.h"
 #include "rtm_render_kernel.h"
@@ -93,9 +98,12 @@ static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hip
 // distance to the correctly rounded results in ulps).  32 the unscaled square root, 33 x / y by reciprocal, 34 the
 // reciprocal alone, 35 x * y + 1.0 (contracted here: the other translation unit's op 7 must not be), 36 / 37 sin / cos of the
 // branch-free sincos as compiled here, 38 one level of the fold (x * y + 0.25: must NOT be contracted), 39 / 40 sin / cos of
-// 2 pi (x 2^-24) by the quadrant-exact sequence the shading block uses (x: a draw's 24-bit integer), 41 the search's light root
+// 2 pi (x 2^-24) by the quadrant-exact sequence the shading block ran until round 7 (x: a draw's 24-bit integer), 41 the search's
+// light root, 42 / 43 sin / cos of 2 pi (x 2^-24) as the shading block takes them now — table point and two series terms
+// (rtm_device.h: sincos_turn24_tab_load / _apply; `tab`: the device's table) —, 44 the shading block's unit-range root
+// (MathSpecT::sqrt64_unit: the light sequence)
 __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, size_t n,
-                                      double* __restrict__ out) {
+                                      double* __restrict__ out, const double2* __restrict__ tab) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double x = a[i], y = b ? b[i] : 0.0;
@@ -117,6 +125,9 @@ __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, cons
             r = out1[0];
             break;
         }
+        case 42: sincos_turn24_tab_apply(sincos_turn24_tab_load(tab, x), s, c); r = s; break;
+        case 43: sincos_turn24_tab_apply(sincos_turn24_tab_load(tab, x), s, c); r = c; break;
+        case 44: { MathSpec m; r = m.sqrt64_unit(x); } break;
         default: break;
     }
     out[i] = r;
@@ -126,8 +137,79 @@ __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, cons
 
 namespace rtm {
 
+// The shading block's sin / cos table (rtm_device.h: sincos_turn24_tab_load): entry i = (sin, cos) of i 2 pi / entries, each
+// evaluated in long double and rounded to double once.  HOST only; rtm_debug_trig_table hands it to the tests.
+int trig_table_host(int entries, double* out) {
+    if (!out || entries < 1 || entries > (1 << 20)) return RTM_ERR_INVALID_ARGUMENT;
+    const long double step = 6.283185307179586476925286766559L / (long double)entries;
+    for (int i = 0; i < entries; ++i) {
+        const long double a = (long double)i * step;
+        out[2 * i] = (double)sinl(a);
+        out[2 * i + 1] = (double)cosl(a);
+    }
+    return RTM_OK;
+}
+
+// ... built and uploaded once per device and kept until release_scratch, next to the host-trig table of the other unit: a
+// constant of the build — nothing of a scene or a frame enters it —, read-only and shared by every stream's launches
+namespace {
+std::mutex g_trig_tab_mu;
+std::map<int, double2*> g_trig_tab;
+}  // namespace
+
+static int ensure_trig_tab(const double2** out) {
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return RTM_ERR_HIP;
+    std::lock_guard<std::mutex> lock(g_trig_tab_mu);
+    const auto it = g_trig_tab.find(device);
+    if (it != g_trig_tab.end()) {
+        *out = it->second;
+        return RTM_OK;
+    }
+    constexpr size_t kBytes = (size_t)rtm_tol::kTrigTabEntries * sizeof(double2);
+    std::vector<double> host(2 * (size_t)rtm_tol::kTrigTabEntries);
+    const int rc = trig_table_host(rtm_tol::kTrigTabEntries, host.data());
+    if (rc != RTM_OK) return rc;
+    void* dev = nullptr;
+    if (hipMalloc(&dev, kBytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return RTM_ERR_HIP;
+    }
+    // (a blocking copy and the null stream drained: whatever stream launches next finds the table written)
+    if (hipMemcpy(dev, host.data(), kBytes, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(dev);
+        return RTM_ERR_HIP;
+    }
+    g_trig_tab[device] = static_cast<double2*>(dev);
+    *out = static_cast<const double2*>(dev);
+    return RTM_OK;
+}
+
+// release_scratch's share: the caller holds the render gate, no launch of `device` (all of them: < 0) is mid-call
+void release_trig_tab(int device) {
+    std::lock_guard<std::mutex> lock(g_trig_tab_mu);
+    for (auto it = g_trig_tab.begin(); it != g_trig_tab.end();) {
+        if (device < 0 || it->first == device) {
+            (void)hipSetDevice(it->first);
+            (void)hipDeviceSynchronize();
+            (void)hipFree(it->second);
+            it = g_trig_tab.erase(it);
+        } else {
+            ++it;
+        }
+    }
+}
+
 int tol_math_probe(int op, const double* a_dev, const double* b_dev, size_t n, double* out_dev) {
-    rtm_tol::tol_math_probe_kernel<<<(unsigned)((n + 255) / 256), 256>>>(op, a_dev, b_dev, n, out_dev);
+    const double2* tab = nullptr;
+    if (op == 42 || op == 43) {
+        if (ensure_trig_tab(&tab) != RTM_OK) {
+            set_last_error("tolerance row: the sin / cos table could not be allocated on the device");
+            return RTM_ERR_HIP;
+        }
+    }
+    rtm_tol::tol_math_probe_kernel<<<(unsigned)((n + 255) / 256), 256>>>(op, a_dev, b_dev, n, out_dev, tab);
     return hipGetLastError() == hipSuccess ? RTM_OK : RTM_ERR_HIP;
 }
 
@@ -145,6 +227,13 @@ int launch_tol(const void* params, size_t params_bytes, unsigned grid, size_t ld
     // distinction this unit's own arithmetic does not keep anywhere else.  The row takes the device's (one table gather and
     // ten instructions per bounce less); the flag is accepted and has no effect here.
     P.scene.trig_fix = nullptr;
+    // ... by table point and two series terms: the table is the device's, made at the first launch
+    const double2* trig_tab = nullptr;
+    if (ensure_trig_tab(&trig_tab) != RTM_OK) {
+        set_last_error("tolerance row: the sin / cos table could not be allocated on the device");
+        return RTM_ERR_HIP;
+    }
+    P.trig_tab = trig_tab;
     hipStream_t stream = (hipStream_t)stream_v;
     const bool any_depth = P.max_bounces < 0 || P.max_bounces > 8;
     if ((!any_depth && P.steal_ws == nullptr) || P.scene.n < 1 || P.scene.n > 24 || P.scene.plane != nullptr ||

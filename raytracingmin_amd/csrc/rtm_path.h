@@ -251,9 +251,15 @@ struct MathSpecT {
     bool bad = false;
     const double* trig_lds = nullptr;  // LDS copy of the sincos constants (optional)
     const double* unit_lds = nullptr;  // ... and the near-unit Normalize table (optional): set_lds
+#if RTM_TOL
+    const double2* trig_tab = nullptr;  // the sin / cos table points in device memory (the launch always has them: launch_tol)
+#endif
     __device__ __forceinline__ void set_lds(const ShadeLds& l) {
         trig_lds = l.trig;
         unit_lds = l.unit;
+#if RTM_TOL
+        trig_tab = l.tab;
+#endif
     }
     __device__ __forceinline__ double sqrt64(double x) {
         bad = bad || !MathFast::sqrt_fast_ok(x);
@@ -261,8 +267,18 @@ struct MathSpecT {
     }
     // sqrt of an operand KNOWN to be a positive normal number of moderate size (r2 and 1 - r2 of a 23-bit draw:
     // [2^-24, 1)): the unscaled sequence without its range check
+    // (the tolerance unit: without the residual step, like the search's light roots — seq_sqrt_batch<K, true>, 2^-45 relative.
+    // Nothing of the scene enters these operands, so no compactness guard; the two roots scale the terms of a direction
+    // that goes through the float-length Normalize next)
     __device__ __forceinline__ double sqrt64_unit(double x) {
+#if RTM_TOL
+        const double in[1] = {x};
+        double out[1];
+        seq_sqrt_batch<1, true>(in, out);
+        return out[0];
+#else
         return seq_sqrt(x);
+#endif
     }
     __device__ __forceinline__ D3 div3(D3 a, double y) {
         bad = bad || !(MathFast::moderate(y) && MathFast::moderate(a.x) && MathFast::moderate(a.y) &&
@@ -281,16 +297,17 @@ struct MathSpecT {
     }
     // sin / cos of r1 = 2 pi u for the draw u = m24 2^-24 (src/Renderer.cpp:88: (2 pi 2^-24) m is the same correctly
     // rounded product as 2 pi (m 2^-24))
-    __device__ __forceinline__ void sincos_draw(double m24, double& sn, double& cs) {
 #if RTM_TOL
-        if (trig_lds)
-            sincos_turn24_k(TrigFromLds{trig_lds}, m24, sn, cs);
-        else
-            sincos_turn24_k(TrigFromRegs{}, m24, sn, cs);
+    // ... in two halves: the table gather where the draw is made, the series and the angle sum where the sine is needed
+    // (rtm_device.h: sincos_turn24_tab_load / _apply)
+    using TrigAhead = TrigTabWord;
+    __device__ __forceinline__ TrigAhead sincos_draw_issue(double m24) const { return sincos_turn24_tab_load(trig_tab, m24); }
+    __device__ __forceinline__ void sincos_draw(const TrigAhead& w, double& sn, double& cs) { sincos_turn24_tab_apply(w, sn, cs); }
 #else
+    __device__ __forceinline__ void sincos_draw(double m24, double& sn, double& cs) {
         sincos_r1((6.283185307179586 * 0x1p-24) * m24, sn, cs);
-#endif
     }
+#endif
     // Magnitude (src/Ray.h:67-69) with the unscaled float sqrt
     __device__ __forceinline__ double magnitude_spec(D3 a) {
         const float len2 = (float)(a.x * a.x + a.y * a.y + a.z * a.z);
@@ -484,6 +501,11 @@ struct MathRefI {
             sincos(x, &sn, &cs);
     }
     __device__ __forceinline__ void sincos_draw(double m24, double& sn, double& cs) { sincos_r1((6.283185307179586 * 0x1p-24) * m24, sn, cs); }
+#if RTM_TOL  // (the two-halves form of MathSpecT: nothing to fetch ahead here)
+    struct TrigAhead { double m24; };
+    __device__ __forceinline__ TrigAhead sincos_draw_issue(double m24) const { return TrigAhead{m24}; }
+    __device__ __forceinline__ void sincos_draw(const TrigAhead& w, double& sn, double& cs) { sincos_draw(w.m24, sn, cs); }
+#endif
 };
 struct MathFastI {
     static constexpr bool bad = false;
@@ -495,6 +517,11 @@ struct MathFastI {
     __device__ __forceinline__ D3 div3(D3 a, double y) { return MathFast::div3(a, y); }
     __device__ __forceinline__ void sincos_r1(double x, double& sn, double& cs) { sincos(x, &sn, &cs); }
     __device__ __forceinline__ void sincos_draw(double m24, double& sn, double& cs) { sincos_r1((6.283185307179586 * 0x1p-24) * m24, sn, cs); }
+#if RTM_TOL  // (the two-halves form of MathSpecT: nothing to fetch ahead here)
+    struct TrigAhead { double m24; };
+    __device__ __forceinline__ TrigAhead sincos_draw_issue(double m24) const { return TrigAhead{m24}; }
+    __device__ __forceinline__ void sincos_draw(const TrigAhead& w, double& sn, double& cs) { sincos_draw(w.m24, sn, cs); }
+#endif
 };
 
 // src/Ray.h:67-72 through a policy
@@ -1609,6 +1636,8 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
 #if !RTM_TOL  // (the tolerance unit takes the device's sin / cos: launch_tol)
     TrigFixWord fixw{0u, 0};
     if (sc.v.trig_fix) fixw = trig_fix_load(sc.v.trig_fix, rng);  // wave-uniform; consumed after the sincos
+#else  // ... by table point and short series: the gather is issued here and consumed where the sine is taken
+    const typename MI::TrigAhead trig_ahead = m.sincos_draw_issue(m24);
 #endif
     const double r2s = m.sqrt64_unit(r2);                 // :90
     // :96-101 — one Normalize on the selected cross product (same values as the two-armed if)
@@ -1629,9 +1658,11 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
             double ux, uz;
             m.normalize_xz(w.z, -w.x, ux, uz);
             const double vx = w.y * uz, vy = -w.x * uz + w.z * ux, vz = -(w.y * ux);
-            m.sincos_draw(m24, sn, cs);
 #if !RTM_TOL
+            m.sincos_draw(m24, sn, cs);
             if (sc.v.trig_fix) trig_fix_apply(fixw, sn, cs);  // wave-uniform
+#else
+            m.sincos_draw(trig_ahead, sn, cs);
 #endif
             const double s1 = m.sqrt64_unit(1.0 - r2);
             out.dir = m.normalize_near_unit(d3(((ux * cs) * r2s + (vx * sn) * r2s) + w.x * s1, (vy * sn) * r2s + w.y * s1,
@@ -1651,9 +1682,11 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
         u = m.normalize_y0(c);  // c.y = (-0)*w.z + 0*w.x is a signed zero for finite w
     }
     const D3 v = cross(w, u);  // :102
-    m.sincos_draw(m24, sn, cs);
 #if !RTM_TOL
+    m.sincos_draw(m24, sn, cs);
     if (sc.v.trig_fix) trig_fix_apply(fixw, sn, cs);  // wave-uniform
+#else
+    m.sincos_draw(trig_ahead, sn, cs);
 #endif
     out.dir = m.normalize_near_unit((u * cs) * r2s + (v * sn) * r2s + w * m.sqrt64_unit(1.0 - r2));  // :103-107
     out.org = hit_point;

@@ -82,6 +82,9 @@ struct RenderParams {
     // tile t (every other call).  The work buffers above stay indexed by launch-local tile.
     const unsigned* __restrict__ tile_map;
     unsigned frame_tiles;
+    // the tolerance translation unit's shading block: sin and cos of the kTrigTabEntries points k 2 pi / kTrigTabEntries
+    // (rtm_device.h: sincos_turn24_tab_load), one table per device, a constant of the build — set by launch_tol, null elsewhere
+    const double2* __restrict__ trig_tab;
 };
 constexpr size_t kTermRowBytes = 3 * 64 * sizeof(double) + 64 * sizeof(unsigned short);  // 1664 = 13 lines of 128 B
 constexpr size_t kStealRowBytes = 3 * 64 * sizeof(double) + 64 * sizeof(unsigned);       // 1792 = 14 lines of 128 B
@@ -386,7 +389,13 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // a compile-time constant for them
     const bool unit_tab = UNROLL <= -1000 ? true : (P.unit_tab != 0u);
     double* park = trig + (unit_tab ? kShadeConstCount : kTrigConstCount);
+#if RTM_TOL
+    ShadeLds shade_lds_tab(trig, unit_tab);
+    shade_lds_tab.tab = P.trig_tab;
+    const ShadeLds shade_lds = shade_lds_tab;
+#else
     const ShadeLds shade_lds(trig, unit_tab);
+#endif
     RecT* rec = reinterpret_cast<RecT*>(park + (PARK ? 6 * 64 : 0));
     // DEFER: [ring 128 x uint4][terms 3 x 64 doubles][per-lane FIFO of ring positions][per-lane count]; kScatter (below):
     // [ring][per pixel: entries added so far, 64 words — a small wave's 128 two-byte tags in their place][per-lane count]
