@@ -16,8 +16,10 @@ extern "C" {
 #endif
 
 /* device sqrt / sqrtf / division / sin / cos and the exact-fast forms on caller data; `op` as in
- * math_probe_kernel (csrc/rtm_seam_kernels.h); ops 32..44: the tolerance row's arithmetic — one-ulp square root, division and
- * reciprocal, a contracted multiply-add, its sin / cos, the unfused fold step (csrc/rtm_kernels_tol.hip) */
+ * math_probe_kernel (csrc/rtm_seam_kernels.h); ops 32..47: the tolerance row's arithmetic — one-ulp square root, division and
+ * reciprocal, a contracted multiply-add, its sin / cos, the unfused fold step; 45..47: the reference forms of 41..43; 48: of 32;
+ * 49..51: a sphere's row of the normal table for r * r = a[i] (csrc/rtm_kernels_tol.hip).  Ops 39, 40, 42, 43, 46, 47 take a draw's
+ * integer: a[i] must be an ODD integer below 2^24 (42 / 43 convert it to an integer, the others round it: other operands differ) */
 int rtm_debug_math_probe(int op, const double* a, const double* b, size_t n, double* out);
 /* The tolerance row's sin / cos table as the HOST builds it for every device (no device is touched; runs in the CPU test
  * suite): out[2 i], out[2 i + 1] = sin, cos of i 2 pi / entries, evaluated in long double and rounded to double once.  The

@@ -292,26 +292,40 @@ __device__ __forceinline__ void sincos_turn24_k(const K& k, const double m24, do
 // the angle-sum formulas.  No quadrant logic, no polynomial constants from LDS; within 3e-16 of the sine and cosine of
 // 2 pi m 2^-24 over all 2^23 draws (tests/test_shade_trig_gpu.py).  Two halves, like trig_fix_load / trig_fix_apply: the
 // gather is issued where the draw is made and its result consumed where the sine is needed, a block of arithmetic later.
+// Since round 8 the split is made in INTEGERS, on the draw's integer m itself (rng_next_mi): with t = m + 512, k = t >> 10
+// (m is odd, so m 2^-10 is never a tie and rint is "add a half and truncate") and fl 2^10 = (t & 1023) - 512, an integer
+// fi in -511 .. 511; the remainder is r = fi ((2 pi / 16384) 2^-10), the same double as fl (2 pi / 16384) because the two
+// differ by a power of two in one factor.  Six instructions, one of them a conversion, where the double form took seven, five
+// of them fp64-rate (tests/test_loop_trims_host.py: every odd m; tests/test_loop_trims_gpu.py: against the double form below).
 constexpr int kTrigTabEntries = 16384;
 struct TrigTabWord {
     double s, c;  // sin and cos of the table point
-    double fl;    // the remainder, in table steps
+    int fi;       // the remainder, in 2^-10 table steps
 };
-__device__ __forceinline__ TrigTabWord sincos_turn24_tab_load(const double2* __restrict__ tab, const double m24) {
-    const double x = m24 * 0x1p-10;
-    const double k = __builtin_rint(x);
-    unsigned off = ((unsigned)(int)k & (unsigned)(kTrigTabEntries - 1)) * (unsigned)sizeof(double2);
+__device__ __forceinline__ TrigTabWord sincos_turn24_tab_load(const double2* __restrict__ tab, const uint32_t m) {
+    const uint32_t t = m + 512u;
+    unsigned off = (t >> 6) & ((unsigned)(kTrigTabEntries - 1) * (unsigned)sizeof(double2));
     asm volatile("" : "+v"(off));  // (opaque, like primary_of's column: nothing of the lane's address is formed outside the trip)
     const double2 e = *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(tab) + off);
-    return TrigTabWord{e.x, e.y, x - k};
+    return TrigTabWord{e.x, e.y, (int)(t & 1023u) - 512};
 }
-__device__ __forceinline__ void sincos_turn24_tab_apply(const TrigTabWord w, double& sn, double& cs) {
-    const double r = w.fl * (6.283185307179586 / kTrigTabEntries);
+__device__ __forceinline__ void sincos_tab_point_apply(const double ws, const double wc, const double r, double& sn, double& cs) {
     const double t = r * r;
     const double cr = __builtin_fma(t, __builtin_fma(t, 1.0 / 24.0, -0.5), 1.0);
     const double sr = __builtin_fma(r * t, -1.0 / 6.0, r);
-    sn = __builtin_fma(w.c, sr, w.s * cr);
-    cs = __builtin_fma(-w.s, sr, w.c * cr);
+    sn = __builtin_fma(wc, sr, ws * cr);
+    cs = __builtin_fma(-ws, sr, wc * cr);
+}
+__device__ __forceinline__ void sincos_turn24_tab_apply(const TrigTabWord w, double& sn, double& cs) {
+    sincos_tab_point_apply(w.s, w.c, (double)w.fi * ((6.283185307179586 / kTrigTabEntries) * 0x1p-10), sn, cs);
+}
+// The split in doubles, as the shading block made it in round 7: the reference form of the one above, run by
+// rtm_debug_math_probe ops 46 / 47 alone.
+__device__ __forceinline__ void sincos_turn24_tab_ref(const double2* __restrict__ tab, const double m24, double& sn, double& cs) {
+    const double x = m24 * 0x1p-10;
+    const double k = __builtin_rint(x);
+    const double2 e = tab[(unsigned)(int)k & (unsigned)(kTrigTabEntries - 1)];
+    sincos_tab_point_apply(e.x, e.y, (x - k) * (6.283185307179586 / kTrigTabEntries), sn, cs);
 }
 #endif
 
@@ -358,13 +372,16 @@ __host__ __device__ __forceinline__ double rng_next(RngStream& s) {
     s.ctr += 0x9E3779B9u;
     return rng_bits_to_u01(x);
 }
-// The draw as the odd integer m = 2 (bits >> 9) + 1 < 2^24 in a double: u = m * 2^-24.  Callers that only compare u
-// with a constant, or scale it by one, fold the 2^-24 into the constant (exact: a power of two) and save the ldexp.
-__host__ __device__ __forceinline__ double rng_next_m(RngStream& s) {
+// The draw as the odd integer m = 2 (bits >> 9) + 1 < 2^24: u = m * 2^-24 (the tolerance unit's sincos_turn24_tab_load splits
+// this integer itself) ...
+__host__ __device__ __forceinline__ uint32_t rng_next_mi(RngStream& s) {
     const uint32_t x = mix32(s.ctr ^ s.k1);
     s.ctr += 0x9E3779B9u;
-    return (double)(2u * (x >> 9) + 1u);
+    return 2u * (x >> 9) + 1u;
 }
+// ... and in a double.  Callers that only compare u with a constant, or scale it by one, fold the 2^-24 into the constant
+// (exact: a power of two) and save the ldexp.
+__host__ __device__ __forceinline__ double rng_next_m(RngStream& s) { return (double)rng_next_mi(s); }
 __host__ __device__ __forceinline__ double rng_u01_at(uint64_t seed_mult, uint32_t pixel, uint32_t sample,
                                                       uint32_t index) {
     RngStream s = rng_open(rng_pixel_key(seed_mult, pixel), sample);

@@ -101,7 +101,10 @@ static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hip
 // 2 pi (x 2^-24) by the quadrant-exact sequence the shading block ran until round 7 (x: a draw's 24-bit integer), 41 the search's
 // light root, 42 / 43 sin / cos of 2 pi (x 2^-24) as the shading block takes them now — table point and two series terms
 // (rtm_device.h: sincos_turn24_tab_load / _apply; `tab`: the device's table) —, 44 the shading block's unit-range root
-// (MathSpecT::sqrt64_unit: the light sequence)
+// (MathSpecT::sqrt64_unit: the light sequence), 45 the light root with its half by a multiply (the form op 41 ran until round 8:
+// its reference), 46 / 47 ops 42 / 43 with the angle split made in doubles (until round 8: their reference), 48 op 32 with its
+// half by a multiply (the full root's reference), 49 / 50 / 51 the normal table's row for a sphere with r * r = x: the length, its
+// refined reciprocal and the float r * r, NaN where the reciprocal is (fill_norm_row, as the render kernels' prologue calls it)
 __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, size_t n,
                                       double* __restrict__ out, const double2* __restrict__ tab) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -125,9 +128,31 @@ __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, cons
             r = out1[0];
             break;
         }
-        case 42: sincos_turn24_tab_apply(sincos_turn24_tab_load(tab, x), s, c); r = s; break;
-        case 43: sincos_turn24_tab_apply(sincos_turn24_tab_load(tab, x), s, c); r = c; break;
+        case 42: sincos_turn24_tab_apply(sincos_turn24_tab_load(tab, (uint32_t)x), s, c); r = s; break;
+        case 43: sincos_turn24_tab_apply(sincos_turn24_tab_load(tab, (uint32_t)x), s, c); r = c; break;
         case 44: { MathSpec m; r = m.sqrt64_unit(x); } break;
+        case 45: {  // op 41 with h0 = 0.5 * y by the multiply (rtm_path.h: half_of_rsq_ref)
+            const double in[1] = {x};
+            double out1[1];
+            seq_sqrt_batch<1, true, true>(in, out1);
+            r = out1[0];
+            break;
+        }
+        case 48: {  // op 32 with h0 = 0.5 * y by the multiply: the full root's reference form
+            const double in[1] = {x};
+            double out1[1];
+            seq_sqrt_batch<1, false, true>(in, out1);
+            r = out1[0];
+            break;
+        }
+        case 49: case 50: case 51: {  // a sphere's row of the normal table for r * r = x (rtm_path.h: fill_norm_row): ms, rinv, r2f
+            double row[3];
+            fill_norm_row(row, x);
+            r = op == 51 ? (double)reinterpret_cast<const float*>(row + 2)[0] : row[op - 49];
+            break;
+        }
+        case 46: sincos_turn24_tab_ref(tab, x, s, c); r = s; break;
+        case 47: sincos_turn24_tab_ref(tab, x, s, c); r = c; break;
         default: break;
     }
     out[i] = r;
@@ -203,7 +228,7 @@ void release_trig_tab(int device) {
 
 int tol_math_probe(int op, const double* a_dev, const double* b_dev, size_t n, double* out_dev) {
     const double2* tab = nullptr;
-    if (op == 42 || op == 43) {
+    if (op == 42 || op == 43 || op == 46 || op == 47) {
         if (ensure_trig_tab(&tab) != RTM_OK) {
             set_last_error("tolerance row: the sin / cos table could not be allocated on the device");
             return RTM_ERR_HIP;

@@ -47,9 +47,26 @@ __device__ __forceinline__ double seq_quot(const double x, const double y, const
     return __builtin_fma(rem, r, q);
 #endif
 }
+#if RTM_TOL
+// 0.5 * y for y = v_rsq_f64(x), by lowering y's exponent field by one: an integer add on the high word (half the issue cost
+// of the fp64 multiply) that hipcc does in place.  Bit for bit 0.5 * y for every NORMAL y — which v_rsq_f64 returns for every
+// positive finite x, subnormal ones included (2^-512 <= y <= 2^537).  For x = +-0 (y infinite), x = +inf (y = 0) and x < 0 or
+// NaN (y NaN) the result here is some other number, and does not matter: s0 = x * y is NaN for each of them, so the root is
+// NaN exactly as with 0.5 * y.  Formed AFTER s0 so that y dies there.  tests/test_loop_trims_gpu.py compares the roots with
+// those of half_of_rsq_ref for all of this, bit for bit.
+__device__ __forceinline__ double half_of_rsq(const double y) {
+    return __hiloint2double(__double2hiint(y) - 0x00100000, __double2loint(y));
+}
+// ... and the multiply it replaces: the reference form, called by rtm_debug_math_probe op 45 alone
+__device__ __forceinline__ double half_of_rsq_ref(const double y) { return 0.5 * y; }
+#endif
 __device__ __forceinline__ double seq_sqrt(const double x) {
     const double y = __builtin_amdgcn_rsq(x);
+#if RTM_TOL
+    const double s0 = x * y, h0 = half_of_rsq(y);
+#else
     const double s0 = x * y, h0 = 0.5 * y;
+#endif
     const double r0 = __builtin_fma(-h0, s0, 0.5);
 #if RTM_TOL
     const double s1 = __builtin_fma(s0, r0, s0);
@@ -64,14 +81,15 @@ __device__ __forceinline__ double seq_sqrt(const double x) {
 #endif
 }
 // K independent roots, stage by stage (K independent dependency chains for the scheduler to interleave)
-template <int K, bool LIGHT = false>
+// (HALF_REF, tolerance unit: h0 by the multiply that half_of_rsq replaces — probe op 45's reference form, nothing else asks for it)
+template <int K, bool LIGHT = false, bool HALF_REF = false>
 __device__ __forceinline__ void seq_sqrt_batch(const double (&x)[K], double (&out)[K]) {
 #if RTM_TOL
     double y[K], s0[K], h0[K], r0[K], s1[K], d0[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) y[k] = __builtin_amdgcn_rsq(x[k]);
 #pragma unroll
-    for (int k = 0; k < K; ++k) { s0[k] = x[k] * y[k]; h0[k] = 0.5 * y[k]; }
+    for (int k = 0; k < K; ++k) { s0[k] = x[k] * y[k]; h0[k] = HALF_REF ? half_of_rsq_ref(y[k]) : half_of_rsq(y[k]); }
 #pragma unroll
     for (int k = 0; k < K; ++k) r0[k] = __builtin_fma(-h0[k], s0[k], 0.5);
 #pragma unroll
@@ -94,7 +112,7 @@ __device__ __forceinline__ void seq_sqrt_batch(const double (&x)[K], double (&ou
         for (int k = 0; k < K; ++k) out[k] = __builtin_fma(d0[k], h0[k], s1[k]);
     }
 #else
-    static_assert(!LIGHT, "light roots are the tolerance unit's");
+    static_assert(!LIGHT && !HALF_REF, "light roots are the tolerance unit's");
     double y[K], s0[K], h0[K], r0[K], s1[K], h1[K], d0[K], s2[K], d1[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) y[k] = __builtin_amdgcn_rsq(x[k]);
@@ -301,7 +319,7 @@ struct MathSpecT {
     // ... in two halves: the table gather where the draw is made, the series and the angle sum where the sine is needed
     // (rtm_device.h: sincos_turn24_tab_load / _apply)
     using TrigAhead = TrigTabWord;
-    __device__ __forceinline__ TrigAhead sincos_draw_issue(double m24) const { return sincos_turn24_tab_load(trig_tab, m24); }
+    __device__ __forceinline__ TrigAhead sincos_draw_issue(uint32_t m) const { return sincos_turn24_tab_load(trig_tab, m); }
     __device__ __forceinline__ void sincos_draw(const TrigAhead& w, double& sn, double& cs) { sincos_turn24_tab_apply(w, sn, cs); }
 #else
     __device__ __forceinline__ void sincos_draw(double m24, double& sn, double& cs) {
@@ -379,6 +397,23 @@ struct MathSpecT {
         }
         return normalize(a);
     }
+#if RTM_TOL
+    // ... handed back as (a, scale) with Normalize(a) = a * scale where the table serves it — the three multiplies are the
+    // caller's (ShadeOut::dir_scale) —, else as (Normalize(a), 1.0)
+    __device__ __forceinline__ D3 normalize_near_unit_split(D3 a, double& scale) {
+        if constexpr (GUARD) {
+            if (unit_lds) {
+                const double sx = a.x * a.x, sy = a.y * a.y, sz = a.z * a.z;
+                const unsigned k = __float_as_uint((float)(sx + sy + sz)) - kUnitWindowFirst;
+                bad = bad | (k >= (unsigned)kUnitWindow);
+                scale = reinterpret_cast<const double2*>(unit_lds)[k & (unsigned)(kUnitWindow - 1)].y;
+                return a;
+            }
+        }
+        scale = 1.0;
+        return normalize(a);
+    }
+#endif
     // Normalize of a vector whose y component is a (signed) zero — Cross((0,1,0), w) for finite w:
     // y*y adds +0 to the squared length and +-0 / m is the same +-0, so only x and z are divided.
     // Anything else in y (NaN from a non-finite w) trips `bad`.
@@ -430,10 +465,11 @@ struct MathSpecT {
         if constexpr (GUARD) {
             const double sx = dv.x * dv.x, sy = dv.y * dv.y, sz = dv.z * dv.z;
             const float len2f = (float)(sx + sy + sz);
-            const bool canon = (len2f == r2f) && (rinv == rinv);
+            const bool canon = len2f == r2f;  // (a row without a refined reciprocal holds NaN here: the render kernel's prologue)
             if (__builtin_amdgcn_ballot_w64(!canon) != 0) return div3_by_magnitude(dv, sx, sy, sz, len2f);
-            // canonical: |dv|^2 rounds to the float r*r of a sphere whose refined reciprocal exists (rinv is NaN when
-            // ms is outside the exact range), so only a tiny component remains to be excluded
+            // canonical: |dv|^2 rounds to the float r*r of a sphere whose refined reciprocal exists (where ms is outside the
+            // exact range rinv is NaN, and so is the row's r2f: no length equals it), so only a tiny component remains to be
+            // excluded
 #if !RTM_TOL
             unsigned lo = (unsigned)__double2hiint(sx);
             const unsigned hy = (unsigned)__double2hiint(sy), hz = (unsigned)__double2hiint(sz);
@@ -447,7 +483,7 @@ struct MathSpecT {
             return D3{one(dv.x), one(dv.y), one(dv.z)};
         } else {
             const float len2f = (float)(dv.x * dv.x + dv.y * dv.y + dv.z * dv.z);
-            const bool canon = (len2f == r2f) && (rinv == rinv);
+            const bool canon = len2f == r2f;  // (a row without a refined reciprocal holds NaN here: the render kernel's prologue)
             if (__builtin_amdgcn_ballot_w64(!canon) != 0) {
                 bad = bad || !sqrtf_fast_ok(len2f);
                 return div3(dv, (double)sqrtf_fast(len2f));
@@ -482,6 +518,19 @@ __device__ __forceinline__ double refined_rcp_or_nan(double y) {
     e = __builtin_fma(-y, r, 1.0);
     return __builtin_fma(r, e, r);
 }
+// A sphere's row of the normal table (SceneLds::lnrm; MathSpecT::normalize_on_sphere reads it) from r2 = (double)(r * r), the
+// float product as the geometry table holds it: |hit - centre| as Magnitude returns it for a point on the sphere, its refined
+// reciprocal, and the float r * r itself — or NaN where that reciprocal is NaN (r * r zero, infinite or NaN): no squared length
+// equals NaN, so the one compare `len2f == r2f` also says "this row's shortcut is valid".  (Such a row's shortcut could not be
+// taken before either: a sphere whose r * r is infinite or NaN never returns a hit, and one with r * r = 0 only a hit point that
+// IS its centre, whose Normalize is 0 / 0 on every path.)
+__device__ __forceinline__ void fill_norm_row(double* row, const double r2) {
+    const double ms = (double)__builtin_sqrtf((float)r2);
+    const double rinv = refined_rcp_or_nan(ms);
+    row[0] = ms;
+    row[1] = rinv;
+    reinterpret_cast<float*>(row + 2)[0] = rinv != rinv ? __builtin_nanf("") : (float)r2;
+}
 // instance adaptors so that path_shade can take any policy as an object
 struct MathRefI {
     static constexpr bool bad = false;
@@ -503,7 +552,7 @@ struct MathRefI {
     __device__ __forceinline__ void sincos_draw(double m24, double& sn, double& cs) { sincos_r1((6.283185307179586 * 0x1p-24) * m24, sn, cs); }
 #if RTM_TOL  // (the two-halves form of MathSpecT: nothing to fetch ahead here)
     struct TrigAhead { double m24; };
-    __device__ __forceinline__ TrigAhead sincos_draw_issue(double m24) const { return TrigAhead{m24}; }
+    __device__ __forceinline__ TrigAhead sincos_draw_issue(uint32_t m) const { return TrigAhead{(double)m}; }
     __device__ __forceinline__ void sincos_draw(const TrigAhead& w, double& sn, double& cs) { sincos_draw(w.m24, sn, cs); }
 #endif
 };
@@ -519,7 +568,7 @@ struct MathFastI {
     __device__ __forceinline__ void sincos_draw(double m24, double& sn, double& cs) { sincos_r1((6.283185307179586 * 0x1p-24) * m24, sn, cs); }
 #if RTM_TOL  // (the two-halves form of MathSpecT: nothing to fetch ahead here)
     struct TrigAhead { double m24; };
-    __device__ __forceinline__ TrigAhead sincos_draw_issue(double m24) const { return TrigAhead{m24}; }
+    __device__ __forceinline__ TrigAhead sincos_draw_issue(uint32_t m) const { return TrigAhead{(double)m}; }
     __device__ __forceinline__ void sincos_draw(const TrigAhead& w, double& sn, double& cs) { sincos_draw(w.m24, sn, cs); }
 #endif
 };
@@ -690,7 +739,8 @@ struct SceneLds {
     const double* lgeom;  // LDS, 4 doubles per sphere
     const double* lmat;   // LDS, 8 doubles per sphere
     const double* lnrm;   // LDS, 3 doubles per sphere: |hit - centre| as Magnitude returns it for a point
-                          // on the sphere, (double)sqrtf((float)(r*r)), its refined reciprocal, the float r*r
+                          // on the sphere, (double)sqrtf((float)(r*r)), its refined reciprocal, the float r*r (NaN where
+                          // the reciprocal is NaN: normalize_on_sphere asks "is this row's shortcut valid" by one compare)
     static constexpr bool kHasNormTable = true;
     static constexpr bool kPlanes = false;
     static constexpr bool kNeverPlanes = true;  // the launchers hand scenes that hold planes to SceneLdsObjects (v.plane is null here)
@@ -1556,9 +1606,50 @@ struct PathCounters {
 // `m` is a math policy object (MathRefI, MathFastI or MathSpec).
 struct ShadeOut {
     D3 org, dir;     // the bounced ray (src/Renderer.cpp:108)
-    uint32_t ctr;    // RNG counter after this invocation's draws
+    uint32_t ctr;    // RNG counter after this invocation's draws (in the tolerance unit read by the primary-hit-reuse loop
+                     // alone, which makes the roulette's draw itself: shade_commit advances the stream in place)
     int draws;       // 0, 1 or 3
+#if RTM_TOL
+    // The tolerance unit's quotient is x * (1 / y) (seq_quot), so where the new direction's Normalize takes its reciprocal from
+    // the near-unit table, `dir` is the vector BEFORE the Normalize and `dir_scale` that reciprocal: the caller forms
+    // dir * dir_scale behind its one check, straight into its own ray (shade_commit) — three multiplies that were there
+    // anyway, and no copy.  1.0 wherever `dir` is already normalized (any other policy: x * 1.0 is x).
+    double dir_scale;
+#endif
 };
+// A continuing path's ray, depth aside, from what the shading block handed back.  Tolerance unit: a bounce makes three draws
+// (src/Renderer.cpp:78,88,89), so the stream moves on in place instead of taking the block's copy of the counter.
+// (the one place that knows how a ShadeOut holds its direction)
+__device__ __forceinline__ D3 bounce_dir(const ShadeOut& o) {
+#if RTM_TOL
+    return o.dir * o.dir_scale;
+#else
+    return o.dir;
+#endif
+}
+__device__ __forceinline__ void shade_commit(const ShadeOut& o, D3& org, D3& dir, RngStream& rng) {
+    org = o.org;
+    dir = bounce_dir(o);
+#if RTM_TOL
+    rng.ctr += 3u * 0x9E3779B9u;
+#else
+    rng.ctr = o.ctr;
+#endif
+}
+// out.dir = Normalize(nd) (src/Renderer.cpp:103-107) — in the tolerance unit as the pair (vector, scale): ShadeOut::dir_scale
+template <class MI>
+__device__ __forceinline__ void set_bounce_dir(MI& m, ShadeOut& out, const D3 nd) {
+#if RTM_TOL
+    if constexpr (is_spec<MI>::value) {
+        out.dir = m.normalize_near_unit_split(nd, out.dir_scale);
+    } else {
+        out.dir_scale = 1.0;
+        out.dir = m.normalize_near_unit(nd);
+    }
+#else
+    out.dir = m.normalize_near_unit(nd);
+#endif
+}
 // The bounce itself (src/Renderer.cpp:79-108): everything after the Russian-roulette test has passed.  `rng` is
 // the stream right after the RR draw; always continues.
 template <class MI, class Scene>
@@ -1631,13 +1722,17 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
     }
     out.draws = 3;
     // :88 r1 = 2 PI u with u = m * 2^-24: (2 PI * 2^-24) * m is the same correctly rounded product as 2 PI * (m * 2^-24)
+#if !RTM_TOL
     const double m24 = rng_next_m(rng);  // (r1 is formed where its sin / cos are taken: sincos_draw)
+#else  // (the tolerance unit splits the draw's integer: no conversion)
+    const uint32_t m24i = rng_next_mi(rng);
+#endif
     const double r2 = rng_next(rng);                      // :89
 #if !RTM_TOL  // (the tolerance unit takes the device's sin / cos: launch_tol)
     TrigFixWord fixw{0u, 0};
     if (sc.v.trig_fix) fixw = trig_fix_load(sc.v.trig_fix, rng);  // wave-uniform; consumed after the sincos
 #else  // ... by table point and short series: the gather is issued here and consumed where the sine is taken
-    const typename MI::TrigAhead trig_ahead = m.sincos_draw_issue(m24);
+    const typename MI::TrigAhead trig_ahead = m.sincos_draw_issue(m24i);
 #endif
     const double r2s = m.sqrt64_unit(r2);                 // :90
     // :96-101 — one Normalize on the selected cross product (same values as the two-armed if)
@@ -1665,8 +1760,8 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
             m.sincos_draw(trig_ahead, sn, cs);
 #endif
             const double s1 = m.sqrt64_unit(1.0 - r2);
-            out.dir = m.normalize_near_unit(d3(((ux * cs) * r2s + (vx * sn) * r2s) + w.x * s1, (vy * sn) * r2s + w.y * s1,
-                                               ((uz * cs) * r2s + (vz * sn) * r2s) + w.z * s1));  // :103-107
+            set_bounce_dir(m, out, d3(((ux * cs) * r2s + (vx * sn) * r2s) + w.x * s1, (vy * sn) * r2s + w.y * s1,
+                                      ((uz * cs) * r2s + (vz * sn) * r2s) + w.z * s1));  // :103-107
             out.org = hit_point;
             out.ctr = rng.ctr;
             return;
@@ -1688,7 +1783,7 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
 #else
     m.sincos_draw(trig_ahead, sn, cs);
 #endif
-    out.dir = m.normalize_near_unit((u * cs) * r2s + (v * sn) * r2s + w * m.sqrt64_unit(1.0 - r2));  // :103-107
+    set_bounce_dir(m, out, (u * cs) * r2s + (v * sn) * r2s + w * m.sqrt64_unit(1.0 - r2));  // :103-107
     out.org = hit_point;
     out.ctr = rng.ctr;
 }
@@ -1708,9 +1803,7 @@ __device__ __forceinline__ bool path_shade_with(MI& m, const Scene& sc, const in
         push(depth, id);
         depth++;
         pc.bounces++;
-        org = o.org;
-        dir = o.dir;
-        rng.ctr = o.ctr;
+        shade_commit(o, org, dir, rng);
     } else {
         rng.ctr += (unsigned)o.draws * 0x9E3779B9u;
     }
@@ -1753,9 +1846,7 @@ __device__ __forceinline__ bool path_shade_spec(const Scene& sc, const int id, c
         push(depth, id);
         depth++;
         pc.bounces++;
-        org = o.org;
-        dir = o.dir;
-        rng.ctr = o.ctr;
+        shade_commit(o, org, dir, rng);
     } else if (stream_after_end) {
         rng.ctr += (unsigned)o.draws * 0x9E3779B9u;
     }
@@ -1789,9 +1880,7 @@ __device__ __forceinline__ bool path_shade_spec_fix(const Scene& sc, int& id, do
         push(depth, id);
         depth++;
         pc.bounces++;
-        org = o.org;
-        dir = o.dir;
-        rng.ctr = o.ctr;
+        shade_commit(o, org, dir, rng);
     } else if (stream_after_end) {
         rng.ctr += (unsigned)o.draws * 0x9E3779B9u;
     }

@@ -451,10 +451,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 lnrm[i * 3 + 2] = P.scene.plane[(size_t)i * 16 + 5];
                 continue;
             }
-            const double ms = (double)__builtin_sqrtf((float)gsrc[i * 4 + 3]);
-            lnrm[i * 3] = ms;
-            lnrm[i * 3 + 1] = refined_rcp_or_nan(ms);
-            reinterpret_cast<float*>(lnrm + i * 3 + 2)[0] = (float)gsrc[i * 4 + 3];  // r*r as the float it is
+            fill_norm_row(lnrm + i * 3, gsrc[i * 4 + 3]);
         }
         __syncthreads();  // one wave per block: orders the LDS writes before the reads
     }
@@ -850,8 +847,8 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             push(depth, sid);
             depth++;
             org = o.org;
-            dir = o.dir;
-            rng.ctr = o.ctr;
+            dir = bounce_dir(o);
+            rng.ctr = o.ctr;  // (two draws on from the roulette's, which this loop makes itself: not shade_commit's three)
             have_fresh_rays = true;
         }
         while (fq_count > 0u) fold_pass(ModeWhole{});
