@@ -19,7 +19,14 @@ extern "C" {
  * math_probe_kernel (csrc/rtm_seam_kernels.h); ops 32..47: the tolerance row's arithmetic — one-ulp square root, division and
  * reciprocal, a contracted multiply-add, its sin / cos, the unfused fold step; 45..47: the reference forms of 41..43; 48: of 32;
  * 49..51: a sphere's row of the normal table for r * r = a[i] (csrc/rtm_kernels_tol.hip).  Ops 39, 40, 42, 43, 46, 47 take a draw's
- * integer: a[i] must be an ODD integer below 2^24 (42 / 43 convert it to an integer, the others round it: other operands differ) */
+ * integer: a[i] must be an ODD integer below 2^24 (42 / 43 convert it to an integer, the others round it: other operands differ).
+ * Ops 52 .. 54: the discriminant stage of the tolerance row's search for a sphere whose centre is on a coordinate axis, on
+ * caller-given rays.  Records of 8 doubles, n a multiple of 8: a = (origin x, y, z, direction x, y, z, unused, unused),
+ * b = (axis 1 / 2 / 3 for x / y / z, the centre's coordinate c on it, r * r, -2 c, K = c c - r * r, unused x 3; the last two as
+ * rtm_debug_axis_rows returns them), out = (b, D4, 0 x 6) with t = b -+ sqrt(D4).  52: the form of rounds 4 to 8, p = c - o_a
+ * with the shared sums of the foreign products (reads c and r * r) — the reference of 53; 53: the expanded form the search
+ * runs, b = c d_a - o.d, D4 = b b - ((-2 c) o_a + o.o + K) (reads c, -2 c and K); 54: the same for a sphere of a signature's
+ * shared-K group, D4 = b b - ((-2 c) o_a + (o.o + K)).  Any other axis value gives (0, 0). */
 int rtm_debug_math_probe(int op, const double* a, const double* b, size_t n, double* out);
 /* The tolerance row's sin / cos table as the HOST builds it for every device (no device is touched; runs in the CPU test
  * suite): out[2 i], out[2 i + 1] = sin, cos of i 2 pi / entries, evaluated in long double and rounded to double once.  The
@@ -66,6 +73,14 @@ int rtm_debug_scene_facts(const rtm_sphere* spheres, size_t n, uint64_t facts[2]
  * the mask those kernels get: bit i = object i's emission is not (+0, +0, +0), all ones where facts[0] is 0.  (RTM_DEBUG_ZERO_SKIP=0
  * in the environment of a render call makes it queue and fold every path end whatever these facts say.) */
 int rtm_debug_zero_term_facts(const rtm_sphere* spheres, size_t n, uint64_t facts[2]);
+/* The axis rows a scene object of these spheres keeps behind its geometry rows for the tolerance row's search, on the HOST (no
+ * device is touched; n <= 32): rows[4 i .. 4 i + 3] = (c, -2 c, K, e) for a sphere that rtm_debug_scene_facts gives an axis, c its
+ * centre's coordinate on that axis and K = c c - r * r from the float product r * r as the geometry row stores it, formed in
+ * long double (one fused operation) and rounded to double; zeros for any other sphere.  e, the same in every axis row and not
+ * read by the kernels: the reach 2^k within which the host has proven the expanded form safe for this scene — no axis sphere can
+ * hit itself, distances stay a sixteenth under the smallest threshold, every sphere lies within it (csrc/rtm_path.h:
+ * kSceneAxisReachShift) —, 0 where it has not: such a scene, or a camera beyond the reach, takes the plain kernels. */
+int rtm_debug_axis_rows(const rtm_sphere* spheres, size_t n, double* rows);
 /* isolated nearest-hit / shading loops timed with s_memtime (profiles/component_bench.py) */
 int rtm_debug_component_bench(int which, const rtm_sphere* spheres, size_t n, int reps, int blocks, int lds_pad,
                               double* cycles_per_rep);

@@ -228,6 +228,7 @@ DEBUG_SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_debug_scene_facts": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtm_debug_zero_term_facts": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtm_debug_axis_rows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtm_debug_grid_build": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.c_size_t]),
     "rtm_debug_denoise_variance_kernel": (C.c_int, [C.c_int, _P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int,

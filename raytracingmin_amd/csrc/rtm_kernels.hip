@@ -118,6 +118,83 @@ static uint64_t axis_pattern(const double* geom, size_t n) {
     }
     return pat;
 }
+// The tolerance unit's AXIS ROWS (rtm_path.h: sphere_disc under RTM_TOL), one of 32 bytes per sphere of a scene of at most 32,
+// kept behind the n geometry rows of an rtm_scene (row n + i belongs to sphere i): for a sphere with pattern a != 0 and centre
+// coordinate c on that axis (c, -2 c, K = c c - r*r, e), for pattern 0 zeros (unused).  K from the row's own c and its stored
+// r*r (geom.w, the float product widened) as one fused long-double operation: TWO roundings, one to 64 bits and one to double —
+// exact for the shipped scenes, the Cornell walls' 200100 among them.  e (not read by the kernels; rtm_debug_axis_rows shows
+// it): the reach 2^k of the expanded form's envelope where the host has proven the SCENE inside it (axis_reach_bits), else 0.  Derived data of the geometry rows: nothing
+// new enters a scene's cache key.
+constexpr size_t kAxisRowsMax = 32;
+static size_t axis_row_count(size_t n) { return n <= kAxisRowsMax ? n : 0; }
+// rtm_path.h, kSceneAxisReachShift: the bound on the expanded q's rounding error for origins within `reach` of the origin
+static double axis_q_err(double own_reach, double reach) {
+    const double m = own_reach > reach ? own_reach : reach;
+    return std::ldexp(m * m, -49);
+}
+static bool axis_self_hit_safe(double c, double r2) {  // test (A)
+    const double r = std::sqrt(r2), own = std::fabs(c) + r;
+    return r > 0.0 && std::isfinite(own) && axis_q_err(own, 0.0) / (2.0 * r) <= std::ldexp((double)1e-5f, -17);
+}
+// SceneView::fold_flags' bits 16..23 (kSceneAxisReachShift): 128 + k where every axis sphere passes (A), and (B) for origins
+// within 2^k, and the whole scene lies within 2^k; 0 where that is not proven (no axis sphere, more than 32 spheres, a sphere
+// outside the envelope)
+static unsigned axis_reach_bits(const double* geom, size_t n, uint64_t pat) {
+    if (axis_row_count(n) == 0 || pat == 0) return 0u;
+    double extent = 0.0, reach = kCompactExtent;
+    for (size_t i = 0; i < n; ++i) {
+        const double* g = geom + i * 4;
+        const double own = std::sqrt(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]) + std::sqrt(std::fabs(g[3]));
+        if (!std::isfinite(own)) return 0u;
+        extent = own > extent ? own : extent;
+        const unsigned a = (unsigned)(pat >> (2 * i)) & 3u;
+        if (a == 0u) continue;
+        if (!axis_self_hit_safe(g[a - 1u], g[3])) return 0u;
+        // (B): err(rho) / (2 r) <= 2^-4 x 1e-5f  <=>  rho^2 <= 2^46 x 1e-5f x r
+        const double rho = std::sqrt(std::ldexp((double)1e-5f * std::sqrt(g[3]), 46));
+        reach = rho < reach ? rho : reach;
+    }
+    const int k = std::ilogb(reach);  // 2^k <= reach
+    if (!(reach >= 1.0) || !(extent <= std::ldexp(1.0, k))) return 0u;
+    return (unsigned)(128 + k) << kSceneAxisReachShift;
+}
+static void axis_rows(const double* geom, size_t n, uint64_t pat, double* rows) {
+    const unsigned e = (axis_reach_bits(geom, n, pat) >> kSceneAxisReachShift) & kSceneAxisReachMask;
+    const double reach = e ? std::ldexp(1.0, (int)e - 128) : 0.0;
+    for (size_t i = 0; i < axis_row_count(n); ++i) {
+        const unsigned a = (unsigned)(pat >> (2 * i)) & 3u;
+        double* row = rows + i * 4;
+        row[0] = row[1] = row[2] = row[3] = 0.0;
+        if (a == 0u) continue;
+        const double c = geom[i * 4 + (a - 1u)];
+        row[0] = c;
+        row[1] = -2.0 * c;
+        row[2] = (double)fmal((long double)c, (long double)c, -(long double)geom[i * 4 + 3]);
+        row[3] = reach;
+    }
+}
+// SceneView::fold_flags' bits 8..15 (kSceneSharedKShift): among the first 8 spheres, the largest group of axis spheres whose
+// axis rows hold one K bit for bit (the lowest group on a tie); 0 where no two do
+static unsigned shared_k_bits(const double* geom, size_t n, uint64_t pat) {
+    if (axis_row_count(n) == 0) return 0u;
+    std::vector<double> rows(n * 4);
+    axis_rows(geom, n, pat, rows.data());
+    unsigned best = 0u, best_count = 1u;
+    for (size_t i = 0; i < n && i < 8; ++i) {
+        if (((pat >> (2 * i)) & 3u) == 0u) continue;
+        unsigned mask = 0u, count = 0u;
+        for (size_t j = i; j < n && j < 8; ++j)
+            if (((pat >> (2 * j)) & 3u) != 0u && std::memcmp(&rows[j * 4 + 2], &rows[i * 4 + 2], sizeof(double)) == 0) {
+                mask |= 1u << j;
+                ++count;
+            }
+        if (count > best_count) {
+            best = mask;
+            best_count = count;
+        }
+    }
+    return best << kSceneSharedKShift;
+}
 
 // SceneView::fold_flags from flattened material rows (colorKD[3], emission[3], kd, kd * 2^24): see kFoldNoLevelEmission
 // kSceneCompact from flattened geometry rows (cx, cy, cz, r*r): every sphere within kCompactExtent of the origin
@@ -591,6 +668,14 @@ int zero_term_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts) {
     facts[0] = zero_term_flags_of(hm.data(), n, &facts[1]) != 0u ? 1u : 0u;
     return RTM_OK;
 }
+// rtm_debug_axis_rows: axis_rows on the HOST, as a scene object of these spheres gets them (tests/test_axis_disc_host.py)
+int axis_rows_host(const rtm_sphere* sp, size_t n, double* rows) {
+    if ((!sp && n) || !rows || n > kAxisRowsMax) return RTM_ERR_INVALID_ARGUMENT;
+    std::vector<double> hg, hm;
+    flatten_scene(sp, n, hg, hm);
+    axis_rows(hg.data(), n, axis_pattern(hg.data(), n), rows);
+    return RTM_OK;
+}
 
 // Build + upload; a scene that gets no grid keeps sc.grid empty (not an error).  `hg`: the host copy of the geometry rows.
 // `hm`: the material rows (kd in column 6), or null.
@@ -670,8 +755,11 @@ static int scene_build_host(rtm_scene& sc, const rtm_sphere* sp, size_t n, int d
     std::vector<double> hg, hm, hs;
     flatten_scene(sp, n, hg, hm, &hs);
     sc.axis_pat = axis_pattern(hg.data(), n);
-    sc.fold_flags = fold_flags_of(hm.data(), n) | compact_flag_of(hg.data(), n) | zero_term_flags_of(hm.data(), n, &sc.emit_mask);
-    int rc = sc.geom.alloc_pooled((n ? n : 1) * 4 * sizeof(double), device);
+    sc.fold_flags = fold_flags_of(hm.data(), n) | compact_flag_of(hg.data(), n) | zero_term_flags_of(hm.data(), n, &sc.emit_mask) |
+                    shared_k_bits(hg.data(), n, sc.axis_pat) | axis_reach_bits(hg.data(), n, sc.axis_pat);
+    hg.resize((n + axis_row_count(n)) * 4);  // the axis rows behind the geometry rows
+    axis_rows(hg.data(), n, sc.axis_pat, hg.data() + n * 4);
+    int rc = sc.geom.alloc_pooled((hg.empty() ? 1 : hg.size() / 4) * 4 * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.mat.alloc_pooled((n + 1) * 8 * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.aux.alloc_pooled(scene_aux_doubles(n) * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.surf.alloc_pooled(hs.size() * sizeof(double), device);
@@ -689,7 +777,7 @@ static int scene_build_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n,
     RTM_HIP_CHECK(hipSetDevice(device));
     sc.device = device;
     sc.n = n;
-    int rc = sc.geom.alloc_pooled((n ? n : 1) * 4 * sizeof(double), device);
+    int rc = sc.geom.alloc_pooled((n ? n + axis_row_count(n) : 1) * 4 * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.mat.alloc_pooled((n + 1) * 8 * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.aux.alloc_pooled(scene_aux_doubles(n) * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.surf.alloc_pooled((n ? n : 1) * 4 * sizeof(double), device);
@@ -703,9 +791,13 @@ static int scene_build_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n,
         std::vector<double> rows(n * 4);
         RTM_HIP_CHECK(hipMemcpy(rows.data(), sc.geom.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
         sc.axis_pat = axis_pattern(rows.data(), n);
+        std::vector<double> arows(n * 4);  // ... and its axis rows go behind them
+        axis_rows(rows.data(), n, sc.axis_pat, arows.data());
+        RTM_HIP_CHECK(hipMemcpy(sc.geom.as<double>() + n * 4, arows.data(), arows.size() * sizeof(double), hipMemcpyHostToDevice));
         std::vector<double> mrows((n + 1) * 8);
         RTM_HIP_CHECK(hipMemcpy(mrows.data(), sc.mat.p, mrows.size() * sizeof(double), hipMemcpyDeviceToHost));
-        sc.fold_flags = fold_flags_of(mrows.data(), n) | compact_flag_of(rows.data(), n) | zero_term_flags_of(mrows.data(), n, &sc.emit_mask);
+        sc.fold_flags = fold_flags_of(mrows.data(), n) | compact_flag_of(rows.data(), n) | zero_term_flags_of(mrows.data(), n, &sc.emit_mask) |
+                        shared_k_bits(rows.data(), n, sc.axis_pat) | axis_reach_bits(rows.data(), n, sc.axis_pat);
     }
     if (n < kGridMinSpheres) return RTM_OK;
     std::vector<double> hg(n * 4);  // the grid is built on the host: the geometry rows come back once

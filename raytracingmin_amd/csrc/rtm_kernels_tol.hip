@@ -44,6 +44,15 @@ static bool compact_launch(const RenderParams& P) {
     const double cam = std::sqrt(P.cam_org.x * P.cam_org.x + P.cam_org.y * P.cam_org.y + P.cam_org.z * P.cam_org.z);
     return (P.scene.fold_flags & kSceneCompact) != 0u && cam <= kCompactExtent;
 }
+// ... and they take the discriminants of axis spheres in the expanded form (rtm_path.h: sphere_disc), whose rounding error grows
+// with (|c| + r)^2 and |o|^2, not with r^2: only for a scene the host has proven inside that form's envelope
+// (kSceneAxisReachShift: no sphere can hit itself, distances stay a sixteenth under the smallest threshold) seen by a camera
+// within the same reach.  A small sphere far out on an axis fails it; the scene then runs the plain exact-n kernels.
+static bool expanded_form_launch(const RenderParams& P) {
+    const unsigned e = (P.scene.fold_flags >> kSceneAxisReachShift) & kSceneAxisReachMask;
+    const double cam = std::sqrt(P.cam_org.x * P.cam_org.x + P.cam_org.y * P.cam_org.y + P.cam_org.z * P.cam_org.z);
+    return e != 0u && cam <= std::ldexp(1.0, (int)e - 128);
+}
 
 // The row's two shapes: a depth cap of at most 8 (kTolCapped: packed records, in-wave stealing) and any other depth (kTolAny:
 // records packed by position and the pooled stack from level 16, rtm_render_kernel.h; no stealing, a whole tile stores its
@@ -60,7 +69,16 @@ static void launch_n(const RenderParams& P, unsigned grid, size_t lds_pad, hipSt
     constexpr int LDS_D = (F & kPackL) != 0 ? 0 : 16;
     unsigned unit_tab;
     render_lds_bytes<F, uint8_t, LDS_D>(P.scene.n, lds_pad, &unit_tab);
-    const bool axis = P.mode == RTM_MODE_REPAIRED && unit_tab == 1u && compact_launch(P);  // rtm_path.h: sphere_disc
+    const bool axis = P.mode == RTM_MODE_REPAIRED && unit_tab == 1u && compact_launch(P) && expanded_form_launch(P);  // rtm_path.h: sphere_disc
+    // (axis_pat holds the signature's low 16 bits, fold_flags' bits 8..15 what goes above them: the spheres that share one K)
+    const unsigned shared_k = (P.scene.fold_flags >> kSceneSharedKShift) & kSceneSharedKMask;
+#define RTM_AXIS_CASE(k, sig)                                                                                    \
+    if (P.scene.n == k && P.scene.axis_pat == ((sig) & 0xFFFFu) && shared_k == ((sig) >> kAxisSharedKShift) && axis) { \
+        launch_tiles<MathFast, F, axis_unroll(k, sig), uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream); \
+        return;                                                                                                  \
+    }
+    RTM_AXIS_CASE(7, kAxisSigCornell7Walls)  // the shipped box: its six walls share one K
+#undef RTM_AXIS_CASE
 #define RTM_AXIS_CASE(k, sig)                                                                                    \
     if (P.scene.n == k && P.scene.axis_pat == sig && axis) {                                                     \
         launch_tiles<MathFast, F, axis_unroll(k, sig), uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream); \
@@ -104,11 +122,35 @@ static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hip
 // (MathSpecT::sqrt64_unit: the light sequence), 45 the light root with its half by a multiply (the form op 41 ran until round 8:
 // its reference), 46 / 47 ops 42 / 43 with the angle split made in doubles (until round 8: their reference), 48 op 32 with its
 // half by a multiply (the full root's reference), 49 / 50 / 51 the normal table's row for a sphere with r * r = x: the length, its
-// refined reciprocal and the float r * r, NaN where the reciprocal is (fill_norm_row, as the render kernels' prologue calls it)
+// refined reciprocal and the float r * r, NaN where the reciprocal is (fill_norm_row, as the render kernels' prologue calls it),
+// 52 / 53 an axis sphere's discriminant stage on caller-given rays, in records of 8 doubles: a = (ox, oy, oz, dx, dy, dz, -, -),
+// b = (pattern 1 / 2 / 3, c, r * r, -2 c, K, -, -, -), out = (b, D4, 0 ..) — 52 the form of rounds 4 to 8 from (c, r * r)
+// (rtm_path.h: sphere_disc_ref, the reference), 53 the expanded form from the axis row (c, -2 c, K) as the search runs it now,
+// 54 the same for a sphere of the signature's shared-K group (oo + K formed first)
 __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, size_t n,
                                       double* __restrict__ out, const double2* __restrict__ tab) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (op >= 52 && op <= 54) {  // records of 8 doubles: every thread of a record computes it, each stores its own slot
+        const size_t j = i & ~(size_t)7;
+        double bb = 0.0, D4 = 0.0;
+        if (b && j + 7 < n) {
+            const D3 org = d3(a[j], a[j + 1], a[j + 2]), dir = d3(a[j + 3], a[j + 4], a[j + 5]);
+            const unsigned pat = (unsigned)b[j];
+            const double c = b[j + 1];
+            if (pat >= 1u && pat <= 3u) {
+                if (op == 52) {
+                    const double4 g = double4{pat == 1u ? c : 0.0, pat == 2u ? c : 0.0, pat == 3u ? c : 0.0, b[j + 2]};
+                    sphere_disc_ref(g, pat, org, dir, AxisSharedRef(org, dir), bb, D4);
+                } else {
+                    const AxisShared A(org, dir);
+                    sphere_disc(double4{}, AxisRow{c, b[j + 3], b[j + 4]}, pat, op == 54, A.oo + b[j + 4], org, dir, A, bb, D4);
+                }
+            }
+        }
+        out[i] = (i & 7) == 0 ? bb : (i & 7) == 1 ? D4 : 0.0;
+        return;
+    }
     const double x = a[i], y = b ? b[i] : 0.0;
     double r = 0.0, s, c;
     switch (op) {

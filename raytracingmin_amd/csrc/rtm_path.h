@@ -629,7 +629,9 @@ struct SceneView {
     // two bits per sphere for the first 32 (sphere i: bits 2i, 2i+1; set by the host where it holds the geometry, else 0):
     // 1 / 2 / 3 = the centre's only non-zero coordinate is x / y / z (the other two are +-0), 0 = anything else.  The
     // chunked search of the LDS-table kernels evaluates such a sphere's discriminant from per-ray shared products
-    // (sphere_disc below): the reference's own roundings, fewer instructions.
+    // (sphere_disc below): the reference's own roundings, fewer instructions.  Non-zero only in the view of an rtm_scene,
+    // whose geometry allocation holds the n axis rows (c, -2 c, c c - r*r, 0) behind the n geometry rows (rtm_kernels.hip:
+    // axis_rows; the tolerance unit's sphere_disc reads row n + i for sphere i).
     unsigned long long axis_pat = 0ull;
     // kFoldNoLevelEmission (set by the host where it holds the material rows, else 0): every object a path can bounce off
     // (kd > 0) has emission (+0, +0, +0) and a colorKD without sign bits, and no emission has a sign bit — the fold's
@@ -650,6 +652,23 @@ constexpr unsigned kFoldZeroTermSkippable = 4u;
 // ... and bit 1, kSceneCompact: every |centre| + radius is finite and at most 1e7 (the launcher adds the camera): what the
 // tolerance unit's light search roots ask for (seq_sqrt_batch)
 constexpr unsigned kSceneCompact = 2u;
+// ... and bits 8..15 (set by the host where it holds the geometry, else 0): the spheres among the first 8 that form the largest
+// group of axis spheres whose axis rows hold ONE K = c c - r*r, bit for bit — at least two, the lowest group on a tie; the six
+// walls of the Cornell box: 0x7E.  The tolerance unit's launcher extends the axis signature with it (kAxisSharedKShift).
+constexpr unsigned kSceneSharedKShift = 8u, kSceneSharedKMask = 0xFFu;
+// ... and bits 16..23 (likewise): the ENVELOPE of the tolerance unit's expanded axis discriminant (sphere_disc), 0 = not proven,
+// else 128 + k: every axis sphere passes the two tests below for origins within 2^k of the scene's origin, and every sphere
+// of the scene lies within that reach (the launcher adds the camera).  The expanded q = (-2 c) o_a + o.o + K sums three terms
+// of up to (|c| + r)^2 or |o|^2 where the form of rounds 4 to 8 squared the EXACT difference c - o_a: its rounding error is
+// bounded by err(o) = 2^-49 max(|c| + r, |o|)^2 (three roundings of partial sums below 4 max^2), not by a multiple of r^2.
+//   (A) a bounce ray leaving sphere i (|o| <= |c| + r) has q = 0 in real arithmetic and the far root t2 = err / (2 r cos theta)
+//       with it; it must stay under Intersect's 1e-5f down to cos theta = 2^-17 (a cosine-weighted bounce is flatter than that
+//       once in 2^34): err(|c| + r) / (2 r) <= 2^-17 x 1e-5f.  A Cornell wall: 3.6e-11 against 7.6e-11; a sphere of radius 100
+//       at 1e6 fails by seven orders and WOULD hit itself (tests/test_axis_disc_host.py shows it in numpy).
+//   (B) from any origin within the reach a distance to sphere i is off by err(reach) / (2 r) at normal incidence: at most a
+//       sixteenth of 1e-5f, the smallest threshold a distance is compared with.
+// A scene outside the envelope takes the plain exact-n kernels (p_o formed as the reference does).
+constexpr unsigned kSceneAxisReachShift = 16u, kSceneAxisReachMask = 0xFFu;
 constexpr double kCompactExtent = 1e7;
 
 // png::PlaneObject::Intersect as this build completes it (include/rtm.h): the reference's first line
@@ -923,26 +942,60 @@ __device__ __forceinline__ void accept_batch(const double (&b)[K], const double 
 // The only bits that can differ are the SIGNS OF ZEROS (0 - (+0) = +0 where -(+0) = -0): a zero product changes no sum it
 // is added to unless the sum is zero itself; b = +-0 gives the same b b, t1, t2 up to a zero's sign, and a zero t is
 // rejected by t < 1e-5f either way.  16 instructions -> 10 (x, y) / 8 (z) without contraction.
-// The tolerance unit (RTM_TOL) also shares the SUMS of the two foreign products (one rounding placed differently, the same
-// error size as the contraction it already has): 11 -> 5.
-struct AxisShared {
+// The tolerance unit (RTM_TOL) shared the SUMS of the two foreign products until round 9 (one rounding placed differently,
+// the same error size as the contraction it already has): 11 -> 5 per sphere behind 10 per ray (AxisSharedRef and
+// sphere_disc_ref below: kept as the reference form of rtm_debug_math_probe op 52).  Since round 9 it takes the EXPANDED
+// form, which never forms p_o: with od = org . dir and oo = org . org once per ray (3 + 3 instructions) and, per sphere, the
+// host's axis row (c, -2 c, K = c c - r*r) behind the scene's geometry rows (rtm_kernels.hip: axis_rows),
+//   b  = (c - o_a) d_a - (foreign products)      = c d_a - od                          (1 fma)
+//   pp - r*r = (c - o_a)^2 + (foreign squares) - r*r = (-2 c) o_a + oo + K             (1 fma + 1 add)
+//   D4 = b b - (pp - r*r)                                                              (1 fma)
+// 4 per sphere behind 6 per ray; and where the signature says that a group of the spheres shares one K (bits 16.. of SIG, from
+// SceneView::fold_flags' bits 8..15: the launcher's proof), oo + K is formed once for the group and a member costs 3:
+//   pp - r*r = (-2 c) o_a + (oo + K)                                                   (1 fma)
+// Within the envelope the host proves per scene (kSceneAxisReachShift above: the launcher's gate) the numerics do not get
+// worse: for a Cornell wall (c = +-10010, r*r = 1e8) the reference form subtracts two numbers near 1e8 on the device, here
+// the host cancels them (K = 200100 exactly) and every term of pp - r*r is below 4e5.  OUTSIDE it they do — a small sphere
+// far out on an axis: three terms of size c^2 cancel where c - o_a was exact —, and such a scene does not get these kernels.
+// DESIGN.md §4 has the error table, the envelope and the margin to primary_tie_risk.
 #if RTM_TOL
-    double Pyz, Pxz, Pxy, Qyz, Qxz, Qxy;
+struct AxisRow {
+    double c, m2c, K;
+};
+// row i of the table behind `geom` (rows n .. 2 n - 1 of an rtm_scene's geometry allocation), wave-uniform: scalar loads
+__device__ __forceinline__ AxisRow load_axis_row_uniform(const double4* geom, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) double* ConstF64Ptr;
+    ConstF64Ptr p = (ConstF64Ptr)(unsigned long long)(geom + i);
+    return AxisRow{p[0], p[1], p[2]};
 #else
-    double Px, Py, Pz, Pxy, Qx, Qy, Qz, Qxy;
+    return AxisRow{geom[i].x, geom[i].y, geom[i].z};
 #endif
+}
+struct AxisShared {
+    double od, oo;
+    __device__ __forceinline__ AxisShared(const D3 org, const D3 dir) : od(dot(org, dir)), oo(dot(org, org)) {}
+};
+struct AxisSharedRef {
+    double Pyz, Pxz, Pxy, Qyz, Qxz, Qxy;
+    __device__ __forceinline__ AxisSharedRef(const D3 org, const D3 dir) {
+        const double px = org.x * dir.x, py = org.y * dir.y, pz = org.z * dir.z;
+        const double qx = org.x * org.x, qy = org.y * org.y, qz = org.z * org.z;
+        Pyz = py + pz; Pxz = px + pz; Pxy = px + py;
+        Qyz = qy + qz; Qxz = qx + qz; Qxy = qx + qy;
+    }
+};
+#else
+struct AxisShared {
+    double Px, Py, Pz, Pxy, Qx, Qy, Qz, Qxy;
     __device__ __forceinline__ AxisShared(const D3 org, const D3 dir) {
         const double px = org.x * dir.x, py = org.y * dir.y, pz = org.z * dir.z;
         const double qx = org.x * org.x, qy = org.y * org.y, qz = org.z * org.z;
-#if RTM_TOL
-        Pyz = py + pz; Pxz = px + pz; Pxy = px + py;
-        Qyz = qy + qz; Qxz = qx + qz; Qxy = qx + qy;
-#else
         Px = px; Py = py; Pz = pz; Pxy = px + py;
         Qx = qx; Qy = qy; Qz = qz; Qxy = qx + qy;
-#endif
     }
 };
+#endif
 // Axis signatures that have an instantiation of the exact-n kernels (nearest_hit: UNROLL <= -1000; the launchers compare
 // SceneView::axis_pat and the sphere count), RTM_AXIS_SIGNATURES below: the shipped scenes whose spheres sit on the axes.
 // ExampleScene/cornellBoxSetting.json — the light on the y axis and the six wall spheres on +x, -x, +y, -y, +z, -z
@@ -955,29 +1008,63 @@ constexpr unsigned kAxisSigSimple5 = (1u << 2) | (1u << 4) | (2u << 6) | (2u << 
 // settingData.json: the light on the y axis, a sphere at the origin, one on the x axis
 constexpr unsigned kAxisSigSetting3 = 2u | (1u << 4);
 constexpr int axis_unroll(const int n, const unsigned sig) { return -(1000 + n + 8 * (int)sig); }
+// The tolerance unit's extension of a signature: bit 16 + i = sphere i belongs to the group that shares one K (kSceneSharedKShift;
+// sphere_disc's expanded form).  The Cornell box with its six walls of one radius at one distance:
+constexpr unsigned kAxisSharedKShift = 16u;
+constexpr unsigned kAxisSigCornell7Walls = kAxisSigCornell7 | (0x7Eu << kAxisSharedKShift);
 // (n, signature) pairs with an instantiation: X(n, sig) for each
 #define RTM_AXIS_SIGNATURES(X) X(7, kAxisSigCornell7) X(5, kAxisSigSimple5) X(3, kAxisSigSetting3)
 // b and D4 of sphere g (src/SettingData.cpp:198-200); pat: 0 general, 1 / 2 / 3 the centre is on the x / y / z axis
+#if RTM_TOL
+// (the tolerance unit: an axis sphere from its axis row `r` — g is not read —, a general one from its geometry row g;
+// shared_k: the sphere belongs to the signature's group of one K and ooK = oo + K is the group's, r.K is not read)
+__device__ __forceinline__ void sphere_disc(const double4 g, const AxisRow r, const unsigned pat, const bool shared_k,
+                                            const double ooK, const D3 org, const D3 dir, const AxisShared& A, double& b,
+                                            double& D4) {
+    if (pat != 0u) {
+        const double oa = pat == 1u ? org.x : pat == 2u ? org.y : org.z;
+        const double da = pat == 1u ? dir.x : pat == 2u ? dir.y : dir.z;
+        b = r.c * da - A.od;
+        const double c = shared_k ? r.m2c * oa + ooK : r.m2c * oa + A.oo + r.K;  // |c_sphere - org|^2 - r*r
+        D4 = b * b - c;
+    } else {
+        const D3 p_o = d3(g.x - org.x, g.y - org.y, g.z - org.z);  // src/SettingData.cpp:198
+        b = dot(p_o, dir);                                          // :199
+        D4 = b * b - dot(p_o, p_o) + g.w;                           // :200
+    }
+}
+// ... and the form it had until round 9 (rtm_debug_math_probe op 52: the reference of op 53)
+__device__ __forceinline__ void sphere_disc_ref(const double4 g, const unsigned pat, const D3 org, const D3 dir,
+                                                const AxisSharedRef& A, double& b, double& D4) {
+    if (pat == 1u) {
+        const double px = g.x - org.x;
+        b = px * dir.x - A.Pyz;
+        D4 = b * b - (px * px + A.Qyz) + g.w;
+    } else if (pat == 2u) {
+        const double py = g.y - org.y;
+        b = py * dir.y - A.Pxz;
+        D4 = b * b - (py * py + A.Qxz) + g.w;
+    } else if (pat == 3u) {
+        const double pz = g.z - org.z;
+        b = pz * dir.z - A.Pxy;
+        D4 = b * b - (A.Qxy + pz * pz) + g.w;
+    } else {
+        const D3 p_o = d3(g.x - org.x, g.y - org.y, g.z - org.z);
+        b = dot(p_o, dir);
+        D4 = b * b - dot(p_o, p_o) + g.w;
+    }
+}
+#else
 __device__ __forceinline__ void sphere_disc(const double4 g, const unsigned pat, const D3 org, const D3 dir,
                                             const AxisShared& A, double& b, double& D4) {
     if (pat == 1u) {
         const double px = g.x - org.x;
-#if RTM_TOL
-        b = px * dir.x - A.Pyz;
-        D4 = b * b - (px * px + A.Qyz) + g.w;
-#else
         b = px * dir.x - A.Py - A.Pz;
         D4 = b * b - (px * px + A.Qy + A.Qz) + g.w;
-#endif
     } else if (pat == 2u) {
         const double py = g.y - org.y;
-#if RTM_TOL
-        b = py * dir.y - A.Pxz;
-        D4 = b * b - (py * py + A.Qxz) + g.w;
-#else
         b = py * dir.y - A.Px - A.Pz;
         D4 = b * b - (A.Qx + py * py + A.Qz) + g.w;
-#endif
     } else if (pat == 3u) {
         const double pz = g.z - org.z;
         b = pz * dir.z - A.Pxy;
@@ -988,6 +1075,7 @@ __device__ __forceinline__ void sphere_disc(const double4 g, const unsigned pat,
         D4 = b * b - dot(p_o, p_o) + g.w;                           // :200
     }
 }
+#endif
 
 // K consecutive spheres starting at i0 as ONE basic block: K independent Intersect evaluations
 // (independent dependency chains the scheduler interleaves), their square roots behind a single
@@ -1047,9 +1135,31 @@ __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, cons
         double b[K], D4[K], sq[K];
         if constexpr (SIG != 0u) {  // the scene's axis signature is a compile-time constant: sphere_disc's branches fold
             const AxisShared A(org, dir);
+#if RTM_TOL
+            double ooK = 0.0;
+#endif
             constexpr int PA = 2;  // spheres whose geometry is fetched together (an axis sphere needs 4 SGPRs, not 8)
 #pragma unroll
             for (int k0 = 0; k0 < K; k0 += PA) {
+#if RTM_TOL
+                // (an axis-signature chunk is the whole scene, i0 == 0 and K == n: sphere i's axis row is row K + i)
+                constexpr unsigned KM = SIG >> kAxisSharedKShift;  // the spheres that share one K: oo + K once, at the first
+                double4 g[PA] = {};
+                AxisRow r[PA] = {};
+#pragma unroll
+                for (int k = 0; k < PA; ++k)
+                    if (k0 + k < K) {
+                        if (((SIG >> (2 * (k0 + k))) & 3u) != 0u) r[k] = load_axis_row_uniform(sc.v.geom, K + i0 + k0 + k);
+                        else g[k] = sc.geom_uniform(i0 + k0 + k);
+                    }
+#pragma unroll
+                for (int k = 0; k < PA; ++k)
+                    if (k0 + k < K) {
+                        const bool shared_k = ((KM >> (k0 + k)) & 1u) != 0u;
+                        if (shared_k && (KM & ((1u << (k0 + k)) - 1u)) == 0u) ooK = A.oo + r[k].K;
+                        sphere_disc(g[k], r[k], (SIG >> (2 * (k0 + k))) & 3u, shared_k, ooK, org, dir, A, b[k0 + k], D4[k0 + k]);
+                    }
+#else
                 double4 g[PA];
 #pragma unroll
                 for (int k = 0; k < PA; ++k)
@@ -1057,6 +1167,7 @@ __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, cons
 #pragma unroll
                 for (int k = 0; k < PA; ++k)
                     if (k0 + k < K) sphere_disc(g[k], (SIG >> (2 * (k0 + k))) & 3u, org, dir, A, b[k0 + k], D4[k0 + k]);
+#endif
                 __builtin_amdgcn_sched_barrier(0);
             }
             // (the tolerance unit's axis-signature instantiations are launched for compact scenes only: light roots, above)
