@@ -203,7 +203,8 @@ int rtm_stream_release(int device, void* stream);
  * spheres_on_device != 0) and uploads the tables; it returns when they are resident, so the caller's
  * array may be freed at once.  A scene belongs to one device.
  * For an all-sphere scene of 64 spheres or more (not counting those that span the scene, like the Cornell walls) the
- * call also builds, on the host (~25 ms per 100 000 spheres plus the upload), a uniform grid over the spheres (~32 B x 6 per sphere +
+ * call also builds, on the host (~25 ms per 100 000 spheres plus the upload; rtm_scene_create_device builds the same grid on
+ * the device), a uniform grid over the spheres (~32 B x 6 per sphere +
  * 8 B per cell, ~2 cells per sphere): renders then find the reference loop's nearest hit (src/Renderer.cpp:58-73:
  * same object, same distance, same image) through the grid instead of testing every sphere for every cast
  * (rtm_options.variant 17; variant 0 picks it when the camera is within about two scene diagonals of the scene and no
@@ -216,6 +217,25 @@ int rtm_scene_create(const rtm_sphere* spheres, size_t n_spheres, int spheres_on
  * up to 255 objects (rtm_options.variant 0, 2 or 9) and by the general per-object kernel beyond (variant 1, which
  * may also be asked for); the other variants know spheres only and refuse them.  HOST pointer. */
 int rtm_scene_create_objects(const rtm_object* objects, size_t n_objects, int device, rtm_scene** out_scene);
+/* A scene from a DEVICE sphere array, built entirely on the device: for spheres that are produced there (a tensor, a particle
+ * step, an animation of a large scene).  The result is what rtm_scene_create(spheres_dev, n_spheres, 1, device, &s) returns for
+ * the same array in every observable way — the grid is the host builder's bit for bit (the same cells, lists in the same
+ * order, the same spheres tested by every ray), so renders, AOVs and mattes, their counters, variant 0's choice, the decision
+ * about an enclosing diffuse sphere, rtm_scene_size and every "no grid" outcome are the same — and differs in three:
+ *   - All device work is enqueued on `stream` (rtm_scene_create uses the device's null stream), so it is ordered after
+ *     whatever produced the array there.  The call returns once the tables are resident, after waiting for `stream`; the
+ *     array may be overwritten or freed at once.  Temporaries come from and return to the device's memory pool on `stream`.
+ *   - Per-sphere data never travels to the host (rtm_scene_create on a device array brings every geometry and material row
+ *     back for the host's grid builder and uploads the grid).  What crosses: 120 bytes down and two doubles up per
+ *     classification round (at most five), the cell-list entry count, the indices and rows of the spheres every ray tests
+ *     (at most 1024 of 44 bytes), the header up; and, for n_spheres <= 32, the rows the small-scene facts are read from, as
+ *     in rtm_scene_create.
+ *   - The arguments are checked before any device call: a null out_scene, null spheres_dev with n_spheres > 0, n_spheres >
+ *     0x7FFFFFFF or a negative device give RTM_ERR_INVALID_ARGUMENT.
+ * rtm_scene_destroy, its deferred release and the use records work as for any scene.
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbol up. */
+int rtm_scene_create_device(const rtm_sphere* spheres_dev, size_t n_spheres, int device, void* stream,
+                            rtm_scene** out_scene);
 int rtm_scene_destroy(rtm_scene* scene);
 size_t rtm_scene_size(const rtm_scene* scene);
 

@@ -59,6 +59,16 @@ int rtm_debug_grid_nearest(const rtm_sphere* spheres, size_t n, const double* or
  * (info is filled: call once without buffers for the sizes). */
 int rtm_debug_grid_build(const rtm_sphere* spheres, size_t n, uint64_t* info, double* pads, uint32_t* ranges, size_t ranges_cap,
                          uint32_t* items, size_t items_cap, int32_t* big, size_t big_cap);
+/* A scene object's grid as the DEVICE holds it, read back in rtm_debug_grid_build's format — for a scene built by
+ * rtm_scene_create (host builder, uploaded) as for one built by rtm_scene_create_device (device kernels): info[12] as above;
+ * ranges[2 x cells]; items[entries] = the low 29 bits of each record's fourth double (the sphere's index); big[...];
+ * extra[0] = the number of records (the one dummy record of a grid without entries included) whose four doubles are not the
+ * scene's geometry row of that index with the index OR-ed into the fourth, extra[1] = 1 where a diffuse sphere encloses the
+ * gridded ones from beyond the pads' reach (variant 0 then leaves the grid alone).  Any buffer and `extra` may be NULL.
+ * RTM_ERR_UNSUPPORTED: the scene has no grid; RTM_ERR_CAPACITY: a buffer is short (info and extra[1] are filled).  Waits for
+ * the scene's device. */
+int rtm_debug_scene_grid(const rtm_scene* scene, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items,
+                         size_t items_cap, int32_t* big, size_t big_cap, uint64_t extra[2]);
 /* What the host finds in a sphere array when it flattens it into the kernels' tables, on the HOST (no device is touched; runs in
  * the CPU test suite): facts[0] = two bits per sphere for the first 32 — 1 / 2 / 3: the centre's only coordinate that is not
  * +-0 is x / y / z (the axis-signature instantiations of the exact-n kernels, csrc/rtm_path.h: sphere_disc) —, facts[1] bit 0:

@@ -144,6 +144,7 @@ SIGNATURES = {
     "rtm_num_variants": (C.c_int, []),
     "rtm_variant_name": (C.c_char_p, [C.c_int]),
     "rtm_scene_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, _P(C.c_void_p)]),
+    "rtm_scene_create_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, _P(C.c_void_p)]),
     "rtm_scene_create_objects": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, _P(C.c_void_p)]),
     "rtm_scene_destroy": (C.c_int, [C.c_void_p]),
     "rtm_scene_size": (C.c_size_t, [C.c_void_p]),
@@ -231,6 +232,8 @@ DEBUG_SIGNATURES = {
     "rtm_debug_axis_rows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtm_debug_grid_build": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rtm_debug_scene_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]),
     "rtm_debug_denoise_variance_kernel": (C.c_int, [C.c_int, _P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int,
                                                     _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_debug_matte_rank": (C.c_int, [C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -49,6 +49,9 @@ int rtm_scene_create(const rtm_sphere* spheres, size_t n_spheres, int spheres_on
                      rtm_scene** out_scene) {
     RTM_GUARD(rtm::scene_create(spheres, n_spheres, spheres_on_device, device, out_scene))
 }
+int rtm_scene_create_device(const rtm_sphere* spheres_dev, size_t n_spheres, int device, void* stream, rtm_scene** out_scene) {
+    RTM_GUARD(rtm::scene_create_device(spheres_dev, n_spheres, device, stream, out_scene))
+}
 int rtm_scene_create_objects(const rtm_object* objects, size_t n_objects, int device, rtm_scene** out_scene) {
     RTM_GUARD(rtm::scene_create_objects(objects, n_objects, device, out_scene))
 }
@@ -212,6 +215,10 @@ int rtm_debug_grid_nearest(const rtm_sphere* sp, size_t n, const double* org, co
 int rtm_debug_grid_build(const rtm_sphere* sp, size_t n, uint64_t* info, double* pads, uint32_t* ranges, size_t ranges_cap,
                          uint32_t* items, size_t items_cap, int32_t* big, size_t big_cap) {
     RTM_GUARD(rtm::grid_build_host(sp, n, info, pads, ranges, ranges_cap, items, items_cap, big, big_cap))
+}
+int rtm_debug_scene_grid(const rtm_scene* scene, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items,
+                         size_t items_cap, int32_t* big, size_t big_cap, uint64_t extra[2]) {
+    RTM_GUARD(rtm::scene_grid_probe(scene, info, ranges, ranges_cap, items, items_cap, big, big_cap, extra))
 }
 int rtm_debug_scene_facts(const rtm_sphere* sp, size_t n, uint64_t facts[2]) { RTM_GUARD(rtm::scene_facts_host(sp, n, facts)) }
 int rtm_debug_zero_term_facts(const rtm_sphere* sp, size_t n, uint64_t facts[2]) { RTM_GUARD(rtm::zero_term_facts_host(sp, n, facts)) }

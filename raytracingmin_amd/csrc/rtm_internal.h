@@ -22,6 +22,7 @@ int wf_nearest_probe(int kind, const rtm_sphere* sp, size_t n, const double* org
                      int32_t* out_id, double* out_t);
 const char* variant_name(int v);
 int scene_create(const rtm_sphere* sp, size_t n, int on_device, int device, rtm_scene** out);
+int scene_create_device(const rtm_sphere* sp_dev, size_t n, int device, void* stream, rtm_scene** out);  // rtm_grid_build.hip
 int scene_create_objects(const rtm_object* objs, size_t n, int device, rtm_scene** out);
 int intersect_objects_batch(const rtm_object* objs, const double* org, const double* dir, size_t n, int mode,
                             int32_t* out_hit, double* out_t, double* out_normal);
@@ -105,6 +106,8 @@ int zero_term_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts);
 int axis_rows_host(const rtm_sphere* sp, size_t n, double* rows);
 int grid_build_host(const rtm_sphere* sp, size_t n, uint64_t* info, double* pads, uint32_t* ranges, size_t ranges_cap,
                     uint32_t* items, size_t items_cap, int32_t* big, size_t big_cap);
+int scene_grid_probe(const rtm_scene* sc, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items, size_t items_cap,
+                     int32_t* big, size_t big_cap, uint64_t* extra);
 int fp64_peak(int waves_per_simd, double min_ms, double* tflops, double* kernel_ms);
 int math_probe(int op, const double* a, const double* b, size_t n, double* out);
 // the labelled tolerance row (rtm_kernels_tol.hip): launches for a planned rtm::RenderParams passed by bytes

@@ -9,6 +9,8 @@
 //   rtm_fp32.h           the separately labelled single-precision row
 //   rtm_seam_kernels.h   per-ray / per-call seams, probes, self-checks, the fp64 peak kernel
 //   rtm_matte.hip        the coverage AOVs' kernels (rtm_matte_kernel.h) and launches, included at the end of this file
+//   rtm_grid_build.hip   rtm_scene_create_device: a scene's grid built by kernels (rtm_grid_build_kernel.h, which also holds the
+//                        per-sphere expressions the host builder below shares with them), included at the end of this file
 //   this file            scene lifetime (flattening, upload, deferred release), per-(device, stream) contexts and scratch,
 //                        variant selection, the sample-split plan, launches, the blocking conveniences, the test hooks
 // Shape of the render kernel: DESIGN.md §4.  No MFMA: there is no dense contraction on this path.  fp64 throughout,
@@ -39,6 +41,7 @@
 
 #include "rtm_render_kernel.h"
 #include "rtm_grid_kernel.h"
+#include "rtm_grid_build_kernel.h"
 #include "rtm_wavefront.h"
 #include "rtm_fp32.h"
 #include "rtm_seam_kernels.h"
@@ -453,8 +456,7 @@ static SceneView view_of(const rtm_scene& sc, const void* grid) {
 // for fewer than kGridMinSpheres gridded spheres (below that the packed-record kernels are as fast or faster:
 // profiles/r3/grid_crossover.txt), non-finite geometry, more than kGridMaxBig big spheres or planes.
 constexpr size_t kGridMinSpheres = 64;  // gridded spheres a scene needs to get a grid (profiles/r3/grid_crossover.txt)
-constexpr int kGridBigCells = 125, kGridMaxBig = 1024, kGridMaxDim = 1024;
-constexpr double kGridDdTol = 4e-7;  // |dir.dir - 1| the pads cover: twice what the reference's float-sqrt Normalize leaves (1.8e-7)
+constexpr int kGridMaxBig = 1024, kGridMaxDim = 1024;  // (kGridBigCells, kGridDdTol: rtm_grid_build_kernel.h, with the per-sphere expressions)
 static double grid_cells_per_sphere() {
     static const double v = [] {
         const char* e = std::getenv("RTM_DEBUG_GRID_CELLS");  // tuning knob: cells per sphere; 0 = build no grid
@@ -469,85 +471,26 @@ struct GridBuild {
     size_t refs = 0;  // entries of `items` that are real (items holds one dummy when there is none)
 };
 static bool n_refs_valid(const GridBuild& B) { return B.refs != 0; }
-static bool make_grid(const double* g, size_t n, GridBuild& out, double* pads_out = nullptr) {
-    const double lambda = grid_cells_per_sphere();
-    if (n < kGridMinSpheres || n >= (1u << 29) || !(lambda > 0.0)) return false;
-    std::vector<double> R(n), pad(n);
-    std::vector<char> is_big(n, 0);
-    std::vector<char> is_plane(n, 0);  // a png::PlaneObject's geometry row is (position, negative "r*r"): tested by every ray
-    for (size_t i = 0; i < n; ++i) {
-        const double* r = g + i * 4;
-        if (!(std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(r[3]))) return false;
-        if (r[3] < 0.0) {
-            is_plane[i] = is_big[i] = 1;
-            R[i] = 0.0;
-            continue;
-        }
-        unsigned long long wbits;
-        std::memcpy(&wbits, &r[3], sizeof wbits);
-        if (wbits & 0x1FFFFFFFull) return false;  // (never: r*r is a float widened to double — the records keep the index there)
-        R[i] = std::sqrt(r[3]);
-    }
-    double lo[3], hi[3], h = 0.0, t_ok = 0.0;
-    size_t n_small = 0;
-    for (size_t i = 0; i < n; ++i) n_small += !is_plane[i];
-    if (n_small < kGridMinSpheres) return false;
-    for (int round = 0; round < 4; ++round) {
-        // box of the small spheres (unpadded), cell edge from its volume, pads from its diagonal
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = HUGE_VAL;
-            hi[k] = -HUGE_VAL;
-        }
-        for (size_t i = 0; i < n; ++i) {
-            if (is_big[i]) continue;
-            for (int k = 0; k < 3; ++k) {
-                lo[k] = std::min(lo[k], g[i * 4 + k] - R[i]);
-                hi[k] = std::max(hi[k], g[i * 4 + k] + R[i]);
-            }
-        }
-        double ext[3], diag2 = 0.0, vol = 1.0, longest = 0.0;
-        for (int k = 0; k < 3; ++k) {
-            ext[k] = hi[k] - lo[k];
-            diag2 += ext[k] * ext[k];
-            longest = std::max(longest, ext[k]);
-        }
-        if (!(longest > 0.0) || !std::isfinite(diag2)) return false;
-        for (int k = 0; k < 3; ++k) vol *= std::max(ext[k], longest * 1e-3);  // (a flat scene still gets cells of a sane size)
-        h = std::cbrt(vol / (lambda * (double)n_small));
-        h = std::max(h, longest / (double)(kGridMaxDim - 2));
-        t_ok = 2.5 * std::sqrt(diag2);
-        size_t changed = 0;
-        n_small = 0;
-        for (size_t i = 0; i < n; ++i) {
-            // (rtm_path.h: a hit at parameter t lies sqrt(r^2 + t^2 (d.d - 1)) from the centre)
-            pad[i] = 0.05 * h + (std::sqrt(R[i] * R[i] + kGridDdTol * t_ok * t_ok) - R[i]) + 1e-6 * t_ok;
-            const double side = 2.0 * (R[i] + pad[i]) / h + 1.0;
-            const char b = is_plane[i] || !(side * side * side <= (double)kGridBigCells);
-            changed += b != is_big[i];
-            is_big[i] = b;
-            n_small += !b;
-        }
-        if (n_small < kGridMinSpheres) return false;
-        if (!changed && round > 0) break;
-    }
-    out.big.clear();
-    for (size_t i = 0; i < n; ++i)
-        if (is_big[i]) out.big.push_back((int)i);
-    if (out.big.size() > (size_t)kGridMaxBig) return false;
-    // the grid's box: the small spheres' padded boxes
+// The scalar arithmetic of a build, host code for the host builder below and for the device build (rtm_grid_build.hip) alike.
+// A classification round's cell edge and pad horizon from the box of the spheres that are not big: the edge from the box's
+// volume, the pads from its diagonal.  false: no grid.
+static bool grid_round_scalars(const double lo[3], const double hi[3], size_t n_small, double lambda, double& h, double& t_ok) {
+    double ext[3], diag2 = 0.0, vol = 1.0, longest = 0.0;
     for (int k = 0; k < 3; ++k) {
-        lo[k] = HUGE_VAL;
-        hi[k] = -HUGE_VAL;
+        ext[k] = hi[k] - lo[k];
+        diag2 += ext[k] * ext[k];
+        longest = std::max(longest, ext[k]);
     }
-    for (size_t i = 0; i < n; ++i) {
-        if (is_big[i]) continue;
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = std::min(lo[k], g[i * 4 + k] - R[i] - pad[i]);
-            hi[k] = std::max(hi[k], g[i * 4 + k] + R[i] + pad[i]);
-        }
-    }
-    if (pads_out) std::memcpy(pads_out, pad.data(), n * sizeof(double));
-    GridHeader& H = out.hdr;
+    if (!(longest > 0.0) || !std::isfinite(diag2)) return false;
+    for (int k = 0; k < 3; ++k) vol *= std::max(ext[k], longest * 1e-3);  // (a flat scene still gets cells of a sane size)
+    h = std::cbrt(vol / (lambda * (double)n_small));
+    h = std::max(h, longest / (double)(kGridMaxDim - 2));
+    t_ok = 2.5 * std::sqrt(diag2);
+    return true;
+}
+// The header from the small spheres' padded box (lo, hi: changed), *cells = the number of cells.  false: no grid.
+static bool grid_header_from_box(double lo[3], const double hi[3], double h, double t_ok, size_t n, size_t n_big, GridHeader& H,
+                                 size_t* cells_out) {
     std::memset(&H, 0, sizeof H);
     size_t cells = 1;
     for (int k = 0; k < 3; ++k) {
@@ -573,41 +516,102 @@ static bool make_grid(const double* g, size_t n, GridBuild& out, double* pads_ou
     if (!(reach > 0.0)) return false;
     H.reach2 = reach * reach;
     H.dd_tol = kGridDdTol;
-    H.n_big = (int)out.big.size();
+    H.n_big = (int)n_big;
+    *cells_out = cells;
+    return true;
+}
+static GridBuildDims grid_build_dims(const GridHeader& H) {
+    GridBuildDims D;
+    for (int k = 0; k < 3; ++k) {
+        D.lo[k] = H.lo[k];
+        D.dim[k] = H.dim[k];
+    }
+    D.h = H.h;
+    return D;
+}
+static bool make_grid(const double* g, size_t n, GridBuild& out, double* pads_out = nullptr) {
+    const double lambda = grid_cells_per_sphere();
+    if (n < kGridMinSpheres || n >= (1u << 29) || !(lambda > 0.0)) return false;
+    std::vector<double> R(n), pad(n);
+    std::vector<char> is_big(n, 0);
+    std::vector<char> is_plane(n, 0);  // a png::PlaneObject's geometry row is (position, negative "r*r"): tested by every ray
+    for (size_t i = 0; i < n; ++i) {
+        const double* r = g + i * 4;
+        if (!(std::isfinite(r[0]) && std::isfinite(r[1]) && std::isfinite(r[2]) && std::isfinite(r[3]))) return false;
+        R[i] = grid_sphere_R(r[3]);
+        if (r[3] < 0.0) {
+            is_plane[i] = is_big[i] = 1;
+            continue;
+        }
+        unsigned long long wbits;
+        std::memcpy(&wbits, &r[3], sizeof wbits);
+        if (wbits & 0x1FFFFFFFull) return false;  // (never: r*r is a float widened to double — the records keep the index there)
+    }
+    double lo[3], hi[3], h = 0.0, t_ok = 0.0;
+    size_t n_small = 0;
+    for (size_t i = 0; i < n; ++i) n_small += !is_plane[i];
+    if (n_small < kGridMinSpheres) return false;
+    for (int round = 0; round < 4; ++round) {
+        // box of the small spheres (unpadded), cell edge from its volume, pads from its diagonal
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = HUGE_VAL;
+            hi[k] = -HUGE_VAL;
+        }
+        for (size_t i = 0; i < n; ++i) {
+            if (is_big[i]) continue;
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = std::min(lo[k], g[i * 4 + k] - R[i]);
+                hi[k] = std::max(hi[k], g[i * 4 + k] + R[i]);
+            }
+        }
+        if (!grid_round_scalars(lo, hi, n_small, lambda, h, t_ok)) return false;
+        size_t changed = 0;
+        n_small = 0;
+        for (size_t i = 0; i < n; ++i) {
+            pad[i] = grid_sphere_pad(R[i], h, t_ok);
+            const char b = is_plane[i] || grid_sphere_is_big(R[i], pad[i], h);
+            changed += b != is_big[i];
+            is_big[i] = b;
+            n_small += !b;
+        }
+        if (n_small < kGridMinSpheres) return false;
+        if (!changed && round > 0) break;
+    }
+    out.big.clear();
+    for (size_t i = 0; i < n; ++i)
+        if (is_big[i]) out.big.push_back((int)i);
+    if (out.big.size() > (size_t)kGridMaxBig) return false;
+    // the grid's box: the small spheres' padded boxes
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = HUGE_VAL;
+        hi[k] = -HUGE_VAL;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (is_big[i]) continue;
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = std::min(lo[k], g[i * 4 + k] - R[i] - pad[i]);
+            hi[k] = std::max(hi[k], g[i * 4 + k] + R[i] + pad[i]);
+        }
+    }
+    if (pads_out) std::memcpy(pads_out, pad.data(), n * sizeof(double));
+    GridHeader& H = out.hdr;
+    size_t cells = 0;
+    if (!grid_header_from_box(lo, hi, h, t_ok, n, out.big.size(), H, &cells)) return false;
+    const GridBuildDims D = grid_build_dims(H);
     // counting sort of (cell, sphere) pairs; spheres are visited in index order, so every cell's list ascends
-    auto cell_range = [&](size_t i, int k, int& a, int& b) {
-        const double c = g[i * 4 + k], e = R[i] + pad[i];
-        a = (int)std::floor((c - e - H.lo[k]) / h);
-        b = (int)std::floor((c + e - H.lo[k]) / h);
-        a = a < 0 ? 0 : a;
-        b = b >= H.dim[k] ? H.dim[k] - 1 : b;
-    };
     out.cell_start.assign(cells + 1, 0u);
     size_t refs = 0;
     for (int pass = 0; pass < 2; ++pass) {
         for (size_t i = 0; i < n; ++i) {
             if (is_big[i]) continue;
-            int a[3], b[3];
-            for (int k = 0; k < 3; ++k) cell_range(i, k, a[k], b[k]);
-            // of the box's cells, those within R + pad of the centre (a hit point is, and lies in its cell)
-            const double reach2 = (R[i] + pad[i]) * (R[i] + pad[i]) * (1.0 + 1e-9);
-            auto gap = [&](int k, int cell) {  // distance from the centre to the cell's slab along axis k
-                const double c0 = H.lo[k] + (double)cell * h, ck = g[i * 4 + k];
-                return ck < c0 ? c0 - ck : (ck > c0 + h ? ck - (c0 + h) : 0.0);
-            };
-            for (int z = a[2]; z <= b[2]; ++z)
-                for (int y = a[1]; y <= b[1]; ++y)
-                    for (int x = a[0]; x <= b[0]; ++x) {
-                        const double gx = gap(0, x), gy = gap(1, y), gz = gap(2, z);
-                        if (gx * gx + gy * gy + gz * gz > reach2) continue;
-                        const size_t c = ((size_t)z * H.dim[1] + y) * H.dim[0] + x;
-                        if (pass == 0) {
-                            ++out.cell_start[c + 1];
-                            ++refs;
-                        } else {
-                            out.items[out.cell_start[c]++] = (unsigned)i;
-                        }
-                    }
+            grid_sphere_cells(g + i * 4, pad[i], D, [&](size_t c) {
+                if (pass == 0) {
+                    ++out.cell_start[c + 1];
+                    ++refs;
+                } else {
+                    out.items[out.cell_start[c]++] = (unsigned)i;
+                }
+            });
         }
         if (pass == 0) {
             if (refs > 0xFFFFFF00ull) return false;
@@ -677,45 +681,72 @@ int axis_rows_host(const rtm_sphere* sp, size_t n, double* rows) {
     return RTM_OK;
 }
 
+// A diffuse sphere that ENCLOSES the gridded ones from farther away than the pads reach (an environment sphere) sends
+// its bounces back from origins the walk cannot serve: each of them would take the exhaustive loop inside the grid
+// kernel, one lane at a time.  Such a scene keeps its grid for variant 17 by name; variant 0 leaves it alone (grid_for).
+// Decided from the rows of the spheres every ray tests: row_of(j, i) = the geometry row of big[j] = i, diffuse_of(j, i) = its
+// kd > 0 — the host builder reads them from its tables, the device build from the few rows that came back.  1 / 0, or -1
+// where a plane is among them and there are no plane rows to judge it by (the scene then gets no grid).
+template <typename RowOf, typename DiffuseOf>
+static int grid_far_bounces_of(const GridHeader& H, const int* big, size_t n_big, const double* plane_rows, RowOf row_of,
+                               DiffuseOf diffuse_of) {
+    int far = 0;
+    const double reach = std::sqrt(H.reach2);
+    for (size_t j = 0; j < n_big; ++j) {
+        const int i = big[j];
+        const double* row = row_of(j, i);
+        const bool diffuse = diffuse_of(j, i);
+        if (row[3] < 0.0) {  // a plane: any of its square's corners beyond the reach?
+            if (!plane_rows) return -1;
+            const double* pl = plane_rows + (size_t)i * 16;
+            for (int c = 0; c < 4 && diffuse; ++c) {
+                double d2 = 0.0;
+                for (int k = 0; k < 3; ++k) {
+                    const double p = pl[k] + ((c & 1) ? pl[6 + k] : -pl[6 + k]) + ((c & 2) ? pl[9 + k] : -pl[9 + k]);
+                    d2 += (p - H.cb[k]) * (p - H.cb[k]);
+                }
+                if (!(std::sqrt(d2) <= reach)) far = 1;
+            }
+            continue;
+        }
+        double d2 = 0.0;
+        for (int k = 0; k < 3; ++k) d2 += (row[k] - H.cb[k]) * (row[k] - H.cb[k]);
+        if (diffuse && std::sqrt(row[3]) - std::sqrt(d2) > reach) far = 1;
+    }
+    return far;
+}
+// Where the tables of a grid lie in an rtm_scene's `grid` block: the header, the cells' ranges, the records, the big list
+struct GridLayout {
+    size_t off_cs, off_items, off_big, bytes;
+};
+static GridLayout grid_layout(size_t n_cells, size_t n_recs, size_t n_big) {
+    GridLayout L;
+    L.off_cs = (sizeof(GridHeader) + 255) & ~(size_t)255;
+    L.off_items = L.off_cs + ((n_cells * 2 * sizeof(unsigned) + 255) & ~(size_t)255);
+    L.off_big = L.off_items + ((n_recs * 4 * sizeof(double) + 255) & ~(size_t)255);
+    L.bytes = L.off_big + (n_big + 1) * sizeof(int);
+    return L;
+}
+
 // Build + upload; a scene that gets no grid keeps sc.grid empty (not an error).  `hg`: the host copy of the geometry rows.
 // `hm`: the material rows (kd in column 6), or null.
 static int build_scene_grid(rtm_scene& sc, const double* hg, const double* hm, size_t n, int device,
                             const double* plane_rows = nullptr) {
     GridBuild B;
     if (!make_grid(hg, n, B)) return RTM_OK;
-    // A diffuse sphere that ENCLOSES the gridded ones from farther away than the pads reach (an environment sphere) sends
-    // its bounces back from origins the walk cannot serve: each of them would take the exhaustive loop inside the grid
-    // kernel, one lane at a time.  Such a scene keeps its grid for variant 17 by name; variant 0 leaves it alone (grid_for).
-    sc.grid_far_bounces = false;
-    const double reach = std::sqrt(B.hdr.reach2);
-    for (int i : B.big) {
-        const bool diffuse = !hm || hm[(size_t)i * 8 + 6] > 0.0;
-        if (hg[(size_t)i * 4 + 3] < 0.0) {  // a plane: any of its square's corners beyond the reach?
-            if (!plane_rows) return RTM_OK;  // (no rows to judge it by: no grid)
-            const double* pl = plane_rows + (size_t)i * 16;
-            for (int c = 0; c < 4 && diffuse; ++c) {
-                double d2 = 0.0;
-                for (int k = 0; k < 3; ++k) {
-                    const double p = pl[k] + ((c & 1) ? pl[6 + k] : -pl[6 + k]) + ((c & 2) ? pl[9 + k] : -pl[9 + k]);
-                    d2 += (p - B.hdr.cb[k]) * (p - B.hdr.cb[k]);
-                }
-                if (!(std::sqrt(d2) <= reach)) sc.grid_far_bounces = true;
-            }
-            continue;
-        }
-        double d2 = 0.0;
-        for (int k = 0; k < 3; ++k) d2 += (hg[(size_t)i * 4 + k] - B.hdr.cb[k]) * (hg[(size_t)i * 4 + k] - B.hdr.cb[k]);
-        if (diffuse && std::sqrt(hg[(size_t)i * 4 + 3]) - std::sqrt(d2) > reach) sc.grid_far_bounces = true;
-    }
-    const size_t off_cs = (sizeof(GridHeader) + 255) & ~(size_t)255;
+    const int far = grid_far_bounces_of(B.hdr, B.big.data(), B.big.size(), plane_rows,
+                                        [&](size_t, int i) { return hg + (size_t)i * 4; },
+                                        [&](size_t, int i) { return !hm || hm[(size_t)i * 8 + 6] > 0.0; });
+    if (far < 0) return RTM_OK;  // (a plane and no rows to judge it by: no grid)
+    sc.grid_far_bounces = far != 0;
     const size_t n_cells = B.cell_start.size() - 1;
+    const GridLayout lay = grid_layout(n_cells, B.items.size(), B.big.size());
+    const size_t off_cs = lay.off_cs, off_items = lay.off_items, off_big = lay.off_big, bytes = lay.bytes;
     std::vector<unsigned> ranges(n_cells * 2);  // (first, one past last) per cell: one 8-byte load per cell step
     for (size_t c = 0; c < n_cells; ++c) {
         ranges[c * 2] = B.cell_start[c];
         ranges[c * 2 + 1] = B.cell_start[c + 1];
     }
-    const size_t off_items = off_cs + ((ranges.size() * sizeof(unsigned) + 255) & ~(size_t)255);
-    const size_t off_big = off_items + ((B.items.size() * 4 * sizeof(double) + 255) & ~(size_t)255);
     // the cell lists as self-contained records: the geometry row with the sphere's index in r*r's 29 zero mantissa bits
     std::vector<double> recs(B.items.size() * 4);
     for (size_t k = 0; k < B.items.size(); ++k) {
@@ -726,7 +757,6 @@ static int build_scene_grid(rtm_scene& sc, const double* hg, const double* hm, s
         wbits |= (unsigned long long)i;
         std::memcpy(&recs[k * 4 + 3], &wbits, sizeof wbits);
     }
-    const size_t bytes = off_big + (B.big.size() + 1) * sizeof(int);
     const int rc = sc.grid.alloc_pooled(bytes, device);
     if (rc != RTM_OK) return rc;
     unsigned char* base = sc.grid.as<unsigned char>();
@@ -772,8 +802,8 @@ static int scene_build_host(rtm_scene& sc, const rtm_sphere* sp, size_t n, int d
     RTM_HIP_CHECK(hipStreamSynchronize(nullptr));
     return want_grid ? build_scene_grid(sc, hg.data(), hm.data(), n, device) : RTM_OK;
 }
-// The same from a DEVICE sphere array.
-static int scene_build_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n, int device) {
+// The same from a DEVICE sphere array: everything but the grid, enqueued on `stream` and waited for.
+static int scene_tables_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n, int device, hipStream_t stream) {
     RTM_HIP_CHECK(hipSetDevice(device));
     sc.device = device;
     sc.n = n;
@@ -782,23 +812,31 @@ static int scene_build_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n,
     if (rc == RTM_OK) rc = sc.aux.alloc_pooled(scene_aux_doubles(n) * sizeof(double), device);
     if (rc == RTM_OK) rc = sc.surf.alloc_pooled((n ? n : 1) * 4 * sizeof(double), device);
     if (rc != RTM_OK) return rc;
-    flatten_scene_kernel<<<(unsigned)((n + 1 + 255) / 256), 256>>>(sp_dev, n, sc.geom.as<double>(), sc.mat.as<double>(), sc.surf.as<double>());
+    flatten_scene_kernel<<<(unsigned)((n + 1 + 255) / 256), 256, 0, stream>>>(sp_dev, n, sc.geom.as<double>(), sc.mat.as<double>(),
+                                                                             sc.surf.as<double>());
     RTM_HIP_CHECK(hipGetLastError());
-    rc = launch_scene_aux(sc.geom.as<double>(), n, sc.aux.as<double>(), nullptr);
+    rc = launch_scene_aux(sc.geom.as<double>(), n, sc.aux.as<double>(), stream);
     if (rc != RTM_OK) return rc;
-    RTM_HIP_CHECK(hipStreamSynchronize(nullptr));
+    RTM_HIP_CHECK(hipStreamSynchronize(stream));
     if (n > 0 && n <= 32) {  // a small scene's rows come back for SceneView::axis_pat (1 KB)
-        std::vector<double> rows(n * 4);
-        RTM_HIP_CHECK(hipMemcpy(rows.data(), sc.geom.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost));
+        std::vector<double> rows(n * 4), mrows((n + 1) * 8);
+        RTM_HIP_CHECK(hipMemcpyAsync(rows.data(), sc.geom.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        RTM_HIP_CHECK(hipMemcpyAsync(mrows.data(), sc.mat.p, mrows.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        RTM_HIP_CHECK(hipStreamSynchronize(stream));
         sc.axis_pat = axis_pattern(rows.data(), n);
         std::vector<double> arows(n * 4);  // ... and its axis rows go behind them
         axis_rows(rows.data(), n, sc.axis_pat, arows.data());
-        RTM_HIP_CHECK(hipMemcpy(sc.geom.as<double>() + n * 4, arows.data(), arows.size() * sizeof(double), hipMemcpyHostToDevice));
-        std::vector<double> mrows((n + 1) * 8);
-        RTM_HIP_CHECK(hipMemcpy(mrows.data(), sc.mat.p, mrows.size() * sizeof(double), hipMemcpyDeviceToHost));
+        RTM_HIP_CHECK(hipMemcpyAsync(sc.geom.as<double>() + n * 4, arows.data(), arows.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+        RTM_HIP_CHECK(hipStreamSynchronize(stream));
         sc.fold_flags = fold_flags_of(mrows.data(), n) | compact_flag_of(rows.data(), n) | zero_term_flags_of(mrows.data(), n, &sc.emit_mask) |
                         shared_k_bits(rows.data(), n, sc.axis_pat) | axis_reach_bits(rows.data(), n, sc.axis_pat);
     }
+    return RTM_OK;
+}
+// ... and the grid, built on the host (rtm_scene_create_device builds it on the device: rtm_grid_build.hip)
+static int scene_build_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n, int device) {
+    const int rc = scene_tables_device(sc, sp_dev, n, device, nullptr);
+    if (rc != RTM_OK) return rc;
     if (n < kGridMinSpheres) return RTM_OK;
     std::vector<double> hg(n * 4);  // the grid is built on the host: the geometry rows come back once
     RTM_HIP_CHECK(hipMemcpy(hg.data(), sc.geom.p, hg.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -3028,3 +3066,5 @@ int device_count(int* count) {
 
 // the coverage AOVs' kernels and launches: part of this translation unit (rtm_matte.hip says why)
 #include "rtm_matte.hip"
+// rtm_scene_create_device: the device build of a scene's grid, and rtm_debug_scene_grid (rtm_scene is private to this unit)
+#include "rtm_grid_build.hip"

@@ -29,6 +29,31 @@ def adaptive_preview(accum, tile_samples, n_samples):
     return accum * (np.float64(n_samples) / k)[..., None]
 
 
+def pack_spheres(center, radius, color, emission):
+    """rtm_sphere[n] as an (n, 80) uint8 tensor on the tensors' device, for Renderer.set_device_spheres: center, color and
+    emission are (n, 3) float64 tensors, radius is (n,) and is cast to float32 (the reference's m_size is a float); the four
+    pad bytes of every record are zero.  Pure tensor operations on the current stream: nothing comes to the host."""
+    import torch
+    parts = {"center": center, "radius": radius, "color": color, "emission": emission}
+    for name, t in parts.items():
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} is not a torch tensor")
+        if t.device != center.device:
+            raise ValueError(f"{name} is on {t.device}, center on {center.device}")
+    n = center.shape[0] if center.dim() == 2 else -1
+    for name in ("center", "color", "emission"):
+        t = parts[name]
+        if t.dtype != torch.float64 or tuple(t.shape) != (n, 3):
+            raise ValueError(f"{name} must be an (n, 3) float64 tensor, got {tuple(t.shape)} {t.dtype}")
+    if tuple(radius.shape) != (n,) or not (radius.dtype.is_floating_point or radius.dtype in (torch.int32, torch.int64)):
+        raise ValueError(f"radius must be an (n,) tensor of numbers, got {tuple(radius.shape)} {radius.dtype}")
+    out = torch.zeros((n, 80), dtype=torch.uint8, device=center.device)
+    d = out.view(torch.float64)  # (n, 10): center, color, emission, (radius, pad)
+    d[:, 0:3], d[:, 3:6], d[:, 6:9] = center, color, emission
+    out.view(torch.float32)[:, 18] = radius.to(torch.float32)
+    return out
+
+
 class Renderer:
     def __init__(self, data: SettingData, mode="repaired", max_bounces=-1, seed=0x5EED, device=0,
                  variant=0, host_trig=True, count_tests=False, integrator="PathTracing"):
@@ -51,6 +76,7 @@ class Renderer:
         self.stats = None
         self._scene = None      # rtm_scene* on self.device (made on first use, kept for the renderer's life)
         self._scene_key = None
+        self._device_scene = None  # rtm_scene* built from a device sphere array (set_device_spheres); wins over data.object
 
     # ---- the scene on the device: flattened and uploaded once per renderer -------------------
     def _scene_handle(self):
@@ -60,6 +86,8 @@ class Renderer:
         object list (replaced, reordered, added, removed entries); camera edits do not count (the camera is not part of
         the uploaded scene).  Edits to ANOTHER SettingData also advance the epoch: a needless re-flatten, never a stale
         scene."""
+        if self._device_scene is not None:  # set_device_spheres: whatever the edit epoch says
+            return self._device_scene
         from .settings import edit_epoch
         objs = self.data.object
         key = (edit_epoch(), id(objs))
@@ -85,10 +113,41 @@ class Renderer:
         _lib.check(_lib.lib().rtm_scratch_bytes(C.byref(st), self._scene_handle(), C.byref(opt), out), "rtm_scratch_bytes")
         return dict(zip(("total", "terms", "records", "pipeline_state", "steal_rows", "primary_table"), (int(v) for v in out)))
 
+    def set_device_spheres(self, packed, stream=None):
+        """Render a sphere array that lives on the device: `packed` is pack_spheres' (n, 80) uint8 tensor (rtm_sphere[n]) on
+        this renderer's device.  The scene — tables and grid — is built by rtm_scene_create_device on `stream` (default: the
+        current torch stream), ordered after whatever wrote the tensor there, without the array coming to the host; the
+        tensor may be overwritten as soon as the call returns.  From then on every render that goes through the renderer's scene
+        object (render_rows_device and every stage built on it) uses that scene, whatever happens to data.object; settings
+        and camera still come from self.data.  Render() goes through the scene object too while a device scene is set;
+        render_rows, the host-array call, reads data.object and would render another scene: it raises RuntimeError then.  Call it again for the next frame
+        of an animation; set_device_spheres(None) or invalidate() returns to data.object."""
+        if packed is None:
+            self.invalidate()
+            return
+        import torch
+        if not isinstance(packed, torch.Tensor):
+            raise ValueError("packed is not a torch tensor")
+        if packed.dtype != torch.uint8 or packed.dim() != 2 or packed.shape[1] != 80 or not packed.is_contiguous():
+            raise ValueError(f"packed must be a contiguous (n, 80) uint8 tensor, got {tuple(packed.shape)} {packed.dtype}")
+        if packed.device.type != "cuda" or packed.device.index != self.device:
+            raise ValueError(f"packed is on {packed.device}, the renderer on cuda:{self.device}")
+        self.invalidate()  # (a refused tensor leaves the renderer's scene as it was)
+        if stream is None:
+            stream = torch.cuda.current_stream(packed.device)
+        hip_stream = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().rtm_scene_create_device(C.c_void_p(packed.data_ptr()), packed.shape[0], self.device,
+                                                      C.c_void_p(hip_stream), C.byref(h)), "rtm_scene_create_device")
+        self._device_scene = h
+
     def invalidate(self):
         if self._scene is not None:
             _lib.lib().rtm_scene_destroy(self._scene)
             self._scene = None
+        if getattr(self, "_device_scene", None) is not None:
+            _lib.lib().rtm_scene_destroy(self._device_scene)
+            self._device_scene = None
 
     def __del__(self):
         if sys.is_finalizing():  # interpreter shutdown: the HIP runtime may be gone already; the process's memory goes with it
@@ -471,6 +530,9 @@ class Renderer:
 
     # ---- host-buffer render (the blocking C entry point) ------------------------------------
     def render_rows(self, row_begin=0, row_end=None, want=("f64",), band=None):
+        if self._device_scene is not None:
+            raise RuntimeError("render_rows renders data.object from the host; this renderer has a device scene "
+                               "(set_device_spheres): use render_rows_device, or set_device_spheres(None) first")
         row_end = self.data.height if row_end is None else row_end
         opt = self._options(row_begin, row_end, band)
         rows, W = _lib.lib().rtm_output_rows(C.byref(opt)), self.data.width
@@ -555,6 +617,10 @@ class Renderer:
                 last = out
             self.image = last["f64"].cpu().numpy()
             rgb8 = np.ascontiguousarray(last["u8"].cpu().numpy())
+        elif self._device_scene is not None:  # set_device_spheres: the scene object, not data.object
+            out, _ = self.render_rows_device(0, self.data.height, want=("f64", "u8"))
+            self.image = out["f64"].cpu().numpy()
+            rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
         else:
             out, _ = self.render_rows(0, self.data.height, want=("f64", "u8"))
             self.image = out["f64"]
