@@ -26,7 +26,12 @@ extern "C" {
  * rtm_debug_axis_rows returns them), out = (b, D4, 0 x 6) with t = b -+ sqrt(D4).  52: the form of rounds 4 to 8, p = c - o_a
  * with the shared sums of the foreign products (reads c and r * r) — the reference of 53; 53: the expanded form the search
  * runs, b = c d_a - o.d, D4 = b b - ((-2 c) o_a + o.o + K) (reads c, -2 c and K); 54: the same for a sphere of a signature's
- * shared-K group, D4 = b b - ((-2 c) o_a + (o.o + K)).  Any other axis value gives (0, 0). */
+ * shared-K group, D4 = b b - ((-2 c) o_a + (o.o + K)).  Any other axis value gives (0, 0).
+ * Ops 55 / 56: the tolerance row's whole nearest-hit search of a seven-sphere scene with the Cornell box's signature (the light on
+ * y, walls on +x, -x, +y, -y, +z, -z sharing one K) on caller-given rays.  a: records as above; b: the scene's table in its first
+ * 56 doubles — 7 geometry rows (cx, cy, cz, r * r), then 7 axis rows as rtm_debug_axis_rows returns them —, n >= 56.  55: the search
+ * with opposite wall pairs, out = (distance, hit id or -1, 1 where the ray's wave took the seven-sphere block instead, 0 x 5);
+ * 56: the seven-sphere block, out = (distance, hit id or -1, 0 x 6).  A wave holds the 8 rays of 64 consecutive doubles. */
 int rtm_debug_math_probe(int op, const double* a, const double* b, size_t n, double* out);
 /* The tolerance row's sin / cos table as the HOST builds it for every device (no device is touched; runs in the CPU test
  * suite): out[2 i], out[2 i + 1] = sin, cos of i 2 pi / entries, evaluated in long double and rounded to double once.  The
@@ -91,6 +96,14 @@ int rtm_debug_zero_term_facts(const rtm_sphere* spheres, size_t n, uint64_t fact
  * hit itself, distances stay a sixteenth under the smallest threshold, every sphere lies within it (csrc/rtm_path.h:
  * kSceneAxisReachShift) —, 0 where it has not: such a scene, or a camera beyond the reach, takes the plain kernels. */
 int rtm_debug_axis_rows(const rtm_sphere* spheres, size_t n, double* rows);
+/* Whether a scene object of these spheres gets the tolerance row's opposite-wall-pair search (one root and one acceptance per
+ * pair, csrc/rtm_path.h: kAxisPairsBit), on the HOST (no device is touched; n <= 32): facts[0] = 1 where the members of the
+ * shared-K group are, two by two in index order, spheres of one radius on one axis at +c and -c bit for bit, the scene is
+ * compact and inside the expanded form's envelope, and the proof's constants hold (gamma / (2 beta) + reach 2^-44 < 1e-5f / 2,
+ * r 2^-17 >= 2 beta; beta = 2^-5, gamma = 2^-25), else 0; facts[1]: bit i = sphere i is the lower member of a pair that passes
+ * the per-pair tests.  (Ops 55 / 56 of rtm_debug_math_probe run that search and the seven-sphere block it replaces on caller
+ * rays: csrc/rtm_kernels_tol.hip.) */
+int rtm_debug_wall_pairs(const rtm_sphere* spheres, size_t n, uint64_t facts[2]);
 /* isolated nearest-hit / shading loops timed with s_memtime (profiles/component_bench.py) */
 int rtm_debug_component_bench(int which, const rtm_sphere* spheres, size_t n, int reps, int blocks, int lds_pad,
                               double* cycles_per_rep);

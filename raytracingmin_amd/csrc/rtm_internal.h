@@ -104,6 +104,7 @@ int grid_nearest_probe(const rtm_sphere* sp, size_t n, const double* org, const 
 int scene_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts);
 int zero_term_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts);
 int axis_rows_host(const rtm_sphere* sp, size_t n, double* rows);
+int wall_pairs_host(const rtm_sphere* sp, size_t n, uint64_t* facts);
 int grid_build_host(const rtm_sphere* sp, size_t n, uint64_t* info, double* pads, uint32_t* ranges, size_t ranges_cap,
                     uint32_t* items, size_t items_cap, int32_t* big, size_t big_cap);
 int scene_grid_probe(const rtm_scene* sc, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items, size_t items_cap,

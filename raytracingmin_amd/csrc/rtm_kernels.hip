@@ -198,6 +198,39 @@ static unsigned shared_k_bits(const double* geom, size_t n, uint64_t pat) {
     }
     return best << kSceneSharedKShift;
 }
+// SceneView::fold_flags' kSceneWallPairs (rtm_path.h: kAxisPairsBit, the tolerance unit's one root and one acceptance per
+// opposite wall pair): set where the members of the shared-K group, taken two by two in index order, are opposite pairs —
+// both on one axis, the lower index at +c and the other at -c bit for bit, one r*r — AND the scene is compact and inside the
+// expanded form's envelope AND the proof's constants hold for it: gamma / (2 beta) + reach 2^-44 < 1e-5f / 2 (what a skipped
+// wall's far root can reach stays under half of Intersect's threshold) and r 2^-17 >= 2 beta for every paired sphere (a bounce
+// ray leaving its own wall at the envelope's smallest cosine passes the proof).  *lower (optional): bit i = sphere i is the
+// lower member of a pair that passes the per-pair tests, whether or not the scene as a whole is granted the extension.
+static unsigned compact_flag_of(const double* geom, size_t n);
+static unsigned wall_pairs_flag(const double* geom, size_t n, uint64_t pat, unsigned* lower = nullptr) {
+    if (lower) *lower = 0u;
+    const unsigned group = (shared_k_bits(geom, n, pat) >> kSceneSharedKShift) & kSceneSharedKMask;
+    const unsigned e = (axis_reach_bits(geom, n, pat) >> kSceneAxisReachShift) & kSceneAxisReachMask;
+    if (group == 0u || e == 0u || compact_flag_of(geom, n) == 0u) return 0u;
+    const double reach = std::ldexp(1.0, (int)e - 128);
+    const bool far_root_ok = kPairGamma / (2.0 * kPairBeta) + std::ldexp(reach, -44) < 0.5 * (double)1e-5f;
+    int members[8], count = 0;
+    for (int i = 0; i < 8; ++i)
+        if ((group >> i) & 1u) members[count++] = i;
+    bool all = far_root_ok && count % 2 == 0;
+    unsigned low = 0u;
+    for (int m = 0; m + 1 < count; m += 2) {
+        const int i = members[m], j = members[m + 1];
+        const unsigned a = (unsigned)(pat >> (2 * i)) & 3u;
+        const double ci = geom[i * 4 + (a - 1u)], cj = geom[j * 4 + (a - 1u)], mci = -ci;
+        const bool ok = a == ((unsigned)(pat >> (2 * j)) & 3u) && ci > 0.0 && std::memcmp(&mci, &cj, sizeof(double)) == 0 &&
+                        std::memcmp(&geom[i * 4 + 3], &geom[j * 4 + 3], sizeof(double)) == 0 &&
+                        std::ldexp(std::sqrt(geom[i * 4 + 3]), -17) >= 2.0 * kPairBeta;
+        if (ok) low |= 1u << i;
+        all = all && ok;
+    }
+    if (lower) *lower = low;
+    return all && count >= 2 ? kSceneWallPairs : 0u;
+}
 
 // SceneView::fold_flags from flattened material rows (colorKD[3], emission[3], kd, kd * 2^24): see kFoldNoLevelEmission
 // kSceneCompact from flattened geometry rows (cx, cy, cz, r*r): every sphere within kCompactExtent of the origin
@@ -680,6 +713,16 @@ int axis_rows_host(const rtm_sphere* sp, size_t n, double* rows) {
     axis_rows(hg.data(), n, axis_pattern(hg.data(), n), rows);
     return RTM_OK;
 }
+// rtm_debug_wall_pairs: wall_pairs_flag on the HOST (tests/test_wall_pairs_host.py)
+int wall_pairs_host(const rtm_sphere* sp, size_t n, uint64_t* facts) {
+    if ((!sp && n) || !facts || n > kAxisRowsMax) return RTM_ERR_INVALID_ARGUMENT;
+    std::vector<double> hg, hm;
+    flatten_scene(sp, n, hg, hm);
+    unsigned lower = 0u;
+    facts[0] = wall_pairs_flag(hg.data(), n, axis_pattern(hg.data(), n), &lower) != 0u ? 1u : 0u;
+    facts[1] = lower;
+    return RTM_OK;
+}
 
 // A diffuse sphere that ENCLOSES the gridded ones from farther away than the pads reach (an environment sphere) sends
 // its bounces back from origins the walk cannot serve: each of them would take the exhaustive loop inside the grid
@@ -786,7 +829,8 @@ static int scene_build_host(rtm_scene& sc, const rtm_sphere* sp, size_t n, int d
     flatten_scene(sp, n, hg, hm, &hs);
     sc.axis_pat = axis_pattern(hg.data(), n);
     sc.fold_flags = fold_flags_of(hm.data(), n) | compact_flag_of(hg.data(), n) | zero_term_flags_of(hm.data(), n, &sc.emit_mask) |
-                    shared_k_bits(hg.data(), n, sc.axis_pat) | axis_reach_bits(hg.data(), n, sc.axis_pat);
+                    shared_k_bits(hg.data(), n, sc.axis_pat) | axis_reach_bits(hg.data(), n, sc.axis_pat) |
+                    wall_pairs_flag(hg.data(), n, sc.axis_pat);
     hg.resize((n + axis_row_count(n)) * 4);  // the axis rows behind the geometry rows
     axis_rows(hg.data(), n, sc.axis_pat, hg.data() + n * 4);
     int rc = sc.geom.alloc_pooled((hg.empty() ? 1 : hg.size() / 4) * 4 * sizeof(double), device);
@@ -829,7 +873,8 @@ static int scene_tables_device(rtm_scene& sc, const rtm_sphere* sp_dev, size_t n
         RTM_HIP_CHECK(hipMemcpyAsync(sc.geom.as<double>() + n * 4, arows.data(), arows.size() * sizeof(double), hipMemcpyHostToDevice, stream));
         RTM_HIP_CHECK(hipStreamSynchronize(stream));
         sc.fold_flags = fold_flags_of(mrows.data(), n) | compact_flag_of(rows.data(), n) | zero_term_flags_of(mrows.data(), n, &sc.emit_mask) |
-                        shared_k_bits(rows.data(), n, sc.axis_pat) | axis_reach_bits(rows.data(), n, sc.axis_pat);
+                        shared_k_bits(rows.data(), n, sc.axis_pat) | axis_reach_bits(rows.data(), n, sc.axis_pat) |
+                        wall_pairs_flag(rows.data(), n, sc.axis_pat);
     }
     return RTM_OK;
 }

@@ -72,12 +72,20 @@ static void launch_n(const RenderParams& P, unsigned grid, size_t lds_pad, hipSt
     const bool axis = P.mode == RTM_MODE_REPAIRED && unit_tab == 1u && compact_launch(P) && expanded_form_launch(P);  // rtm_path.h: sphere_disc
     // (axis_pat holds the signature's low 16 bits, fold_flags' bits 8..15 what goes above them: the spheres that share one K)
     const unsigned shared_k = (P.scene.fold_flags >> kSceneSharedKShift) & kSceneSharedKMask;
+    // ... and kSceneWallPairs the bit above those: the group's members are opposite pairs (rtm_path.h: kAxisPairsBit).  Not for
+    // the any-depth kernel with the sample split: there the second code path costs 28 bytes of scratch that its twin does not
+    // have (-Rpass-analysis=kernel-resource-usage; profiles/r10/wall_pairs.md), so that shape keeps the seven-sphere block.
+    constexpr bool kPairsShape = (F & (kPackL | kSplit)) != (kPackL | kSplit);
+    const unsigned pairs = kPairsShape && (P.scene.fold_flags & kSceneWallPairs) != 0u ? kAxisPairsBit : 0u;
 #define RTM_AXIS_CASE(k, sig)                                                                                    \
-    if (P.scene.n == k && P.scene.axis_pat == ((sig) & 0xFFFFu) && shared_k == ((sig) >> kAxisSharedKShift) && axis) { \
+    if (P.scene.n == k && P.scene.axis_pat == ((sig) & 0xFFFFu) && ((shared_k << kAxisSharedKShift) | pairs) == ((sig) & ~0xFFFFu) && axis) { \
         launch_tiles<MathFast, F, axis_unroll(k, sig), uint8_t, LDS_D, kTolWavesPerSimd>(P, grid, lds_pad, stream); \
         return;                                                                                                  \
     }
-    RTM_AXIS_CASE(7, kAxisSigCornell7Walls)  // the shipped box: its six walls share one K
+    if constexpr (kPairsShape) {
+        RTM_AXIS_CASE(7, kAxisSigCornell7Pairs)  // the shipped box: its six walls share one K and are three opposite pairs
+    }
+    RTM_AXIS_CASE(7, kAxisSigCornell7Walls)  // ... without being opposite pairs, and the shape left out above
 #undef RTM_AXIS_CASE
 #define RTM_AXIS_CASE(k, sig)                                                                                    \
     if (P.scene.n == k && P.scene.axis_pat == sig && axis) {                                                     \
@@ -126,7 +134,11 @@ static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hip
 // 52 / 53 an axis sphere's discriminant stage on caller-given rays, in records of 8 doubles: a = (ox, oy, oz, dx, dy, dz, -, -),
 // b = (pattern 1 / 2 / 3, c, r * r, -2 c, K, -, -, -), out = (b, D4, 0 ..) — 52 the form of rounds 4 to 8 from (c, r * r)
 // (rtm_path.h: sphere_disc_ref, the reference), 53 the expanded form from the axis row (c, -2 c, K) as the search runs it now,
-// 54 the same for a sphere of the signature's shared-K group (oo + K formed first)
+// 54 the same for a sphere of the signature's shared-K group (oo + K formed first),
+// 55 / 56 the whole nearest-hit search of a seven-sphere scene with the Cornell box's signature on caller-given rays (records as
+// above; b: the scene's 7 geometry rows and, behind them, its 7 axis rows, 56 doubles, as a scene object keeps them): 55 with the
+// opposite wall pairs (kAxisSigCornell7Pairs), out = (distance, hit id, 1 where the ray's wave took the seven-sphere block, 0 ..),
+// 56 the seven-sphere block itself (kAxisSigCornell7Walls), out = (distance, hit id, 0 ..)
 __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, size_t n,
                                       double* __restrict__ out, const double2* __restrict__ tab) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -149,6 +161,22 @@ __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, cons
             }
         }
         out[i] = (i & 7) == 0 ? bb : (i & 7) == 1 ? D4 : 0.0;
+        return;
+    }
+    if (op == 55 || op == 56) {  // (as above: every thread of a record computes it; a wave holds 8 rays)
+        const size_t j = i & ~(size_t)7;
+        double dis = DBL_MAX;
+        int hit = -1;
+        bool fell_back = false;
+        if (b && n >= 56 && j + 7 < n) {
+            const D3 org = d3(a[j], a[j + 1], a[j + 2]), dir = d3(a[j + 3], a[j + 4], a[j + 5]);
+            SceneGlobal sc{};
+            sc.v.geom = reinterpret_cast<const double4*>(b);
+            sc.v.n = 7;
+            if (op == 55) sphere_chunk<MathFast, 7, SceneGlobal, false, kAxisSigCornell7Pairs>(sc, 0, org, dir, dis, hit, &fell_back);
+            else sphere_chunk<MathFast, 7, SceneGlobal, false, kAxisSigCornell7Walls>(sc, 0, org, dir, dis, hit);
+        }
+        out[i] = (i & 7) == 0 ? dis : (i & 7) == 1 ? (double)hit : (i & 7) == 2 ? (fell_back ? 1.0 : 0.0) : 0.0;
         return;
     }
     const double x = a[i], y = b ? b[i] : 0.0;

@@ -930,6 +930,40 @@ __device__ __forceinline__ void accept_batch(const double (&b)[K], const double 
 #pragma unroll
     for (int k = 0; k < K; ++k) accept_update(b[k], sq[k], i0 + k, dis, hit_object);
 }
+// accept_batch<K, true> for candidates whose sphere index is a PER-LANE value (the tolerance unit's wall pairs, sphere_chunk:
+// each lane tests the wall of a pair that ITS ray heads for).  idx[k] ascends with k in every lane, so ties still go to the
+// lower index — in the packed minimum by the index field, in the general updates by their order.
+template <int K>
+__device__ __forceinline__ void accept_batch_lane(const double (&b)[K], const double (&sq)[K], const uint32_t (&idx)[K],
+                                                  double& dis, int& hit_object) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(K <= 7, "three bits of index, 7 = none");
+    double t1v[K];
+    unsigned long long far = 0ull;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const double t1 = b[k] - sq[k], t2 = b[k] + sq[k];
+        const unsigned long long near = __builtin_amdgcn_ballot_w64(t1 > 0.001);
+        far |= __builtin_amdgcn_ballot_w64(t2 >= (double)1e-5f) & ~near;
+        const uint32_t lo = ((uint32_t)__double2loint(t1) & ~7u) | idx[k];
+        t1v[k] = __hiloint2double((int)sel_u32_mask(near, (uint32_t)__double2hiint(t1), 0x7FF80000u), (int)lo);
+    }
+    if (far == 0ull) {
+        double best = dis;  // DBL_MAX: index field 7
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            double m;
+            asm("v_min_f64 %0, %1, %2" : "=v"(m) : "v"(best), "v"(t1v[k]));
+            best = m;
+        }
+        dis = best;
+        hit_object = (int)((((uint32_t)__double2loint(best)) + 1u) & 7u) - 1;  // 7 -> -1
+        return;
+    }
+#endif
+#pragma unroll
+    for (int k = 0; k < K; ++k) accept_update(b[k], sq[k], (int)idx[k], dis, hit_object);
+}
 
 // Discriminants of spheres whose centre lies ON A COORDINATE AXIS (SceneView::axis_pat; the six walls and the light of the
 // shipped Cornell box, every sphere of simpleSetting1.json): with c = (cx, 0, 0) the reference's p_o = c - org is
@@ -1012,6 +1046,26 @@ constexpr int axis_unroll(const int n, const unsigned sig) { return -(1000 + n +
 // sphere_disc's expanded form).  The Cornell box with its six walls of one radius at one distance:
 constexpr unsigned kAxisSharedKShift = 16u;
 constexpr unsigned kAxisSigCornell7Walls = kAxisSigCornell7 | (0x7Eu << kAxisSharedKShift);
+// ... and bit 24 (from SceneView::fold_flags' kSceneWallPairs: the host's proof, rtm_kernels.hip: wall_pairs_flag): the members
+// of the shared-K group are OPPOSITE PAIRS in index order — (1, 2), (3, 4), (5, 6) for the Cornell box —, the two of a pair on
+// one axis with centres +c (the lower index) and -c, bit for bit.  A ray can enter at most the wall it heads for, except from
+// within a hair of the other one: the search takes ONE root and ONE acceptance per pair where the other wall is proven to
+// miss (sphere_chunk_pairs below), and the plain seven-sphere block for the whole wave where some lane cannot prove it.
+constexpr unsigned kAxisPairsBit = 1u << 24;
+constexpr unsigned kAxisSigCornell7Pairs = kAxisSigCornell7Walls | kAxisPairsBit;
+constexpr unsigned kSceneWallPairs = 1u << 24;  // SceneView::fold_flags
+// The proof.  The wall a ray does NOT head for has b_u = -|c| |d_a| - o.d and
+// q_u = 2 |c| (o_a sgn d_a) + o.o + K, the very numbers sphere_disc forms for it.  Where b_u <= -beta and q_u >= 2 tau b_u
+// (tau = gamma / (2 beta) = 2^-21; b_u is negative, so this admits a q_u down to -2 tau |b_u|) its near root b_u - s is negative
+// and its far root b_u + s = -q_u / (|b_u| + s) is at most tau = 4.8e-7, plus the light root's 2^-44 |b_u|: under half of
+// Intersect's 1e-5f within any reach the host admits (gamma / (2 beta) + reach 2^-44 < 1e-5f / 2), so nothing of that wall can be
+// accepted.  The bound on q_u scales with |b_u| because a bounce ray's q for the wall it LEAVES is not 0 but t^2 (d.d - 1), up to
+// 2e-4 either way — the direction's length comes from a float root, 1.2e-7 off —: a constant -gamma would fail half of all bounce
+// rays, -2 tau |b_u| = -2 tau r cos fails the ones flatter than cos = 2e-3.  beta keeps b_u's own rounding out of it and is
+// small enough for every bounce ray down to cos = 2^-17 (the host asks r 2^-17 >= 2 beta of a paired sphere).  NaN operands
+// compare false: not proven.
+constexpr double kPairBeta = 0.03125, kPairGamma = 2.98023223876953125e-8;  // 2^-5, 2^-25
+constexpr double kPairTau = kPairGamma / (2.0 * kPairBeta);                    // 2^-21
 // (n, signature) pairs with an instantiation: X(n, sig) for each
 #define RTM_AXIS_SIGNATURES(X) X(7, kAxisSigCornell7) X(5, kAxisSigSimple5) X(3, kAxisSigSetting3)
 // b and D4 of sphere g (src/SettingData.cpp:198-200); pat: 0 general, 1 / 2 / 3 the centre is on the x / y / z axis
@@ -1053,6 +1107,47 @@ __device__ __forceinline__ void sphere_disc_ref(const double4 g, const unsigned 
         b = dot(p_o, dir);
         D4 = b * b - dot(p_o, p_o) + g.w;
     }
+}
+// One opposite pair of a kAxisPairsBit signature on axis `pat`, from the row of its LOWER member (c > 0: the host's proof).
+// pair_unproven: b_u and q_u of the wall the ray does NOT head for — centre -c sgn(d_a) —, the numbers sphere_disc forms for it;
+// returns "this lane has NOT proven that it misses" (kPairBeta, kPairTau above).  pair_disc, once the wave has proven all its
+// pairs: the wall the ray heads for with sphere_disc's own operands,
+//   b = |c| |d_a| - o.d,   q = (-2 |c|) (o_a sgn d_a) + ooK,   D4 = b b - q
+// (the same exact products, so the same roundings: b, D4, root and t1 keep their bits).  |d_a| and -o.d are operand modifiers,
+// spelled out: left to itself hipcc negates o.d in place to get a v_fmac for one pair and then materialises every |d_a|, seven
+// more instructions a trip.
+__device__ __forceinline__ double pair_signed_origin(const unsigned pat, const D3 org, const D3 dir) {  // o_a sgn(d_a)
+    const double oa = pat == 1u ? org.x : pat == 2u ? org.y : org.z;
+    const double da = pat == 1u ? dir.x : pat == 2u ? dir.y : dir.z;
+    const uint32_t sign = (uint32_t)__double2hiint(da) & 0x80000000u;
+    return __hiloint2double((int)((uint32_t)__double2hiint(oa) ^ sign), __double2loint(oa));
+}
+__device__ __forceinline__ bool pair_unproven(const AxisRow r, const unsigned pat, const double ooK, const D3 org, const D3 dir,
+                                              const AxisShared& A) {
+    const double da = pat == 1u ? dir.x : pat == 2u ? dir.y : dir.z;
+    double bu;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_fma_f64 %0, -%1, |%2|, -%3" : "=v"(bu) : "s"(r.c), "v"(da), "v"(A.od));
+#else
+    bu = __builtin_fma(-r.c, __builtin_fabs(da), -A.od);
+#endif
+    const double qu = __builtin_fma(-r.m2c, pair_signed_origin(pat, org, dir), ooK);
+    return !(bu <= -kPairBeta && __builtin_fma(-2.0 * kPairTau, bu, qu) >= 0.0);
+}
+__device__ __forceinline__ void pair_disc(const AxisRow r, const unsigned pat, const double ooK, const D3 org, const D3 dir,
+                                          const AxisShared& A, double& b, double& D4) {
+    const double da = pat == 1u ? dir.x : pat == 2u ? dir.y : dir.z;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_fma_f64 %0, %1, |%2|, -%3" : "=v"(b) : "s"(r.c), "v"(da), "v"(A.od));
+#else
+    b = __builtin_fma(r.c, __builtin_fabs(da), -A.od);
+#endif
+    D4 = __builtin_fma(b, b, -__builtin_fma(r.m2c, pair_signed_origin(pat, org, dir), ooK));
+}
+// ... and the pair's candidate index: the lower member where d_a's sign bit is clear, the upper one where it is set
+__device__ __forceinline__ uint32_t pair_index(const unsigned pat, const D3 dir, const int lower) {
+    const double da = pat == 1u ? dir.x : pat == 2u ? dir.y : dir.z;
+    return (uint32_t)lower + ((uint32_t)__double2hiint(da) >> 31);
 }
 #else
 __device__ __forceinline__ void sphere_disc(const double4 g, const unsigned pat, const D3 org, const D3 dir,
@@ -1124,7 +1219,7 @@ __device__ __forceinline__ void sphere_chunk_g(const double4 (&g)[K], const int 
 constexpr int kGeomPhase = 2;
 template <class M, int K, class Scene, bool EARLY_OUT = false, unsigned SIG = 0u>
 __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, const D3 org, const D3 dir,
-                                             double& dis, int& hit_object) {
+                                             double& dis, int& hit_object, bool* pairs_fell_back = nullptr) {
     static_assert(SIG == 0u || (K > kGeomPhase && K < 8 && !EARLY_OUT), "an axis signature names the spheres of ONE exact chunk");
     constexpr int PH = kGeomPhase;
     if constexpr (K > PH && !EARLY_OUT) {
@@ -1136,6 +1231,50 @@ __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, cons
         if constexpr (SIG != 0u) {  // the scene's axis signature is a compile-time constant: sphere_disc's branches fold
             const AxisShared A(org, dir);
 #if RTM_TOL
+            if constexpr ((SIG & kAxisPairsBit) != 0u) {
+                // Opposite wall pairs (kAxisPairsBit): per pair the wall the ray heads for is a candidate, the other one is
+                // proven to miss from b_u and q_u alone — K - pairs discriminants, roots and acceptances.  One lane that cannot
+                // prove it sends the WAVE to the plain block below, before any root is taken, so that (dis, hit_object) are that
+                // block's in every trip: the proof only ever drops a sphere the block would not have accepted.
+                constexpr unsigned KMP = (SIG >> kAxisSharedKShift) & 0xFFu;
+                constexpr int KC = K - __builtin_popcount(KMP) / 2;  // candidates
+                double pooK = 0.0;
+                bool unproven = false;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const int rank = __builtin_popcount(KMP & ((1u << k) - 1u));  // members of the group below k
+                    if (((KMP >> k) & 1u) == 0u || (rank & 1) != 0) continue;     // the lower member of each pair
+                    const AxisRow r = load_axis_row_uniform(sc.v.geom, K + i0 + k);
+                    if (rank == 0) pooK = A.oo + r.K;
+                    unproven |= pair_unproven(r, (SIG >> (2 * k)) & 3u, pooK, org, dir, A);
+                }
+                if (__builtin_amdgcn_ballot_w64(unproven) == 0ull) {
+                    double pb[KC], pD4[KC], psq[KC];
+                    uint32_t idx[KC];
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        const unsigned pat = (SIG >> (2 * k)) & 3u;
+                        const int rank = __builtin_popcount(KMP & ((1u << k) - 1u));
+                        const bool member = ((KMP >> k) & 1u) != 0u;
+                        if (member && (rank & 1) != 0) continue;  // a pair's upper member: served by its lower one
+                        const int slot = k - rank / 2;
+                        if (member) pair_disc(load_axis_row_uniform(sc.v.geom, K + i0 + k), pat, pooK, org, dir, A, pb[slot], pD4[slot]);
+                        else if (pat != 0u) sphere_disc(double4{}, load_axis_row_uniform(sc.v.geom, K + i0 + k), pat, false, 0.0, org, dir, A, pb[slot], pD4[slot]);
+                        else sphere_disc(sc.geom_uniform(i0 + k), AxisRow{}, 0u, false, 0.0, org, dir, A, pb[slot], pD4[slot]);
+                    }
+                    M::template sqrt64_batch_hit<KC, true>(pD4, psq);
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        const int rank = __builtin_popcount(KMP & ((1u << k) - 1u));
+                        const bool member = ((KMP >> k) & 1u) != 0u;
+                        if (member && (rank & 1) != 0) continue;
+                        idx[k - rank / 2] = member ? pair_index((SIG >> (2 * k)) & 3u, dir, i0 + k) : (uint32_t)(i0 + k);
+                    }
+                    accept_batch_lane<KC>(pb, psq, idx, dis, hit_object);
+                    return;
+                }
+                if (pairs_fell_back) *pairs_fell_back = true;  // (rtm_debug_math_probe op 55 alone passes one)
+            }
             double ooK = 0.0;
 #endif
             constexpr int PA = 2;  // spheres whose geometry is fetched together (an axis sphere needs 4 SGPRs, not 8)
@@ -1143,7 +1282,7 @@ __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, cons
             for (int k0 = 0; k0 < K; k0 += PA) {
 #if RTM_TOL
                 // (an axis-signature chunk is the whole scene, i0 == 0 and K == n: sphere i's axis row is row K + i)
-                constexpr unsigned KM = SIG >> kAxisSharedKShift;  // the spheres that share one K: oo + K once, at the first
+                constexpr unsigned KM = (SIG >> kAxisSharedKShift) & 0xFFu;  // the spheres that share one K: oo + K once, at the first
                 double4 g[PA] = {};
                 AxisRow r[PA] = {};
 #pragma unroll
