@@ -104,6 +104,11 @@ int rtm_debug_axis_rows(const rtm_sphere* spheres, size_t n, double* rows);
  * the per-pair tests.  (Ops 55 / 56 of rtm_debug_math_probe run that search and the seven-sphere block it replaces on caller
  * rays: csrc/rtm_kernels_tol.hip.) */
 int rtm_debug_wall_pairs(const rtm_sphere* spheres, size_t n, uint64_t facts[2]);
+/* The dynamic LDS bytes of a tolerance-row launch for a scene of n spheres (1 .. 24), on the HOST (no device is touched;
+ * csrc/rtm_render_kernel.h: render_lds_bytes): any_depth 0 the depth-capped shape, 1 the any-depth one; split: with the sample
+ * split; rows 1: the scene tables with one 64-byte row per sphere (SceneLdsRows: the axis-signature kernels), 0: three tables.
+ * out[0] = bytes per workgroup (one wave), out[1] = 1 where they include the near-unit Normalize table. */
+int rtm_debug_tol_lds_bytes(int n, int any_depth, int split, int rows, uint64_t out[2]);
 /* isolated nearest-hit / shading loops timed with s_memtime (profiles/component_bench.py) */
 int rtm_debug_component_bench(int which, const rtm_sphere* spheres, size_t n, int reps, int blocks, int lds_pad,
                               double* cycles_per_rep);

@@ -231,6 +231,7 @@ DEBUG_SIGNATURES = {
     "rtm_debug_zero_term_facts": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtm_debug_axis_rows": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "rtm_debug_wall_pairs": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "rtm_debug_tol_lds_bytes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "rtm_debug_grid_build": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
                                        C.c_size_t, C.c_void_p, C.c_size_t]),
     "rtm_debug_scene_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,

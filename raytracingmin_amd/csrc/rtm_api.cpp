@@ -224,6 +224,7 @@ int rtm_debug_scene_facts(const rtm_sphere* sp, size_t n, uint64_t facts[2]) { R
 int rtm_debug_zero_term_facts(const rtm_sphere* sp, size_t n, uint64_t facts[2]) { RTM_GUARD(rtm::zero_term_facts_host(sp, n, facts)) }
 int rtm_debug_axis_rows(const rtm_sphere* sp, size_t n, double* rows) { RTM_GUARD(rtm::axis_rows_host(sp, n, rows)) }
 int rtm_debug_wall_pairs(const rtm_sphere* sp, size_t n, uint64_t facts[2]) { RTM_GUARD(rtm::wall_pairs_host(sp, n, facts)) }
+int rtm_debug_tol_lds_bytes(int n, int any_depth, int split, int rows, uint64_t out[2]) { RTM_GUARD(rtm::tol_lds_bytes(n, any_depth, split, rows, out)) }
 int rtm_debug_fp64_peak(int waves_per_simd, double min_ms, double* tflops, double* kernel_ms) {
     RTM_GUARD(rtm::fp64_peak(waves_per_simd, min_ms, tflops, kernel_ms))
 }

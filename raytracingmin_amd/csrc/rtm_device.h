@@ -187,7 +187,7 @@ struct ShadeLds {
     const double* trig = nullptr;
     const double* unit = nullptr;
 #if RTM_TOL
-    const double2* tab = nullptr;  // not LDS: the device's sin / cos table points (sincos_turn24_tab_load; RenderParams::trig_tab)
+    const double2* tab = nullptr;  // not LDS: the device's sin / cos table points (sincos_turn24_tab_load; g_trig_tab)
 #endif
     __device__ __forceinline__ ShadeLds() {}
     __device__ __forceinline__ ShadeLds(const double* t, bool with_unit = false) : trig(t), unit(with_unit && t ? t + kTrigConstCount : nullptr) {}
@@ -298,6 +298,10 @@ __device__ __forceinline__ void sincos_turn24_k(const K& k, const double m24, do
 // differ by a power of two in one factor.  Six instructions, one of them a conversion, where the double form took seven, five
 // of them fp64-rate (tests/test_loop_trims_host.py: every odd m; tests/test_loop_trims_gpu.py: against the double form below).
 constexpr int kTrigTabEntries = 16384;
+// The table itself: a variable of the code object, filled once per device by the host (rtm_kernels_tol.hip: ensure_trig_tab).  Its
+// address is a constant of the link (s_getpc_b64 and two scalar adds where the gather is issued): as a kernel argument the pointer
+// was a loop-invariant SGPR pair that hipcc spilled to VGPR lanes and read back with two v_readlane_b32 in every trip.
+__device__ double2 g_trig_tab[kTrigTabEntries];
 struct TrigTabWord {
     double s, c;  // sin and cos of the table point
     int fi;       // the remainder, in 2^-10 table steps

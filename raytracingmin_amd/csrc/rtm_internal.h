@@ -114,6 +114,7 @@ int math_probe(int op, const double* a, const double* b, size_t n, double* out);
 // the labelled tolerance row (rtm_kernels_tol.hip): launches for a planned rtm::RenderParams passed by bytes
 int launch_tol(const void* render_params, size_t params_bytes, unsigned grid, size_t lds_pad, void* stream);
 int tol_math_probe(int op, const double* a_dev, const double* b_dev, size_t n, double* out_dev);  // ops 32.. of math_probe
+int tol_lds_bytes(int n, int any_depth, int split, int rows, uint64_t* out);  // rtm_debug_tol_lds_bytes (rtm_kernels_tol.hip)
 int trig_table_host(int entries, double* out);  // the row's sin / cos table as the host builds it (rtm_debug_trig_table)
 void release_trig_tab(int device);              // ... and the devices' copies, dropped by release_scratch
 

@@ -1307,7 +1307,7 @@ template <class M, unsigned F, typename RecT, int LDS_D, int WPE>
 static bool launch_exact_n(const RenderParams& P, unsigned grid, hipStream_t stream) {
     const size_t pad = debug_lds_pad();
     unsigned unit_tab;
-    render_lds_bytes<F, RecT, LDS_D>(P.scene.n, pad, &unit_tab);
+    render_lds_bytes<F, RecT, LDS_D>(P.scene.n, lds_rows_for(-1000), pad, &unit_tab);  // (the axis kernels' layout: their cases below are what this answer is for)
 #define RTM_AXIS_CASE(k, sig)                                                                           \
     if (P.scene.n == k && P.scene.axis_pat == sig && P.mode == RTM_MODE_REPAIRED && unit_tab == 1u) {   \
         launch_tiles<M, F, axis_unroll(k, sig), RecT, LDS_D, WPE>(P, grid, pad, stream);                \

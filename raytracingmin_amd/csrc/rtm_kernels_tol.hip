@@ -68,7 +68,7 @@ template <unsigned F>
 static void launch_n(const RenderParams& P, unsigned grid, size_t lds_pad, hipStream_t stream) {
     constexpr int LDS_D = (F & kPackL) != 0 ? 0 : 16;
     unsigned unit_tab;
-    render_lds_bytes<F, uint8_t, LDS_D>(P.scene.n, lds_pad, &unit_tab);
+    render_lds_bytes<F, uint8_t, LDS_D>(P.scene.n, lds_rows_for(-1000), lds_pad, &unit_tab);  // (the axis kernels' layout: `axis` below is what this answer is for)
     const bool axis = P.mode == RTM_MODE_REPAIRED && unit_tab == 1u && compact_launch(P) && expanded_form_launch(P);  // rtm_path.h: sphere_disc
     // (axis_pat holds the signature's low 16 bits, fold_flags' bits 8..15 what goes above them: the spheres that share one K)
     const unsigned shared_k = (P.scene.fold_flags >> kSceneSharedKShift) & kSceneSharedKMask;
@@ -245,19 +245,19 @@ int trig_table_host(int entries, double* out) {
     return RTM_OK;
 }
 
-// ... built and uploaded once per device and kept until release_scratch, next to the host-trig table of the other unit: a
-// constant of the build — nothing of a scene or a frame enters it —, read-only and shared by every stream's launches
+// ... a variable of the device code (rtm_device.h: g_trig_tab), filled once per device: a constant of the build — nothing of a
+// scene or a frame enters it —, read-only and shared by every stream's launches
 namespace {
 std::mutex g_trig_tab_mu;
-std::map<int, double2*> g_trig_tab;
+std::map<int, const double2*> g_trig_tab_filled;  // device -> the variable's address there
 }  // namespace
 
 static int ensure_trig_tab(const double2** out) {
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return RTM_ERR_HIP;
     std::lock_guard<std::mutex> lock(g_trig_tab_mu);
-    const auto it = g_trig_tab.find(device);
-    if (it != g_trig_tab.end()) {
+    const auto it = g_trig_tab_filled.find(device);
+    if (it != g_trig_tab_filled.end()) {
         *out = it->second;
         return RTM_OK;
     }
@@ -266,41 +266,39 @@ static int ensure_trig_tab(const double2** out) {
     const int rc = trig_table_host(rtm_tol::kTrigTabEntries, host.data());
     if (rc != RTM_OK) return rc;
     void* dev = nullptr;
-    if (hipMalloc(&dev, kBytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return RTM_ERR_HIP;
-    }
     // (a blocking copy and the null stream drained: whatever stream launches next finds the table written)
-    if (hipMemcpy(dev, host.data(), kBytes, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+    if (hipGetSymbolAddress(&dev, HIP_SYMBOL(rtm_tol::g_trig_tab)) != hipSuccess || dev == nullptr ||
+        hipMemcpy(dev, host.data(), kBytes, hipMemcpyHostToDevice) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(dev);
         return RTM_ERR_HIP;
     }
-    g_trig_tab[device] = static_cast<double2*>(dev);
+    g_trig_tab_filled[device] = static_cast<const double2*>(dev);
     *out = static_cast<const double2*>(dev);
     return RTM_OK;
 }
 
-// release_scratch's share: the caller holds the render gate, no launch of `device` (all of them: < 0) is mid-call
-void release_trig_tab(int device) {
-    std::lock_guard<std::mutex> lock(g_trig_tab_mu);
-    for (auto it = g_trig_tab.begin(); it != g_trig_tab.end();) {
-        if (device < 0 || it->first == device) {
-            (void)hipSetDevice(it->first);
-            (void)hipDeviceSynchronize();
-            (void)hipFree(it->second);
-            it = g_trig_tab.erase(it);
-        } else {
-            ++it;
-        }
-    }
+// release_scratch's share: nothing — the table lives in the code object, not in memory this library allocated, and stays filled
+void release_trig_tab(int device) { (void)device; }
+
+// rtm_debug_tol_lds_bytes: what launch_tiles asks for, per shape of the row (HOST only; tests/test_trip_slots_host.py)
+int tol_lds_bytes(int n, int any_depth, int split, int rows, uint64_t* out) {
+    using namespace rtm_tol;
+    if (!out || n < 1 || n > 24) return RTM_ERR_INVALID_ARGUMENT;
+    unsigned unit = 0u;
+    const bool r = rows != 0;
+    size_t b;
+    if (any_depth) b = split ? render_lds_bytes<kTolAny | kSplit, uint8_t, 0>(n, r, 0, &unit) : render_lds_bytes<kTolAny, uint8_t, 0>(n, r, 0, &unit);
+    else b = split ? render_lds_bytes<kTolCapped | kSplit, uint8_t, 16>(n, r, 0, &unit) : render_lds_bytes<kTolCapped, uint8_t, 16>(n, r, 0, &unit);
+    out[0] = (uint64_t)b;
+    out[1] = unit;
+    return RTM_OK;
 }
 
 int tol_math_probe(int op, const double* a_dev, const double* b_dev, size_t n, double* out_dev) {
     const double2* tab = nullptr;
     if (op == 42 || op == 43 || op == 46 || op == 47) {
         if (ensure_trig_tab(&tab) != RTM_OK) {
-            set_last_error("tolerance row: the sin / cos table could not be allocated on the device");
+            set_last_error("tolerance row: the sin / cos table could not be written on the device");
             return RTM_ERR_HIP;
         }
     }
@@ -322,13 +320,12 @@ int launch_tol(const void* params, size_t params_bytes, unsigned grid, size_t ld
     // distinction this unit's own arithmetic does not keep anywhere else.  The row takes the device's (one table gather and
     // ten instructions per bounce less); the flag is accepted and has no effect here.
     P.scene.trig_fix = nullptr;
-    // ... by table point and two series terms: the table is the device's, made at the first launch
+    // ... by table point and two series terms: the table is the device's, filled at the first launch (the kernels name it)
     const double2* trig_tab = nullptr;
     if (ensure_trig_tab(&trig_tab) != RTM_OK) {
-        set_last_error("tolerance row: the sin / cos table could not be allocated on the device");
+        set_last_error("tolerance row: the sin / cos table could not be written on the device");
         return RTM_ERR_HIP;
     }
-    P.trig_tab = trig_tab;
     hipStream_t stream = (hipStream_t)stream_v;
     const bool any_depth = P.max_bounces < 0 || P.max_bounces > 8;
     if ((!any_depth && P.steal_ws == nullptr) || P.scene.n < 1 || P.scene.n > 24 || P.scene.plane != nullptr ||

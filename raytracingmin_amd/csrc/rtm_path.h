@@ -784,6 +784,40 @@ struct SceneLds {
     }
 };
 
+// The same for the tolerance unit's axis-signature kernels (rtm_render_kernel.h: lds_rows_for, kRowTab): everything the shading
+// block reads by hit id in ONE 64-byte row per sphere — centre, r * r, the normal row (length, refined reciprocal, float r * r)
+// and kd * 2^24 —, so that one shift of the id serves every read through immediate offsets (three tables with strides of 32, 64
+// and 24 bytes took three address computations a trip, one of them a 64-bit multiply-add on a spilled base).  The material rows
+// the fold reads stay a table of their own behind the rows.
+constexpr int kLdsRowDoubles = 8;
+struct SceneLdsRows {
+    SceneView v;
+    const double* lrow;  // LDS, 8 doubles per sphere: cx, cy, cz, r * r, fill_norm_row's three, kd * 2^24
+    const double* lmat;  // LDS, 8 doubles per sphere
+    static constexpr bool kHasNormTable = true;
+    static constexpr bool kPlanes = false;
+    static constexpr bool kNeverPlanes = true;
+    __device__ __forceinline__ double norm_m(int id) const { return lrow[id * kLdsRowDoubles + 4]; }
+    __device__ __forceinline__ double norm_rinv(int id) const { return lrow[id * kLdsRowDoubles + 5]; }
+    __device__ __forceinline__ float norm_r2f(int id) const { return reinterpret_cast<const float*>(lrow + id * kLdsRowDoubles + 6)[0]; }
+    __device__ __forceinline__ int n() const { return v.n; }
+    __device__ __forceinline__ double4 geom_uniform(int i) const { return load_geom_uniform(v.geom, i); }
+    __device__ __forceinline__ D3 center(int id) const {
+        const double* g = lrow + id * kLdsRowDoubles;
+        return D3{g[0], g[1], g[2]};
+    }
+    __device__ __forceinline__ double kd(int id) const { return lmat[id * 8 + 6]; }
+    __device__ __forceinline__ double kd24(int id) const { return lrow[id * kLdsRowDoubles + 7]; }
+    __device__ __forceinline__ D3 emission(int id) const {
+        const double* m = lmat + id * 8;
+        return D3{m[3], m[4], m[5]};
+    }
+    __device__ __forceinline__ D3 color_kd(int id) const {
+        const double* m = lmat + id * 8;
+        return D3{m[0], m[1], m[2]};
+    }
+};
+
 // Small scenes that hold png::PlaneObject entries (include/rtm.h: rtm_object), for the chunked fast kernels: the same
 // LDS tables, where a plane's geometry row is (position, negative "r*r") and its 3-double row of the normal-length
 // table holds the plane's NORMAL instead (a sphere's normal-length shortcut is not used in such scenes).  A plane's
@@ -1119,8 +1153,13 @@ __device__ __forceinline__ void sphere_disc_ref(const double4 g, const unsigned 
 __device__ __forceinline__ double pair_signed_origin(const unsigned pat, const D3 org, const D3 dir) {  // o_a sgn(d_a)
     const double oa = pat == 1u ? org.x : pat == 2u ? org.y : org.z;
     const double da = pat == 1u ? dir.x : pat == 2u ? dir.y : dir.z;
-    const uint32_t sign = (uint32_t)__double2hiint(da) & 0x80000000u;
-    return __hiloint2double((int)((uint32_t)__double2hiint(oa) ^ sign), __double2loint(oa));
+#if defined(__HIP_DEVICE_COMPILE__)
+    // o_hi ^ (d_hi & sign bit) as ONE v_bitop3_b32 (truth table 0x78 = a ^ (b & c)): left to itself hipcc makes a v_and and a v_xor
+    const uint32_t hi = __builtin_amdgcn_bitop3_b32((uint32_t)__double2hiint(oa), (uint32_t)__double2hiint(da), 0x80000000u, 0x78);
+#else
+    const uint32_t hi = (uint32_t)__double2hiint(oa) ^ ((uint32_t)__double2hiint(da) & 0x80000000u);
+#endif
+    return __hiloint2double((int)hi, __double2loint(oa));
 }
 __device__ __forceinline__ bool pair_unproven(const AxisRow r, const unsigned pat, const double ooK, const D3 org, const D3 dir,
                                               const AxisShared& A) {

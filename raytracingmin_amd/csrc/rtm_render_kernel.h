@@ -82,9 +82,6 @@ struct RenderParams {
     // tile t (every other call).  The work buffers above stay indexed by launch-local tile.
     const unsigned* __restrict__ tile_map;
     unsigned frame_tiles;
-    // the tolerance translation unit's shading block: sin and cos of the kTrigTabEntries points k 2 pi / kTrigTabEntries
-    // (rtm_device.h: sincos_turn24_tab_load), one table per device, a constant of the build — set by launch_tol, null elsewhere
-    const double2* __restrict__ trig_tab;
 };
 constexpr size_t kTermRowBytes = 3 * 64 * sizeof(double) + 64 * sizeof(unsigned short);  // 1664 = 13 lines of 128 B
 constexpr size_t kStealRowBytes = 3 * 64 * sizeof(double) + 64 * sizeof(unsigned);       // 1792 = 14 lines of 128 B
@@ -149,7 +146,17 @@ inline bool unit_table_fits(size_t lds) {
 // LDS copy of the scene tables: n geometry rows (4 doubles) + n+1 material rows (8 doubles, the last
 // one is the identity row) + n normal-length rows (3 doubles: |hit - centre| as Magnitude returns it, its refined
 // reciprocal, and the float r*r in the low word of the third)
-__host__ __device__ inline size_t lds_table_bytes(int n) { return ((size_t)n * 7 + ((size_t)n + 1) * 8) * sizeof(double); }
+// rows: the tolerance unit's axis-signature kernels keep geometry, normal row and kd * 2^24 of a sphere in one 8-double row
+// (rtm_path.h: SceneLdsRows) — 8 bytes per sphere more
+__host__ __device__ inline size_t lds_table_bytes(int n, bool rows) {
+    return ((size_t)n * (rows ? 8 : 7) + ((size_t)n + 1) * 8) * sizeof(double);
+}
+// Which instantiations take the row layout: the tolerance unit's axis-signature kernels (UNROLL <= -1000: exactly 7 spheres,
+// the headline kernel among them).  Tried for every table kernel and not kept elsewhere (profiles/r11/trip_slots.md): the exact
+// unit's -105 .. -107 kernels went from 24 to 40 bytes of scratch and the tolerance unit's generic n < 8 kernel from 8 to 16; the
+// chunked kernel (UNROLL 8) serves 8 .. 256 spheres, where 8 bytes a sphere more cost its any-depth tolerance shape a wave per CU
+// at 22 and 23 spheres and the near-unit table at 24.
+constexpr bool lds_rows_for(int unroll) { return RTM_TOL != 0 && unroll <= -1000; }
 
 // src/Renderer.cpp:227-232; sx, sy in 1..SS
 __device__ __forceinline__ D3 primary_dir(const RenderParams& P, int x, int y, int sx, int sy) {
@@ -279,7 +286,8 @@ constexpr unsigned kDefer = 1u << 5, kPackL = 1u << 6, kReuse = 1u << 7, kPlanes
 //   UNROLL  spheres whose geometry is fetched together (wave-uniform loads)
 //   RecT    hit-record type (u8 when n_spheres <= 256), LDS_D: record depth staged in LDS per lane
 //   WPE     launch bound: waves per SIMD
-// Dynamic LDS layout (16-byte aligned base): [geom n*4 doubles][mat (n+1)*8][norm n*2] (kLdsTab), [camera 10]
+// Dynamic LDS layout (16-byte aligned base): [geom n*4 doubles][mat (n+1)*8][norm n*3] (kLdsTab; lds_rows_for(UNROLL), the
+// tolerance unit's axis-signature kernels: [rows n*8][mat (n+1)*8], rtm_path.h: SceneLdsRows), [camera 10]
 // [sincos constants 16][accumulator + primary direction 6 x 64] (kPark), then the record stack
 // [LDS_D][64] or the fold queue (kDefer).  render_lds_bytes, just above the kernel, is a launch's size of it.
 //   kLdsTab scene tables (centres + materials) copied to LDS for the per-lane look-ups
@@ -342,8 +350,8 @@ constexpr size_t kFoldQueueBytesLS = kFoldQueueBytesS + kFoldRing * 8 + 64 * 8;
 // RTM_DEBUG_LDS_PAD knob): the carve-up at the top of the kernel, term by term.  *unit_tab: the launch holds the near-unit
 // Normalize table too (where its bytes do not cost a wave per CU: unit_table_fits) — RenderParams::unit_tab.
 template <unsigned F, typename RecT, int LDS_D>
-inline size_t render_lds_bytes(int n, size_t pad, unsigned* unit_tab) {
-    size_t b = (F & kLdsTab) ? lds_table_bytes(n) : 0;  // scene tables
+inline size_t render_lds_bytes(int n, bool rows, size_t pad, unsigned* unit_tab) {
+    size_t b = (F & kLdsTab) ? lds_table_bytes(n, rows) : 0;  // scene tables
     b += (10 + kTrigConstCount) * sizeof(double);        // camera, sincos constants
     if (F & kPark) b += 6 * 64 * sizeof(double);         // accumulator + primary direction
     if (!(F & (kPack8 | kPackL))) b += (size_t)LDS_D * 64 * sizeof(RecT);  // record stack: unpacked records only
@@ -379,10 +387,12 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // row's index and the empty record word as immediates).  Measured and not kept (profiles/r4/ctn_ab.txt): the
     // tolerance row does not move, the exact kernel loses 3 %.
     const int scene_n = P.scene.n;
-    double* lgeom = reinterpret_cast<double*>(lds_raw);
-    double* lmat = lgeom + (LDS_TAB ? scene_n * 4 : 0);
-    double* lnrm = lmat + (LDS_TAB ? (scene_n + 1) * 8 : 0);
-    double* cam = reinterpret_cast<double*>(lds_raw + (LDS_TAB ? lds_table_bytes(scene_n) : 0));
+    constexpr bool kRowTab = LDS_TAB && lds_rows_for(UNROLL);  // one row per sphere: SceneLdsRows
+    static_assert(!(kRowTab && PLANES), "a plane's normal has no place in a sphere's row");
+    double* lgeom = reinterpret_cast<double*>(lds_raw);  // (kRowTab: the rows)
+    double* lmat = lgeom + (LDS_TAB ? scene_n * (kRowTab ? kLdsRowDoubles : 4) : 0);
+    [[maybe_unused]] double* lnrm = lmat + (LDS_TAB ? (scene_n + 1) * 8 : 0);
+    double* cam = reinterpret_cast<double*>(lds_raw + (LDS_TAB ? lds_table_bytes(scene_n, kRowTab) : 0));
     double* trig = cam + 10;                 // 9 camera doubles + pad
     // the shading constants: sincos and — where the launcher found the LDS for it — the near-unit Normalize table
     // wave-uniform; the axis-signature instantiations are launched only when the table is there (the launchers check), so it is
@@ -391,7 +401,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     double* park = trig + (unit_tab ? kShadeConstCount : kTrigConstCount);
 #if RTM_TOL
     ShadeLds shade_lds_tab(trig, unit_tab);
-    shade_lds_tab.tab = P.trig_tab;
+    shade_lds_tab.tab = g_trig_tab;
     const ShadeLds shade_lds = shade_lds_tab;
 #else
     const ShadeLds shade_lds(trig, unit_tab);
@@ -442,9 +452,14 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     __syncthreads();
     if constexpr (LDS_TAB) {
         const double* gsrc = reinterpret_cast<const double*>(P.scene.geom);
-        for (int i = lane; i < scene_n * 4; i += 64) lgeom[i] = gsrc[i];
+        for (int i = lane; i < scene_n * 4; i += 64) lgeom[kRowTab ? (i >> 2) * kLdsRowDoubles + (i & 3) : i] = gsrc[i];
         for (int i = lane; i < (scene_n + 1) * 8; i += 64) lmat[i] = P.scene.mat[i];
         for (int i = lane; i < scene_n; i += 64) {
+            if constexpr (kRowTab) {
+                fill_norm_row(lgeom + i * kLdsRowDoubles + 4, gsrc[i * 4 + 3]);
+                lgeom[i * kLdsRowDoubles + 7] = P.scene.mat[i * 8 + 7];
+                continue;
+            }
             if (PLANES && gsrc[i * 4 + 3] < 0.0) {  // a plane's row: its normal (SceneLdsObjects::plane_normal)
                 lnrm[i * 3] = P.scene.plane[(size_t)i * 16 + 3];
                 lnrm[i * 3 + 1] = P.scene.plane[(size_t)i * 16 + 4];
@@ -455,8 +470,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
         }
         __syncthreads();  // one wave per block: orders the LDS writes before the reads
     }
+    using SceneTab = typename std::conditional<kRowTab, SceneLdsRows, SceneLds>::type;
     using Scene = typename std::conditional<PLANES, SceneLdsObjects,
-                                            typename std::conditional<LDS_TAB, SceneLds, SceneGlobal>::type>::type;
+                                            typename std::conditional<LDS_TAB, SceneTab, SceneGlobal>::type>::type;
     Scene sc;
     sc.v = P.scene;
     sc.v.n = scene_n;
@@ -464,7 +480,10 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // constant there (the shading block's "literal mode: the normal stays 0" arm and its wave-uniform test go away; a literal-mode
     // render of such a scene takes the plain exact-n kernel)
     const int mode = UNROLL <= -1000 ? (int)RTM_MODE_REPAIRED : P.mode;
-    if constexpr (LDS_TAB) {
+    if constexpr (kRowTab) {
+        sc.lrow = lgeom;
+        sc.lmat = lmat;
+    } else if constexpr (LDS_TAB) {
         sc.lgeom = lgeom;
         sc.lmat = lmat;
         sc.lnrm = lnrm;
@@ -1430,7 +1449,7 @@ __global__ __launch_bounds__(64) void steal_finalize_kernel(const RenderParams P
 // render_tiles_kernel<M, F, UNROLL, RecT, LDS_D, WPE> over `grid` tiles with render_lds_bytes' LDS and RenderParams::unit_tab
 template <class M, unsigned F, int UNROLL, typename RecT, int LDS_D, int WPE>
 void launch_tiles(RenderParams P, unsigned grid, size_t pad, hipStream_t stream) {
-    const size_t lds = render_lds_bytes<F, RecT, LDS_D>(P.scene.n, pad, &P.unit_tab);
+    const size_t lds = render_lds_bytes<F, RecT, LDS_D>(P.scene.n, lds_rows_for(UNROLL), pad, &P.unit_tab);
     render_tiles_kernel<M, F, UNROLL, RecT, LDS_D, WPE><<<grid, 64, lds, stream>>>(P);
 }
 // after a split launch (kSplit): one block per split tile
