@@ -1,7 +1,7 @@
 // rtm_grid_build.hip — rtm_scene_create_device (include/rtm.h): a scene object made from a DEVICE sphere array without the
 // array, or anything of its size, travelling to the host; and rtm_debug_scene_grid (include/rtm_debug.h), which reads a scene's
 // grid back.  The kernels are in rtm_grid_build_kernel.h; the scalar arithmetic of a build and the per-sphere expressions are
-// the host builder's own (rtm_kernels.hip: make_grid), so the tables are the ones make_grid makes, bit for bit.
+// the host builder's own (rtm_scene_facts.h: make_grid's; rtm_grid_exprs.h), so the tables are the ones make_grid makes, bit for bit.
 // NOT a translation unit of its own: rtm_scene is private to rtm_kernels.hip, which includes this file at its end.
 //
 // The stages, all on the caller's stream ("Building the grid on the device"):

@@ -1,6 +1,6 @@
-// rtm_host.h — what the host side of every entry point does alike: refuse with a message, select the device, ask whether
-// the launches it queued were accepted.  Host-only inline functions, no device code; included by the .hip units next to
-// rtm_internal.h.  What is a stage's own (its parameter ranges, aliasing rules, size limits and their messages) stays in
+// rtm_host.h — what the host side of every entry point does alike where it needs HIP: turn a failed HIP call into a refusal,
+// select the device, ask whether the launches it queued were accepted.  Host-only inline functions, no device code; included
+// by the .hip units next to rtm_internal.h (which holds the refusals themselves: fail, invalid, unsupported).  What is a stage's own (its parameter ranges, aliasing rules, size limits and their messages) stays in
 // the stage's file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,14 +12,7 @@
 
 namespace rtm {
 
-// records `message` for rtm_last_error and hands `code` back: `return fail(...)`
-inline int fail(int code, const std::string& message) {
-    set_last_error(message);
-    return code;
-}
-inline int invalid(const std::string& what) { return fail(RTM_ERR_INVALID_ARGUMENT, what); }
-inline int unsupported(const std::string& what) { return fail(RTM_ERR_UNSUPPORTED, what); }
-
+// (fail / invalid / unsupported, which need nothing of HIP: rtm_internal.h)
 // `expr` is a HIP call: on failure, its text and HIP's message become the last error and the function returns RTM_ERR_HIP
 #define RTM_HIP_CHECK(expr)                                                                  \
     do {                                                                                     \

@@ -9,8 +9,16 @@
 
 namespace rtm {
 
+// rtm_last_error's message (rtm_scene.cpp)
 void set_last_error(const std::string& s);
 const char* last_error();
+// records `message` for rtm_last_error and hands `code` back: `return fail(...)`
+inline int fail(int code, const std::string& message) {
+    set_last_error(message);
+    return code;
+}
+inline int invalid(const std::string& what) { return fail(RTM_ERR_INVALID_ARGUMENT, what); }
+inline int unsupported(const std::string& what) { return fail(RTM_ERR_UNSUPPORTED, what); }
 
 // device path (rtm_kernels.hip)
 int device_count(int* count);
@@ -101,16 +109,17 @@ int component_bench(int which, const rtm_sphere* sp, size_t n, int reps, int blo
 int selfcheck(int kind, unsigned long long* mismatches);
 int grid_nearest_probe(const rtm_sphere* sp, size_t n, const double* org, const double* dir, size_t n_rays, int32_t* out_id,
                        double* out_t, uint32_t* out_tests, uint32_t* out_steps, uint64_t* info);
+int scene_grid_probe(const rtm_scene* sc, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items, size_t items_cap,
+                     int32_t* big, size_t big_cap, uint64_t* extra);  // rtm_grid_build.hip
+int fp64_peak(int waves_per_simd, double min_ms, double* tflops, double* kernel_ms);
+int math_probe(int op, const double* a, const double* b, size_t n, double* out);
+// the host-only test hooks of the scene proofs and the host grid builder (rtm_scene_facts.cpp): no device is touched
 int scene_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts);
 int zero_term_facts_host(const rtm_sphere* sp, size_t n, uint64_t* facts);
 int axis_rows_host(const rtm_sphere* sp, size_t n, double* rows);
 int wall_pairs_host(const rtm_sphere* sp, size_t n, uint64_t* facts);
 int grid_build_host(const rtm_sphere* sp, size_t n, uint64_t* info, double* pads, uint32_t* ranges, size_t ranges_cap,
                     uint32_t* items, size_t items_cap, int32_t* big, size_t big_cap);
-int scene_grid_probe(const rtm_scene* sc, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items, size_t items_cap,
-                     int32_t* big, size_t big_cap, uint64_t* extra);
-int fp64_peak(int waves_per_simd, double min_ms, double* tflops, double* kernel_ms);
-int math_probe(int op, const double* a, const double* b, size_t n, double* out);
 // the labelled tolerance row (rtm_kernels_tol.hip): launches for a planned rtm::RenderParams passed by bytes
 int launch_tol(const void* render_params, size_t params_bytes, unsigned grid, size_t lds_pad, void* stream);
 int tol_math_probe(int op, const double* a_dev, const double* b_dev, size_t n, double* out_dev);  // ops 32.. of math_probe
@@ -118,7 +127,7 @@ int tol_lds_bytes(int n, int any_depth, int split, int rows, uint64_t* out);  //
 int trig_table_host(int entries, double* out);  // the row's sin / cos table as the host builds it (rtm_debug_trig_table)
 void release_trig_tab(int device);              // ... and the devices' copies, dropped by release_scratch
 
-// host side (rtm_scene.cpp, rtm_image.cpp)
+// host side: scene input and image output (rtm_scene.cpp, rtm_image.cpp)
 int scene_parse_json(const char* text, size_t len, int literal_loader, rtm_settings* st,
                      rtm_sphere* spheres, size_t capacity, size_t* n_spheres);
 int scene_parse_json_objects(const char* text, size_t len, int literal_loader, rtm_settings* st,

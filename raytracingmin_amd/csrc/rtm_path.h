@@ -9,6 +9,8 @@
 
 #include "../../include/rtm.h"
 #include "rtm_device.h"
+#include "rtm_grid_header.h"  // GridHeader
+#include "rtm_scene_flags.h"  // SceneView::fold_flags' bits and the constants of the host proofs behind them
 
 namespace RTM_NS {
 
@@ -587,22 +589,7 @@ __device__ __forceinline__ D3 normalize_i(MI& m, D3 a) {
 // Scene policies.  geom[i] = (cx, cy, cz, (double)(float)(r*r)); mat[i*8..] = colorKD.xyz,
 // emission.xyz, kd, pad (the fold reads the first six doubles of a row as three 16-byte loads).
 // ------------------------------------------------------------------------------------------------
-// Uniform grid over a large scene's spheres (rtm_kernels.hip: build_scene_grid; nearest_hit_grid below).  Device memory,
-// read through wave-uniform scalar loads.  A sphere is listed in every cell its box — centre +- (radius + pad_i) —
-// overlaps; the few spheres whose box would cover too many cells are in `big` instead and are tested by every ray.
-struct GridHeader {
-    double lo[3], hi[3];  // the grid's box: hi = lo + dim * h
-    double h, inv_h;      // cell edge
-    double cb[3], reach2; // a ray whose origin is farther than sqrt(reach2) from the box's centre cb, ...
-    double dd_tol;        // ... or whose |dir.dir - 1| is larger, takes the exhaustive loop (the pads do not cover it)
-    double t_ok;          // the largest hit parameter the pads were sized for (host side; reach2 follows from it)
-    int dim[3];
-    int n_big;
-    unsigned n_recs, pad_;
-    const uint2* cell_range;     // per cell (dim[0]*dim[1]*dim[2] of them): first and one-past-last entry of its list in `recs`
-    const double4* recs;         // a cell's spheres, self-contained: (cx, cy, cz, r*r | index), ascending index within a cell
-    const int* big;              // n_big sphere indices, ascending
-};
+// (GridHeader, the uniform grid over a large scene's spheres: rtm_grid_header.h)
 
 struct SceneView {
     const double4* __restrict__ geom;
@@ -630,7 +617,7 @@ struct SceneView {
     // 1 / 2 / 3 = the centre's only non-zero coordinate is x / y / z (the other two are +-0), 0 = anything else.  The
     // chunked search of the LDS-table kernels evaluates such a sphere's discriminant from per-ray shared products
     // (sphere_disc below): the reference's own roundings, fewer instructions.  Non-zero only in the view of an rtm_scene,
-    // whose geometry allocation holds the n axis rows (c, -2 c, c c - r*r, 0) behind the n geometry rows (rtm_kernels.hip:
+    // whose geometry allocation holds the n axis rows (c, -2 c, c c - r*r, 0) behind the n geometry rows (rtm_scene_facts.cpp:
     // axis_rows; the tolerance unit's sphere_disc reads row n + i for sphere i).
     unsigned long long axis_pat = 0ull;
     // kFoldNoLevelEmission (set by the host where it holds the material rows, else 0): every object a path can bounce off
@@ -645,31 +632,8 @@ struct SceneView {
     // it matters: render_tiles_kernel's path-end block), so the deferred-fold kernels do not queue such a path end.
     unsigned long long emit_mask = ~0ull;
 };
-constexpr unsigned kFoldNoLevelEmission = 1u;
-// ... bit 2, kFoldZeroTermSkippable: kFoldNoLevelEmission holds, every colorKD of an object a path can bounce off is finite
-// (no 0 x inf) and the scene has at most 63 objects (SceneView::emit_mask has a bit for each)
-constexpr unsigned kFoldZeroTermSkippable = 4u;
-// ... and bit 1, kSceneCompact: every |centre| + radius is finite and at most 1e7 (the launcher adds the camera): what the
-// tolerance unit's light search roots ask for (seq_sqrt_batch)
-constexpr unsigned kSceneCompact = 2u;
-// ... and bits 8..15 (set by the host where it holds the geometry, else 0): the spheres among the first 8 that form the largest
-// group of axis spheres whose axis rows hold ONE K = c c - r*r, bit for bit — at least two, the lowest group on a tie; the six
-// walls of the Cornell box: 0x7E.  The tolerance unit's launcher extends the axis signature with it (kAxisSharedKShift).
-constexpr unsigned kSceneSharedKShift = 8u, kSceneSharedKMask = 0xFFu;
-// ... and bits 16..23 (likewise): the ENVELOPE of the tolerance unit's expanded axis discriminant (sphere_disc), 0 = not proven,
-// else 128 + k: every axis sphere passes the two tests below for origins within 2^k of the scene's origin, and every sphere
-// of the scene lies within that reach (the launcher adds the camera).  The expanded q = (-2 c) o_a + o.o + K sums three terms
-// of up to (|c| + r)^2 or |o|^2 where the form of rounds 4 to 8 squared the EXACT difference c - o_a: its rounding error is
-// bounded by err(o) = 2^-49 max(|c| + r, |o|)^2 (three roundings of partial sums below 4 max^2), not by a multiple of r^2.
-//   (A) a bounce ray leaving sphere i (|o| <= |c| + r) has q = 0 in real arithmetic and the far root t2 = err / (2 r cos theta)
-//       with it; it must stay under Intersect's 1e-5f down to cos theta = 2^-17 (a cosine-weighted bounce is flatter than that
-//       once in 2^34): err(|c| + r) / (2 r) <= 2^-17 x 1e-5f.  A Cornell wall: 3.6e-11 against 7.6e-11; a sphere of radius 100
-//       at 1e6 fails by seven orders and WOULD hit itself (tests/test_axis_disc_host.py shows it in numpy).
-//   (B) from any origin within the reach a distance to sphere i is off by err(reach) / (2 r) at normal incidence: at most a
-//       sixteenth of 1e-5f, the smallest threshold a distance is compared with.
-// A scene outside the envelope takes the plain exact-n kernels (p_o formed as the reference does).
-constexpr unsigned kSceneAxisReachShift = 16u, kSceneAxisReachMask = 0xFFu;
-constexpr double kCompactExtent = 1e7;
+// (fold_flags' bits — kFoldNoLevelEmission, kFoldZeroTermSkippable, kSceneCompact, kSceneSharedKShift, kSceneAxisReachShift,
+// kSceneWallPairs — and kCompactExtent: rtm_scene_flags.h, with the host proofs' constants)
 
 // png::PlaneObject::Intersect as this build completes it (include/rtm.h): the reference's first line
 // (src/SettingData.cpp:244), the sphere's near threshold, then the square's extent.
@@ -1014,7 +978,7 @@ __device__ __forceinline__ void accept_batch_lane(const double (&b)[K], const do
 // the same error size as the contraction it already has): 11 -> 5 per sphere behind 10 per ray (AxisSharedRef and
 // sphere_disc_ref below: kept as the reference form of rtm_debug_math_probe op 52).  Since round 9 it takes the EXPANDED
 // form, which never forms p_o: with od = org . dir and oo = org . org once per ray (3 + 3 instructions) and, per sphere, the
-// host's axis row (c, -2 c, K = c c - r*r) behind the scene's geometry rows (rtm_kernels.hip: axis_rows),
+// host's axis row (c, -2 c, K = c c - r*r) behind the scene's geometry rows (rtm_scene_facts.cpp: axis_rows),
 //   b  = (c - o_a) d_a - (foreign products)      = c d_a - od                          (1 fma)
 //   pp - r*r = (c - o_a)^2 + (foreign squares) - r*r = (-2 c) o_a + oo + K             (1 fma + 1 add)
 //   D4 = b b - (pp - r*r)                                                              (1 fma)
@@ -1080,26 +1044,15 @@ constexpr int axis_unroll(const int n, const unsigned sig) { return -(1000 + n +
 // sphere_disc's expanded form).  The Cornell box with its six walls of one radius at one distance:
 constexpr unsigned kAxisSharedKShift = 16u;
 constexpr unsigned kAxisSigCornell7Walls = kAxisSigCornell7 | (0x7Eu << kAxisSharedKShift);
-// ... and bit 24 (from SceneView::fold_flags' kSceneWallPairs: the host's proof, rtm_kernels.hip: wall_pairs_flag): the members
+// ... and bit 24 (from SceneView::fold_flags' kSceneWallPairs: the host's proof, rtm_scene_facts.cpp: wall_pairs_flag): the members
 // of the shared-K group are OPPOSITE PAIRS in index order — (1, 2), (3, 4), (5, 6) for the Cornell box —, the two of a pair on
 // one axis with centres +c (the lower index) and -c, bit for bit.  A ray can enter at most the wall it heads for, except from
 // within a hair of the other one: the search takes ONE root and ONE acceptance per pair where the other wall is proven to
 // miss (sphere_chunk_pairs below), and the plain seven-sphere block for the whole wave where some lane cannot prove it.
 constexpr unsigned kAxisPairsBit = 1u << 24;
 constexpr unsigned kAxisSigCornell7Pairs = kAxisSigCornell7Walls | kAxisPairsBit;
-constexpr unsigned kSceneWallPairs = 1u << 24;  // SceneView::fold_flags
-// The proof.  The wall a ray does NOT head for has b_u = -|c| |d_a| - o.d and
-// q_u = 2 |c| (o_a sgn d_a) + o.o + K, the very numbers sphere_disc forms for it.  Where b_u <= -beta and q_u >= 2 tau b_u
-// (tau = gamma / (2 beta) = 2^-21; b_u is negative, so this admits a q_u down to -2 tau |b_u|) its near root b_u - s is negative
-// and its far root b_u + s = -q_u / (|b_u| + s) is at most tau = 4.8e-7, plus the light root's 2^-44 |b_u|: under half of
-// Intersect's 1e-5f within any reach the host admits (gamma / (2 beta) + reach 2^-44 < 1e-5f / 2), so nothing of that wall can be
-// accepted.  The bound on q_u scales with |b_u| because a bounce ray's q for the wall it LEAVES is not 0 but t^2 (d.d - 1), up to
-// 2e-4 either way — the direction's length comes from a float root, 1.2e-7 off —: a constant -gamma would fail half of all bounce
-// rays, -2 tau |b_u| = -2 tau r cos fails the ones flatter than cos = 2e-3.  beta keeps b_u's own rounding out of it and is
-// small enough for every bounce ray down to cos = 2^-17 (the host asks r 2^-17 >= 2 beta of a paired sphere).  NaN operands
-// compare false: not proven.
-constexpr double kPairBeta = 0.03125, kPairGamma = 2.98023223876953125e-8;  // 2^-5, 2^-25
-constexpr double kPairTau = kPairGamma / (2.0 * kPairBeta);                    // 2^-21
+// (kSceneWallPairs, SceneView::fold_flags' bit for it, and the proof with its constants kPairBeta, kPairGamma, kPairTau:
+// rtm_scene_flags.h)
 // (n, signature) pairs with an instantiation: X(n, sig) for each
 #define RTM_AXIS_SIGNATURES(X) X(7, kAxisSigCornell7) X(5, kAxisSigSimple5) X(3, kAxisSigSetting3)
 // b and D4 of sphere g (src/SettingData.cpp:198-200); pat: 0 general, 1 / 2 / 3 the centre is on the x / y / z axis

@@ -8,6 +8,7 @@
 //   superSamples default to 10 / 1; unknown keys are ignored like from_json does; objectType 2 is the
 //   build-defined plane (rtm.h: rtm_object; keys "03 up", "04 target", "01 size" = width); any other objectType
 //   is an error (HEAD would push a nullptr and crash at src/Renderer.cpp:66).
+// Also the home of the last-error message (set_last_error / last_error).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -24,6 +25,13 @@
 #include "rtm_internal.h"
 
 namespace rtm {
+
+// rtm_last_error's message, per thread.  Here, in a unit without HIP, so that host-only code (rtm_scene_facts.cpp) links with
+// this file alone.
+static thread_local std::string g_last_error;
+void set_last_error(const std::string& s) { g_last_error = s; }
+const char* last_error() { return g_last_error.c_str(); }
+
 namespace {
 
 struct JsonError : std::runtime_error {
