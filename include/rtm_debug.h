@@ -31,7 +31,14 @@ extern "C" {
  * y, walls on +x, -x, +y, -y, +z, -z sharing one K) on caller-given rays.  a: records as above; b: the scene's table in its first
  * 56 doubles — 7 geometry rows (cx, cy, cz, r * r), then 7 axis rows as rtm_debug_axis_rows returns them —, n >= 56.  55: the search
  * with opposite wall pairs, out = (distance, hit id or -1, 1 where the ray's wave took the seven-sphere block instead, 0 x 5);
- * 56: the seven-sphere block, out = (distance, hit id or -1, 0 x 6).  A wave holds the 8 rays of 64 consecutive doubles. */
+ * 56: the seven-sphere block, out = (distance, hit id or -1, 0 x 6).  A wave holds the 8 rays of 64 consecutive doubles.
+ * Ops 57 / 58: the words a lane of the tolerance row's render loops leaves the Russian roulette with.  Records of 8 doubles, n a
+ * multiple of 8, ONE LANE per record (lane i computes record i, so a wave holds 64 records and the caller decides which of its
+ * lanes continue): a = (p0, p1 of a pixel key, ctr, k1 of a stream, the sample index n' to restart with, ended != 0, unused x 2),
+ * the 32-bit words as doubles, b unused; the stream makes the roulette's draw first.  out = (the integer m of the bounce's first
+ * draw, of its second, ctr, k1 of the stream the lane goes on with, 0 x 4): for a continuing lane its two draws and the stream
+ * three draws on, for an ended lane (0, 0, the stream of sample n').  57: through the one mix32 pair both kinds of lane share
+ * (csrc/rtm_device.h: rng_merged_mix); 58: through rng_next_mi, rng_next and rng_open — the reference of 57. */
 int rtm_debug_math_probe(int op, const double* a, const double* b, size_t n, double* out);
 /* The tolerance row's sin / cos table as the HOST builds it for every device (no device is touched; runs in the CPU test
  * suite): out[2 i], out[2 i + 1] = sin, cos of i 2 pi / entries, evaluated in long double and rounded to double once.  The

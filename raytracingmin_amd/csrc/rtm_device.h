@@ -386,6 +386,25 @@ __host__ __device__ __forceinline__ uint32_t rng_next_mi(RngStream& s) {
 // ... and in a double.  Callers that only compare u with a constant, or scale it by one, fold the 2^-24 into the constant
 // (exact: a power of two) and save the ldexp.
 __host__ __device__ __forceinline__ double rng_next_m(RngStream& s) { return (double)rng_next_mi(s); }
+// One pair of mix32 bodies for both kinds of lane behind the roulette (round 13).  A lane whose path goes on needs the bits of
+// its next two draws, mix32(ctr ^ k1) and mix32((ctr + phi) ^ k1) of the stream `s` as the roulette's draw left it; a lane
+// whose path has ended needs the stream of the sample it restarts with, rng_open(pk, n_next) — the same two bodies on other
+// inputs.  Each lane forms its inputs in its own region and the wave runs the bodies once.  out = (first word, second word):
+// the bits of draws `s` would make next (rng_bits_to_mi / rng_bits_to_u01 turn them into the draws), or (ctr, k1) of the
+// opened stream.  No word of any stream changes: only where the instructions sit.
+__host__ __device__ __forceinline__ uint32_t rng_bits_to_mi(uint32_t x) { return 2u * (x >> 9) + 1u; }
+__host__ __device__ __forceinline__ RngStream rng_merged_mix(const bool ended, const RngPixelKey pk, const uint32_t n_next,
+                                                             const RngStream s) {
+    uint32_t a, b;
+    if (ended) {
+        a = pk.p0 + n_next * 0x9E3779B9u;
+        b = pk.p1 ^ (n_next * 0x85EBCA6Bu);
+    } else {
+        a = s.ctr ^ s.k1;
+        b = (s.ctr + 0x9E3779B9u) ^ s.k1;
+    }
+    return RngStream{mix32(a), mix32(b)};
+}
 __host__ __device__ __forceinline__ double rng_u01_at(uint64_t seed_mult, uint32_t pixel, uint32_t sample,
                                                       uint32_t index) {
     RngStream s = rng_open(rng_pixel_key(seed_mult, pixel), sample);

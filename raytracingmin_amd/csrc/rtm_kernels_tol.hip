@@ -138,7 +138,12 @@ static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hip
 // 55 / 56 the whole nearest-hit search of a seven-sphere scene with the Cornell box's signature on caller-given rays (records as
 // above; b: the scene's 7 geometry rows and, behind them, its 7 axis rows, 56 doubles, as a scene object keeps them): 55 with the
 // opposite wall pairs (kAxisSigCornell7Pairs), out = (distance, hit id, 1 where the ray's wave took the seven-sphere block, 0 ..),
-// 56 the seven-sphere block itself (kAxisSigCornell7Walls), out = (distance, hit id, 0 ..)
+// 56 the seven-sphere block itself (kAxisSigCornell7Walls), out = (distance, hit id, 0 ..),
+// 57 / 58 the words a lane leaves the roulette with, in records of 8 doubles, ONE LANE per record (lane i: record i), a = (p0, p1,
+// ctr, k1, n', ended, -, -) with the 32-bit words as doubles; the stream (ctr, k1) makes the roulette's draw first; out = (m of the
+// bounce's first draw, m of its second, ctr, k1 of the stream the lane goes on with, 0 ..) — a continuing lane's two draws and
+// its stream three draws on, an ended lane's (0, 0, rng_open((p0, p1), n')): 57 through rng_merged_mix (one mix32 pair for both
+// kinds of lane, as the render loops run it), 58 through rng_next_mi / rng_next / rng_open (its reference)
 __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, size_t n,
                                       double* __restrict__ out, const double2* __restrict__ tab) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -177,6 +182,39 @@ __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, cons
             else sphere_chunk<MathFast, 7, SceneGlobal, false, kAxisSigCornell7Walls>(sc, 0, org, dir, dis, hit);
         }
         out[i] = (i & 7) == 0 ? dis : (i & 7) == 1 ? (double)hit : (i & 7) == 2 ? (fell_back ? 1.0 : 0.0) : 0.0;
+        return;
+    }
+    if (op == 57 || op == 58) {  // ONE lane per record (a wave holds 64 records: the caller mixes the two kinds of lane in it)
+        if (i * 8 + 7 >= n) return;
+        const double* q = a + i * 8;
+        const RngPixelKey pk{(uint32_t)q[0], (uint32_t)q[1]};
+        RngStream st{(uint32_t)q[2], (uint32_t)q[3]};
+        const uint32_t n_next = (uint32_t)q[4];
+        const bool ended = q[5] != 0.0;
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        (void)rng_next_mi(st);  // the roulette's draw
+        if (op == 57) {
+            const RngStream m = rng_merged_mix(ended, pk, n_next, st);
+            if (ended) {
+                w[2] = m.ctr;
+                w[3] = m.k1;
+            } else {
+                w[0] = rng_bits_to_mi(m.ctr);
+                w[1] = (uint32_t)(rng_bits_to_u01(m.k1) * 16777216.0);
+                w[2] = st.ctr + 2u * 0x9E3779B9u;
+                w[3] = st.k1;
+            }
+        } else if (ended) {
+            st = rng_open(pk, n_next);
+            w[2] = st.ctr;
+            w[3] = st.k1;
+        } else {
+            w[0] = rng_next_mi(st);
+            w[1] = (uint32_t)(rng_next(st) * 16777216.0);
+            w[2] = st.ctr;
+            w[3] = st.k1;
+        }
+        for (int k = 0; k < 8; ++k) out[i * 8 + k] = k < 4 ? (double)w[k] : 0.0;
         return;
     }
     const double x = a[i], y = b ? b[i] : 0.0;

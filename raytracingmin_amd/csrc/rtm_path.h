@@ -1040,6 +1040,9 @@ constexpr unsigned kAxisSigSimple5 = (1u << 2) | (1u << 4) | (2u << 6) | (2u << 
 // settingData.json: the light on the y axis, a sphere at the origin, one on the x axis
 constexpr unsigned kAxisSigSetting3 = 2u | (1u << 4);
 constexpr int axis_unroll(const int n, const unsigned sig) { return -(1000 + n + 8 * (int)sig); }
+// ... and the sphere count back out of it (n < 8: the code's low three bits)
+constexpr int axis_unroll_n(const int unroll) { return (-unroll - 1000) & 7; }
+static_assert(axis_unroll_n(axis_unroll(7, kAxisSigCornell7)) == 7 && axis_unroll_n(axis_unroll(3, kAxisSigSetting3)) == 3, "");
 // The tolerance unit's extension of a signature: bit 16 + i = sphere i belongs to the group that shares one K (kSceneSharedKShift;
 // sphere_disc's expanded form).  The Cornell box with its six walls of one radius at one distance:
 constexpr unsigned kAxisSharedKShift = 16u;
@@ -1894,10 +1897,56 @@ __device__ __forceinline__ void set_bounce_dir(MI& m, ShadeOut& out, const D3 nd
 }
 // The bounce itself (src/Renderer.cpp:79-108): everything after the Russian-roulette test has passed.  `rng` is
 // the stream right after the RR draw; always continues.
+#if RTM_TOL
+// What a deferred-fold render loop hands the speculative shading block so that a lane whose path ENDS in this trip opens its next
+// sample's stream inside the mix32 pair of the bounce's two draws (rtm_device.h: rng_merged_mix; round 13): the pixel's key and
+// the sample index the lane restarts with, add_lane_bit(n, m_inc) — the loop's own rule, formed in the ended lanes' region.
+// `next`: that stream, valid for every lane whose path ended (whichever attempt counted: path_shade_spec_fix).
+struct StreamReopen {
+    RngPixelKey pkey;
+    uint32_t n;
+    unsigned long long m_inc;
+    RngStream next;
+    __device__ __forceinline__ uint32_t n_next() const { return add_lane_bit(n, m_inc); }
+};
+#endif
+// `pre`: the bits of the bounce's two draws where the caller has already mixed them (tolerance unit, rng_merged_mix)
 template <class MI, class Scene>
 __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const int id, const double dis, const int mode,
-                                                 const D3 org, const D3 dir, RngStream rng, ShadeOut& out);
+                                                 const D3 org, const D3 dir, RngStream rng, ShadeOut& out,
+                                                 const RngStream* pre = nullptr);
 
+#if RTM_TOL
+// path_shade_core of the speculative block with the stream hand-over: the three ways a path ends (:116, the depth cap, :112) fall
+// into one region that forms rng_open's inputs, the continuing lanes form their two draws', and the whole wave runs the two mix32
+// bodies once, between the roulette and the bounce.  Same draws, same order, same counters.  (`term` is the ended path's as in
+// path_shade_core, its TWIN below: the end conditions, `term` and out.draws there and here must stay the same.)
+template <class MI, class Scene>
+__device__ __forceinline__ bool path_shade_core_reopen(MI& m, const Scene& sc, const int id, const double dis, const int mode,
+                                                       const int max_bounces, const D3 org, const D3 dir, const int depth,
+                                                       RngStream rng, D3& term, ShadeOut& out, StreamReopen& ro) {
+    out.draws = 0;
+    bool pass = false;
+    if (id >= 0 && !(max_bounces >= 0 && depth >= max_bounces)) {  // (a hit below the depth cap: the only case that draws)
+        out.draws = 1;
+        pass = rng_next_m(rng) <= sc.kd24(id);  // :78
+    }
+    uint32_t n_next = 0u;
+    if (!pass) {  // ended — :116 a miss, the depth cap, :112; a continuing lane's `term` is left alone, as in the twin
+        if (id < 0) term = d3(0, 0, 0);
+        else term = sc.emission(id);
+        n_next = ro.n_next();
+    }
+    const RngStream w = rng_merged_mix(!pass, ro.pkey, n_next, rng);
+    ro.next = w;
+    if (!pass) return false;
+    path_bounce_core(m, sc, id, dis, mode, org, dir, rng, out, &w);
+    return true;
+}
+#endif
+
+// (TWIN: path_shade_core_reopen above restates these three ways a path ends, their `term` and their draw count around one
+// shared mix32 pair — a change to either is a change to both; tests/test_merged_mix_gpu.py renders through both.)
 template <class MI, class Scene>
 __device__ __forceinline__ bool path_shade_core(MI& m, const Scene& sc, const int id, const double dis,
                                                 const int mode, const int max_bounces, const D3 org, const D3 dir,
@@ -1925,7 +1974,8 @@ __device__ __forceinline__ bool path_shade_core(MI& m, const Scene& sc, const in
 
 template <class MI, class Scene>
 __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const int id, const double dis, const int mode,
-                                                 const D3 org, const D3 dir, RngStream rng, ShadeOut& out) {
+                                                 const D3 org, const D3 dir, RngStream rng, ShadeOut& out,
+                                                 [[maybe_unused]] const RngStream* pre) {
     const D3 hit_point = dir * dis + org;  // :79
     // D2: in literal mode the caller's normal stays (0,0,0); repaired: src/SettingData.cpp:214-215
     D3 normal = d3(0, 0, 0);
@@ -1967,9 +2017,11 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
 #if !RTM_TOL
     const double m24 = rng_next_m(rng);  // (r1 is formed where its sin / cos are taken: sincos_draw)
 #else  // (the tolerance unit splits the draw's integer: no conversion)
-    const uint32_t m24i = rng_next_mi(rng);
+    // (... and where the caller has mixed both draws' bits already, takes them: rng_merged_mix)
+    const uint32_t m24i = pre ? rng_bits_to_mi(pre->ctr) : rng_next_mi(rng);
+    if (pre) rng.ctr += 2u * 0x9E3779B9u;
 #endif
-    const double r2 = rng_next(rng);                      // :89
+    const double r2 = (RTM_TOL && pre) ? rng_bits_to_u01(pre->k1) : rng_next(rng);  // :89
 #if !RTM_TOL  // (the tolerance unit takes the device's sin / cos: launch_tol)
     TrigFixWord fixw{0u, 0};
     if (sc.v.trig_fix) fixw = trig_fix_load(sc.v.trig_fix, rng);  // wave-uniform; consumed after the sincos
@@ -2105,16 +2157,21 @@ template <class Scene, typename PushFn, typename FixFn>
 __device__ __forceinline__ bool path_shade_spec_fix(const Scene& sc, int& id, double& dis, const int mode, const int max_bounces,
                                                     D3& org, D3& dir, int& depth, RngStream& rng, D3& term, PathCounters& pc,
                                                     PushFn push, const ShadeLds lds, const bool flagged, FixFn fix,
-                                                    const bool stream_after_end = true) {
+                                                    const bool stream_after_end = true, StreamReopen* reopen = nullptr) {
     ShadeOut o;
     typename std::conditional<Scene::kPlanes, MathSpecZ, MathSpec>::type m;
     m.set_lds(lds);
-    bool cont = path_shade_core(m, sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, o);
+    // (`reopen`: a lane whose path ends here leaves with its next sample's stream in reopen->next — path_shade_core_reopen)
+    bool cont = reopen ? path_shade_core_reopen(m, sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, o, *reopen)
+                       : path_shade_core(m, sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, o);
     if (__builtin_amdgcn_ballot_w64(m.bad || flagged) != 0) {
         fix(id, dis);
         MathRefI r;
         r.set_lds(lds);
+        // from the trip's incoming state, with its own unmerged draws; a flagged lane's hit may have changed, and with it whether
+        // its path ends: every lane's next stream is opened again, plainly (rare)
         cont = path_shade_core(r, sc, id, dis, mode, max_bounces, org, dir, depth, rng, term, o);
+        if (reopen) reopen->next = rng_open(reopen->pkey, reopen->n_next());
     }
     pc.casts++;
     pc.draws += (unsigned)o.draws;

@@ -387,6 +387,14 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // row's index and the empty record word as immediates).  Measured and not kept (profiles/r4/ctn_ab.txt): the
     // tolerance row does not move, the exact kernel loses 3 %.
     const int scene_n = P.scene.n;
+    // ... and the index an empty record word is filled with: for the tolerance unit's axis-signature instantiations the sphere
+    // count their UNROLL encodes (rtm_path.h: axis_unroll; launched for exactly that count) — the word is then a constant of
+    // the code where the render loop restarts a path, not a spilled scalar pair read back.  For this word only (round 4: the
+    // count as a constant everywhere was worth nothing or a loss).
+    // Not for the any-depth kernel with the sample split: it pays for either of round 13's two items with 12 bytes of scratch
+    // that its parent does not have (-Rpass-analysis=kernel-resource-usage; profiles/r13/merged_mix.md), like kPairsShape.
+    constexpr bool kAxisTolShape = RTM_TOL != 0 && UNROLL <= -1000 && (F & (kPackL | kSplit)) != (kPackL | kSplit);
+    [[maybe_unused]] const int empty_n = kAxisTolShape ? axis_unroll_n(UNROLL) : scene_n;
     constexpr bool kRowTab = LDS_TAB && lds_rows_for(UNROLL);  // one row per sphere: SceneLdsRows
     static_assert(!(kRowTab && PLANES), "a plane's normal has no place in a sphere's row");
     double* lgeom = reinterpret_cast<double*>(lds_raw);  // (kRowTab: the rows)
@@ -513,6 +521,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
     // (round 4, later: the any-depth kernels too — PACKL has no stealing, a lane only ever asks for its OWN pixel's word and
     // reads it from the pre-pass's table when it moves on to a sub-pixel: no LDS, no register pair across the loop)
     constexpr bool kPrimFix = (RTM_TOL != 0) && (STEAL || PACKL);
+    // ... and a lane whose path ends opens its next sample's stream inside the mix32 pair of the bounce's draws (rtm_path.h:
+    // path_shade_core_reopen; round 13): the deferred-fold loops of the tolerance unit's axis-signature kernels
+    [[maybe_unused]] constexpr bool kReopen = kPrimFix && DEFER && !REUSE && kAxisTolShape;
     unsigned long long* prim_mask = reinterpret_cast<unsigned long long*>(fq_pend + 3 * 64);  // STEAL: behind its two arrays
     [[maybe_unused]] auto own_prim_mask = [&]() -> unsigned long long {
         if constexpr (STEAL) {
@@ -617,7 +628,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
         park[5 * 64 + lane] = pdir.z;
     }
 
-    unsigned long long recq = packed8_empty(scene_n);  // PACK8 records, most recent bounce in the low byte
+    unsigned long long recq = packed8_empty(empty_n);  // PACK8 records, most recent bounce in the low byte
     auto push = [&](int d, int id) {
         if constexpr (PACK8) {
             recq = (recq << 8) | (unsigned long long)(unsigned)id;
@@ -900,6 +911,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
             PathCounters unused = {0, 0, 0};
             bool cont;
 #if RTM_TOL
+            // the next sample's stream of a lane whose path ends in this trip: opened inside the bounce's draws (rtm_path.h:
+            // path_shade_core_reopen), for the sample index the restart below moves the lane to
+            [[maybe_unused]] StreamReopen reopen{pkey, n, m_live, RngStream{0u, 0u}};
             if constexpr (kPrimFix) {
                 double dis;
                 hit_id = nearest_hit<M, UNROLL>(sc, org, dir, dis);
@@ -910,12 +924,18 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                                                const int id_ref = nearest_hit_exactfp(sc, org, dir, dis_ref);
                                                id_fix = flagged ? id_ref : id_fix;
                                                dis_fix = flagged ? dis_ref : dis_fix;
-                                           }, /*stream_after_end=*/false);  // (a path end reopens the lane's stream below)
+                                           }, /*stream_after_end=*/false, kReopen ? &reopen : nullptr);  // (kReopen: a path end takes its next stream from there)
             } else
 #endif
             cont = path_step<M, UNROLL>(sc, mode, P.max_bounces, org, dir, depth, rng, term, unused, push,
                                         shade_lds, &hit_id, /*stream_after_end=*/false);
-            if (PACKL && cont && stack.overflow) cont = false;  // records exhausted: the call fails loudly
+            if (PACKL && cont && stack.overflow) {  // records exhausted: the call fails loudly
+                cont = false;
+#if RTM_TOL
+                // (the lane went on: what it holds are its draws' bits, not the stream the restart below takes)
+                if constexpr (kReopen) reopen.next = rng_open(pkey, reopen.n_next());
+#endif
+            }
             // counters (src/Renderer.cpp has none; rtm_stats): one cast per live lane, one draw for the RR test of a
             // hit below the depth cap, two more and a bounce when the path continues
             // (lane masks from compares, combined as scalars: a ballot of a bool that is no compare goes through a VGPR and
@@ -1031,7 +1051,11 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 org = P.cam_org;
                 dir = d3(park[3 * 64 + lane], park[4 * 64 + lane], park[5 * 64 + lane]);
                 depth = 0;
-                recq = packed8_empty(scene_n);
+                recq = packed8_empty(empty_n);
+#if RTM_TOL
+                if constexpr (kReopen) rng = reopen.next;  // == rng_open(pkey, n)
+                else
+#endif
                 rng = rng_open(pkey, n);
             }
             const unsigned added = (unsigned)__builtin_popcountll(m_queued);  // queued entries only
@@ -1095,7 +1119,9 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                                                const int id_ref = nearest_hit_exactfp(sc, org, dir, dis_ref);
                                                id_fix = flagged ? id_ref : id_fix;
                                                dis_fix = flagged ? dis_ref : dis_fix;
-                                           }, /*stream_after_end=*/false);  // (a path end reopens the lane's stream below)
+                                           }, /*stream_after_end=*/false);  // (a path end reopens the lane's stream below: plainly —
+                                                                            // the main loop's hand-over here costs the headline kernel
+                                                                            // its 128th register and 8 bytes of scratch)
             } else
 #endif
             cont = path_step<M, UNROLL>(sc, mode, P.max_bounces, org, dir, depth, rng, term, unused, push, shade_lds, &hit_id,
@@ -1205,7 +1231,7 @@ __global__ __launch_bounds__(64, WPE) void render_tiles_kernel(const RenderParam
                 busy = got;
                 org = P.cam_org;
                 depth = 0;
-                recq = packed8_empty(scene_n);
+                recq = packed8_empty(empty_n);
                 if constexpr (kPrimFix) prim_fix = prim_fix && got;
             }
             if (added != 0u) {
