@@ -38,7 +38,13 @@ extern "C" {
  * the 32-bit words as doubles, b unused; the stream makes the roulette's draw first.  out = (the integer m of the bounce's first
  * draw, of its second, ctr, k1 of the stream the lane goes on with, 0 x 4): for a continuing lane its two draws and the stream
  * three draws on, for an ended lane (0, 0, the stream of sample n').  57: through the one mix32 pair both kinds of lane share
- * (csrc/rtm_device.h: rng_merged_mix); 58: through rng_next_mi, rng_next and rng_open — the reference of 57. */
+ * (csrc/rtm_device.h: rng_merged_mix); 58: through rng_next_mi, rng_next and rng_open — the reference of 57.
+ * Ops 59 / 60: a bounce direction of the tolerance row's shading block BEFORE its final Normalize (src/Renderer.cpp:96-107).
+ * Records and lanes as for 57 / 58: a = (w.x, w.y, w.z of the turned normal, the odd integers m1 and m2 < 2^24 of the bounce's
+ * two draws — the angle 2 pi m1 2^-24 and r2 = m2 2^-24 —, unused x 3), b unused, out = (nd.x, nd.y, nd.z, 1 where the lane set
+ * the block's `bad` flag, 0 x 4).  No component of w may be zero (such a lane is another branch's in the render loops).
+ * 59: from one reciprocal root, k = sqrt(r2) / y, without the orthonormal basis (csrc/rtm_path.h: bounce_nd_fused), as the block
+ * runs it; 60: with the basis built, a refined reciprocal and a root (bounce_nd_basis) — the reference of 59. */
 int rtm_debug_math_probe(int op, const double* a, const double* b, size_t n, double* out);
 /* The tolerance row's sin / cos table as the HOST builds it for every device (no device is touched; runs in the CPU test
  * suite): out[2 i], out[2 i + 1] = sin, cos of i 2 pi / entries, evaluated in long double and rounded to double once.  The

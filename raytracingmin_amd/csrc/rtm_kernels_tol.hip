@@ -143,7 +143,11 @@ static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hip
 // ctr, k1, n', ended, -, -) with the 32-bit words as doubles; the stream (ctr, k1) makes the roulette's draw first; out = (m of the
 // bounce's first draw, m of its second, ctr, k1 of the stream the lane goes on with, 0 ..) — a continuing lane's two draws and
 // its stream three draws on, an ended lane's (0, 0, rng_open((p0, p1), n')): 57 through rng_merged_mix (one mix32 pair for both
-// kinds of lane, as the render loops run it), 58 through rng_next_mi / rng_next / rng_open (its reference)
+// kinds of lane, as the render loops run it), 58 through rng_next_mi / rng_next / rng_open (its reference),
+// 59 / 60 a bounce direction before its Normalize, records and lanes as 57 / 58, a = (w.x, w.y, w.z, m1, m2, -, -, -) with w the
+// turned normal (no zero component) and m1, m2 the odd integers of the bounce's two draws, out = (nd.x, nd.y, nd.z, 1 where the
+// lane set `bad`, 0 ..): 59 from one reciprocal root, without the basis (rtm_path.h: bounce_nd_fused, as the shading block runs
+// it), 60 with the basis built (bounce_nd_basis: the form of rounds 2 to 13, its reference)
 __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, size_t n,
                                       double* __restrict__ out, const double2* __restrict__ tab) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -215,6 +219,20 @@ __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, cons
             w[3] = st.k1;
         }
         for (int k = 0; k < 8; ++k) out[i * 8 + k] = k < 4 ? (double)w[k] : 0.0;
+        return;
+    }
+    if (op == 59 || op == 60) {  // ONE lane per record, as above; `tab`: the device's sin / cos table
+        if (i * 8 + 7 >= n) return;
+        const double* q = a + i * 8;
+        const D3 w = d3(q[0], q[1], q[2]);
+        const uint32_t m1 = (uint32_t)q[3];
+        const double r2 = (double)(uint32_t)q[4] * (1.0 / 16777216.0);  // rng_bits_to_u01's value for the draw's integer
+        MathSpec m;
+        m.trig_tab = tab;
+        const MathSpec::TrigAhead ahead = m.sincos_draw_issue(m1);
+        const D3 nd = op == 59 ? bounce_nd_fused(m, w, r2, ahead) : bounce_nd_basis(m, w, r2, ahead);
+        const double res[4] = {nd.x, nd.y, nd.z, m.bad ? 1.0 : 0.0};
+        for (int k = 0; k < 8; ++k) out[i * 8 + k] = k < 4 ? res[k] : 0.0;
         return;
     }
     const double x = a[i], y = b ? b[i] : 0.0;
@@ -334,7 +352,7 @@ int tol_lds_bytes(int n, int any_depth, int split, int rows, uint64_t* out) {
 
 int tol_math_probe(int op, const double* a_dev, const double* b_dev, size_t n, double* out_dev) {
     const double2* tab = nullptr;
-    if (op == 42 || op == 43 || op == 46 || op == 47) {
+    if (op == 42 || op == 43 || op == 46 || op == 47 || op == 59 || op == 60) {
         if (ensure_trig_tab(&tab) != RTM_OK) {
             set_last_error("tolerance row: the sin / cos table could not be written on the device");
             return RTM_ERR_HIP;

@@ -458,6 +458,31 @@ struct MathSpecT {
         ux = one(cx);
         uz = one(cz);
     }
+#if RTM_TOL
+    // What a bounce direction needs of that Normalize and of sqrt(r2) together (path_bounce_core: bounce_nd_fused): their
+    // QUOTIENT k = sqrt(r2) / y, y the same float-island length of (cx, +-0, cz) with the same guard, and L = cx^2 + cz^2, the
+    // double sum y is taken from.  y * y is exact in a double (24 x 24 bits), so with p = r2 (y * y)
+    //   k = r2 * rsqrt(p) = r2 / (sqrt(r2) y)
+    // is ONE reciprocal root — the light sequence of sqrt64_unit with r2 in the place of its operand in the last two steps
+    // (k0 = r2 y0, k = k0 + k0 r0; 1.5 e^2 = 2^-45 relative, plus p's one rounding) — where the reciprocal of y and the root of
+    // r2 were two transcendentals and a refinement each.
+    // Range of p: r2 is an odd multiple of 2^-24 in (0, 1), so in [2^-24, 1); sqrtf_fast_ok(len2) puts len2 in [2^-96, 2^128),
+    // y in [2^-48, 2^64) and y * y in [2^-96, 2^128): p is in [2^-120, 2^128), a positive normal number well inside what the
+    // unscaled sequence takes ([2^-767, 2^1023): MathFast::sqrt_fast_ok), and v_rsq_f64(p) in (2^-64, 2^60] is normal, which
+    // is what half_of_rsq asks for.  No condition to add to `bad`.
+    __device__ __forceinline__ void bounce_scale_xz(double cx, double cz, double r2, double& k, double& L) {
+        const double sx = cx * cx, sz = cz * cz;
+        L = sx + sz;
+        const float len2 = (float)L;
+        bad = bad | !sqrtf_fast_ok(len2);
+        const double y = (double)sqrtf_fast(len2);
+        const double p = r2 * (y * y);
+        const double y0 = __builtin_amdgcn_rsq(p);
+        const double k0 = r2 * y0, s0 = p * y0, h0 = half_of_rsq(y0);  // (h0 last: y0 dies there, see half_of_rsq)
+        const double r0 = __builtin_fma(-h0, s0, 0.5);
+        k = __builtin_fma(k0, r0, k0);
+    }
+#endif
     // Normalize(hit - centre) (src/SettingData.cpp:214-215) for a hit point that is ON its sphere to
     // float precision: then (float)|dv|^2 is exactly (float)(r*r), so Magnitude returns the
     // per-sphere constant `ms` and the reciprocal refinement of the three divisions is the
@@ -1972,6 +1997,41 @@ __device__ __forceinline__ bool path_shade_core(MI& m, const Scene& sc, const in
     return true;
 }
 
+#if RTM_TOL
+// The bounce direction before its Normalize (src/Renderer.cpp:96-107) of the guarded speculative block where no lane of the wave
+// takes the x axis (path_bounce_core's comment has the structural zeros), for w with no zero component and the draws r2 and
+// `ahead` (the angle's table point).  u and v both carry 1 / y (y: the float-island length of c = (w.z, +-0, -w.x)) and both
+// are multiplied by sqrt(r2): with k = sqrt(r2) / y and L = w.z^2 + w.x^2, from w x c = (-w.x w.y, L, -w.y w.z),
+//   nd.x = k ( w.z cos - w.x w.y sin) + w.x s1  =  w.z a + w.x t        a = k cos, b = k sin
+//   nd.y = k L sin                    + w.y s1  =  b L   + w.y s1       t = s1 - b w.y
+//   nd.z = k (-w.x cos - w.y w.z sin) + w.z s1  = -w.x a + w.z t        s1 = sqrt(1 - r2)
+// — one reciprocal root (MathSpecT::bounce_scale_xz) and 9 more instructions where bounce_nd_basis takes a refined reciprocal,
+// a light root and 19.  The same quantity to the same 2^-45 per component (tests/test_bounce_fused_host.py).
+template <class MI>
+__device__ __forceinline__ D3 bounce_nd_fused(MI& m, const D3 w, const double r2, const typename MI::TrigAhead& ahead) {
+    double k, L, sn, cs;
+    m.bounce_scale_xz(w.z, -w.x, r2, k, L);
+    m.sincos_draw(ahead, sn, cs);
+    const double s1 = m.sqrt64_unit(1.0 - r2);
+    const double a = k * cs, b = k * sn;
+    const double t = __builtin_fma(-b, w.y, s1);
+    return d3(__builtin_fma(w.z, a, w.x * t), __builtin_fma(b, L, w.y * s1), __builtin_fma(-w.x, a, w.z * t));
+}
+// ... and with the basis built: the form of rounds 2 to 13.  No render kernel runs it any more (none gained scratch or lost a
+// wave with the fused form: profiles/r14/bounce_fused.md); rtm_debug_math_probe op 60 does, as op 59's reference.
+template <class MI>
+__device__ __forceinline__ D3 bounce_nd_basis(MI& m, const D3 w, const double r2, const typename MI::TrigAhead& ahead) {
+    double ux, uz, sn, cs;
+    const double r2s = m.sqrt64_unit(r2);  // :90
+    m.normalize_xz(w.z, -w.x, ux, uz);
+    const double vx = w.y * uz, vy = -w.x * uz + w.z * ux, vz = -(w.y * ux);
+    m.sincos_draw(ahead, sn, cs);
+    const double s1 = m.sqrt64_unit(1.0 - r2);
+    return d3(((ux * cs) * r2s + (vx * sn) * r2s) + w.x * s1, (vy * sn) * r2s + w.y * s1,
+              ((uz * cs) * r2s + (vz * sn) * r2s) + w.z * s1);
+}
+#endif
+
 template <class MI, class Scene>
 __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const int id, const double dis, const int mode,
                                                  const D3 org, const D3 dir, RngStream rng, ShadeOut& out,
@@ -2028,7 +2088,9 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
 #else  // ... by table point and short series: the gather is issued here and consumed where the sine is taken
     const typename MI::TrigAhead trig_ahead = m.sincos_draw_issue(m24i);
 #endif
+#if !RTM_TOL
     const double r2s = m.sqrt64_unit(r2);                 // :90
+#endif  // (the tolerance unit: where the branch taken needs it — the guarded flavour's own branch has it inside k, bounce_nd_fused)
     // :96-101 — one Normalize on the selected cross product (same values as the two-armed if)
     const bool use_y = fabs(w.x) > (double)FLT_MIN;
     const bool some_x_axis = __builtin_amdgcn_ballot_w64(!use_y) != 0;  // some lane has |w.x| <= FLT_MIN (e.g. literal mode)
@@ -2044,23 +2106,26 @@ __device__ __forceinline__ void path_bounce_core(MI& m, const Scene& sc, const i
             //                   = (w.y*u.z, -w.x*u.z + w.z*u.x, -(w.y*u.x))             [products are never 0]
             //   nd.y = ((+-0)*cos*r2s + (v.y*sin)*r2s) + w.y*s = (v.y*sin)*r2s + w.y*s   [v.y = L > 0, sin != 0]
             // 12 fp64 instructions fewer than the literal form.
+#if !RTM_TOL
             double ux, uz;
             m.normalize_xz(w.z, -w.x, ux, uz);
             const double vx = w.y * uz, vy = -w.x * uz + w.z * ux, vz = -(w.y * ux);
-#if !RTM_TOL
             m.sincos_draw(m24, sn, cs);
             if (sc.v.trig_fix) trig_fix_apply(fixw, sn, cs);  // wave-uniform
-#else
-            m.sincos_draw(trig_ahead, sn, cs);
-#endif
             const double s1 = m.sqrt64_unit(1.0 - r2);
             set_bounce_dir(m, out, d3(((ux * cs) * r2s + (vx * sn) * r2s) + w.x * s1, (vy * sn) * r2s + w.y * s1,
                                       ((uz * cs) * r2s + (vz * sn) * r2s) + w.z * s1));  // :103-107
+#else  // ... and the tolerance unit takes the factor u, v and sqrt(r2) share as one reciprocal root, without the basis
+            set_bounce_dir(m, out, bounce_nd_fused(m, w, r2, trig_ahead));  // :103-107
+#endif
             out.org = hit_point;
             out.ctr = rng.ctr;
             return;
         }
     }
+#if RTM_TOL
+    const double r2s = m.sqrt64_unit(r2);                 // :90
+#endif
     D3 c = cross(d3(0, 1, 0), w);
     D3 u;
     if (some_x_axis) {
