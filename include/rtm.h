@@ -582,6 +582,65 @@ size_t rtm_tonemap_work_bytes(int32_t width, int32_t height);
 int rtm_tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, rtm_tonemap_stats* stats_out_dev, void* stream);
 
+/* ---- bloom (glare): the light a bright part of an HDR frame scatters into its surround, added in linear space before the
+ * display transform — a bright pass, a pyramid of 4-tap down filters, an up pass that blends each coarser level into the
+ * finer, and the add-back.  Opt-in: every other stage and its defaults stay.
+ * Input: color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32; 4-byte alignment is enough).  Arithmetic in
+ * float, without contraction.  lum(c) = (0.2126 c_R + 0.7152 c_G) + 0.0722 c_B (rtm_tonemap's).
+ *   1 counting    a pixel COUNTS iff its three components are finite.  A pixel that does not count is (0, 0, 0) for steps
+ *                 2-5: it contributes no light.
+ *   2 bright pass per full-resolution pixel, never stored: x = max(c, 0) per channel, Y = lum(x), T = threshold,
+ *                 K = knee T,
+ *                   soft = min(max(Y - T + K, 0), 2K);  soft = soft soft / (4K + 1e-5f)
+ *                   g = max(soft, Y - T) / max(Y, 1e-5f);  b0 = x g
+ *                 g is continuous in Y.  threshold = 0 passes everything (g = Y / max(Y, 1e-5f)).  A frame whose every Y is at
+ *                 or below T - K (with knee = 0: at or below the threshold) gives a bloom of exactly +0.
+ *   3 down        level 0 is b0 at W_0 x H_0 = width x height; level l = 1..L has W_l = ceil(W_{l-1} / 2), H_l likewise (a
+ *                 side that has reached 1 stays 1), and
+ *                   d_l(X, Y) = sum over dy, dx in {-1, 0, 1, 2} of k[dx] k[dy] d_{l-1}(2X + dx, 2Y + dy) / (K_x K_y),
+ *                 d_0 = b0, k = {1/8, 3/8, 3/8, 1/8}.  Taps outside level l-1's frame are skipped (not clamped); K_x is the sum
+ *                 of k over the dx in the frame, K_y likewise: the library's skip-and-renormalise rule, and separable.  The
+ *                 horizontal pass comes first.  The tap 2X is always in the frame; the filter is centred on 2X + 0.5, the
+ *                 centre of the coarse pixel.
+ *   4 up          u_L = d_L; for l = L-1 .. 1: u_l = (1 - scatter) d_l + scatter up_l(u_{l+1}).  up_l resamples level l+1 to
+ *                 W_l x H_l: for the fine column x, X0 = floor((x - 1) / 2) (floor division: x = 0 gives -1), the taps are X0
+ *                 and X0 + 1 with the weights (1/4, 3/4) for even x and (3/4, 1/4) for odd x (the fine pixel's centre is at
+ *                 x / 2 - 1/4 in coarse coordinates); rows alike.  Taps outside the frame are skipped and the rest
+ *                 renormalised; the 3/4 tap is always in the frame.  up is the exact counterpart of step 3's alignment.
+ *   5 combine     B = up_0(u_1) at full resolution.  A pixel that counts: out_f32 = c + intensity B per channel (c, not x).
+ *                 A pixel that does not count: out_f32 is its input, bit for bit — bloom adds light, it does not repair, and
+ *                 rtm_tonemap downstream still sees the pixel as not counting.  bloom_out_dev (nullable, height x width x 3
+ *                 floats) receives B at every pixel.  out_u8 (nullable) is the denoisers' store of the call's own out_f32:
+ *                 rtm_quantise of (double)out_f32, out of range (NaN included) -> 0.
+ * It follows that a constant frame c >= 0 with threshold 0 gives B = c at every level, and that intensity = 0 leaves every
+ * counting pixel equal to its input.
+ * The divisions may be the device's fast forms: against a float64 evaluation of the steps above every out_f32 component of a
+ * counting pixel and every bloom_out component is within 1e-4 max(1, |ref|); out_u8 is exact given the call's own out_f32.
+ * No atomics: the same inputs give the same bits on every call, on any stream, at any alignment of color.
+ * work_dev: DEVICE, 256-byte aligned, rtm_bloom_work_bytes = the sum over l = 1..L of round256(16 W_l H_l) bytes: one plane
+ * of 16-byte records per level (u_l overwrites d_l in place: the up pass reads d_l only at the pixel it writes); the plane of
+ * level 1 is about 4 bytes per full-resolution pixel.  0 for a non-positive size or levels outside 1..8, SIZE_MAX when the
+ * frame (12 bytes a pixel) or the sum does not fit a size_t.  The call allocates nothing, keeps no per-(device, stream)
+ * state, needs no serialisation and only ENQUEUES 2L launches on `stream`.  out_f32_dev == color_dev (in place) is allowed:
+ * the pyramid is read from color before the combine, in stream order.  Null params, color_dev or work_dev, all three outputs
+ * null, a non-positive size, a NaN, infinite or out-of-range parameter, levels outside 1..8, a frame or bloom_out pointer
+ * that is not 4-byte aligned, a misaligned work_dev, work_dev equal to any other buffer, bloom_out_dev equal to color_dev or
+ * out_f32_dev, out_u8_dev equal to color_dev, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A frame
+ * of 2^31 pixels or more: RTM_ERR_UNSUPPORTED, as rtm_tonemap.
+ * Defaults: RTM_BLOOM_DEFAULTS below, the customary ones of this filter (what Renderer.Render(bloom=True) and rtm_cli --bloom
+ * use).  Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+typedef struct rtm_bloom_params { /* 20 bytes */
+    float threshold;   /* finite, >= 0: luminance above which a pixel blooms           */
+    float knee;        /* in [0, 1]: the soft knee, as a fraction of the threshold     */
+    float intensity;   /* finite, >= 0                                                  */
+    float scatter;     /* in [0, 1]: how much of each coarser level reaches the finer  */
+    int32_t levels;    /* L, 1..8                                                       */
+} rtm_bloom_params;
+#define RTM_BLOOM_DEFAULTS {1.0f, 0.5f, 0.2f, 0.7f, 6} /* of rtm_bloom_params */
+size_t rtm_bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
+int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+              void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream);
+
 /* ---- AOV-guided upsampling: a frame traced at 1/f of the resolution in each axis, brought to full size by a joint
  * bilateral upsample (Kopf et al. 2007) steered by the full-resolution first-hit planes, with the albedo demodulated so that
  * material colour comes back at full resolution.  The AOVs have no random draws and cost one cheap kernel at any size; the

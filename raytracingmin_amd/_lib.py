@@ -106,6 +106,11 @@ class rtm_tonemap_stats(C.Structure):  # what rtm_tonemap leaves in stats_out_de
     _fields_ = [("log_average", C.c_float), ("max_luminance", C.c_float), ("exposure", C.c_float), ("pixels", C.c_uint32)]
 
 
+class rtm_bloom_params(C.Structure):  # include/rtm.h: rtm_bloom (20 bytes)
+    _fields_ = [("threshold", C.c_float), ("knee", C.c_float), ("intensity", C.c_float), ("scatter", C.c_float),
+                ("levels", C.c_int32)]
+
+
 COMPARE_DTYPES = {"float32": 0, "float64": 1}  # include/rtm.h: RTM_COMPARE_F32, RTM_COMPARE_F64
 COMPARE_MAPS = {"abs": 0, "ssim": 1}  # RTM_COMPARE_MAP_*
 
@@ -174,6 +179,9 @@ SIGNATURES = {
     "rtm_tonemap_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_tonemap": (C.c_int, [_P(rtm_tonemap_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_bloom_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rtm_bloom": (C.c_int, [_P(rtm_bloom_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_upsample_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_upsample": (C.c_int, [_P(rtm_upsample_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
                                _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

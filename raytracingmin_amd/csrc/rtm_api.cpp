@@ -129,6 +129,11 @@ int rtm_tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height,
                 void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, rtm_tonemap_stats* stats_out_dev, void* stream) {
     RTM_GUARD(rtm::tonemap(params, width, height, device, color_dev, work_dev, out_f32_dev, out_u8_dev, stats_out_dev, stream))
 }
+size_t rtm_bloom_work_bytes(int32_t width, int32_t height, int32_t levels) { return rtm::bloom_work_bytes(width, height, levels); }
+int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color_dev, void* work_dev,
+              float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream) {
+    RTM_GUARD(rtm::bloom(params, width, height, device, color_dev, work_dev, out_f32_dev, out_u8_dev, bloom_out_dev, stream))
+}
 size_t rtm_upsample_work_bytes(int32_t low_width, int32_t low_height) { return rtm::upsample_work_bytes(low_width, low_height); }
 int rtm_upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device,
                  const float* color_low_dev, const rtm_aov_buffers* guide_low_dev, const rtm_aov_buffers* guide_high_dev,

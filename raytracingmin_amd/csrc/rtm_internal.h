@@ -74,6 +74,10 @@ int denoise_variance_kernel_probe(int form, const rtm_denoise_var_params* params
 size_t tonemap_work_bytes(int32_t width, int32_t height);
 int tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int device, const float* color, void* work,
             float* out32, uint8_t* out8, rtm_tonemap_stats* stats_out, void* stream);
+// bloom (rtm_bloom.hip)
+size_t bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
+int bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color, void* work, float* out32,
+          uint8_t* out8, float* bloom_out, void* stream);
 // AOV-guided upsampling (rtm_upsample.hip)
 size_t upsample_work_bytes(int32_t low_width, int32_t low_height);
 int upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device, const float* color_low,

@@ -12,6 +12,8 @@
 //           [--denoise-variance]                 (the variance-guided one: STEM_denoised_var.bmp, .jpg, STEM_variance.pfm)
 //           [--display [clamp|reinhard|aces]] [--exposure auto|EV] [--linear] [--no-dither]
 //                                                (the display transform of the last stage: STEM_display.bmp, .jpg)
+//           [--bloom [INTENSITY]] [--bloom-threshold T] [--bloom-levels L]
+//                                                (with --display: bloom the frame before the display transform)
 //           [--preview F [--preview-only]]       (the frame traced at 1/F of the resolution per axis, denoised there and upsampled
 //                                                by the first-hit feature buffers: STEM_preview.bmp, .jpg; -only: no full render)
 //           [--pfm]                              (the float frame of the last stage: STEM.pfm)
@@ -83,6 +85,10 @@ static void usage() {
         "            asked for on one GPU (the --denoise-variance frame, else the --denoise frame, else the frame itself):\n"
         "            STEM_display.bmp and STEM_display.jpg.  --exposure auto|EV : Reinhard's log-average key 0.18 (default) or\n"
         "            a fixed number of stops; --linear : no sRGB transfer function; --no-dither : the truncating 8-bit store\n"
+        "--bloom [INTENSITY] [--bloom-threshold T] [--bloom-levels L] : with --display, bloom every frame the display transform\n"
+        "            is given (rtm_bloom: a bright pass above luminance T, default 1, a pyramid of L levels, 1..8, default 6, and\n"
+        "            INTENSITY, default 0.2, times the result added back in linear space): STEM_display.*, STEM_preview_display.*,\n"
+        "            STEM_over_display.*, --display-pfm and what --flip sees are those of the bloomed frame\n"
         "--preview F [--preview-only] : also write a fast preview on one GPU: the scene traced at width / F x height / F (F in\n"
         "            2..8, dividing both; F^2 fewer paths), denoised there (rtm_denoise at its defaults) and brought to full size\n"
         "            by rtm_upsample, guided by the first-hit feature buffers at both resolutions: STEM_preview.bmp and\n"
@@ -127,6 +133,8 @@ int main(int argc, char* argv[]) {
     float adaptive_threshold = 0.f;
     int display = 0, preview = 0, preview_only = 0;
     rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
+    int bloom = 0;
+    rtm_bloom_params bloom_prm = RTM_BLOOM_DEFAULTS;
     int pfm = 0;
     std::string dump_f32, compare_ref, flip_ref;
     int display_pfm = 0, flip_map = 0, flip_ppd_given = 0;
@@ -196,6 +204,29 @@ int main(int argc, char* argv[]) {
             }
         } else if (c == "--linear") display_prm.transfer = RTM_TRANSFER_LINEAR;
         else if (c == "--no-dither") display_prm.dither = 0;
+        else if (c == "--bloom" || c == "--bloom-threshold" || c == "--bloom-levels") {
+            // a number, all of it; --bloom alone may stand without one (anything that is not a number is the next option)
+            const std::string m = i + 1 < argc ? argv[i + 1] : "";
+            char* end = nullptr;
+            const double v = std::strtod(m.c_str(), &end);
+            const bool number = !m.empty() && end == m.c_str() + m.size();
+            bool ok = number || c == "--bloom";
+            if (number) ++i;
+            if (c == "--bloom") {
+                bloom = 1;
+                if (number) ok = std::isfinite(bloom_prm.intensity = (float)v) && v >= 0.0;
+            } else if (c == "--bloom-threshold") {
+                if (number) ok = std::isfinite(bloom_prm.threshold = (float)v) && v >= 0.0;
+            } else if (number) {
+                ok = v == std::floor(v) && v >= 1.0 && v <= 8.0;
+                if (ok) bloom_prm.levels = (int)v;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "%s takes %s, got %s\n", c.c_str(),
+                             c == "--bloom-levels" ? "a number of levels in 1..8" : "a finite number that is not negative", m.c_str());
+                return 2;
+            }
+        }
         else if (c == "--pfm") pfm = 1;
         else if (c == "--compare" && i + 1 < argc) compare_ref = argv[++i];
         else if (c == "--display-pfm") display_pfm = 1;
@@ -318,6 +349,10 @@ int main(int argc, char* argv[]) {
                              "does not combine with --preview-only\n");
         return 2;
     }
+    if (bloom && !display) {
+        std::fprintf(stderr, "--bloom blooms the frame the display transform shows: it requires --display\n");
+        return 2;
+    }
     if ((flip_map || flip_ppd_given) && flip_ref.empty()) {
         std::fprintf(stderr, "--flip-map and --flip-ppd require --flip REF.pfm\n");
         return 2;
@@ -418,6 +453,19 @@ int main(int argc, char* argv[]) {
     }
     // a later stage takes the float frame of the last one
     const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background;
+    // --bloom: the frame a display transform is about to be given, bloomed into `out`; without --bloom the frame itself
+    const auto for_display = [&](const float* frame, std::vector<float>& out) -> const float* {
+        if (!bloom) return frame;
+        std::string err;
+        if (const int brc = rtm_node_bloom(&st, opt.device, &bloom_prm, frame, &out, err); brc != RTM_OK) {
+            std::fprintf(stderr, "bloom failed: %s (%s)\n", rtm_strerror(brc), err.c_str());
+            return nullptr;
+        }
+        return out.data();
+    };
+    if (bloom)
+        std::printf("bloom: threshold %.6g, knee %.6g, intensity %.6g, scatter %.6g, levels %d\n", (double)bloom_prm.threshold,
+                    (double)bloom_prm.knee, (double)bloom_prm.intensity, (double)bloom_prm.scatter, bloom_prm.levels);
     if (preview) {  // STEM_preview.bmp / .jpg, and their display transform
         std::string err;
         std::vector<float> shown;
@@ -431,7 +479,10 @@ int main(int argc, char* argv[]) {
                     stem.c_str(), st.width / preview, st.height / preview, (unsigned long long)ps.samples, ps.kernel_ms);
         if (display) {
             rtm_tonemap_stats ts;
-            rc = rtm_node_write_display(&st, opt.device, &display_prm, shown.data(), stem + "_preview", &ts, err);
+            std::vector<float> bloomed;
+            const float* frame = for_display(shown.data(), bloomed);
+            if (!frame) return 1;
+            rc = rtm_node_write_display(&st, opt.device, &display_prm, frame, stem + "_preview", &ts, err);
             if (rc != RTM_OK) {
                 std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
                 return 1;
@@ -553,7 +604,10 @@ int main(int argc, char* argv[]) {
     if (display) {
         std::string err;
         rtm_tonemap_stats ts;
-        rc = rtm_node_write_display(&st, opt.device, &display_prm, shown.empty() ? rgb32.data() : shown.data(), stem, &ts, err,
+        std::vector<float> bloomed;
+        const float* frame = for_display(shown.empty() ? rgb32.data() : shown.data(), bloomed);
+        if (!frame) return 1;
+        rc = rtm_node_write_display(&st, opt.device, &display_prm, frame, stem, &ts, err,
                                     display_pfm || !flip_ref.empty() ? &displayed : nullptr);
         if (rc != RTM_OK) {
             std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
@@ -607,7 +661,10 @@ int main(int argc, char* argv[]) {
         if (background) std::printf("background: %s_over.bmp, %s_over.jpg\n", stem.c_str(), stem.c_str());
         if (background && display) {
             rtm_tonemap_stats ts;
-            rc = rtm_node_write_display(&st, opt.device, &display_prm, over.data(), stem + "_over", &ts, err);
+            std::vector<float> bloomed;
+            const float* frame = for_display(over.data(), bloomed);
+            if (!frame) return 1;
+            rc = rtm_node_write_display(&st, opt.device, &display_prm, frame, stem + "_over", &ts, err);
             if (rc != RTM_OK) {
                 std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
                 return 1;

@@ -784,6 +784,45 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
     return RTM_OK;
 }
 
+// --bloom (rtm_node.h): rtm_bloom of the frame, in place, on the default stream.
+int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* prm, const float* f32_host,
+                   std::vector<float>* f32_out, std::string& err) {
+    if (hipSetDevice(device) != hipSuccess) {
+        err = "no HIP device " + std::to_string(device);
+        return RTM_ERR_NO_DEVICE;
+    }
+    const size_t bytes = (size_t)st->width * st->height * 3 * sizeof(float);
+    const size_t work_bytes = rtm_bloom_work_bytes(st->width, st->height, prm->levels);
+    float* color = nullptr;
+    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_bloom asks of work_dev
+    int rc = RTM_OK;
+    if (work_bytes == 0 || work_bytes == SIZE_MAX) {
+        err = "bloom's frame size or levels are out of range";
+        rc = RTM_ERR_INVALID_ARGUMENT;
+    } else if (hipMalloc((void**)&color, bytes) != hipSuccess || hipMalloc(&work, work_bytes) != hipSuccess) {
+        err = "no device memory for bloom's buffers";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK && hipMemcpy(color, f32_host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        err = "copying the frame to the device failed";
+        rc = RTM_ERR_HIP;
+    }
+    if (rc == RTM_OK) {
+        rc = rtm_bloom(prm, st->width, st->height, device, color, work, color, nullptr, nullptr, nullptr);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
+    }
+    if (rc == RTM_OK) {
+        f32_out->resize(bytes / sizeof(float));
+        if (hipMemcpy(f32_out->data(), color, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+            err = "copying the bloomed frame back failed";
+            rc = RTM_ERR_HIP;
+        }
+    }
+    (void)hipFree(color);
+    (void)hipFree(work);
+    return rc;
+}
+
 // --compare (rtm_node.h): rtm_compare of the two frames on the default stream.
 int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host, const float* reference_host,
                      rtm_compare_result* result, std::string& err) {

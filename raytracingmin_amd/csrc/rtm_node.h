@@ -54,6 +54,11 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* params, const float* f32_host,
                            const std::string& stem, rtm_tonemap_stats* stats, std::string& err,
                            std::vector<float>* f32_out = nullptr);
+// Bloom (rtm_bloom, rtm_cli --bloom) of a float frame (HOST, height x width x 3) on device `device`: the frame is copied to the
+// device, bloomed in place by one call on the default stream and copied back into f32_out, for the display transform that
+// follows.
+int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* params, const float* f32_host,
+                   std::vector<float>* f32_out, std::string& err);
 // Two float frames (HOST, height x width x 3; `frame` under test, `reference`) compared on device `device` (rtm_compare at its
 // default parameters, rtm_cli --compare): both are copied to the device, one call on the default stream, the record copied back.
 int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host, const float* reference_host,

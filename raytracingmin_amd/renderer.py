@@ -557,7 +557,7 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None):
+    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -571,6 +571,9 @@ class Renderer:
         <fileName>_display.bmp and <fileName>_display.jpg (q=60): the display transform (write_display) of the last stage
         asked for — the variance-denoised frame with denoise="variance", the denoised one with denoise=True, else the frame
         itself.  The plain files and self.image do not change.
+        bloom=True (or a dict of bloom()'s parameters: threshold, knee, intensity, scatter, levels) blooms every frame the
+        display transform is given (write_display's bloom), so the _display, _over_display and _preview_display files are
+        those of the bloomed last stage.  It needs tonemap: linear HDR through the reference's quantiser would only clip.
         preview=F also writes <fileName>_preview.bmp and <fileName>_preview.jpg (q=60): the frame traced at 1 / F of the
         resolution in each axis, denoised there and upsampled by the AOVs (write_preview); with tonemap, the display transform
         of the preview as well, as <fileName>_preview_display.bmp / .jpg.  F must divide the width and the height.
@@ -604,6 +607,11 @@ class Renderer:
             if unknown:
                 raise ValueError(f"tonemap's parameters are {tuple(TONEMAP_DEFAULTS)}, got {sorted(unknown)}")
             _tonemap_params(**display)  # a bad parameter raises here, before anything is rendered
+        bloom_prm = _bloom_option(bloom)
+        if bloom_prm is not None:
+            if display is None:
+                raise ValueError("bloom needs tonemap: it is applied to the frame the display transform shows")
+            display["bloom"] = bloom_prm  # write_display's
         if adaptive is not None:
             if passes > 1:
                 raise ValueError("adaptive and passes > 1 do not combine")
@@ -651,15 +659,20 @@ class Renderer:
                 self.write_display(fileName + "_preview", frame=shown, **display)
         return rgb8
 
-    def write_display(self, fileName, frame=None, **params):
+    def write_display(self, fileName, frame=None, bloom=None, **params):
         """<fileName>_display.bmp and <fileName>_display.jpg (q=60): the display transform tonemap(**params) (default: the
         ACES curve at automatic exposure, sRGB, dithered) of `frame`, an (H, W, 3) float32 CUDA tensor, or of self.image
-        rounded to float like out_f32 — what rtm_cli --display writes.  Returns the (H, W, 3) uint8 pixels."""
+        rounded to float like out_f32 — what rtm_cli --display writes.  bloom=True (or a dict of bloom()'s parameters) blooms
+        the frame first, what rtm_cli --display --bloom writes; `frame` itself is left as it is.  Returns the (H, W, 3) uint8
+        pixels."""
         import torch
         _tonemap_params(**params)
+        bloom_prm = _bloom_option(bloom)
         if frame is None:
             dev = torch.device("cuda", self.device)
             frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        if bloom_prm is not None:
+            frame = _bloom(frame, **bloom_prm)["f32"]
         rgb8 = np.ascontiguousarray(tonemap(frame, want=("u8",), **params)["u8"].cpu().numpy())
         L = _lib.lib()
         H, W = self.data.height, self.data.width
@@ -1067,6 +1080,70 @@ def tonemap(color, op=TONEMAP_DEFAULTS["op"], transfer=TONEMAP_DEFAULTS["transfe
     _lib.check(L.rtm_tonemap(C.byref(prm), W, H, dev.index, color.data_ptr(), ptr("work"), ptr("f32"), ptr("u8"),
                              ptr("stats"), C.c_void_p(s.cuda_stream)), "rtm_tonemap")
     return out
+
+
+# include/rtm.h: RTM_BLOOM_DEFAULTS
+BLOOM_DEFAULTS = {"threshold": 1.0, "knee": 0.5, "intensity": 0.2, "scatter": 0.7, "levels": 6}
+
+
+def _bloom_params(threshold=BLOOM_DEFAULTS["threshold"], knee=BLOOM_DEFAULTS["knee"], intensity=BLOOM_DEFAULTS["intensity"],
+                  scatter=BLOOM_DEFAULTS["scatter"], levels=BLOOM_DEFAULTS["levels"]):
+    """bloom()'s parameters as an rtm_bloom_params; a ValueError names what the library would refuse.  No device use."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 1 <= int(levels) <= 8:
+        raise ValueError(f"levels is an integer in 1..8, got {levels!r}")
+    for name, v in (("threshold", threshold), ("knee", knee), ("intensity", intensity), ("scatter", scatter)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not np.isfinite(float(v)):
+            raise ValueError(f"{name} is a finite number, got {v!r}")
+    threshold, knee, intensity, scatter = float(threshold), float(knee), float(intensity), float(scatter)
+    if threshold < 0.0 or intensity < 0.0:
+        raise ValueError(f"threshold and intensity are non-negative, got {threshold!r} and {intensity!r}")
+    if not (0.0 <= knee <= 1.0 and 0.0 <= scatter <= 1.0):
+        raise ValueError(f"knee and scatter are in [0, 1], got {knee!r} and {scatter!r}")
+    return _lib.rtm_bloom_params(threshold, knee, intensity, scatter, int(levels))
+
+
+def _bloom_option(bloom):
+    """Render's and write_display's `bloom`: None for off, else the dict of bloom()'s parameters, checked.  No device use."""
+    if bloom is None or bloom is False:
+        return None
+    if bloom is not True and not isinstance(bloom, dict):
+        raise ValueError(f"bloom is False, True or a dict of bloom()'s parameters, got {bloom!r}")
+    prm = {} if bloom is True else dict(bloom)
+    unknown = set(prm) - set(BLOOM_DEFAULTS)
+    if unknown:
+        raise ValueError(f"bloom's parameters are {tuple(BLOOM_DEFAULTS)}, got {sorted(unknown)}")
+    _bloom_params(**prm)
+    return prm
+
+
+def bloom(color, threshold=BLOOM_DEFAULTS["threshold"], knee=BLOOM_DEFAULTS["knee"], intensity=BLOOM_DEFAULTS["intensity"],
+          scatter=BLOOM_DEFAULTS["scatter"], levels=BLOOM_DEFAULTS["levels"], want=("f32",), stream=None, out_f32=None):
+    """Bloom (include/rtm.h: rtm_bloom) on the device: the light the bright parts of an HDR frame scatter into their surround,
+    added in linear space; run it before tonemap().  `color` is an (H, W, 3) float32 torch CUDA tensor (any 4-byte-aligned
+    contiguous view).  threshold: the luminance above which a pixel blooms; knee in [0, 1]: the soft knee as a fraction of
+    the threshold; intensity: how much of the bloom is added; scatter in [0, 1]: how much of each coarser level reaches the
+    finer; levels 1..8: the depth of the pyramid.  Returns a dict of the names in `want`: "f32" (H, W, 3) float32 (the frame
+    plus intensity times the bloom), "u8" (H, W, 3) uint8 (rtm_quantise of it), "bloom" (H, W, 3) float32 (the bloom alone).
+    out_f32: the tensor to write "f32" into; `color` itself blooms in place.  Enqueued on `stream` (a torch.cuda.Stream or a
+    raw hipStream_t handle; default: the current stream) with a work buffer allocated here; nothing waits for it and nothing
+    is copied to the host."""
+    prm = _bloom_params(threshold, knee, intensity, scatter, levels)
+    _check_want(want, ("f32", "u8", "bloom"))
+    import torch
+    _need_device("bloom")
+    H, W = _frame_size(color, "color", non_empty=True)
+    dev = color.device
+    _check_out_f32(out_f32, want, H, W, dev)
+    s = _stream_of(stream, dev)
+    L = _lib.lib()
+    specs = {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8), "bloom": ((H, W, 3), torch.float32)}
+    out, ptr = _stage_tensors(s, dev, want, specs, max(256, L.rtm_bloom_work_bytes(W, H, prm.levels)), out_f32=out_f32)
+    _lib.check(L.rtm_bloom(C.byref(prm), W, H, dev.index, color.data_ptr(), ptr("work"), ptr("f32"), ptr("u8"), ptr("bloom"),
+                           C.c_void_p(s.cuda_stream)), "rtm_bloom")
+    return out
+
+
+_bloom = bloom  # for Renderer's methods, whose own parameter is named bloom
 
 
 def tonemap_stats(words):
