@@ -56,6 +56,36 @@ static std::string json_number(double v) {
     return buf;
 }
 
+// a number, all of it: false for an empty text and for one with anything behind the number
+static bool parse_number(const std::string& text, double& v) {
+    char* end = nullptr;
+    v = std::strtod(text.c_str(), &end);
+    return !text.empty() && end == text.c_str() + text.size();
+}
+
+// the line of a stage that failed, and the exit status
+static int fail(const char* stage, int rc, const std::string& detail) {
+    std::fprintf(stderr, "%s failed: %s (%s)\n", stage, rtm_strerror(rc), detail.c_str());
+    return 1;
+}
+
+// the reference frame of --compare or --flip (`flag`): a three-channel float map of the frame's size
+static bool read_reference(const char* flag, const std::string& path, const rtm_settings& st, std::vector<float>& out) {
+    int rw = 0, rh = 0, rcomp = 0;
+    bool ok = rtm_read_pfm(path.c_str(), &rw, &rh, &rcomp, nullptr, 0) == 1;
+    if (ok && (rw != st.width || rh != st.height || rcomp != 3)) {
+        std::fprintf(stderr, "%s: %s is %d x %d x %d, the frame is %d x %d x 3\n", flag, path.c_str(), rw, rh, rcomp, st.width,
+                     st.height);
+        return false;
+    }
+    if (ok) {
+        out.resize((size_t)rw * rh * 3);
+        ok = rtm_read_pfm(path.c_str(), &rw, &rh, &rcomp, out.data(), out.size()) == 1;
+    }
+    if (!ok) std::fprintf(stderr, "%s: cannot read %s as a little-endian float map\n", flag, path.c_str());
+    return ok;
+}
+
 static void usage() {
     std::printf(
         "Usage: rtm_cli [OPTION]...\n\n"
@@ -190,14 +220,13 @@ int main(int argc, char* argv[]) {
             if (m == "clamp" || m == "reinhard" || m == "aces") ++i;  // anything else is the next option: the default curve
         } else if (c == "--exposure" && i + 1 < argc) {
             const std::string m = argv[++i];
-            char* end = nullptr;
-            const float ev = (float)std::strtod(m.c_str(), &end);  // (double first, as Python's float() then C float)
+            double ev = 0.0;
             if (m == "auto") {
                 display_prm.auto_exposure = 1;
                 display_prm.ev = 0.0f;
-            } else if (end != m.c_str() && *end == '\0') {
+            } else if (parse_number(m, ev)) {
                 display_prm.auto_exposure = 0;
-                display_prm.ev = ev;
+                display_prm.ev = (float)ev;  // (double first, as Python's float() then C float)
             } else {
                 std::fprintf(stderr, "--exposure takes auto or a number of stops, got %s\n", m.c_str());
                 return 2;
@@ -207,9 +236,8 @@ int main(int argc, char* argv[]) {
         else if (c == "--bloom" || c == "--bloom-threshold" || c == "--bloom-levels") {
             // a number, all of it; --bloom alone may stand without one (anything that is not a number is the next option)
             const std::string m = i + 1 < argc ? argv[i + 1] : "";
-            char* end = nullptr;
-            const double v = std::strtod(m.c_str(), &end);
-            const bool number = !m.empty() && end == m.c_str() + m.size();
+            double v = 0.0;
+            const bool number = parse_number(m, v);
             bool ok = number || c == "--bloom";
             if (number) ++i;
             if (c == "--bloom") {
@@ -234,10 +262,9 @@ int main(int argc, char* argv[]) {
         else if (c == "--flip-map") flip_map = 1;
         else if (c == "--flip-ppd" && i + 1 < argc) {
             const std::string m = argv[++i];
-            char* end = nullptr;
-            flip_prm.pixels_per_degree = std::strtod(m.c_str(), &end);
             flip_ppd_given = 1;
-            if (end == m.c_str() || *end != '\0' || !(flip_prm.pixels_per_degree >= 8.0 && flip_prm.pixels_per_degree <= 128.0)) {
+            double& ppd = flip_prm.pixels_per_degree;
+            if (!parse_number(m, ppd) || !(ppd >= 8.0 && ppd <= 128.0)) {
                 std::fprintf(stderr, "--flip-ppd takes a number of pixels per degree in [8, 128], got %s\n", m.c_str());
                 return 2;
             }
@@ -249,10 +276,8 @@ int main(int argc, char* argv[]) {
             bool ok = !m.empty();
             for (size_t at = 0; ok && at <= m.size();) {
                 const size_t comma = std::min(m.find(',', at), m.size());
-                const std::string item = m.substr(at, comma - at);
-                char* end = nullptr;
-                const double d = std::strtod(item.c_str(), &end);
-                ok = !item.empty() && end == item.c_str() + item.size() && std::isfinite(d);
+                double d = 0.0;
+                ok = parse_number(m.substr(at, comma - at), d) && std::isfinite(d);
                 v.push_back(d);
                 at = comma + 1;
             }
@@ -289,88 +314,49 @@ int main(int argc, char* argv[]) {
             }
         }
     }
-    if (passes > 0 && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--passes renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
-        return 2;
-    }
-    if (adaptive && (passes > 0 || gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--adaptive renders on one GPU: it does not combine with --passes, --gpus > 1, --virtual-strips or "
-                             "--force-rccl\n");
-        return 2;
-    }
-    if (aov && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--aov renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
-        return 2;
-    }
-    if (denoise && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--denoise runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
-        return 2;
-    }
-    if (denoise_variance && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--denoise-variance runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or "
-                             "--force-rccl\n");
-        return 2;
-    }
-    if (display && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--display runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
-        return 2;
-    }
-    if (preview_only && preview == 0) {
-        std::fprintf(stderr, "--preview-only requires --preview F\n");
-        return 2;
-    }
-    if (preview != 0 && (preview < 2 || preview > 8)) {
-        std::fprintf(stderr, "--preview takes a factor in 2..8, got %d\n", preview);
-        return 2;
-    }
-    if (preview && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--preview runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl\n");
-        return 2;
-    }
-    if (preview_only && (adaptive || passes > 0)) {
-        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --adaptive or --passes\n");
-        return 2;
-    }
-    if (preview_only && (denoise || denoise_variance || !dump_f32.empty())) {
-        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --denoise, --denoise-variance or "
-                             "--dump-f32\n");
-        return 2;
-    }
-    if (preview_only && (pfm || !compare_ref.empty())) {
-        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --pfm or --compare\n");
-        return 2;
-    }
-    if (preview_only && !flip_ref.empty()) {
-        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --flip\n");
-        return 2;
-    }
-    if (display_pfm && (!display || preview_only)) {
-        std::fprintf(stderr, "--display-pfm writes the display transform's float frame of the full render: it requires --display and "
-                             "does not combine with --preview-only\n");
-        return 2;
-    }
-    if (bloom && !display) {
-        std::fprintf(stderr, "--bloom blooms the frame the display transform shows: it requires --display\n");
-        return 2;
-    }
-    if ((flip_map || flip_ppd_given) && flip_ref.empty()) {
-        std::fprintf(stderr, "--flip-map and --flip-ppd require --flip REF.pfm\n");
-        return 2;
-    }
+    // What does not combine, in the order it is looked at: the first refusal that applies is the one that is printed.
+    const bool many = gpus > 1 || virtual_strips > 0 || force_rccl;  // anything but the plain one-GPU render
     const bool mattes = alpha || !matte_ids.empty() || background;
-    if (mattes && (gpus > 1 || virtual_strips > 0 || force_rccl)) {
-        std::fprintf(stderr, "--alpha, --matte and --background run on one GPU: they do not combine with --gpus > 1, --virtual-strips or "
-                             "--force-rccl\n");
-        return 2;
-    }
-    if (mattes && preview_only) {
-        std::fprintf(stderr, "--preview-only skips the full render: it does not combine with --alpha, --matte or --background\n");
-        return 2;
-    }
-    if (matte_layers_given && matte_ids.empty()) {
-        std::fprintf(stderr, "--matte-layers requires --matte ID[,ID...]\n");
-        return 2;
-    }
+    const std::string bad_preview = "--preview takes a factor in 2..8, got " + std::to_string(preview);
+    const struct {
+        bool applies;
+        const char* text;
+    } refusals[] = {
+        {passes > 0 && many,
+         "--passes renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {adaptive && (passes > 0 || many),
+         "--adaptive renders on one GPU: it does not combine with --passes, --gpus > 1, --virtual-strips or --force-rccl"},
+        {aov && many, "--aov renders on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {denoise && many, "--denoise runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {denoise_variance && many,
+         "--denoise-variance runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {display && many, "--display runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {preview_only && preview == 0, "--preview-only requires --preview F"},
+        {preview != 0 && (preview < 2 || preview > 8), bad_preview.c_str()},
+        {preview && many, "--preview runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {preview_only && (adaptive || passes > 0),
+         "--preview-only skips the full render: it does not combine with --adaptive or --passes"},
+        {preview_only && (denoise || denoise_variance || !dump_f32.empty()),
+         "--preview-only skips the full render: it does not combine with --denoise, --denoise-variance or --dump-f32"},
+        {preview_only && (pfm || !compare_ref.empty()),
+         "--preview-only skips the full render: it does not combine with --pfm or --compare"},
+        {preview_only && !flip_ref.empty(), "--preview-only skips the full render: it does not combine with --flip"},
+        {display_pfm && (!display || preview_only),
+         "--display-pfm writes the display transform's float frame of the full render: it requires --display and does not combine "
+         "with --preview-only"},
+        {bloom && !display, "--bloom blooms the frame the display transform shows: it requires --display"},
+        {(flip_map || flip_ppd_given) && flip_ref.empty(), "--flip-map and --flip-ppd require --flip REF.pfm"},
+        {mattes && many,
+         "--alpha, --matte and --background run on one GPU: they do not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {mattes && preview_only,
+         "--preview-only skips the full render: it does not combine with --alpha, --matte or --background"},
+        {matte_layers_given && matte_ids.empty(), "--matte-layers requires --matte ID[,ID...]"},
+    };
+    for (const auto& r : refusals)
+        if (r.applies) {
+            std::fprintf(stderr, "%s\n", r.text);
+            return 2;
+        }
     if (!file_exists(json_file)) {  // src/main.cpp:36-39
         std::printf("saving the sample scene json file: %s\n", json_file.c_str());
         if (rtm_scene_save_sample_json(json_file.c_str()) != RTM_OK) return 1;
@@ -415,87 +401,49 @@ int main(int argc, char* argv[]) {
         std::fprintf(stderr, "--preview %d does not divide the %d x %d frame\n", preview, st.width, st.height);
         return 2;
     }
-    std::vector<float> reference;  // --compare: read before anything is rendered, so that a bad file costs no render
-    if (!compare_ref.empty()) {
-        int rw = 0, rh = 0, rcomp = 0;
-        if (rtm_read_pfm(compare_ref.c_str(), &rw, &rh, &rcomp, nullptr, 0) != 1) {
-            std::fprintf(stderr, "--compare: cannot read %s as a little-endian float map\n", compare_ref.c_str());
-            return 1;
-        }
-        if (rw != st.width || rh != st.height || rcomp != 3) {
-            std::fprintf(stderr, "--compare: %s is %d x %d x %d, the frame is %d x %d x 3\n", compare_ref.c_str(), rw, rh, rcomp,
-                         st.width, st.height);
-            return 1;
-        }
-        reference.resize((size_t)rw * rh * 3);
-        if (rtm_read_pfm(compare_ref.c_str(), &rw, &rh, &rcomp, reference.data(), reference.size()) != 1) {
-            std::fprintf(stderr, "--compare: cannot read %s as a little-endian float map\n", compare_ref.c_str());
-            return 1;
-        }
-    }
-    std::vector<float> flip_reference;  // --flip: likewise
-    if (!flip_ref.empty()) {
-        int rw = 0, rh = 0, rcomp = 0;
-        if (rtm_read_pfm(flip_ref.c_str(), &rw, &rh, &rcomp, nullptr, 0) != 1) {
-            std::fprintf(stderr, "--flip: cannot read %s as a little-endian float map\n", flip_ref.c_str());
-            return 1;
-        }
-        if (rw != st.width || rh != st.height || rcomp != 3) {
-            std::fprintf(stderr, "--flip: %s is %d x %d x %d, the frame is %d x %d x 3\n", flip_ref.c_str(), rw, rh, rcomp, st.width,
-                         st.height);
-            return 1;
-        }
-        flip_reference.resize((size_t)rw * rh * 3);
-        if (rtm_read_pfm(flip_ref.c_str(), &rw, &rh, &rcomp, flip_reference.data(), flip_reference.size()) != 1) {
-            std::fprintf(stderr, "--flip: cannot read %s as a little-endian float map\n", flip_ref.c_str());
-            return 1;
-        }
-    }
+    // --compare and --flip: read before anything is rendered, so that a bad file costs no render
+    std::vector<float> reference, flip_reference;
+    if (!compare_ref.empty() && !read_reference("--compare", compare_ref, st, reference)) return 1;
+    if (!flip_ref.empty() && !read_reference("--flip", flip_ref, st, flip_reference)) return 1;
     // a later stage takes the float frame of the last one
     const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background;
-    // --bloom: the frame a display transform is about to be given, bloomed into `out`; without --bloom the frame itself
-    const auto for_display = [&](const float* frame, std::vector<float>& out) -> const float* {
-        if (!bloom) return frame;
-        std::string err;
-        if (const int brc = rtm_node_bloom(&st, opt.device, &bloom_prm, frame, &out, err); brc != RTM_OK) {
-            std::fprintf(stderr, "bloom failed: %s (%s)\n", rtm_strerror(brc), err.c_str());
-            return nullptr;
-        }
-        return out.data();
-    };
     if (bloom)
         std::printf("bloom: threshold %.6g, knee %.6g, intensity %.6g, scatter %.6g, levels %d\n", (double)bloom_prm.threshold,
                     (double)bloom_prm.knee, (double)bloom_prm.intensity, (double)bloom_prm.scatter, bloom_prm.levels);
-    if (preview) {  // STEM_preview.bmp / .jpg, and their display transform
+    // --display of one frame: bloomed first with --bloom, then STEM<suffix>_display.bmp / .jpg and their line, which gives
+    // the statistics for the frame itself (no suffix); the exit status, 0 when all went well
+    const auto show = [&](const float* frame, const std::string& suffix, std::vector<float>* f32_out) {
         std::string err;
+        std::vector<float> bloomed;
+        if (bloom) {
+            const int brc = rtm_node_bloom(&st, opt.device, &bloom_prm, frame, &bloomed, err);
+            if (brc != RTM_OK) return fail("bloom", brc, err);
+            frame = bloomed.data();
+        }
+        rtm_tonemap_stats ts;
+        const std::string name = stem + suffix;
+        const int drc = rtm_node_write_display(&st, opt.device, &display_prm, frame, name, &ts, err, f32_out);
+        if (drc != RTM_OK) return fail("display", drc, err);
+        if (suffix.empty())
+            std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",
+                        name.c_str(), name.c_str(), (double)ts.log_average, (double)ts.max_luminance, (double)ts.exposure, ts.pixels);
+        else
+            std::printf("display: %s_display.bmp, %s_display.jpg\n", name.c_str(), name.c_str());
+        return 0;
+    };
+    std::string err;  // a stage's account of its failure: main returns at the first one
+    if (preview) {  // STEM_preview.bmp / .jpg, and their display transform
         std::vector<float> shown;
         rtm_stats ps;
         rc = rtm_node_write_preview(&st, spheres.data(), n, &opt, preview, stem, err, display ? &shown : nullptr, &ps);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "preview failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        if (rc != RTM_OK) return fail("preview", rc, err);
         std::printf("preview: %s_preview.bmp, %s_preview.jpg (%d x %d traced, %llu samples, kernel %.3f ms)\n", stem.c_str(),
                     stem.c_str(), st.width / preview, st.height / preview, (unsigned long long)ps.samples, ps.kernel_ms);
-        if (display) {
-            rtm_tonemap_stats ts;
-            std::vector<float> bloomed;
-            const float* frame = for_display(shown.data(), bloomed);
-            if (!frame) return 1;
-            rc = rtm_node_write_display(&st, opt.device, &display_prm, frame, stem + "_preview", &ts, err);
-            if (rc != RTM_OK) {
-                std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-                return 1;
-            }
-            std::printf("display: %s_preview_display.bmp, %s_preview_display.jpg\n", stem.c_str(), stem.c_str());
-        }
+        if (display && show(shown.data(), "_preview", nullptr) != 0) return 1;
         if (preview_only) {
             if (aov) {
                 rc = rtm_node_write_aov(&st, spheres.data(), n, &opt, stem, err);
-                if (rc != RTM_OK) {
-                    std::fprintf(stderr, "aov failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-                    return 1;
-                }
+                if (rc != RTM_OK) return fail("aov", rc, err);
             }
             return 0;
         }
@@ -504,48 +452,28 @@ int main(int argc, char* argv[]) {
     const size_t vals = (size_t)st.width * st.height * 3;
     std::vector<uint8_t> rgb8(vals);
     std::vector<float> rgb32(dump_f32.empty() && !denoise && !denoise_variance && !want_last ? 0 : vals);
+    float* const out32 = rgb32.empty() ? nullptr : rgb32.data();
     rtm_stats stats;
     std::vector<uint32_t> tile_samples;
     if (adaptive) {
-        std::string err;
         rtm_adaptive_params prm;
         prm.min_samples = adaptive_min > 0 ? (uint32_t)adaptive_min : 0u;
         prm.threshold = adaptive_threshold;
-        rc = rtm_node_render_adaptive(&st, spheres.data(), n, &opt, &prm, rgb32.empty() ? nullptr : rgb32.data(), rgb8.data(),
-                                      tile_samples, &stats, err);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "render failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        rc = rtm_node_render_adaptive(&st, spheres.data(), n, &opt, &prm, out32, rgb8.data(), tile_samples, &stats, err);
     } else if (passes > 0) {
-        std::string err;
-        rc = rtm_node_render_passes(&st, spheres.data(), n, &opt, passes, rgb32.empty() ? nullptr : rgb32.data(), rgb8.data(),
-                                    &stats, err);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "render failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
-    } else if (gpus > 1 || virtual_strips > 0 || force_rccl) {
+        rc = rtm_node_render_passes(&st, spheres.data(), n, &opt, passes, out32, rgb8.data(), &stats, err);
+    } else if (many) {
         int have = 0;
         if (rtm_device_count(&have) != RTM_OK || have < gpus) {
             std::fprintf(stderr, "--gpus %d requested, %d HIP device(s) present\n", gpus, have);
             return 1;
         }
-        std::string err;
-        rc = rtm_node_render(&st, spheres.data(), n, &opt, gpus, virtual_strips, force_rccl,
-                             rgb32.empty() ? nullptr : rgb32.data(), rgb8.data(), &stats, err);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "render failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        rc = rtm_node_render(&st, spheres.data(), n, &opt, gpus, virtual_strips, force_rccl, out32, rgb8.data(), &stats, err);
     } else {
-        rc = rtm_render_objects(&st, spheres.data(), n, &opt, nullptr, rgb32.empty() ? nullptr : rgb32.data(), rgb8.data(),
-                                &stats);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "render failed: %s (%s)\n", rtm_strerror(rc), rtm_last_error_detail());
-            return 1;
-        }
+        rc = rtm_render_objects(&st, spheres.data(), n, &opt, nullptr, out32, rgb8.data(), &stats);
+        if (rc != RTM_OK) err = rtm_last_error_detail();
     }
+    if (rc != RTM_OK) return fail("render", rc, err);
     if (!dump_f32.empty()) {
         FILE* f = std::fopen(dump_f32.c_str(), "wb");
         if (!f || std::fwrite(rgb32.data(), sizeof(float), vals, f) != vals) {
@@ -570,52 +498,27 @@ int main(int argc, char* argv[]) {
         if (rtm_write_pfm((stem + "_spp.pfm").c_str(), st.width, st.height, 1, spp.data()) != 1) return 1;
     }
     if (aov) {
-        std::string err;
         rc = rtm_node_write_aov(&st, spheres.data(), n, &opt, stem, err);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "aov failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        if (rc != RTM_OK) return fail("aov", rc, err);
         std::printf("aov: %s_depth.pfm, %s_normal.pfm, %s_albedo.pfm, %s_normal.bmp, %s_albedo.bmp\n", stem.c_str(), stem.c_str(),
                     stem.c_str(), stem.c_str(), stem.c_str());
     }
     std::vector<float> shown;  // the float frame of the last stage, when --display, --pfm or --compare follows a denoiser
     if (denoise) {
-        std::string err;
         rc = rtm_node_write_denoised(&st, spheres.data(), n, &opt, rgb32.data(), stem, err,
                                      want_last && !denoise_variance ? &shown : nullptr);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "denoise failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        if (rc != RTM_OK) return fail("denoise", rc, err);
         std::printf("denoise: %s_denoised.bmp, %s_denoised.jpg\n", stem.c_str(), stem.c_str());
     }
     if (denoise_variance) {
-        std::string err;
         rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, rgb32.data(), stem, err, want_last ? &shown : nullptr);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "denoise-variance failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        if (rc != RTM_OK) return fail("denoise-variance", rc, err);
         std::printf("denoise-variance: %s_denoised_var.bmp, %s_denoised_var.jpg, %s_variance.pfm\n", stem.c_str(), stem.c_str(),
                     stem.c_str());
     }
+    const float* last = shown.empty() ? rgb32.data() : shown.data();
     std::vector<float> displayed;  // the display transform's float frame, when --display-pfm or --flip follows --display
-    if (display) {
-        std::string err;
-        rtm_tonemap_stats ts;
-        std::vector<float> bloomed;
-        const float* frame = for_display(shown.empty() ? rgb32.data() : shown.data(), bloomed);
-        if (!frame) return 1;
-        rc = rtm_node_write_display(&st, opt.device, &display_prm, frame, stem, &ts, err,
-                                    display_pfm || !flip_ref.empty() ? &displayed : nullptr);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
-        std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",
-                    stem.c_str(), stem.c_str(), (double)ts.log_average, (double)ts.max_luminance, (double)ts.exposure, ts.pixels);
-    }
+    if (display && show(last, "", display_pfm || !flip_ref.empty() ? &displayed : nullptr) != 0) return 1;
     if (display_pfm) {
         if (rtm_write_pfm((stem + "_display.pfm").c_str(), st.width, st.height, 3, displayed.data()) != 1) {
             std::fprintf(stderr, "cannot write %s_display.pfm\n", stem.c_str());
@@ -623,7 +526,6 @@ int main(int argc, char* argv[]) {
         }
         std::printf("display-pfm: %s_display.pfm\n", stem.c_str());
     }
-    const float* last = shown.empty() ? rgb32.data() : shown.data();
     if (pfm) {
         if (rtm_write_pfm((stem + ".pfm").c_str(), st.width, st.height, 3, last) != 1) {
             std::fprintf(stderr, "cannot write %s.pfm\n", stem.c_str());
@@ -632,13 +534,9 @@ int main(int argc, char* argv[]) {
         std::printf("pfm: %s.pfm\n", stem.c_str());
     }
     if (!compare_ref.empty()) {
-        std::string err;
         rtm_compare_result cr;
         rc = rtm_node_compare(&st, opt.device, last, reference.data(), &cr, err);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "compare failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        if (rc != RTM_OK) return fail("compare", rc, err);
         std::printf("compare: {\"max_abs\": %s, \"mse\": %s, \"psnr\": %s, \"rel_mse\": %s, \"ssim\": %s, \"pixels\": %llu, "
                     "\"outside\": %llu, \"nonfinite\": %llu, \"nonfinite_mismatch\": %llu, \"argmax_x\": %d, \"argmax_y\": %d}\n",
                     json_number(cr.max_abs).c_str(), json_number(cr.mse).c_str(), json_number(cr.psnr).c_str(),
@@ -647,33 +545,17 @@ int main(int argc, char* argv[]) {
                     cr.argmax_x, cr.argmax_y);
     }
     if (mattes) {
-        std::string err;
         std::vector<float> over;
         rc = rtm_node_write_mattes(&st, spheres.data(), n, &opt, alpha != 0, matte_layers, matte_ids, background ? &composite_prm : nullptr,
                                    background ? last : nullptr, stem, err, background && display ? &over : nullptr);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "mattes failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        if (rc != RTM_OK) return fail("mattes", rc, err);
         if (alpha) std::printf("alpha: %s_alpha.pfm\n", stem.c_str());
         if (!matte_ids.empty())
             std::printf("matte: %s_matte.pfm, %s_matte.bmp (%d ids, %d layers)\n", stem.c_str(), stem.c_str(), (int)matte_ids.size(), matte_layers);
         if (background) std::printf("background: %s_over.bmp, %s_over.jpg\n", stem.c_str(), stem.c_str());
-        if (background && display) {
-            rtm_tonemap_stats ts;
-            std::vector<float> bloomed;
-            const float* frame = for_display(over.data(), bloomed);
-            if (!frame) return 1;
-            rc = rtm_node_write_display(&st, opt.device, &display_prm, frame, stem + "_over", &ts, err);
-            if (rc != RTM_OK) {
-                std::fprintf(stderr, "display failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-                return 1;
-            }
-            std::printf("display: %s_over_display.bmp, %s_over_display.jpg\n", stem.c_str(), stem.c_str());
-        }
+        if (background && display && show(over.data(), "_over", nullptr) != 0) return 1;
     }
     if (!flip_ref.empty()) {
-        std::string err;
         rtm_flip_result fr;
         std::vector<float> fmap;
         if (display)
@@ -682,10 +564,7 @@ int main(int argc, char* argv[]) {
             flip_prm.transfer = RTM_TRANSFER_LINEAR;  // the last stage's frame, taken as linear
         rc = rtm_node_flip(&st, opt.device, &flip_prm, display ? displayed.data() : last, flip_reference.data(), &fr,
                            flip_map ? &fmap : nullptr, err);
-        if (rc != RTM_OK) {
-            std::fprintf(stderr, "flip failed: %s (%s)\n", rtm_strerror(rc), err.c_str());
-            return 1;
-        }
+        if (rc != RTM_OK) return fail("flip", rc, err);
         // the weighted median as the published tool pools it: bin i weighs its count times its centre (i + 0.5) / 256; the
         // centre of the first bin at which the running weight reaches half of the total (bin resolution, 1/256)
         double run[256], total = 0.0, median = 0.0;

@@ -24,6 +24,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rtm.h"
@@ -174,6 +175,93 @@ class Stages {
     bool stop_ = false, quiet_ = false;
     std::thread dog_;
 };
+
+// What the one-GPU stages below (--passes, --adaptive and every stage that follows the render) share.  Their device
+// arrays and scenes are owned, so a stage returns at its first failure and everything it holds is released.
+
+// A device array of `count` T (bytes for void), freed with its owner.  Until alloc succeeds with a count above zero it
+// holds null, which is what the library calls take for an output that is not asked for.
+template <class T>
+struct DevBuf {
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p_) (void)hipFree(p_);
+    }
+    // wanted == false: not asked for, nothing is allocated and that is no failure
+    bool alloc(size_t count, bool wanted = true) { return !wanted || hipMalloc((void**)&p_, count * kSize) == hipSuccess; }
+    bool upload(const T* host, size_t count) { return hipMemcpy(p_, host, count * kSize, hipMemcpyHostToDevice) == hipSuccess; }
+    bool download(T* host, size_t count) const { return hipMemcpy(host, p_, count * kSize, hipMemcpyDeviceToHost) == hipSuccess; }
+    T* get() const { return p_; }
+
+  private:
+    static constexpr size_t kSize = sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+    T* p_ = nullptr;
+};
+
+// A scene handle, destroyed with its owner.
+struct Scene {
+    Scene() = default;
+    Scene(const Scene&) = delete;
+    Scene& operator=(const Scene&) = delete;
+    ~Scene() {
+        if (s_) (void)rtm_scene_destroy(s_);
+    }
+    int create(const rtm_object* objects, size_t n, int device) { return rtm_scene_create_objects(objects, n, device, &s_); }
+    rtm_scene* get() const { return s_; }
+
+  private:
+    rtm_scene* s_ = nullptr;
+};
+
+// The first-hit feature planes of `pix` pixels; the object ids only where the stage reads them.
+struct AovPlanes {
+    DevBuf<float> depth, normal, albedo;
+    DevBuf<int32_t> object;
+    bool alloc(size_t pix, bool with_object) {
+        return depth.alloc(pix) && normal.alloc(pix * 3) && albedo.alloc(pix * 3) && object.alloc(pix, with_object);
+    }
+    rtm_aov_buffers view() const { return rtm_aov_buffers{depth.get(), normal.get(), albedo.get(), object.get()}; }
+};
+
+int fail(std::string& err, int rc, const std::string& text) {
+    err = text;
+    return rc;
+}
+int open_device(int device, std::string& err) {
+    if (hipSetDevice(device) != hipSuccess) return fail(err, RTM_ERR_NO_DEVICE, "no HIP device " + std::to_string(device));
+    return RTM_OK;
+}
+int open_scene(const rtm_object* objects, size_t n, int device, Scene& scene, std::string& err) {
+    if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+    const int rc = scene.create(objects, n, device);
+    return rc == RTM_OK ? rc : fail(err, rc, std::string("scene: ") + rtm_last_error_detail());
+}
+
+// the counters of one part or pass into the frame's; kernel_ms is the caller's (parts overlap in time, passes do not)
+void add_counts(rtm_stats* total, const rtm_stats& s) {
+    total->samples += s.samples;
+    total->casts += s.casts;
+    total->bounces += s.bounces;
+    total->draws += s.draws;
+    total->variant = s.variant;
+}
+// the u8 frame back, and the f32 frame when asked; a null host pointer: not asked for
+bool frame_back(const DevBuf<uint8_t>& d8, uint8_t* u8_host, const DevBuf<float>& d32, float* f32_host, size_t vals) {
+    return (!u8_host || d8.download(u8_host, vals)) && (!f32_host || d32.download(f32_host, vals));
+}
+// a nullable output vector at its size: where frame_back copies to
+float* sized(std::vector<float>* v, size_t count) {
+    if (!v) return nullptr;
+    v->resize(count);
+    return v->data();
+}
+// <name>.jpg at the reference's quality 60 and <name>.bmp
+bool write_jpg_bmp(const std::string& name, const rtm_settings* st, const uint8_t* rgb8) {
+    return rtm_write_jpg((name + ".jpg").c_str(), st->width, st->height, 3, rgb8, 60) == 1 &&
+           rtm_write_bmp((name + ".bmp").c_str(), st->width, st->height, 3, rgb8) == 1;
+}
 }  // namespace
 
 int rtm_node_render(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* base,
@@ -296,15 +384,11 @@ int rtm_node_render(const rtm_settings* st, const rtm_object* objects, size_t n,
         std::memset(total, 0, sizeof *total);
         for (int r = 0; r < parts; ++r) {
             const rtm_stats& s = part[r].stats;
-            total->samples += s.samples;
-            total->casts += s.casts;
-            total->bounces += s.bounces;
-            total->draws += s.draws;
+            add_counts(total, s);
             // parts on different GPUs overlap in time: the frame's kernel time is the longest part;
             // virtual parts on one GPU run back to back
             total->kernel_ms = virtual_strips > 0 ? total->kernel_ms + s.kernel_ms
                                                   : (s.kernel_ms > total->kernel_ms ? s.kernel_ms : total->kernel_ms);
-            total->variant = s.variant;
             total->split = s.split;
         }
     }
@@ -317,158 +401,82 @@ int rtm_node_render(const rtm_settings* st, const rtm_object* objects, size_t n,
 int rtm_node_render_passes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int passes,
                            float* out_f32_host, uint8_t* out_u8_host, rtm_stats* total, std::string& err) {
     const unsigned N = (unsigned)st->super_samples * (unsigned)st->super_samples * (unsigned)st->samples;
-    if (passes < 1 || (unsigned)passes > N) {
-        err = "--passes " + std::to_string(passes) + ": must be in [1, " + std::to_string(N) + "] (the frame's samples per pixel)";
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (hipSetDevice(opt->device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(opt->device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    rtm_scene* scene = nullptr;
-    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
-    if (rc != RTM_OK) {
-        err = std::string("scene: ") + rtm_last_error_detail();
-        return rc;
-    }
+    if (passes < 1 || (unsigned)passes > N)
+        return fail(err, RTM_ERR_INVALID_ARGUMENT,
+                    "--passes " + std::to_string(passes) + ": must be in [1, " + std::to_string(N) + "] (the frame's samples per pixel)");
+    Scene scene;
+    if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
     const size_t vals = (size_t)st->width * st->height * 3;
-    double* accum = nullptr;
-    float* d32 = nullptr;
-    uint8_t* d8 = nullptr;
-    if (hipMalloc((void**)&accum, vals * sizeof(double)) != hipSuccess ||
-        (out_f32_host && hipMalloc((void**)&d32, vals * sizeof(float)) != hipSuccess) ||
-        (out_u8_host && hipMalloc((void**)&d8, vals) != hipSuccess)) {
-        err = "no device memory for the frame";
-        rc = RTM_ERR_HIP;
-    }
+    DevBuf<double> accum;
+    DevBuf<float> d32;
+    DevBuf<uint8_t> d8;
+    if (!accum.alloc(vals) || !d32.alloc(vals, out_f32_host != nullptr) || !d8.alloc(vals, out_u8_host != nullptr))
+        return fail(err, RTM_ERR_HIP, "no device memory for the frame");
     std::memset(total, 0, sizeof *total);
     const unsigned q = N / (unsigned)passes, r = N % (unsigned)passes;
     unsigned a = 0;
-    for (int i = 0; rc == RTM_OK && i < passes; ++i) {
+    for (int i = 0; i < passes; ++i) {
         const unsigned b = a + q + ((unsigned)i < r ? 1u : 0u);
         rtm_stats s;
-        rc = rtm_render_scene_samples(st, scene, opt, a, b, accum, d32, d8, nullptr, &s);
-        if (rc != RTM_OK) {
-            err = rtm_last_error_detail();
-            break;
-        }
+        const int rc = rtm_render_scene_samples(st, scene.get(), opt, a, b, accum.get(), d32.get(), d8.get(), nullptr, &s);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
         std::printf("pass %d/%d: samples [%u, %u) %.3f ms\n", i + 1, passes, a, b, s.kernel_ms);
-        total->samples += s.samples;
-        total->casts += s.casts;
-        total->bounces += s.bounces;
-        total->draws += s.draws;
+        add_counts(total, s);
         total->kernel_ms += s.kernel_ms;
-        total->variant = s.variant;
         a = b;
     }
-    if (rc == RTM_OK && ((out_u8_host && hipMemcpy(out_u8_host, d8, vals, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (out_f32_host && hipMemcpy(out_f32_host, d32, vals * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
-        err = "copying the frame back failed";
-        rc = RTM_ERR_HIP;
-    }
-    (void)hipFree(accum);
-    (void)hipFree(d32);
-    (void)hipFree(d8);
-    (void)rtm_scene_destroy(scene);
-    return rc;
+    if (!frame_back(d8, out_u8_host, d32, out_f32_host, vals)) return fail(err, RTM_ERR_HIP, "copying the frame back failed");
+    return RTM_OK;
 }
 
 // --adaptive (rtm_node.h): rtm_render_adaptive of the whole frame on the default stream, outputs and sample map copied back.
 int rtm_node_render_adaptive(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
                              const rtm_adaptive_params* prm, float* out_f32_host, uint8_t* out_u8_host,
                              std::vector<uint32_t>& tile_samples, rtm_stats* total, std::string& err) {
-    if (hipSetDevice(opt->device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(opt->device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    rtm_scene* scene = nullptr;
-    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
-    if (rc != RTM_OK) {
-        err = std::string("scene: ") + rtm_last_error_detail();
-        return rc;
-    }
+    Scene scene;
+    if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
     const size_t vals = (size_t)st->width * st->height * 3;
     const size_t tiles = (size_t)((st->width + 7) / 8) * (size_t)((st->height + 7) / 8);
     tile_samples.assign(tiles, 0u);
-    double* accum = nullptr;
-    float* d32 = nullptr;
-    uint8_t* d8 = nullptr;
-    uint32_t* dts = nullptr;
-    void* work = nullptr;
-    if (hipMalloc((void**)&accum, vals * sizeof(double)) != hipSuccess ||
-        (out_f32_host && hipMalloc((void**)&d32, vals * sizeof(float)) != hipSuccess) ||
-        (out_u8_host && hipMalloc((void**)&d8, vals) != hipSuccess) ||
-        hipMalloc((void**)&dts, tiles * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&work, rtm_adaptive_work_bytes(st, opt)) != hipSuccess) {
-        err = "no device memory for the frame";
-        rc = RTM_ERR_HIP;
+    DevBuf<double> accum;
+    DevBuf<float> d32;
+    DevBuf<uint8_t> d8;
+    DevBuf<uint32_t> dts;
+    DevBuf<void> work;
+    if (!accum.alloc(vals) || !d32.alloc(vals, out_f32_host != nullptr) || !d8.alloc(vals, out_u8_host != nullptr) ||
+        !dts.alloc(tiles) || !work.alloc(rtm_adaptive_work_bytes(st, opt)))
+        return fail(err, RTM_ERR_HIP, "no device memory for the frame");
+    const int rc = rtm_render_adaptive(st, scene.get(), opt, prm, accum.get(), d32.get(), d8.get(), dts.get(), work.get(), nullptr, total);
+    if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+    if (!frame_back(d8, out_u8_host, d32, out_f32_host, vals) || !dts.download(tile_samples.data(), tiles))
+        return fail(err, RTM_ERR_HIP, "copying the frame back failed");
+    double sum = 0.0;
+    for (size_t t = 0; t < tiles; ++t) {
+        const int tx = (int)(t % (size_t)((st->width + 7) / 8)), ty = (int)(t / (size_t)((st->width + 7) / 8));
+        sum += (double)tile_samples[t] * std::min(8, st->width - 8 * tx) * std::min(8, st->height - 8 * ty);
     }
-    if (rc == RTM_OK) {
-        rc = rtm_render_adaptive(st, scene, opt, prm, accum, d32, d8, dts, work, nullptr, total);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
-    if (rc == RTM_OK && ((out_u8_host && hipMemcpy(out_u8_host, d8, vals, hipMemcpyDeviceToHost) != hipSuccess) ||
-                         (out_f32_host && hipMemcpy(out_f32_host, d32, vals * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
-                         hipMemcpy(tile_samples.data(), dts, tiles * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)) {
-        err = "copying the frame back failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        double sum = 0.0;
-        for (size_t t = 0; t < tiles; ++t) {
-            const int tx = (int)(t % (size_t)((st->width + 7) / 8)), ty = (int)(t / (size_t)((st->width + 7) / 8));
-            sum += (double)tile_samples[t] * std::min(8, st->width - 8 * tx) * std::min(8, st->height - 8 * ty);
-        }
-        std::printf("adaptive: threshold %g, min_samples %u: mean %.2f samples per pixel of %d\n", (double)prm->threshold,
-                    prm->min_samples, sum / ((double)st->width * st->height), st->super_samples * st->super_samples * st->samples);
-    }
-    (void)hipFree(accum);
-    (void)hipFree(d32);
-    (void)hipFree(d8);
-    (void)hipFree(dts);
-    (void)hipFree(work);
-    (void)rtm_scene_destroy(scene);
-    return rc;
+    std::printf("adaptive: threshold %g, min_samples %u: mean %.2f samples per pixel of %d\n", (double)prm->threshold,
+                prm->min_samples, sum / ((double)st->width * st->height), st->super_samples * st->super_samples * st->samples);
+    return RTM_OK;
 }
 
 // --aov (rtm_node.h): one rtm_render_aov of the frame on the default stream, then the five files.
 int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
                        const std::string& stem, std::string& err) {
-    if (hipSetDevice(opt->device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(opt->device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    rtm_scene* scene = nullptr;
-    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
-    if (rc != RTM_OK) {
-        err = std::string("scene: ") + rtm_last_error_detail();
-        return rc;
-    }
     const size_t pix = (size_t)st->width * st->height;
-    rtm_aov_buffers dev;
-    std::memset(&dev, 0, sizeof dev);
-    if (hipMalloc((void**)&dev.depth, pix * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.normal, pix * 3 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.albedo, pix * 3 * sizeof(float)) != hipSuccess) {
-        err = "no device memory for the AOV planes";
-        rc = RTM_ERR_HIP;
-    }
     std::vector<float> depth(pix), normal(pix * 3), albedo(pix * 3);
-    if (rc == RTM_OK) {
-        rc = rtm_render_aov(st, scene, opt, &dev, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
+    {  // the device's part; what it holds is released before the files are written
+        Scene scene;
+        if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
+        AovPlanes planes;
+        if (!planes.alloc(pix, false)) return fail(err, RTM_ERR_HIP, "no device memory for the AOV planes");
+        const rtm_aov_buffers dev = planes.view();
+        const int rc = rtm_render_aov(st, scene.get(), opt, &dev, nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!planes.depth.download(depth.data(), pix) || !planes.normal.download(normal.data(), pix * 3) ||
+            !planes.albedo.download(albedo.data(), pix * 3))
+            return fail(err, RTM_ERR_HIP, "copying the AOV planes back failed");
     }
-    if (rc == RTM_OK && (hipMemcpy(depth.data(), dev.depth, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(normal.data(), dev.normal, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(albedo.data(), dev.albedo, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
-        err = "copying the AOV planes back failed";
-        rc = RTM_ERR_HIP;
-    }
-    (void)hipFree(dev.depth);
-    (void)hipFree(dev.normal);
-    (void)hipFree(dev.albedo);
-    (void)rtm_scene_destroy(scene);
-    if (rc != RTM_OK) return rc;
     const int w = st->width, h = st->height;
     bool ok = rtm_write_pfm((stem + "_depth.pfm").c_str(), w, h, 1, depth.data()) == 1 &&
               rtm_write_pfm((stem + "_normal.pfm").c_str(), w, h, 3, normal.data()) == 1 &&
@@ -481,10 +489,7 @@ int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t
     for (size_t i = 0; i < v.size(); ++i) v[i] = (double)albedo[i];
     ok = ok && rtm_quantise(v.data(), v.size(), rgb8.data()) == RTM_OK &&
          rtm_write_bmp((stem + "_albedo.bmp").c_str(), w, h, 3, rgb8.data()) == 1;
-    if (!ok) {
-        err = "cannot write the AOV files of " + stem;
-        return RTM_ERR_IO;
-    }
+    if (!ok) return fail(err, RTM_ERR_IO, "cannot write the AOV files of " + stem);
     return RTM_OK;
 }
 
@@ -493,64 +498,39 @@ int rtm_node_write_aov(const rtm_settings* st, const rtm_object* objects, size_t
 int rtm_node_write_mattes(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, bool want_alpha,
                           int layers, const std::vector<int32_t>& ids, const rtm_composite_params* background,
                           const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* over_out) {
-    if (hipSetDevice(opt->device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(opt->device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    rtm_scene* scene = nullptr;
-    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
-    if (rc != RTM_OK) {
-        err = std::string("scene: ") + rtm_last_error_detail();
-        return rc;
-    }
     const size_t pix = (size_t)st->width * st->height;
-    const bool want_matte = !ids.empty();
-    rtm_matte_buffers dev;
-    std::memset(&dev, 0, sizeof dev);
-    int32_t* sel = nullptr;
-    float* matte = nullptr;
-    float* color = nullptr;  // the frame, composited in place
-    uint8_t* over8 = nullptr;
-    if (hipMalloc((void**)&dev.alpha, pix * sizeof(float)) != hipSuccess ||
-        (want_matte && (hipMalloc((void**)&dev.id, pix * layers * sizeof(int32_t)) != hipSuccess ||
-                        hipMalloc((void**)&dev.coverage, pix * layers * sizeof(float)) != hipSuccess ||
-                        hipMalloc((void**)&sel, ids.size() * sizeof(int32_t)) != hipSuccess ||
-                        hipMalloc((void**)&matte, pix * sizeof(float)) != hipSuccess)) ||
-        (background && (hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess ||
-                        hipMalloc((void**)&over8, pix * 3) != hipSuccess))) {
-        err = "no device memory for the coverage planes";
-        rc = RTM_ERR_HIP;
+    const bool want_matte = !ids.empty(), want_over = background != nullptr;
+    std::vector<float> alpha_h(pix), matte_h(want_matte ? pix : 0), over_h(want_over && over_out ? pix * 3 : 0);
+    std::vector<uint8_t> over8_h(want_over ? pix * 3 : 0);
+    {  // the device's part; what it holds is released before the files are written
+        Scene scene;
+        if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
+        DevBuf<float> alpha;
+        DevBuf<int32_t> id;
+        DevBuf<float> coverage;
+        DevBuf<int32_t> sel;
+        DevBuf<float> matte;
+        DevBuf<float> color;  // the frame, composited in place
+        DevBuf<uint8_t> over8;
+        if (!alpha.alloc(pix) || !id.alloc(pix * layers, want_matte) || !coverage.alloc(pix * layers, want_matte) ||
+            !sel.alloc(ids.size(), want_matte) || !matte.alloc(pix, want_matte) || !color.alloc(pix * 3, want_over) ||
+            !over8.alloc(pix * 3, want_over))
+            return fail(err, RTM_ERR_HIP, "no device memory for the coverage planes");
+        if ((want_matte && !sel.upload(ids.data(), ids.size())) || (want_over && !color.upload(f32_host, pix * 3)))
+            return fail(err, RTM_ERR_HIP, "copying the id list or the frame to the device failed");
+        const rtm_matte_buffers dev = {id.get(), coverage.get(), alpha.get()};
+        int rc = rtm_render_mattes(st, scene.get(), opt, layers, &dev, nullptr);
+        if (rc == RTM_OK && want_matte)
+            rc = rtm_matte(st->width, st->height, layers, opt->device, dev.id, dev.coverage, sel.get(), (int32_t)ids.size(), matte.get(),
+                           nullptr);
+        if (rc == RTM_OK && want_over)
+            rc = rtm_composite(background, st->width, st->height, opt->device, color.get(), dev.alpha, nullptr, color.get(), over8.get(),
+                               nullptr);
+        if (rc != RTM_OK) return err.empty() ? fail(err, rc, rtm_last_error_detail()) : rc;
+        if (!alpha.download(alpha_h.data(), pix) || (want_matte && !matte.download(matte_h.data(), pix)) ||
+            (want_over && !over8.download(over8_h.data(), pix * 3)) || (!over_h.empty() && !color.download(over_h.data(), pix * 3)))
+            return fail(err, RTM_ERR_HIP, "copying the coverage planes back failed");
     }
-    if (rc == RTM_OK && ((want_matte && hipMemcpy(sel, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) ||
-                         (background && hipMemcpy(color, f32_host, pix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))) {
-        err = "copying the id list or the frame to the device failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) rc = rtm_render_mattes(st, scene, opt, layers, &dev, nullptr);
-    if (rc == RTM_OK && want_matte)
-        rc = rtm_matte(st->width, st->height, layers, opt->device, dev.id, dev.coverage, sel, (int32_t)ids.size(), matte, nullptr);
-    if (rc == RTM_OK && background)
-        rc = rtm_composite(background, st->width, st->height, opt->device, color, dev.alpha, nullptr, color, over8, nullptr);
-    if (rc != RTM_OK && err.empty()) err = rtm_last_error_detail();
-    std::vector<float> alpha_h(pix), matte_h(want_matte ? pix : 0), over_h(background && over_out ? pix * 3 : 0);
-    std::vector<uint8_t> over8_h(background ? pix * 3 : 0);
-    if (rc == RTM_OK &&
-        (hipMemcpy(alpha_h.data(), dev.alpha, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess ||
-         (want_matte && hipMemcpy(matte_h.data(), matte, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
-         (background && hipMemcpy(over8_h.data(), over8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess) ||
-         (!over_h.empty() && hipMemcpy(over_h.data(), color, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
-        err = "copying the coverage planes back failed";
-        rc = RTM_ERR_HIP;
-    }
-    (void)hipFree(dev.alpha);
-    (void)hipFree(dev.id);
-    (void)hipFree(dev.coverage);
-    (void)hipFree(sel);
-    (void)hipFree(matte);
-    (void)hipFree(color);
-    (void)hipFree(over8);
-    (void)rtm_scene_destroy(scene);
-    if (rc != RTM_OK) return rc;
     const int w = st->width, h = st->height;
     bool ok = !want_alpha || rtm_write_pfm((stem + "_alpha.pfm").c_str(), w, h, 1, alpha_h.data()) == 1;
     if (want_matte) {
@@ -560,446 +540,214 @@ int rtm_node_write_mattes(const rtm_settings* st, const rtm_object* objects, siz
         ok = ok && rtm_write_pfm((stem + "_matte.pfm").c_str(), w, h, 1, matte_h.data()) == 1 &&
              rtm_quantise(v.data(), v.size(), grey.data()) == RTM_OK && rtm_write_bmp((stem + "_matte.bmp").c_str(), w, h, 3, grey.data()) == 1;
     }
-    if (background)
+    if (want_over)
         ok = ok && rtm_write_bmp((stem + "_over.bmp").c_str(), w, h, 3, over8_h.data()) == 1 &&
              rtm_write_jpg((stem + "_over.jpg").c_str(), w, h, 3, over8_h.data(), 60) == 1;
-    if (!ok) {
-        err = "cannot write the matte files of " + stem;
-        return RTM_ERR_IO;
-    }
+    if (!ok) return fail(err, RTM_ERR_IO, "cannot write the matte files of " + stem);
     if (over_out) *over_out = std::move(over_h);
     return RTM_OK;
 }
 
-// --denoise (rtm_node.h): the frame's AOVs (rtm_render_aov), then rtm_denoise of its f32 at the default parameters on the
-// default stream, then the two files.
-int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
-                            const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* f32_out) {
-    if (hipSetDevice(opt->device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(opt->device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    rtm_scene* scene = nullptr;
-    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
-    if (rc != RTM_OK) {
-        err = std::string("scene: ") + rtm_last_error_detail();
-        return rc;
-    }
-    const size_t pix = (size_t)st->width * st->height;
-    const size_t work_bytes = rtm_denoise_work_bytes(st->width, st->height);
-    rtm_aov_buffers dev;
-    std::memset(&dev, 0, sizeof dev);
-    float *color = nullptr, *out32 = nullptr;
-    uint8_t* out8 = nullptr;
-    void* work = nullptr;
-    if (hipMalloc((void**)&dev.depth, pix * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.normal, pix * 3 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.albedo, pix * 3 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.object, pix * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
-        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) || hipMalloc(&work, work_bytes) != hipSuccess) {
-        err = "no device memory for the denoiser's buffers";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && hipMemcpy(color, f32_host, pix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        err = "copying the frame to the device failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        rc = rtm_render_aov(st, scene, opt, &dev, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
-    if (rc == RTM_OK) {
-        const rtm_denoise_params prm = RTM_DENOISE_DEFAULTS;
-        rc = rtm_denoise(&prm, st->width, st->height, opt->device, color, &dev, work, out32, out8, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
+namespace {
+// --denoise and --denoise-variance: the frame's AOVs (rtm_render_aov), then rtm_denoise or rtm_denoise_variance of its f32
+// at the default parameters on the default stream, then the files.  The variance-guided one has a variance plane more, its
+// own work size, "_var" in its file names and <stem>_variance.pfm.
+int write_denoised(bool variance, const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
+                   const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* f32_out) {
+    const int w = st->width, h = st->height;
+    const size_t pix = (size_t)w * h;
     std::vector<uint8_t> rgb8(pix * 3);
-    if (rc == RTM_OK && hipMemcpy(rgb8.data(), out8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess) {
-        err = "copying the denoised frame back failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && f32_out) {
-        f32_out->resize(pix * 3);
-        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            err = "copying the denoised frame back failed";
-            rc = RTM_ERR_HIP;
+    std::vector<float> variance_h(variance ? pix : 0);
+    {  // the device's part; what it holds is released before the files are written
+        Scene scene;
+        if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
+        const size_t work_bytes = variance ? rtm_denoise_variance_work_bytes(w, h) : rtm_denoise_work_bytes(w, h);
+        AovPlanes planes;
+        DevBuf<float> color;
+        DevBuf<uint8_t> out8;
+        DevBuf<float> var, out32;
+        DevBuf<void> work;
+        if (!planes.alloc(pix, true) || !color.alloc(pix * 3) || !out8.alloc(pix * 3) || !var.alloc(pix, variance) ||
+            !out32.alloc(pix * 3, f32_out != nullptr) || !work.alloc(work_bytes))
+            return fail(err, RTM_ERR_HIP, "no device memory for the denoiser's buffers");
+        if (!color.upload(f32_host, pix * 3)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+        const rtm_aov_buffers dev = planes.view();
+        int rc = rtm_render_aov(st, scene.get(), opt, &dev, nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (variance) {
+            const rtm_denoise_var_params prm = RTM_DENOISE_VAR_DEFAULTS;
+            rc = rtm_denoise_variance(&prm, w, h, opt->device, color.get(), &dev, work.get(), out32.get(), out8.get(), var.get(), nullptr);
+        } else {
+            const rtm_denoise_params prm = RTM_DENOISE_DEFAULTS;
+            rc = rtm_denoise(&prm, w, h, opt->device, color.get(), &dev, work.get(), out32.get(), out8.get(), nullptr);
         }
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, pix * 3), pix * 3) || (variance && !var.download(variance_h.data(), pix)))
+            return fail(err, RTM_ERR_HIP, "copying the denoised frame back failed");
     }
-    (void)hipFree(dev.depth);
-    (void)hipFree(dev.normal);
-    (void)hipFree(dev.albedo);
-    (void)hipFree(dev.object);
-    (void)hipFree(color);
-    (void)hipFree(out32);
-    (void)hipFree(out8);
-    (void)hipFree(work);
-    (void)rtm_scene_destroy(scene);
-    if (rc != RTM_OK) return rc;
-    const bool ok = rtm_write_jpg((stem + "_denoised.jpg").c_str(), st->width, st->height, 3, rgb8.data(), 60) == 1 &&
-                    rtm_write_bmp((stem + "_denoised.bmp").c_str(), st->width, st->height, 3, rgb8.data()) == 1;
-    if (!ok) {
-        err = "cannot write the denoised files of " + stem;
-        return RTM_ERR_IO;
-    }
+    const bool ok = write_jpg_bmp(stem + (variance ? "_denoised_var" : "_denoised"), st, rgb8.data()) &&
+                    (!variance || rtm_write_pfm((stem + "_variance.pfm").c_str(), w, h, 1, variance_h.data()) == 1);
+    if (!ok)
+        return fail(err, RTM_ERR_IO, std::string("cannot write the ") + (variance ? "variance-guided " : "") + "denoised files of " + stem);
     return RTM_OK;
 }
+}  // namespace
 
-// --denoise-variance (rtm_node.h): as rtm_node_write_denoised with rtm_denoise_variance, plus the variance plane.
+// --denoise (rtm_node.h)
+int rtm_node_write_denoised(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
+                            const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* f32_out) {
+    return write_denoised(false, st, objects, n, opt, f32_host, stem, err, f32_out);
+}
+
+// --denoise-variance (rtm_node.h)
 int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
                                      const float* f32_host, const std::string& stem, std::string& err,
                                      std::vector<float>* f32_out) {
-    if (hipSetDevice(opt->device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(opt->device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    rtm_scene* scene = nullptr;
-    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
-    if (rc != RTM_OK) {
-        err = std::string("scene: ") + rtm_last_error_detail();
-        return rc;
-    }
-    const size_t pix = (size_t)st->width * st->height;
-    const size_t work_bytes = rtm_denoise_variance_work_bytes(st->width, st->height);
-    rtm_aov_buffers dev;
-    std::memset(&dev, 0, sizeof dev);
-    float *color = nullptr, *var = nullptr, *out32 = nullptr;
-    uint8_t* out8 = nullptr;
-    void* work = nullptr;
-    if (hipMalloc((void**)&dev.depth, pix * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.normal, pix * 3 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.albedo, pix * 3 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&dev.object, pix * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
-        hipMalloc((void**)&var, pix * sizeof(float)) != hipSuccess ||
-        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) || hipMalloc(&work, work_bytes) != hipSuccess) {
-        err = "no device memory for the denoiser's buffers";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && hipMemcpy(color, f32_host, pix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        err = "copying the frame to the device failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        rc = rtm_render_aov(st, scene, opt, &dev, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
-    if (rc == RTM_OK) {
-        const rtm_denoise_var_params prm = RTM_DENOISE_VAR_DEFAULTS;
-        rc = rtm_denoise_variance(&prm, st->width, st->height, opt->device, color, &dev, work, out32, out8, var, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
-    std::vector<uint8_t> rgb8(pix * 3);
-    std::vector<float> variance(pix);
-    if (rc == RTM_OK && (hipMemcpy(rgb8.data(), out8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(variance.data(), var, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)) {
-        err = "copying the denoised frame back failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && f32_out) {
-        f32_out->resize(pix * 3);
-        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            err = "copying the denoised frame back failed";
-            rc = RTM_ERR_HIP;
-        }
-    }
-    (void)hipFree(dev.depth);
-    (void)hipFree(dev.normal);
-    (void)hipFree(dev.albedo);
-    (void)hipFree(dev.object);
-    (void)hipFree(color);
-    (void)hipFree(out32);
-    (void)hipFree(out8);
-    (void)hipFree(var);
-    (void)hipFree(work);
-    (void)rtm_scene_destroy(scene);
-    if (rc != RTM_OK) return rc;
-    const bool ok = rtm_write_jpg((stem + "_denoised_var.jpg").c_str(), st->width, st->height, 3, rgb8.data(), 60) == 1 &&
-                    rtm_write_bmp((stem + "_denoised_var.bmp").c_str(), st->width, st->height, 3, rgb8.data()) == 1 &&
-                    rtm_write_pfm((stem + "_variance.pfm").c_str(), st->width, st->height, 1, variance.data()) == 1;
-    if (!ok) {
-        err = "cannot write the variance-guided denoised files of " + stem;
-        return RTM_ERR_IO;
-    }
-    return RTM_OK;
+    return write_denoised(true, st, objects, n, opt, f32_host, stem, err, f32_out);
 }
 
 // --display (rtm_node.h): rtm_tonemap of the frame on the default stream, then the two files.
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* prm, const float* f32_host,
                            const std::string& stem, rtm_tonemap_stats* stats, std::string& err, std::vector<float>* f32_out) {
-    if (hipSetDevice(device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(device);
-        return RTM_ERR_NO_DEVICE;
-    }
     const size_t pix = (size_t)st->width * st->height;
-    const size_t work_bytes = rtm_tonemap_work_bytes(st->width, st->height);
-    float* color = nullptr;
-    float* out32 = nullptr;  // only when f32_out is asked for
-    uint8_t* out8 = nullptr;
-    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_tonemap asks of work_dev
-    rtm_tonemap_stats* stats_dev = nullptr;
-    int rc = RTM_OK;
-    if (hipMalloc((void**)&color, pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
-        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) ||
-        hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc((void**)&stats_dev, sizeof(rtm_tonemap_stats)) != hipSuccess) {
-        err = "no device memory for the display transform's buffers";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && hipMemcpy(color, f32_host, pix * 3 * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-        err = "copying the frame to the device failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        rc = rtm_tonemap(prm, st->width, st->height, device, color, work, out32, out8, stats_dev, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
     std::vector<uint8_t> rgb8(pix * 3);
     rtm_tonemap_stats got;
     std::memset(&got, 0, sizeof got);
-    if (rc == RTM_OK && (hipMemcpy(rgb8.data(), out8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess ||
-                         hipMemcpy(&got, stats_dev, sizeof got, hipMemcpyDeviceToHost) != hipSuccess)) {
-        err = "copying the display frame back failed";
-        rc = RTM_ERR_HIP;
+    {  // the device's part; what it holds is released before the files are written
+        if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+        const size_t work_bytes = rtm_tonemap_work_bytes(st->width, st->height);
+        DevBuf<float> color;
+        DevBuf<uint8_t> out8;
+        DevBuf<float> out32;  // only when f32_out is asked for
+        DevBuf<void> work;    // hipMalloc's alignment is 256 bytes or more, what rtm_tonemap asks of work_dev
+        DevBuf<rtm_tonemap_stats> stats_dev;
+        if (!color.alloc(pix * 3) || !out8.alloc(pix * 3) || !out32.alloc(pix * 3, f32_out != nullptr) || !work.alloc(work_bytes) ||
+            !stats_dev.alloc(1))
+            return fail(err, RTM_ERR_HIP, "no device memory for the display transform's buffers");
+        if (!color.upload(f32_host, pix * 3)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+        const int rc = rtm_tonemap(prm, st->width, st->height, device, color.get(), work.get(), out32.get(), out8.get(), stats_dev.get(),
+                                   nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, pix * 3), pix * 3) || !stats_dev.download(&got, 1))
+            return fail(err, RTM_ERR_HIP, "copying the display frame back failed");
     }
-    if (rc == RTM_OK && f32_out) {
-        f32_out->resize(pix * 3);
-        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            err = "copying the display frame back failed";
-            rc = RTM_ERR_HIP;
-        }
-    }
-    (void)hipFree(color);
-    (void)hipFree(out32);
-    (void)hipFree(out8);
-    (void)hipFree(work);
-    (void)hipFree(stats_dev);
-    if (rc != RTM_OK) return rc;
     if (stats) *stats = got;
-    const bool ok = rtm_write_jpg((stem + "_display.jpg").c_str(), st->width, st->height, 3, rgb8.data(), 60) == 1 &&
-                    rtm_write_bmp((stem + "_display.bmp").c_str(), st->width, st->height, 3, rgb8.data()) == 1;
-    if (!ok) {
-        err = "cannot write the display files of " + stem;
-        return RTM_ERR_IO;
-    }
+    if (!write_jpg_bmp(stem + "_display", st, rgb8.data())) return fail(err, RTM_ERR_IO, "cannot write the display files of " + stem);
     return RTM_OK;
 }
 
 // --bloom (rtm_node.h): rtm_bloom of the frame, in place, on the default stream.
 int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* prm, const float* f32_host,
                    std::vector<float>* f32_out, std::string& err) {
-    if (hipSetDevice(device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    const size_t bytes = (size_t)st->width * st->height * 3 * sizeof(float);
+    if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+    const size_t vals = (size_t)st->width * st->height * 3;
     const size_t work_bytes = rtm_bloom_work_bytes(st->width, st->height, prm->levels);
-    float* color = nullptr;
-    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_bloom asks of work_dev
-    int rc = RTM_OK;
-    if (work_bytes == 0 || work_bytes == SIZE_MAX) {
-        err = "bloom's frame size or levels are out of range";
-        rc = RTM_ERR_INVALID_ARGUMENT;
-    } else if (hipMalloc((void**)&color, bytes) != hipSuccess || hipMalloc(&work, work_bytes) != hipSuccess) {
-        err = "no device memory for bloom's buffers";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && hipMemcpy(color, f32_host, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        err = "copying the frame to the device failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        rc = rtm_bloom(prm, st->width, st->height, device, color, work, color, nullptr, nullptr, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
-    if (rc == RTM_OK) {
-        f32_out->resize(bytes / sizeof(float));
-        if (hipMemcpy(f32_out->data(), color, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-            err = "copying the bloomed frame back failed";
-            rc = RTM_ERR_HIP;
-        }
-    }
-    (void)hipFree(color);
-    (void)hipFree(work);
-    return rc;
+    DevBuf<float> color;
+    DevBuf<void> work;  // hipMalloc's alignment is 256 bytes or more, what rtm_bloom asks of work_dev
+    if (work_bytes == 0 || work_bytes == SIZE_MAX)
+        return fail(err, RTM_ERR_INVALID_ARGUMENT, "bloom's frame size or levels are out of range");
+    if (!color.alloc(vals) || !work.alloc(work_bytes)) return fail(err, RTM_ERR_HIP, "no device memory for bloom's buffers");
+    if (!color.upload(f32_host, vals)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+    const int rc = rtm_bloom(prm, st->width, st->height, device, color.get(), work.get(), color.get(), nullptr, nullptr, nullptr);
+    if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+    if (!color.download(sized(f32_out, vals), vals)) return fail(err, RTM_ERR_HIP, "copying the bloomed frame back failed");
+    return RTM_OK;
 }
+
+namespace {
+// --compare and --flip: the two frames up, the work buffer, `call` on the default stream, the record back and, when
+// map_out is given, the height x width plane back.  `what` names the stage in the messages.  A work size of SIZE_MAX
+// (a frame the stage does not serve) is no device memory, as an allocation of it would be.
+template <class Result, class Call>
+int frame_pair(const rtm_settings* st, const float* frame_host, const float* reference_host, size_t work_bytes, Result* result,
+               std::vector<float>* map_out, const std::string& what, std::string& err, Call call) {
+    const size_t pix = (size_t)st->width * st->height;
+    DevBuf<float> a, b;
+    DevBuf<void> work;  // hipMalloc's alignment is 256 bytes or more, what rtm_compare and rtm_flip ask of work_dev
+    DevBuf<Result> result_dev;
+    DevBuf<float> map_dev;
+    if (work_bytes == SIZE_MAX || !a.alloc(pix * 3) || !b.alloc(pix * 3) || !work.alloc(work_bytes) || !result_dev.alloc(1) ||
+        !map_dev.alloc(pix, map_out != nullptr))
+        return fail(err, RTM_ERR_HIP, "no device memory for the " + what + "'s buffers");
+    if (!a.upload(frame_host, pix * 3) || !b.upload(reference_host, pix * 3))
+        return fail(err, RTM_ERR_HIP, "copying the frames to the device failed");
+    const int rc = call(a.get(), b.get(), work.get(), result_dev.get(), map_dev.get());
+    if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+    if (!result_dev.download(result, 1)) return fail(err, RTM_ERR_HIP, "copying the " + what + "'s record back failed");
+    if (map_out && !map_dev.download(sized(map_out, pix), pix)) return fail(err, RTM_ERR_HIP, "copying the " + what + "'s map back failed");
+    return RTM_OK;
+}
+}  // namespace
 
 // --compare (rtm_node.h): rtm_compare of the two frames on the default stream.
 int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host, const float* reference_host,
                      rtm_compare_result* result, std::string& err) {
-    if (hipSetDevice(device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    const size_t bytes = (size_t)st->width * st->height * 3 * sizeof(float);
-    const size_t work_bytes = rtm_compare_work_bytes(st->width, st->height);
-    float *a = nullptr, *b = nullptr;
-    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_compare asks of work_dev
-    rtm_compare_result* result_dev = nullptr;
-    int rc = RTM_OK;
-    if (hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess ||
-        hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc((void**)&result_dev, sizeof(rtm_compare_result)) != hipSuccess) {
-        err = "no device memory for the comparison's buffers";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && (hipMemcpy(a, frame_host, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-                         hipMemcpy(b, reference_host, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-        err = "copying the frames to the device failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        const rtm_compare_params prm = RTM_COMPARE_DEFAULTS;
-        rc = rtm_compare(&prm, st->width, st->height, device, a, b, work, result_dev, nullptr, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
-    if (rc == RTM_OK && hipMemcpy(result, result_dev, sizeof *result, hipMemcpyDeviceToHost) != hipSuccess) {
-        err = "copying the comparison's record back failed";
-        rc = RTM_ERR_HIP;
-    }
-    (void)hipFree(a);
-    (void)hipFree(b);
-    (void)hipFree(work);
-    (void)hipFree(result_dev);
-    return rc;
+    if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+    const rtm_compare_params prm = RTM_COMPARE_DEFAULTS;
+    return frame_pair(st, frame_host, reference_host, rtm_compare_work_bytes(st->width, st->height), result, nullptr, "comparison", err,
+                      [&](const float* a, const float* b, void* work, rtm_compare_result* result_dev, float*) {
+                          return rtm_compare(&prm, st->width, st->height, device, a, b, work, result_dev, nullptr, nullptr);
+                      });
 }
 
 // --flip (rtm_node.h): rtm_flip of the two frames on the default stream.
 int rtm_node_flip(const rtm_settings* st, int device, const rtm_flip_params* prm, const float* frame_host,
                   const float* reference_host, rtm_flip_result* result, std::vector<float>* map_out, std::string& err) {
-    if (hipSetDevice(device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    const size_t pix = (size_t)st->width * st->height;
-    const size_t bytes = pix * 3 * sizeof(float);
-    const size_t work_bytes = rtm_flip_work_bytes(st->width, st->height);
-    float *a = nullptr, *b = nullptr, *map_dev = nullptr;
-    void* work = nullptr;  // hipMalloc's alignment is 256 bytes or more, what rtm_flip asks of work_dev
-    rtm_flip_result* result_dev = nullptr;
-    int rc = RTM_OK;
-    if (work_bytes == SIZE_MAX || hipMalloc((void**)&a, bytes) != hipSuccess || hipMalloc((void**)&b, bytes) != hipSuccess ||
-        hipMalloc(&work, work_bytes) != hipSuccess || hipMalloc((void**)&result_dev, sizeof(rtm_flip_result)) != hipSuccess ||
-        (map_out && hipMalloc((void**)&map_dev, pix * sizeof(float)) != hipSuccess)) {
-        err = "no device memory for the perceptual difference's buffers";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && (hipMemcpy(a, frame_host, bytes, hipMemcpyHostToDevice) != hipSuccess ||
-                         hipMemcpy(b, reference_host, bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-        err = "copying the frames to the device failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        rc = rtm_flip(prm, st->width, st->height, device, a, b, work, result_dev, map_dev, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
-    }
-    if (rc == RTM_OK && hipMemcpy(result, result_dev, sizeof *result, hipMemcpyDeviceToHost) != hipSuccess) {
-        err = "copying the perceptual difference's record back failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && map_out) {
-        map_out->resize(pix);
-        if (hipMemcpy(map_out->data(), map_dev, pix * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            err = "copying the perceptual difference's map back failed";
-            rc = RTM_ERR_HIP;
-        }
-    }
-    (void)hipFree(a);
-    (void)hipFree(b);
-    (void)hipFree(map_dev);
-    (void)hipFree(work);
-    (void)hipFree(result_dev);
-    return rc;
+    if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+    return frame_pair(st, frame_host, reference_host, rtm_flip_work_bytes(st->width, st->height), result, map_out, "perceptual difference",
+                      err, [&](const float* a, const float* b, void* work, rtm_flip_result* result_dev, float* map_dev) {
+                          return rtm_flip(prm, st->width, st->height, device, a, b, work, result_dev, map_dev, nullptr);
+                      });
 }
 
 // --preview (rtm_node.h): the low render, its AOVs and rtm_denoise, the full AOVs, rtm_upsample, all on the default stream,
 // then the two files.
 int rtm_node_write_preview(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int factor,
                            const std::string& stem, std::string& err, std::vector<float>* f32_out, rtm_stats* stats) {
-    if (factor < 2 || factor > 8 || st->width % factor != 0 || st->height % factor != 0) {
-        err = "--preview " + std::to_string(factor) + ": a factor in 2..8 that divides the width and the height";
-        return RTM_ERR_INVALID_ARGUMENT;
-    }
-    if (hipSetDevice(opt->device) != hipSuccess) {
-        err = "no HIP device " + std::to_string(opt->device);
-        return RTM_ERR_NO_DEVICE;
-    }
-    rtm_scene* scene = nullptr;
-    int rc = rtm_scene_create_objects(objects, n, opt->device, &scene);
-    if (rc != RTM_OK) {
-        err = std::string("scene: ") + rtm_last_error_detail();
-        return rc;
-    }
-    rtm_settings lo_st = *st;
-    lo_st.width = st->width / factor;
-    lo_st.height = st->height / factor;
-    rtm_options lo_opt = *opt;
-    lo_opt.row_begin = 0;
-    lo_opt.row_end = lo_st.height;
-    const size_t lo_pix = (size_t)lo_st.width * lo_st.height, pix = (size_t)st->width * st->height;
-    rtm_aov_buffers lo, hi;
-    std::memset(&lo, 0, sizeof lo);
-    std::memset(&hi, 0, sizeof hi);
-    float *color = nullptr, *den = nullptr, *out32 = nullptr;
-    uint8_t* out8 = nullptr;
-    void *dn_work = nullptr, *up_work = nullptr;
-    auto planes = [](rtm_aov_buffers& b, size_t p) {
-        return hipMalloc((void**)&b.depth, p * sizeof(float)) == hipSuccess && hipMalloc((void**)&b.normal, p * 3 * sizeof(float)) == hipSuccess &&
-               hipMalloc((void**)&b.albedo, p * 3 * sizeof(float)) == hipSuccess && hipMalloc((void**)&b.object, p * sizeof(int32_t)) == hipSuccess;
-    };
-    if (!planes(lo, lo_pix) || !planes(hi, pix) || hipMalloc((void**)&color, lo_pix * 3 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void**)&den, lo_pix * 3 * sizeof(float)) != hipSuccess || hipMalloc((void**)&out8, pix * 3) != hipSuccess ||
-        (f32_out && hipMalloc((void**)&out32, pix * 3 * sizeof(float)) != hipSuccess) ||
-        hipMalloc(&dn_work, rtm_denoise_work_bytes(lo_st.width, lo_st.height)) != hipSuccess ||
-        hipMalloc(&up_work, rtm_upsample_work_bytes(lo_st.width, lo_st.height)) != hipSuccess) {
-        err = "no device memory for the preview's buffers";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK) {
-        rc = rtm_render_scene(&lo_st, scene, &lo_opt, nullptr, color, nullptr, nullptr, stats);
-        if (rc == RTM_OK) rc = rtm_render_aov(&lo_st, scene, &lo_opt, &lo, nullptr);
+    if (factor < 2 || factor > 8 || st->width % factor != 0 || st->height % factor != 0)
+        return fail(err, RTM_ERR_INVALID_ARGUMENT,
+                    "--preview " + std::to_string(factor) + ": a factor in 2..8 that divides the width and the height");
+    const size_t pix = (size_t)st->width * st->height;
+    std::vector<uint8_t> rgb8(pix * 3);
+    {  // the device's part; what it holds is released before the files are written
+        Scene scene;
+        if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
+        rtm_settings lo_st = *st;
+        lo_st.width = st->width / factor;
+        lo_st.height = st->height / factor;
+        rtm_options lo_opt = *opt;
+        lo_opt.row_begin = 0;
+        lo_opt.row_end = lo_st.height;
+        const size_t lo_pix = (size_t)lo_st.width * lo_st.height;
+        AovPlanes lo_planes, hi_planes;
+        DevBuf<float> color, den;
+        DevBuf<uint8_t> out8;
+        DevBuf<float> out32;
+        DevBuf<void> dn_work, up_work;
+        if (!lo_planes.alloc(lo_pix, true) || !hi_planes.alloc(pix, true) || !color.alloc(lo_pix * 3) || !den.alloc(lo_pix * 3) ||
+            !out8.alloc(pix * 3) || !out32.alloc(pix * 3, f32_out != nullptr) ||
+            !dn_work.alloc(rtm_denoise_work_bytes(lo_st.width, lo_st.height)) ||
+            !up_work.alloc(rtm_upsample_work_bytes(lo_st.width, lo_st.height)))
+            return fail(err, RTM_ERR_HIP, "no device memory for the preview's buffers");
+        const rtm_aov_buffers lo = lo_planes.view(), hi = hi_planes.view();
+        int rc = rtm_render_scene(&lo_st, scene.get(), &lo_opt, nullptr, color.get(), nullptr, nullptr, stats);
+        if (rc == RTM_OK) rc = rtm_render_aov(&lo_st, scene.get(), &lo_opt, &lo, nullptr);
         if (rc == RTM_OK) {
             const rtm_denoise_params prm = RTM_DENOISE_DEFAULTS;
-            rc = rtm_denoise(&prm, lo_st.width, lo_st.height, opt->device, color, &lo, dn_work, den, nullptr, nullptr);
+            rc = rtm_denoise(&prm, lo_st.width, lo_st.height, opt->device, color.get(), &lo, dn_work.get(), den.get(), nullptr, nullptr);
         }
-        if (rc == RTM_OK) rc = rtm_render_aov(st, scene, opt, &hi, nullptr);
+        if (rc == RTM_OK) rc = rtm_render_aov(st, scene.get(), opt, &hi, nullptr);
         if (rc == RTM_OK) {
             rtm_upsample_params prm = RTM_UPSAMPLE_DEFAULTS;
             prm.factor = factor;
-            rc = rtm_upsample(&prm, lo_st.width, lo_st.height, opt->device, den, &lo, &hi, up_work, out32, out8, nullptr);
+            rc = rtm_upsample(&prm, lo_st.width, lo_st.height, opt->device, den.get(), &lo, &hi, up_work.get(), out32.get(), out8.get(),
+                              nullptr);
         }
         if (rc == RTM_OK) rc = rtm_stream_status(opt->device, nullptr);
-        if (rc != RTM_OK) err = rtm_last_error_detail();
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, pix * 3), pix * 3))
+            return fail(err, RTM_ERR_HIP, "copying the preview back failed");
     }
-    std::vector<uint8_t> rgb8(pix * 3);
-    if (rc == RTM_OK && hipMemcpy(rgb8.data(), out8, pix * 3, hipMemcpyDeviceToHost) != hipSuccess) {
-        err = "copying the preview back failed";
-        rc = RTM_ERR_HIP;
-    }
-    if (rc == RTM_OK && f32_out) {
-        f32_out->resize(pix * 3);
-        if (hipMemcpy(f32_out->data(), out32, pix * 3 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-            err = "copying the preview back failed";
-            rc = RTM_ERR_HIP;
-        }
-    }
-    for (rtm_aov_buffers* b : {&lo, &hi}) {
-        (void)hipFree(b->depth);
-        (void)hipFree(b->normal);
-        (void)hipFree(b->albedo);
-        (void)hipFree(b->object);
-    }
-    (void)hipFree(color);
-    (void)hipFree(den);
-    (void)hipFree(out32);
-    (void)hipFree(out8);
-    (void)hipFree(dn_work);
-    (void)hipFree(up_work);
-    (void)rtm_scene_destroy(scene);
-    if (rc != RTM_OK) return rc;
-    const bool ok = rtm_write_jpg((stem + "_preview.jpg").c_str(), st->width, st->height, 3, rgb8.data(), 60) == 1 &&
-                    rtm_write_bmp((stem + "_preview.bmp").c_str(), st->width, st->height, 3, rgb8.data()) == 1;
-    if (!ok) {
-        err = "cannot write the preview files of " + stem;
-        return RTM_ERR_IO;
-    }
+    if (!write_jpg_bmp(stem + "_preview", st, rgb8.data())) return fail(err, RTM_ERR_IO, "cannot write the preview files of " + stem);
     return RTM_OK;
 }

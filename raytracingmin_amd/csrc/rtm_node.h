@@ -1,4 +1,5 @@
-// rtm_node.h — single-process multi-GPU render + RCCL gather used by rtm_cli (rtm_node.cpp).
+// rtm_node.h — what rtm_cli runs on the device (rtm_node.cpp): the single-process multi-GPU render with its RCCL gather, and
+// the one-GPU stages of a run, each a host wrapper around one library stage that copies in, calls, copies back and writes files.
 #pragma once
 #include <string>
 #include <vector>
