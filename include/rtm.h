@@ -641,6 +641,60 @@ size_t rtm_bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
 int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color_dev,
               void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream);
 
+/* ---- depth of field (defocus): a focus distance and an aperture applied to a finished frame by its depth plane — a
+ * depth-aware gather blur (scatter-as-gather) whose per-pixel circle of confusion follows the thin-lens law.  A focused
+ * foreground stays sharp against a blurred background; a blurred foreground spills over what is behind it.  Opt-in, after the
+ * denoisers and before rtm_bloom (glare forms behind the lens) and rtm_tonemap: every other stage and its defaults stay.
+ * Inputs: color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32; 4-byte alignment is enough) and depth
+ * (DEVICE, height x width floats, as rtm_render_aov writes it: positive, +inf on a miss).  Depth is the distance along the
+ * primary ray, so the surface in focus is a sphere around the camera's origin, not a plane: build-defined, the reference has
+ * no lens.  Arithmetic in float, without contraction.  zf = focus_distance, A = aperture, R = max_radius, pi_f = (float)pi.
+ *   1 counting   a pixel COUNTS iff its three colour components are finite and its depth is > 0 (+inf counts; NaN, 0 and
+ *                negative do not).  A pixel that does not count contributes to no other pixel; its out_f32 is its input, bit
+ *                for bit, its coc_out is +0 and its out_u8 the usual store of its own out_f32.
+ *   2 circle     s = A max(1 - zf / z, -FLT_MAX); for z = +inf the quotient is +0, so s = A; a quotient that overflows (a
+ *                depth tiny against zf) counts as the largest float, so that A = 0 gives -0 and never NaN.  s is clamped to
+ *                [-R, R]: negative in front of the focus, positive behind it.  r = |s|, m = max(r, 0.5f), ia = 1 / ((pi_f m) m): the reciprocal area of
+ *                the pixel's disc; the floor of half a pixel makes a sharp pixel a disc of one pixel.
+ *   3 taps       q = p + (dx, dy), dx and dy in -R..R.  Taps outside the frame or not counting are skipped, not clamped (the
+ *                library's skip-and-renormalise rule).  d = sqrtf((float)(dx dx + dy dy)).
+ *   4 which disc behind = z_q > z_p, as the floats they are (+inf > finite is true, inf > inf is false);
+ *                (r_e, ia_e) = (behind && r_p < r_q) ? (r_p, ia_p) : (r_q, ia_q).  A tap in front of p spreads over p with its
+ *                own disc; a tap behind p spreads no further than p's own blur, so a focused foreground does not take on its
+ *                background.
+ *   5 weight     w = min(max(r_e + 0.5f - d, 0), 1) ia_e: a disc with a one-pixel linear edge, continuous in every input.
+ *                The centre tap always has w > 0.
+ *   6 combine    out = (sum of w c_q) / (sum of w) per channel.  If no tap other than the centre has w > 0, out is the input,
+ *                bit for bit.  Taps whose weight is +0 may be skipped: adding +0 changes no sum.  The order of the sums is
+ *                the implementation's (rows, then columns), but fixed: the same inputs give the same bits on every call, on
+ *                any stream, at any alignment of color.  No atomics.
+ *   7 outputs    coc_out_dev (nullable, height x width floats) receives s.  out_u8 (nullable) is rtm_quantise of
+ *                (double)out_f32, out of range (NaN included) -> 0, as in the other stages.
+ * It follows that aperture = 0 returns every pixel bit for bit (every r is 0, and every non-centre weight +0); that a frame
+ * of one constant colour over any depths stays that colour, within the tolerance; and that a pixel with r_p = 0 whose nearer
+ * neighbours all have r = 0 keeps its words, however blurred what lies behind it.
+ * The divisions and the reciprocal may be the device's fast forms: against a float64 evaluation of the steps above every
+ * out_f32 component of a counting pixel and every coc_out value is within 1e-4 max(1, |ref|); out_u8 is exact given the
+ * call's own out_f32.
+ * The call keeps no state, allocates nothing, needs no work buffer and no serialisation, and only ENQUEUES one launch on
+ * `stream`.  Null params, color_dev or depth_dev, all three outputs null, a non-positive size, a focus_distance that is NaN,
+ * infinite or not positive, an aperture that is NaN, infinite or negative, max_radius outside 1..16, a float pointer that is
+ * not 4-byte aligned, any output equal to color_dev or depth_dev (a gather cannot run in place), coc_out_dev equal to
+ * out_f32_dev, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A frame of 2^31 pixels or more, or
+ * one of 2^23 or more tiles of 32 x 16 pixels (ceil(width / 32) ceil(height / 16): a launch has one 512-lane block a tile,
+ * so a frame thinner than a tile reaches the launch's limit of 2^32 lanes first): RTM_ERR_UNSUPPORTED, as rtm_tonemap.
+ * Defaults: RTM_DEFOCUS_DEFAULTS below (what Renderer.Render(dof=True) and rtm_cli --dof use, with the focus at the camera's
+ * target distance).  Added after RTM_ABI_VERSION 5 without changing it: callers look the symbol up. */
+typedef struct rtm_defocus_params { /* 12 bytes */
+    float focus_distance; /* zf: finite, > 0, in depth's units.  No default: 0 is refused                                */
+    float aperture;       /* A: finite, >= 0: the blur radius, in pixels, of a point at infinity.  The thin lens's       */
+                          /* f^2 / (N (zf - f)) and the pixel pitch are folded into it                                   */
+    int32_t max_radius;   /* R: 1..16, in pixels: radii are clamped to it and the window is (2R+1)^2                     */
+} rtm_defocus_params;
+#define RTM_DEFOCUS_DEFAULTS {0.0f, 4.0f, 8} /* of rtm_defocus_params; the caller sets focus_distance */
+int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream);
+
 /* ---- AOV-guided upsampling: a frame traced at 1/f of the resolution in each axis, brought to full size by a joint
  * bilateral upsample (Kopf et al. 2007) steered by the full-resolution first-hit planes, with the albedo demodulated so that
  * material colour comes back at full resolution.  The AOVs have no random draws and cost one cheap kernel at any size; the

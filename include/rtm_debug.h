@@ -132,6 +132,12 @@ int rtm_debug_component_bench(int which, const rtm_sphere* spheres, size_t n, in
  * null-ness of the guide pointers is read); variance_out_dev receives v0.  Only enqueues on `stream`. */
 int rtm_debug_denoise_variance_kernel(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
                                       const rtm_aov_buffers* guide_dev, void* work_dev, float* variance_out_dev, void* stream);
+/* rtm_defocus with one form of its kernel (profiles/defocus_pass.py, and the test that holds the forms against each other):
+ * form 0 is the call as shipped, form 1 runs every block over all (2R+1)^2 taps, without the per-tile window bound and the
+ * pass-through of sharp tiles.  Arguments, refusals and bits are rtm_defocus's.  Only enqueues on `stream`. */
+int rtm_debug_defocus_form(int form, const rtm_defocus_params* params, int32_t width, int32_t height, int device,
+                           const float* color_dev, const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                           float* coc_out_dev, void* stream);
 /* rtm_render_mattes' ranking alone (csrc/rtm_matte_kernel.h: matte_rank) on caller-given id lists, so that ties, truncation
  * and lists of 64 distinct ids can be pinned without rays.  DEVICE buffers: ids_dev holds n_pixels lists of SS^2 ids each
  * (pixel-major), any negative id is a miss; a small kernel loads 64 pixels' lists into the render kernel's LDS layout and calls

@@ -111,6 +111,12 @@ class rtm_bloom_params(C.Structure):  # include/rtm.h: rtm_bloom (20 bytes)
                 ("levels", C.c_int32)]
 
 
+class rtm_defocus_params(C.Structure):  # include/rtm.h: rtm_defocus (12 bytes)
+    _fields_ = [("focus_distance", C.c_float), ("aperture", C.c_float), ("max_radius", C.c_int32)]
+
+
+DEFOCUS_DEFAULTS = {"aperture": 4.0, "max_radius": 8}  # RTM_DEFOCUS_DEFAULTS; the caller sets focus_distance
+
 COMPARE_DTYPES = {"float32": 0, "float64": 1}  # include/rtm.h: RTM_COMPARE_F32, RTM_COMPARE_F64
 COMPARE_MAPS = {"abs": 0, "ssim": 1}  # RTM_COMPARE_MAP_*
 
@@ -182,6 +188,8 @@ SIGNATURES = {
     "rtm_bloom_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rtm_bloom": (C.c_int, [_P(rtm_bloom_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_defocus": (C.c_int, [_P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_upsample_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_upsample": (C.c_int, [_P(rtm_upsample_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
                                _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -246,6 +254,8 @@ DEBUG_SIGNATURES = {
                                        C.c_void_p]),
     "rtm_debug_denoise_variance_kernel": (C.c_int, [C.c_int, _P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int,
                                                     _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_debug_defocus_form": (C.c_int, [C.c_int, _P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_debug_matte_rank": (C.c_int, [C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
     "rtm_debug_component_bench": (C.c_int, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int,

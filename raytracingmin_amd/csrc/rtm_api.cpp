@@ -134,6 +134,10 @@ int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int
               float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream) {
     RTM_GUARD(rtm::bloom(params, width, height, device, color_dev, work_dev, out_f32_dev, out_u8_dev, bloom_out_dev, stream))
 }
+int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream) {
+    RTM_GUARD(rtm::defocus(params, width, height, device, color_dev, depth_dev, out_f32_dev, out_u8_dev, coc_out_dev, stream))
+}
 size_t rtm_upsample_work_bytes(int32_t low_width, int32_t low_height) { return rtm::upsample_work_bytes(low_width, low_height); }
 int rtm_upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device,
                  const float* color_low_dev, const rtm_aov_buffers* guide_low_dev, const rtm_aov_buffers* guide_high_dev,
@@ -205,6 +209,12 @@ int rtm_debug_wf_nearest(int kind, const rtm_sphere* sp, size_t n, const double*
 int rtm_debug_denoise_variance_kernel(int form, const rtm_denoise_var_params* params, int32_t width, int32_t height, int device,
                                       const rtm_aov_buffers* guide_dev, void* work_dev, float* variance_out_dev, void* stream) {
     RTM_GUARD(rtm::denoise_variance_kernel_probe(form, params, width, height, device, guide_dev, work_dev, variance_out_dev, stream))
+}
+int rtm_debug_defocus_form(int form, const rtm_defocus_params* params, int32_t width, int32_t height, int device,
+                           const float* color_dev, const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                           float* coc_out_dev, void* stream) {
+    RTM_GUARD(rtm::defocus_form_probe(form, params, width, height, device, color_dev, depth_dev, out_f32_dev, out_u8_dev, coc_out_dev,
+                                      stream))
 }
 int rtm_debug_matte_rank(int32_t super_samples, int32_t layers, int device, const int32_t* ids_dev, size_t n_pixels,
                          int32_t* id_out_dev, float* coverage_out_dev, float* alpha_out_dev, void* stream) {

@@ -78,6 +78,11 @@ int tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int
 size_t bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
 int bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color, void* work, float* out32,
           uint8_t* out8, float* bloom_out, void* stream);
+// depth of field (rtm_defocus.hip); the probe runs one form of the kernel (rtm_debug_defocus_form)
+int defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color, const float* depth,
+            float* out32, uint8_t* out8, float* coc_out, void* stream);
+int defocus_form_probe(int form, const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color,
+                       const float* depth, float* out32, uint8_t* out8, float* coc_out, void* stream);
 // AOV-guided upsampling (rtm_upsample.hip)
 size_t upsample_work_bytes(int32_t low_width, int32_t low_height);
 int upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device, const float* color_low,

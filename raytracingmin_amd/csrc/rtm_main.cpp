@@ -14,6 +14,9 @@
 //                                                (the display transform of the last stage: STEM_display.bmp, .jpg)
 //           [--bloom [INTENSITY]] [--bloom-threshold T] [--bloom-levels L]
 //                                                (with --display: bloom the frame before the display transform)
+//           [--dof [APERTURE]] [--focus DISTANCE | --focus-pixel X,Y] [--dof-radius R]
+//                                                (depth of field of the last stage by the depth plane: STEM_dof.bmp, .jpg; the
+//                                                defocused frame then is the last stage's for what follows)
 //           [--preview F [--preview-only]]       (the frame traced at 1/F of the resolution per axis, denoised there and upsampled
 //                                                by the first-hit feature buffers: STEM_preview.bmp, .jpg; -only: no full render)
 //           [--pfm]                              (the float frame of the last stage: STEM.pfm)
@@ -119,6 +122,12 @@ static void usage() {
         "            is given (rtm_bloom: a bright pass above luminance T, default 1, a pyramid of L levels, 1..8, default 6, and\n"
         "            INTENSITY, default 0.2, times the result added back in linear space): STEM_display.*, STEM_preview_display.*,\n"
         "            STEM_over_display.*, --display-pfm and what --flip sees are those of the bloomed frame\n"
+        "--dof [APERTURE] [--focus DISTANCE | --focus-pixel X,Y] [--dof-radius R] : also write the depth of field (rtm_defocus) of\n"
+        "            the last stage asked for on one GPU, by the frame's depth plane: STEM_dof.bmp and STEM_dof.jpg.  APERTURE: the\n"
+        "            blur radius, in pixels, of a point at infinity (default 4); --dof-radius R : the largest radius, 1..16 (default\n"
+        "            8); the focus is at the camera's target distance, at --focus DISTANCE, or at what pixel X,Y shows.  The\n"
+        "            defocused frame then is the frame of the last stage for --pfm, --compare, --flip, --background and --display\n"
+        "            (with --bloom: the glare of the defocused frame)\n"
         "--preview F [--preview-only] : also write a fast preview on one GPU: the scene traced at width / F x height / F (F in\n"
         "            2..8, dividing both; F^2 fewer paths), denoised there (rtm_denoise at its defaults) and brought to full size\n"
         "            by rtm_upsample, guided by the first-hit feature buffers at both resolutions: STEM_preview.bmp and\n"
@@ -165,6 +174,8 @@ int main(int argc, char* argv[]) {
     rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
     int bloom = 0;
     rtm_bloom_params bloom_prm = RTM_BLOOM_DEFAULTS;
+    int dof = 0, focus_given = 0, focus_pixel_given = 0, dof_radius_given = 0, focus_x = 0, focus_y = 0;
+    rtm_defocus_params dof_prm = RTM_DEFOCUS_DEFAULTS;
     int pfm = 0;
     std::string dump_f32, compare_ref, flip_ref;
     int display_pfm = 0, flip_map = 0, flip_ppd_given = 0;
@@ -254,6 +265,46 @@ int main(int argc, char* argv[]) {
                              c == "--bloom-levels" ? "a number of levels in 1..8" : "a finite number that is not negative", m.c_str());
                 return 2;
             }
+        }
+        else if (c == "--dof" || c == "--focus" || c == "--dof-radius") {
+            // a number, all of it; --dof alone may stand without one (anything that is not a number is the next option)
+            const std::string m = i + 1 < argc ? argv[i + 1] : "";
+            double v = 0.0;
+            const bool number = parse_number(m, v);
+            bool ok = number || c == "--dof";
+            if (number) ++i;
+            if (c == "--dof") {
+                dof = 1;
+                if (number) ok = std::isfinite(dof_prm.aperture = (float)v) && v >= 0.0;
+            } else if (c == "--focus") {
+                focus_given = 1;
+                if (number) ok = std::isfinite(dof_prm.focus_distance = (float)v) && dof_prm.focus_distance > 0.0f;
+            } else {
+                dof_radius_given = 1;
+                ok = number && v == std::floor(v) && v >= 1.0 && v <= 16.0;
+                if (ok) dof_prm.max_radius = (int)v;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "%s takes %s, got %s\n", c.c_str(),
+                             c == "--dof"     ? "a finite aperture that is not negative"
+                             : c == "--focus" ? "a finite distance above zero"
+                                              : "a radius in 1..16",
+                             m.c_str());
+                return 2;
+            }
+        } else if (c == "--focus-pixel") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = m.find(',');
+            double x = 0.0, y = 0.0;
+            const bool ok = comma != std::string::npos && parse_number(m.substr(0, comma), x) && parse_number(m.substr(comma + 1), y) &&
+                            x == std::floor(x) && y == std::floor(y) && x >= 0.0 && y >= 0.0 && x <= 2147483647.0 && y <= 2147483647.0;
+            if (!ok) {
+                std::fprintf(stderr, "--focus-pixel takes a pixel X,Y, two whole numbers from 0, got %s\n", m.c_str());
+                return 2;
+            }
+            focus_pixel_given = 1;
+            focus_x = (int)x;
+            focus_y = (int)y;
         }
         else if (c == "--pfm") pfm = 1;
         else if (c == "--compare" && i + 1 < argc) compare_ref = argv[++i];
@@ -345,6 +396,10 @@ int main(int argc, char* argv[]) {
          "--display-pfm writes the display transform's float frame of the full render: it requires --display and does not combine "
          "with --preview-only"},
         {bloom && !display, "--bloom blooms the frame the display transform shows: it requires --display"},
+        {(focus_given || focus_pixel_given || dof_radius_given) && !dof, "--focus, --focus-pixel and --dof-radius require --dof"},
+        {focus_given && focus_pixel_given, "--dof focuses at --focus DISTANCE or at --focus-pixel X,Y, not at both"},
+        {dof && many, "--dof runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {dof && preview_only, "--preview-only skips the full render: it does not combine with --dof"},
         {(flip_map || flip_ppd_given) && flip_ref.empty(), "--flip-map and --flip-ppd require --flip REF.pfm"},
         {mattes && many,
          "--alpha, --matte and --background run on one GPU: they do not combine with --gpus > 1, --virtual-strips or --force-rccl"},
@@ -406,7 +461,32 @@ int main(int argc, char* argv[]) {
     if (!compare_ref.empty() && !read_reference("--compare", compare_ref, st, reference)) return 1;
     if (!flip_ref.empty() && !read_reference("--flip", flip_ref, st, flip_reference)) return 1;
     // a later stage takes the float frame of the last one
-    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background;
+    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof;
+    if (dof) {  // the focus, known before anything is rendered: --focus, what --focus-pixel shows, else the camera's target
+        if (focus_pixel_given) {
+            if (focus_x >= st.width || focus_y >= st.height) {
+                std::fprintf(stderr, "--focus-pixel %d,%d is outside the %d x %d frame\n", focus_x, focus_y, st.width, st.height);
+                return 2;
+            }
+            std::string ferr;
+            rc = rtm_node_depth_at(&st, spheres.data(), n, &opt, focus_x, focus_y, &dof_prm.focus_distance, ferr);
+            if (rc != RTM_OK) return fail("focus-pixel", rc, ferr);
+            if (!(std::isfinite(dof_prm.focus_distance) && dof_prm.focus_distance > 0.0f)) {
+                std::fprintf(stderr, "--focus-pixel %d,%d is a miss: its primary ray hits nothing\n", focus_x, focus_y);
+                return 2;
+            }
+        } else if (!focus_given) {
+            double d2 = 0.0;
+            for (int k = 0; k < 3; ++k) d2 += (st.camera.target[k] - st.camera.origin[k]) * (st.camera.target[k] - st.camera.origin[k]);
+            dof_prm.focus_distance = (float)std::sqrt(d2);
+            if (!(std::isfinite(dof_prm.focus_distance) && dof_prm.focus_distance > 0.0f)) {
+                std::fprintf(stderr, "--dof: the camera's target is its origin, there is no target distance: give --focus DISTANCE\n");
+                return 2;
+            }
+        }
+        std::printf("dof: focus %.6g, aperture %.6g, max radius %d\n", (double)dof_prm.focus_distance, (double)dof_prm.aperture,
+                    dof_prm.max_radius);
+    }
     if (bloom)
         std::printf("bloom: threshold %.6g, knee %.6g, intensity %.6g, scatter %.6g, levels %d\n", (double)bloom_prm.threshold,
                     (double)bloom_prm.knee, (double)bloom_prm.intensity, (double)bloom_prm.scatter, bloom_prm.levels);
@@ -515,6 +595,12 @@ int main(int argc, char* argv[]) {
         if (rc != RTM_OK) return fail("denoise-variance", rc, err);
         std::printf("denoise-variance: %s_denoised_var.bmp, %s_denoised_var.jpg, %s_variance.pfm\n", stem.c_str(), stem.c_str(),
                     stem.c_str());
+    }
+    if (dof) {  // of the last stage so far; its frame then is the last stage's
+        std::vector<float> defocused;
+        rc = rtm_node_write_dof(&st, spheres.data(), n, &opt, &dof_prm, shown.empty() ? rgb32.data() : shown.data(), stem, err, &defocused);
+        if (rc != RTM_OK) return fail("dof", rc, err);
+        shown.swap(defocused);
     }
     const float* last = shown.empty() ? rgb32.data() : shown.data();
     std::vector<float> displayed;  // the display transform's float frame, when --display-pfm or --flip follows --display

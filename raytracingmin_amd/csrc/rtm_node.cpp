@@ -654,6 +654,54 @@ int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* p
     return RTM_OK;
 }
 
+// --dof (rtm_node.h): the depth plane and rtm_defocus of the frame behind it on the default stream, then the two files.
+int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
+                       const rtm_defocus_params* prm, const float* f32_host, const std::string& stem, std::string& err,
+                       std::vector<float>* f32_out) {
+    const int w = st->width, h = st->height;
+    const size_t pix = (size_t)w * h;
+    std::vector<uint8_t> rgb8(pix * 3);
+    {  // the device's part; what it holds is released before the files are written
+        Scene scene;
+        if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
+        DevBuf<float> color, depth, out32;
+        DevBuf<uint8_t> out8;
+        if (!color.alloc(pix * 3) || !depth.alloc(pix) || !out32.alloc(pix * 3) || !out8.alloc(pix * 3))
+            return fail(err, RTM_ERR_HIP, "no device memory for the depth of field's buffers");
+        if (!color.upload(f32_host, pix * 3)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+        const rtm_aov_buffers dev = {depth.get(), nullptr, nullptr, nullptr};
+        int rc = rtm_render_aov(st, scene.get(), opt, &dev, nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        rc = rtm_defocus(prm, w, h, opt->device, color.get(), depth.get(), out32.get(), out8.get(), nullptr, nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, pix * 3), pix * 3))
+            return fail(err, RTM_ERR_HIP, "copying the defocused frame back failed");
+    }
+    if (!write_jpg_bmp(stem + "_dof", st, rgb8.data())) return fail(err, RTM_ERR_IO, "cannot write the depth of field files of " + stem);
+    return RTM_OK;
+}
+
+// --focus-pixel (rtm_node.h): the depth plane of the pixel's row alone
+int rtm_node_depth_at(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int x, int y,
+                      float* depth_out, std::string& err) {
+    if (x < 0 || x >= st->width || y < 0 || y >= st->height)
+        return fail(err, RTM_ERR_INVALID_ARGUMENT, "the pixel is outside the frame");
+    Scene scene;
+    if (const int rc = open_scene(objects, n, opt->device, scene, err); rc != RTM_OK) return rc;
+    DevBuf<float> depth;
+    if (!depth.alloc((size_t)st->width)) return fail(err, RTM_ERR_HIP, "no device memory for a row of the depth plane");
+    rtm_options row = *opt;
+    row.row_begin = y;
+    row.row_end = y + 1;
+    const rtm_aov_buffers dev = {depth.get(), nullptr, nullptr, nullptr};
+    const int rc = rtm_render_aov(st, scene.get(), &row, &dev, nullptr);
+    if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+    std::vector<float> host((size_t)st->width);
+    if (!depth.download(host.data(), host.size())) return fail(err, RTM_ERR_HIP, "copying the depth row back failed");
+    *depth_out = host[(size_t)x];
+    return RTM_OK;
+}
+
 namespace {
 // --compare and --flip: the two frames up, the work buffer, `call` on the default stream, the record back and, when
 // map_out is given, the height x width plane back.  `what` names the stage in the messages.  A work size of SIZE_MAX

@@ -60,6 +60,15 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
 // follows.
 int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* params, const float* f32_host,
                    std::vector<float>* f32_out, std::string& err);
+// Depth of field (rtm_defocus, rtm_cli --dof) of a float frame (HOST, height x width x 3) on device opt->device: the frame's depth
+// plane (rtm_render_aov), one rtm_defocus call behind it on the default stream, then <stem>_dof.bmp and <stem>_dof.jpg
+// (quality 60); the defocused float frame comes back in f32_out, for the stages that follow.
+int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
+                       const rtm_defocus_params* params, const float* f32_host, const std::string& stem, std::string& err,
+                       std::vector<float>* f32_out);
+// The depth AOV at pixel (x, y) of the frame, which must lie inside it (rtm_cli --focus-pixel): +inf on a miss.
+int rtm_node_depth_at(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int x, int y,
+                      float* depth, std::string& err);
 // Two float frames (HOST, height x width x 3; `frame` under test, `reference`) compared on device `device` (rtm_compare at its
 // default parameters, rtm_cli --compare): both are copied to the device, one call on the default stream, the record copied back.
 int rtm_node_compare(const rtm_settings* st, int device, const float* frame_host, const float* reference_host,

@@ -557,7 +557,8 @@ class Renderer:
         self.stats = s.as_dict()
         return out, self.stats
 
-    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False):
+    def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False,
+               dof=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -574,6 +575,12 @@ class Renderer:
         bloom=True (or a dict of bloom()'s parameters: threshold, knee, intensity, scatter, levels) blooms every frame the
         display transform is given (write_display's bloom), so the _display, _over_display and _preview_display files are
         those of the bloomed last stage.  It needs tonemap: linear HDR through the reference's quantiser would only clip.
+        dof=None or False: no depth of field.  dof=True (or a dict of focus_distance or focus_pixel, aperture, max_radius:
+        write_dof's parameters) also writes
+        <fileName>_dof.bmp and <fileName>_dof.jpg (q=60): the last stage asked for (variance-denoised, denoised, else the
+        frame) defocused by the frame's depth plane, with the focus at the camera's target distance unless the dict says
+        otherwise.  The defocused frame then is the last stage: with tonemap, bloom and the display transform take it (bloom
+        is lens glare, so it comes after the lens), and so does mattes' background.
         preview=F also writes <fileName>_preview.bmp and <fileName>_preview.jpg (q=60): the frame traced at 1 / F of the
         resolution in each axis, denoised there and upsampled by the AOVs (write_preview); with tonemap, the display transform
         of the preview as well, as <fileName>_preview_display.bmp / .jpg.  F must divide the width and the height.
@@ -607,6 +614,9 @@ class Renderer:
             if unknown:
                 raise ValueError(f"tonemap's parameters are {tuple(TONEMAP_DEFAULTS)}, got {sorted(unknown)}")
             _tonemap_params(**display)  # a bad parameter raises here, before anything is rendered
+        dof_prm = _dof_option(dof, self.data.width, self.data.height)
+        if dof_prm is not None and dof_prm.get("focus_distance") is None:  # a miss raises here, before anything is rendered
+            dof_prm["focus_distance"] = self.focus_distance(dof_prm.pop("focus_pixel", None))
         bloom_prm = _bloom_option(bloom)
         if bloom_prm is not None:
             if display is None:
@@ -642,11 +652,13 @@ class Renderer:
         if aov:
             self.write_aov(fileName)
         frame = None  # the f32 frame the display stage shows, when it is not self.image
-        keep = display is not None or (matte_prm is not None and matte_prm.get("background") is not None)
+        keep = display is not None or (matte_prm is not None and matte_prm.get("background") is not None) or dof_prm is not None
         if denoise == "variance":
             frame = self.write_denoised_variance(fileName, _keep=keep)
         elif denoise:
             frame = self.write_denoised(fileName, _keep=keep)
+        if dof_prm is not None:
+            frame = self.write_dof(fileName, frame=frame, **dof_prm)
         if display is not None:
             self.write_display(fileName, frame=frame, **display)
         if matte_prm is not None:
@@ -681,6 +693,48 @@ class Renderer:
         if not (ok_j and ok_b):
             raise _lib.RtmError(-3, f"could not write {fileName}_display.jpg/.bmp")
         return rgb8
+
+    def focus_distance(self, pixel=None):
+        """A focus distance for defocus(), in the depth plane's units.  Without a pixel: |camera.target - camera.origin|,
+        computed in double and rounded to float — the look-at point is in focus (no device use).  pixel=(x, y): the depth AOV
+        at that pixel, what the primary ray through it hits first; a pixel outside the frame or one whose ray misses is a
+        ValueError."""
+        if pixel is None:
+            cam = self.data.camera
+            zf = float(np.float32(np.sqrt(sum((float(t) - float(o)) ** 2 for t, o in zip(cam.target, cam.origin)))))
+            if not (np.isfinite(zf) and zf > 0.0):
+                raise ValueError("the camera's target is its origin (or out of float's range): there is no target distance")
+            return zf
+        x, y = _focus_pixel(pixel, self.data.width, self.data.height)
+        z = float(self.render_aov(y, y + 1, want=("depth",))["depth"][0, x].item())
+        if not (np.isfinite(z) and z > 0.0):
+            raise ValueError(f"the focus pixel ({x}, {y}) is a miss: its primary ray hits nothing")
+        return z
+
+    def write_dof(self, fileName, frame=None, focus_distance=None, focus_pixel=None, aperture=_lib.DEFOCUS_DEFAULTS["aperture"],
+                  max_radius=_lib.DEFOCUS_DEFAULTS["max_radius"]):
+        """<fileName>_dof.bmp and <fileName>_dof.jpg (q=60): defocus() of `frame`, an (H, W, 3) float32 CUDA tensor, or of
+        self.image rounded to float like out_f32, by the frame's depth AOV — what rtm_cli --dof writes.  The focus is
+        focus_distance, else the depth at focus_pixel=(x, y), else the camera's target distance (Renderer.focus_distance).
+        Returns the defocused float32 frame on the device."""
+        import torch
+        if focus_distance is not None and focus_pixel is not None:
+            raise ValueError("write_dof takes focus_distance or focus_pixel, not both")
+        zf = self.focus_distance(focus_pixel) if focus_distance is None else focus_distance
+        _defocus_params(zf, aperture, max_radius)
+        if frame is None:
+            dev = torch.device("cuda", self.device)
+            frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        depth = self.render_aov(want=("depth",))["depth"]
+        out = defocus(frame, depth, zf, aperture, max_radius, want=("f32", "u8"))
+        rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
+        L = _lib.lib()
+        H, W = self.data.height, self.data.width
+        ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_dof.jpg"), W, H, 3, rgb8.ctypes.data, 60)
+        ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_dof.bmp"), W, H, 3, rgb8.ctypes.data)
+        if not (ok_j and ok_b):
+            raise _lib.RtmError(-3, f"could not write {fileName}_dof.jpg/.bmp")
+        return out["f32"]
 
     def write_denoised(self, fileName, _keep=False):
         """<fileName>_denoised.jpg (q=60) and <fileName>_denoised.bmp: self.image (the frame just rendered) rounded to float
@@ -1144,6 +1198,88 @@ def bloom(color, threshold=BLOOM_DEFAULTS["threshold"], knee=BLOOM_DEFAULTS["kne
 
 
 _bloom = bloom  # for Renderer's methods, whose own parameter is named bloom
+
+
+# include/rtm.h: RTM_DEFOCUS_DEFAULTS (focus_distance has no default: the caller sets it)
+DEFOCUS_DEFAULTS = dict(_lib.DEFOCUS_DEFAULTS)
+
+
+def _defocus_params(focus_distance, aperture=DEFOCUS_DEFAULTS["aperture"], max_radius=DEFOCUS_DEFAULTS["max_radius"]):
+    """defocus()'s parameters as an rtm_defocus_params; a ValueError names what the library would refuse.  No device use."""
+    if isinstance(max_radius, bool) or not isinstance(max_radius, (int, np.integer)) or not 1 <= int(max_radius) <= 16:
+        raise ValueError(f"max_radius is an integer in 1..16, got {max_radius!r}")
+    for name, v in (("focus_distance", focus_distance), ("aperture", aperture)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not np.isfinite(float(v)):
+            raise ValueError(f"{name} is a finite number, got {v!r}")
+    # as the library sees them: rounded to float
+    with np.errstate(over="ignore", under="ignore"):
+        zf, a = float(np.float32(focus_distance)), float(np.float32(aperture))
+    if not (np.isfinite(zf) and zf > 0.0):
+        raise ValueError(f"focus_distance is positive (and finite as a float), got {focus_distance!r}")
+    if not (np.isfinite(a) and a >= 0.0):
+        raise ValueError(f"aperture is non-negative (and finite as a float), got {aperture!r}")
+    return _lib.rtm_defocus_params(zf, a, int(max_radius))
+
+
+_DOF_KEYS = ("focus_distance", "focus_pixel", "aperture", "max_radius")
+
+
+def _focus_pixel(pixel, width, height):
+    """(x, y) of a focus pixel inside the width x height frame, or a ValueError.  No device use."""
+    ok = isinstance(pixel, (tuple, list)) and len(pixel) == 2 and all(
+        isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in pixel)
+    if not ok or not (0 <= int(pixel[0]) < width and 0 <= int(pixel[1]) < height):
+        raise ValueError(f"the focus pixel is (x, y), integers inside the {width}x{height} frame, got {pixel!r}")
+    return int(pixel[0]), int(pixel[1])
+
+
+def _dof_option(dof, width, height):
+    """Render's `dof`: None (or False, like Render's other stage arguments) for off, else the dict of its parameters (a
+    subset of _DOF_KEYS), checked as far as that needs no device: the focus distance of a focus_pixel is read from the depth plane later."""
+    if dof is None or dof is False:
+        return None
+    if dof is not True and not isinstance(dof, dict):
+        raise ValueError(f"dof is None, False, True or a dict of {_DOF_KEYS}, got {dof!r}")
+    prm = {} if dof is True else dict(dof)
+    unknown = set(prm) - set(_DOF_KEYS)
+    if unknown:
+        raise ValueError(f"dof's parameters are {_DOF_KEYS}, got {sorted(unknown)}")
+    if prm.get("focus_distance") is not None and prm.get("focus_pixel") is not None:
+        raise ValueError("dof takes focus_distance or focus_pixel, not both")
+    if prm.get("focus_pixel") is not None:
+        prm["focus_pixel"] = _focus_pixel(prm["focus_pixel"], width, height)
+    lens = {k: prm[k] for k in ("aperture", "max_radius") if k in prm}
+    _defocus_params(1.0 if prm.get("focus_distance") is None else prm["focus_distance"], **lens)
+    return prm
+
+
+def defocus(color, depth, focus_distance, aperture=DEFOCUS_DEFAULTS["aperture"], max_radius=DEFOCUS_DEFAULTS["max_radius"],
+            want=("f32",), stream=None):
+    """Depth of field (include/rtm.h: rtm_defocus) on the device: a depth-aware gather blur of a finished frame whose
+    per-pixel circle of confusion follows the thin-lens law; run it after the denoisers and before bloom() and tonemap().
+    `color` is an (H, W, 3) float32 torch CUDA tensor (any 4-byte-aligned contiguous view), `depth` the (H, W) float32 plane
+    of Renderer.render_aov on the same device.  focus_distance: the depth that is sharp (Renderer.focus_distance gives the
+    camera's, or a pixel's); aperture: the blur radius, in pixels, of a point at infinity (0: the identity); max_radius 1..16:
+    the clamp of every radius, and the half-width of the window.  Returns a dict of the names in `want`: "f32" (H, W, 3)
+    float32, "u8" (H, W, 3) uint8 (rtm_quantise of it), "coc" (H, W) float32 (the signed radius: negative in front of the
+    focus).  The outputs are tensors of the call's own: a gather cannot run in place.  Enqueued on `stream` (a
+    torch.cuda.Stream or a raw hipStream_t handle; default: the current stream); nothing waits for it and nothing is copied
+    to the host."""
+    prm = _defocus_params(focus_distance, aperture, max_radius)
+    _check_want(want, ("f32", "u8", "coc"))
+    import torch
+    _need_device("defocus")
+    H, W = _frame_size(color, "color", non_empty=True)
+    dev = color.device
+    if not (isinstance(depth, torch.Tensor) and depth.device == dev and depth.dtype == torch.float32
+            and tuple(depth.shape) == (H, W) and depth.is_contiguous()):
+        raise ValueError(f"depth must be a contiguous ({H}, {W}) float32 tensor on {dev}")
+    s = _stream_of(stream, dev)
+    specs = {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8), "coc": ((H, W), torch.float32)}
+    out, ptr = _stage_tensors(s, dev, want, specs)
+    _lib.check(_lib.lib().rtm_defocus(C.byref(prm), W, H, dev.index, color.data_ptr(), depth.data_ptr(), ptr("f32"), ptr("u8"),
+                                      ptr("coc"), C.c_void_p(s.cuda_stream)), "rtm_defocus")
+    return out
 
 
 def tonemap_stats(words):
