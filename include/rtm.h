@@ -695,6 +695,68 @@ typedef struct rtm_defocus_params { /* 12 bytes */
 int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream);
 
+/* ---- resize: a frame or a single-channel plane brought to another size by a separable filter — thumbnails, a 4K trace
+ * filtered down to 1080p, a plane (alpha, matte, variance, spp map) brought beside a frame of another size.  Opt-in, after
+ * rtm_defocus and before rtm_bloom and rtm_tonemap, in linear light: every other stage and its defaults stay.  It is for
+ * radiance-like and coverage-like planes: depth, object ids and normals must not be averaged.
+ * Input: src (DEVICE, h x w x C floats, C = channels in {1, 3}, interleaved like out_f32; 4-byte alignment is enough).
+ * Output: H x W x C.  Any W, H >= 1; the axes are independent (an enlargement in x with a reduction in y is legal).
+ *   1 kernels    k(t) with half-width r.  BOX: r = 1/2, k = 1 on -1/2 < t <= 1/2.  TRIANGLE: r = 1, k = max(0, 1 - |t|).
+ *                MITCHELL (B = C = 1/3): r = 2, k = (7|t|^3 - 12|t|^2 + 16/3) / 6 for |t| < 1 and
+ *                (-7/3 |t|^3 + 12|t|^2 - 20|t| + 32/3) / 6 for 1 <= |t| < 2.  LANCZOS3: r = 3, k(0) = 1, otherwise
+ *                k = sinc(pi t) sinc(pi t / 3) for |t| < 3, sinc(x) = sin x / x.  Every kernel is 0 outside its support.
+ *   2 taps       per axis, all positions in integers.  n is the source length, N the destination length, M = max(n, N),
+ *                q = 2r in {1, 2, 4, 6}.  When reducing, the kernel is stretched by M / N (the antialiasing); when enlarging
+ *                it is not.  T = ceil(q M / N) taps per destination index.  For destination index X:
+ *                b = (2X + 1) n - N (the centre is u = b / 2N in source pixel coordinates: (X + 1/2) n/N = u + 1/2);
+ *                j0 = floor((b - q M) / (2N)) + 1, floor toward minus infinity; tap i = 0..T-1 is source index j = j0 + i;
+ *                a = 2N j - b in 64-bit integers; t = a / (2M), one double division.  BOX is decided in integers: k = 1
+ *                iff -M < a <= M.  These T taps are exactly the integers in (u - rM/N, u + rM/N], and the raw weights of
+ *                every X have a positive sum.
+ *   3 tables     w^[X][i] = k(t_i) / (sum over all T taps, in the frame or not, of k(t)), evaluated in double and rounded
+ *                to float, by a device kernel (its double sin) into the work buffer.
+ *   4 counting   a source pixel COUNTS iff all its C components are finite: m = 1, else m = 0.  A pixel that does not
+ *                count contributes nothing (it is selected out, not multiplied by zero); a tap outside the frame is skipped.
+ *   5 horizontal arithmetic in float, without contraction, taps ascending: for every source row y and destination column
+ *                X the record (sum_i w^x[X][i] m c_k for each channel k, sum_i w^x[X][i] m): 16 bytes for C = 3, 8 for C = 1.
+ *   6 vertical   Nk = sum_i w^y[Y][i] rec_k(j0y + i, X), taps ascending, and D likewise from the records' last field, over
+ *                the rows inside the frame.  out_k = Nk / D when D >= 0.0625f; otherwise every channel of the pixel is a
+ *                quiet NaN: resize does not repair, and rtm_tonemap downstream still sees the pixel as not counting.  This
+ *                is skip-and-renormalise written as a normalised convolution, which keeps it separable around holes.  A
+ *                frame whose pixels all count never meets the threshold (every per-axis sum is above 0.5).
+ *   7 outputs    out_u8 (nullable) is rtm_quantise of (double)out_f32, out of range (NaN included) -> 0, as in the other
+ *                stages.  MITCHELL and LANCZOS3 have negative lobes: an output may undershoot 0 next to a bright edge (or
+ *                overshoot); nothing here clamps, the stages downstream (rtm_tonemap, rtm_quantise) already do.
+ * It follows that W = w, H = h with BOX or TRIANGLE returns every counting pixel == its input (the tables are exactly
+ * {0, 1}; MITCHELL at equal size is a blur by design, LANCZOS3 the input within the tolerance); that a constant frame stays
+ * that constant at any size pair and filter, also around holes wherever D >= 1/16; and that BOX at w = fW, h = fH is the
+ * mean of each f x f block.
+ * The divisions may be the device's fast forms: against a float64 evaluation with the float-rounded tables every out_f32
+ * component is within 1e-4 max(1, |ref|); where the output is NaN is exact for inputs whose reference D stays 1e-3 away
+ * from 1/16; out_u8 is exact given the call's own out_f32.  No atomics: the same inputs give the same bits on every call,
+ * on any stream, at any 4-byte alignment of src and out_f32.
+ * work_dev (DEVICE, 256-byte aligned) holds rtm_resize_work_bytes = round256(rec W h) + round256(4 W Tx) + round256(4 H Ty)
+ * + round256(4 (W + H)) bytes: the records (rec = 16 for C = 3, 8 for C = 1), the two tables and the two j0 arrays.  It
+ * returns 0 for a non-positive size or a filter or channels out of range, SIZE_MAX when a term or the sum does not fit a
+ * size_t.  The call allocates nothing, keeps no per-(device, stream) state, needs no serialisation and only ENQUEUES three
+ * launches on `stream` of `device`: tables, horizontal, vertical.
+ * Null params, src_dev or work_dev, both outputs null, a non-positive size, filter outside 0..3, channels not 1 or 3, a
+ * float pointer that is not 4-byte aligned, a work_dev that is not 256-byte aligned or equal to any other buffer,
+ * out_f32_dev or out_u8_dev equal to src_dev (a gather cannot run in place), a negative device: RTM_ERR_INVALID_ARGUMENT,
+ * before any device call.  w h, W H or W h (the intermediate) of 2^31 or more: RTM_ERR_UNSUPPORTED, as rtm_tonemap; so is
+ * an axis with q max(n, N) of 2^31 or more (a side of 3.5e8 pixels for LANCZOS3), whose first tap or tap count would leave 32 bits.
+ * Defaults: RTM_RESIZE_DEFAULTS below.  Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+enum { RTM_RESIZE_BOX = 0, RTM_RESIZE_TRIANGLE = 1, RTM_RESIZE_MITCHELL = 2, RTM_RESIZE_LANCZOS3 = 3 };
+typedef struct rtm_resize_params { /* 8 bytes */
+    int32_t filter;   /* RTM_RESIZE_*                                                                                     */
+    int32_t channels; /* C: 1 (a plane) or 3 (a frame)                                                                    */
+} rtm_resize_params;
+#define RTM_RESIZE_DEFAULTS {RTM_RESIZE_MITCHELL, 3}
+size_t rtm_resize_work_bytes(int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height, int32_t filter,
+                             int32_t channels);
+int rtm_resize(const rtm_resize_params* params, int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height,
+               int device, const float* src_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
+
 /* ---- AOV-guided upsampling: a frame traced at 1/f of the resolution in each axis, brought to full size by a joint
  * bilateral upsample (Kopf et al. 2007) steered by the full-resolution first-hit planes, with the albedo demodulated so that
  * material colour comes back at full resolution.  The AOVs have no random draws and cost one cheap kernel at any size; the

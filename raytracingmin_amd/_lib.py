@@ -117,6 +117,14 @@ class rtm_defocus_params(C.Structure):  # include/rtm.h: rtm_defocus (12 bytes)
 
 DEFOCUS_DEFAULTS = {"aperture": 4.0, "max_radius": 8}  # RTM_DEFOCUS_DEFAULTS; the caller sets focus_distance
 
+
+class rtm_resize_params(C.Structure):  # include/rtm.h: rtm_resize (8 bytes)
+    _fields_ = [("filter", C.c_int32), ("channels", C.c_int32)]
+
+
+RESIZE_FILTERS = ("box", "triangle", "mitchell", "lanczos3")  # RTM_RESIZE_BOX .. RTM_RESIZE_LANCZOS3, in the enum's order
+RESIZE_DEFAULTS = {"filter": "mitchell"}  # RTM_RESIZE_DEFAULTS; channels follows the tensor
+
 COMPARE_DTYPES = {"float32": 0, "float64": 1}  # include/rtm.h: RTM_COMPARE_F32, RTM_COMPARE_F64
 COMPARE_MAPS = {"abs": 0, "ssim": 1}  # RTM_COMPARE_MAP_*
 
@@ -190,6 +198,9 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_defocus": (C.c_int, [_P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_resize_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rtm_resize": (C.c_int, [_P(rtm_resize_params), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p,
+                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_upsample_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_upsample": (C.c_int, [_P(rtm_upsample_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, _P(rtm_aov_buffers),
                                _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -138,6 +138,15 @@ int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height,
                 const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream) {
     RTM_GUARD(rtm::defocus(params, width, height, device, color_dev, depth_dev, out_f32_dev, out_u8_dev, coc_out_dev, stream))
 }
+size_t rtm_resize_work_bytes(int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height, int32_t filter,
+                             int32_t channels) {
+    return rtm::resize_work_bytes(src_width, src_height, dst_width, dst_height, filter, channels);
+}
+int rtm_resize(const rtm_resize_params* params, int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height,
+               int device, const float* src_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
+    RTM_GUARD(rtm::resize(params, src_width, src_height, dst_width, dst_height, device, src_dev, work_dev, out_f32_dev, out_u8_dev,
+                          stream))
+}
 size_t rtm_upsample_work_bytes(int32_t low_width, int32_t low_height) { return rtm::upsample_work_bytes(low_width, low_height); }
 int rtm_upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device,
                  const float* color_low_dev, const rtm_aov_buffers* guide_low_dev, const rtm_aov_buffers* guide_high_dev,

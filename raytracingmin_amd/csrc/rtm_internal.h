@@ -83,6 +83,11 @@ int defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int
             float* out32, uint8_t* out8, float* coc_out, void* stream);
 int defocus_form_probe(int form, const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color,
                        const float* depth, float* out32, uint8_t* out8, float* coc_out, void* stream);
+// filtered resampling (rtm_resize.hip)
+size_t resize_work_bytes(int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height, int32_t filter,
+                         int32_t channels);
+int resize(const rtm_resize_params* params, int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height, int device,
+           const float* src, void* work, float* out32, uint8_t* out8, void* stream);
 // AOV-guided upsampling (rtm_upsample.hip)
 size_t upsample_work_bytes(int32_t low_width, int32_t low_height);
 int upsample(const rtm_upsample_params* params, int32_t low_width, int32_t low_height, int device, const float* color_low,

@@ -17,6 +17,9 @@
 //           [--dof [APERTURE]] [--focus DISTANCE | --focus-pixel X,Y] [--dof-radius R]
 //                                                (depth of field of the last stage by the depth plane: STEM_dof.bmp, .jpg; the
 //                                                defocused frame then is the last stage's for what follows)
+//           [--resize WxH [--resize-filter box|triangle|mitchell|lanczos3]]
+//                                                (the last stage's float frame resized on the device: STEM_resized.bmp, .jpg; the
+//                                                resized frame then is the last stage's for --display, --pfm, --display-pfm)
 //           [--preview F [--preview-only]]       (the frame traced at 1/F of the resolution per axis, denoised there and upsampled
 //                                                by the first-hit feature buffers: STEM_preview.bmp, .jpg; -only: no full render)
 //           [--pfm]                              (the float frame of the last stage: STEM.pfm)
@@ -128,6 +131,11 @@ static void usage() {
         "            8); the focus is at the camera's target distance, at --focus DISTANCE, or at what pixel X,Y shows.  The\n"
         "            defocused frame then is the frame of the last stage for --pfm, --compare, --flip, --background and --display\n"
         "            (with --bloom: the glare of the defocused frame)\n"
+        "--resize WxH [--resize-filter box|triangle|mitchell|lanczos3] : also write the last stage asked for (render, denoiser or\n"
+        "            --dof) resized to W x H on one GPU (rtm_resize, in linear light; default filter mitchell; antialiased when it\n"
+        "            shrinks): STEM_resized.bmp and STEM_resized.jpg.  The resized frame then is the frame of the last stage for\n"
+        "            --display (with --bloom), --pfm and --display-pfm; it does not combine with --compare, --flip, --alpha, --matte\n"
+        "            or --background, which work at the render's size\n"
         "--preview F [--preview-only] : also write a fast preview on one GPU: the scene traced at width / F x height / F (F in\n"
         "            2..8, dividing both; F^2 fewer paths), denoised there (rtm_denoise at its defaults) and brought to full size\n"
         "            by rtm_upsample, guided by the first-hit feature buffers at both resolutions: STEM_preview.bmp and\n"
@@ -176,6 +184,8 @@ int main(int argc, char* argv[]) {
     rtm_bloom_params bloom_prm = RTM_BLOOM_DEFAULTS;
     int dof = 0, focus_given = 0, focus_pixel_given = 0, dof_radius_given = 0, focus_x = 0, focus_y = 0;
     rtm_defocus_params dof_prm = RTM_DEFOCUS_DEFAULTS;
+    int resize = 0, resize_filter_given = 0, resize_w = 0, resize_h = 0;
+    rtm_resize_params resize_prm = RTM_RESIZE_DEFAULTS;
     int pfm = 0;
     std::string dump_f32, compare_ref, flip_ref;
     int display_pfm = 0, flip_map = 0, flip_ppd_given = 0;
@@ -306,6 +316,34 @@ int main(int argc, char* argv[]) {
             focus_x = (int)x;
             focus_y = (int)y;
         }
+        else if (c == "--resize") {
+            // WxH: two whole numbers from 1, all of the text
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            const size_t x = m.find('x');
+            double vw = 0.0, vh = 0.0;
+            const bool ok = x != std::string::npos && parse_number(m.substr(0, x), vw) && parse_number(m.substr(x + 1), vh) &&
+                            vw == std::floor(vw) && vh == std::floor(vh) && vw >= 1.0 && vh >= 1.0 && vw <= 2147483647.0 &&
+                            vh <= 2147483647.0;
+            if (!ok) {
+                std::fprintf(stderr, "--resize takes a size WxH, two whole numbers from 1, got %s\n", m.c_str());
+                return 2;
+            }
+            resize = 1;
+            resize_w = (int)vw;
+            resize_h = (int)vh;
+        } else if (c == "--resize-filter") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            static const char* const names[] = {"box", "triangle", "mitchell", "lanczos3"};  // RTM_RESIZE_*, in the enum's order
+            int which = -1;
+            for (int k = 0; k < 4; ++k)
+                if (m == names[k]) which = k;
+            if (which < 0) {
+                std::fprintf(stderr, "--resize-filter takes box, triangle, mitchell or lanczos3, got %s\n", m.c_str());
+                return 2;
+            }
+            resize_filter_given = 1;
+            resize_prm.filter = which;
+        }
         else if (c == "--pfm") pfm = 1;
         else if (c == "--compare" && i + 1 < argc) compare_ref = argv[++i];
         else if (c == "--display-pfm") display_pfm = 1;
@@ -400,6 +438,12 @@ int main(int argc, char* argv[]) {
         {focus_given && focus_pixel_given, "--dof focuses at --focus DISTANCE or at --focus-pixel X,Y, not at both"},
         {dof && many, "--dof runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
         {dof && preview_only, "--preview-only skips the full render: it does not combine with --dof"},
+        {resize_filter_given && !resize, "--resize-filter requires --resize WxH"},
+        {resize && many, "--resize runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {resize && preview_only, "--preview-only skips the full render: it does not combine with --resize"},
+        {resize && (!compare_ref.empty() || !flip_ref.empty()),
+         "--resize does not combine with --compare or --flip: their references are checked against the render's size"},
+        {resize && mattes, "--resize does not combine with --alpha, --matte or --background: the composite runs at the render's size"},
         {(flip_map || flip_ppd_given) && flip_ref.empty(), "--flip-map and --flip-ppd require --flip REF.pfm"},
         {mattes && many,
          "--alpha, --matte and --background run on one GPU: they do not combine with --gpus > 1, --virtual-strips or --force-rccl"},
@@ -461,7 +505,7 @@ int main(int argc, char* argv[]) {
     if (!compare_ref.empty() && !read_reference("--compare", compare_ref, st, reference)) return 1;
     if (!flip_ref.empty() && !read_reference("--flip", flip_ref, st, flip_reference)) return 1;
     // a later stage takes the float frame of the last one
-    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof;
+    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof || resize;
     if (dof) {  // the focus, known before anything is rendered: --focus, what --focus-pixel shows, else the camera's target
         if (focus_pixel_given) {
             if (focus_x >= st.width || focus_y >= st.height) {
@@ -492,17 +536,17 @@ int main(int argc, char* argv[]) {
                     (double)bloom_prm.knee, (double)bloom_prm.intensity, (double)bloom_prm.scatter, bloom_prm.levels);
     // --display of one frame: bloomed first with --bloom, then STEM<suffix>_display.bmp / .jpg and their line, which gives
     // the statistics for the frame itself (no suffix); the exit status, 0 when all went well
-    const auto show = [&](const float* frame, const std::string& suffix, std::vector<float>* f32_out) {
+    const auto show = [&](const rtm_settings& fs, const float* frame, const std::string& suffix, std::vector<float>* f32_out) {
         std::string err;
         std::vector<float> bloomed;
         if (bloom) {
-            const int brc = rtm_node_bloom(&st, opt.device, &bloom_prm, frame, &bloomed, err);
+            const int brc = rtm_node_bloom(&fs, opt.device, &bloom_prm, frame, &bloomed, err);
             if (brc != RTM_OK) return fail("bloom", brc, err);
             frame = bloomed.data();
         }
         rtm_tonemap_stats ts;
         const std::string name = stem + suffix;
-        const int drc = rtm_node_write_display(&st, opt.device, &display_prm, frame, name, &ts, err, f32_out);
+        const int drc = rtm_node_write_display(&fs, opt.device, &display_prm, frame, name, &ts, err, f32_out);
         if (drc != RTM_OK) return fail("display", drc, err);
         if (suffix.empty())
             std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",
@@ -519,7 +563,7 @@ int main(int argc, char* argv[]) {
         if (rc != RTM_OK) return fail("preview", rc, err);
         std::printf("preview: %s_preview.bmp, %s_preview.jpg (%d x %d traced, %llu samples, kernel %.3f ms)\n", stem.c_str(),
                     stem.c_str(), st.width / preview, st.height / preview, (unsigned long long)ps.samples, ps.kernel_ms);
-        if (display && show(shown.data(), "_preview", nullptr) != 0) return 1;
+        if (display && show(st, shown.data(), "_preview", nullptr) != 0) return 1;
         if (preview_only) {
             if (aov) {
                 rc = rtm_node_write_aov(&st, spheres.data(), n, &opt, stem, err);
@@ -602,18 +646,29 @@ int main(int argc, char* argv[]) {
         if (rc != RTM_OK) return fail("dof", rc, err);
         shown.swap(defocused);
     }
+    rtm_settings last_st = st;  // the last stage's size: the render's, unless --resize follows
+    if (resize) {  // of the last stage so far, in linear light; its frame then is the last stage's
+        std::vector<float> resized;
+        rc = rtm_node_write_resized(&st, opt.device, &resize_prm, resize_w, resize_h, shown.empty() ? rgb32.data() : shown.data(), stem,
+                                    err, &resized);
+        if (rc != RTM_OK) return fail("resize", rc, err);
+        shown.swap(resized);
+        last_st.width = resize_w;
+        last_st.height = resize_h;
+        std::printf("resize: %s_resized.bmp, %s_resized.jpg (%d x %d)\n", stem.c_str(), stem.c_str(), resize_w, resize_h);
+    }
     const float* last = shown.empty() ? rgb32.data() : shown.data();
     std::vector<float> displayed;  // the display transform's float frame, when --display-pfm or --flip follows --display
-    if (display && show(last, "", display_pfm || !flip_ref.empty() ? &displayed : nullptr) != 0) return 1;
+    if (display && show(last_st, last, "", display_pfm || !flip_ref.empty() ? &displayed : nullptr) != 0) return 1;
     if (display_pfm) {
-        if (rtm_write_pfm((stem + "_display.pfm").c_str(), st.width, st.height, 3, displayed.data()) != 1) {
+        if (rtm_write_pfm((stem + "_display.pfm").c_str(), last_st.width, last_st.height, 3, displayed.data()) != 1) {
             std::fprintf(stderr, "cannot write %s_display.pfm\n", stem.c_str());
             return 1;
         }
         std::printf("display-pfm: %s_display.pfm\n", stem.c_str());
     }
     if (pfm) {
-        if (rtm_write_pfm((stem + ".pfm").c_str(), st.width, st.height, 3, last) != 1) {
+        if (rtm_write_pfm((stem + ".pfm").c_str(), last_st.width, last_st.height, 3, last) != 1) {
             std::fprintf(stderr, "cannot write %s.pfm\n", stem.c_str());
             return 1;
         }
@@ -639,7 +694,7 @@ int main(int argc, char* argv[]) {
         if (!matte_ids.empty())
             std::printf("matte: %s_matte.pfm, %s_matte.bmp (%d ids, %d layers)\n", stem.c_str(), stem.c_str(), (int)matte_ids.size(), matte_layers);
         if (background) std::printf("background: %s_over.bmp, %s_over.jpg\n", stem.c_str(), stem.c_str());
-        if (background && display && show(over.data(), "_over", nullptr) != 0) return 1;
+        if (background && display && show(st, over.data(), "_over", nullptr) != 0) return 1;
     }
     if (!flip_ref.empty()) {
         rtm_flip_result fr;

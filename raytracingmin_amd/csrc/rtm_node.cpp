@@ -681,6 +681,36 @@ int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t
     return RTM_OK;
 }
 
+// --resize (rtm_node.h): rtm_resize of the frame on the default stream, then the two files at the new size.
+int rtm_node_write_resized(const rtm_settings* st, int device, const rtm_resize_params* prm, int dst_width, int dst_height,
+                           const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* f32_out) {
+    const size_t src_vals = (size_t)st->width * st->height * 3, dst_vals = (size_t)dst_width * dst_height * 3;
+    rtm_settings dst = *st;  // the size the files are written at
+    dst.width = dst_width;
+    dst.height = dst_height;
+    // known before anything is allocated: a size the library will refuse must not size a host vector first
+    const size_t work_bytes = rtm_resize_work_bytes(st->width, st->height, dst_width, dst_height, prm->filter, prm->channels);
+    if (prm->channels != 3 || work_bytes == 0 || work_bytes == SIZE_MAX || dst_vals / 3 > 0x7FFFFFFFu)
+        return fail(err, RTM_ERR_INVALID_ARGUMENT, "resize's sizes or filter are out of range");
+    std::vector<uint8_t> rgb8(dst_vals);
+    {  // the device's part; what it holds is released before the files are written
+        if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+        DevBuf<float> color, out32;
+        DevBuf<uint8_t> out8;
+        DevBuf<void> work;  // hipMalloc's alignment is 256 bytes or more, what rtm_resize asks of work_dev
+        if (!color.alloc(src_vals) || !out32.alloc(dst_vals) || !out8.alloc(dst_vals) || !work.alloc(work_bytes))
+            return fail(err, RTM_ERR_HIP, "no device memory for resize's buffers");
+        if (!color.upload(f32_host, src_vals)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+        const int rc = rtm_resize(prm, st->width, st->height, dst_width, dst_height, device, color.get(), work.get(), out32.get(),
+                                  out8.get(), nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, dst_vals), dst_vals))
+            return fail(err, RTM_ERR_HIP, "copying the resized frame back failed");
+    }
+    if (!write_jpg_bmp(stem + "_resized", &dst, rgb8.data())) return fail(err, RTM_ERR_IO, "cannot write the resized files of " + stem);
+    return RTM_OK;
+}
+
 // --focus-pixel (rtm_node.h): the depth plane of the pixel's row alone
 int rtm_node_depth_at(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int x, int y,
                       float* depth_out, std::string& err) {

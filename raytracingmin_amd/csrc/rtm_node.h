@@ -66,6 +66,11 @@ int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* p
 int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
                        const rtm_defocus_params* params, const float* f32_host, const std::string& stem, std::string& err,
                        std::vector<float>* f32_out);
+// Resize (rtm_resize, rtm_cli --resize) of a float frame (HOST, height x width x 3) on device `device` to dst_width x dst_height:
+// one rtm_resize call on the default stream, then <stem>_resized.bmp and <stem>_resized.jpg (quality 60) at the new size; the
+// resized float frame comes back in f32_out, for the stages that follow.
+int rtm_node_write_resized(const rtm_settings* st, int device, const rtm_resize_params* params, int dst_width, int dst_height,
+                           const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* f32_out);
 // The depth AOV at pixel (x, y) of the frame, which must lie inside it (rtm_cli --focus-pixel): +inf on a miss.
 int rtm_node_depth_at(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt, int x, int y,
                       float* depth, std::string& err);

@@ -558,7 +558,7 @@ class Renderer:
         return out, self.stats
 
     def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False,
-               dof=None):
+               dof=None, resize=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -581,6 +581,11 @@ class Renderer:
         frame) defocused by the frame's depth plane, with the focus at the camera's target distance unless the dict says
         otherwise.  The defocused frame then is the last stage: with tonemap, bloom and the display transform take it (bloom
         is lens glare, so it comes after the lens), and so does mattes' background.
+        resize=None: no resize.  resize=(W, H) or (W, H, filter) (width first, as rtm_cli --resize WxH; filter one of
+        RESIZE_FILTERS, default "mitchell") also writes <fileName>_resized.bmp and <fileName>_resized.jpg (q=60): the last
+        stage asked for (defocused, variance-denoised, denoised, else the frame) brought to W x H by resize() in linear light
+        (write_resized).  The resized frame then is the last stage for tonemap and bloom, whose _display files have its size.
+        It does not combine with mattes' background: the composite runs at the render's size.
         preview=F also writes <fileName>_preview.bmp and <fileName>_preview.jpg (q=60): the frame traced at 1 / F of the
         resolution in each axis, denoised there and upsampled by the AOVs (write_preview); with tonemap, the display transform
         of the preview as well, as <fileName>_preview_display.bmp / .jpg.  F must divide the width and the height.
@@ -617,6 +622,9 @@ class Renderer:
         dof_prm = _dof_option(dof, self.data.width, self.data.height)
         if dof_prm is not None and dof_prm.get("focus_distance") is None:  # a miss raises here, before anything is rendered
             dof_prm["focus_distance"] = self.focus_distance(dof_prm.pop("focus_pixel", None))
+        resize_prm = _resize_option(resize)
+        if resize_prm is not None and matte_prm is not None and matte_prm.get("background") is not None:
+            raise ValueError("resize does not combine with mattes' background: the composite runs at the render's size")
         bloom_prm = _bloom_option(bloom)
         if bloom_prm is not None:
             if display is None:
@@ -653,12 +661,15 @@ class Renderer:
             self.write_aov(fileName)
         frame = None  # the f32 frame the display stage shows, when it is not self.image
         keep = display is not None or (matte_prm is not None and matte_prm.get("background") is not None) or dof_prm is not None
+        keep = keep or resize_prm is not None
         if denoise == "variance":
             frame = self.write_denoised_variance(fileName, _keep=keep)
         elif denoise:
             frame = self.write_denoised(fileName, _keep=keep)
         if dof_prm is not None:
             frame = self.write_dof(fileName, frame=frame, **dof_prm)
+        if resize_prm is not None:
+            frame = self.write_resized(fileName, frame=frame, **resize_prm)
         if display is not None:
             self.write_display(fileName, frame=frame, **display)
         if matte_prm is not None:
@@ -687,7 +698,7 @@ class Renderer:
             frame = _bloom(frame, **bloom_prm)["f32"]
         rgb8 = np.ascontiguousarray(tonemap(frame, want=("u8",), **params)["u8"].cpu().numpy())
         L = _lib.lib()
-        H, W = self.data.height, self.data.width
+        H, W = rgb8.shape[:2]  # the frame's own size: the render's, unless it was resized
         ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_display.jpg"), W, H, 3, rgb8.ctypes.data, 60)
         ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_display.bmp"), W, H, 3, rgb8.ctypes.data)
         if not (ok_j and ok_b):
@@ -734,6 +745,25 @@ class Renderer:
         ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_dof.bmp"), W, H, 3, rgb8.ctypes.data)
         if not (ok_j and ok_b):
             raise _lib.RtmError(-3, f"could not write {fileName}_dof.jpg/.bmp")
+        return out["f32"]
+
+    def write_resized(self, fileName, size, frame=None, filter=_lib.RESIZE_DEFAULTS["filter"]):
+        """<fileName>_resized.bmp and <fileName>_resized.jpg (q=60): resize() of `frame`, an (h, w, 3) float32 CUDA tensor, or
+        of self.image rounded to float like out_f32, to size = (H, W) (height first, as resize()) — what rtm_cli --resize
+        writes.  Returns the resized float32 frame on the device."""
+        import torch
+        _resize_args(size, filter)
+        if frame is None:
+            dev = torch.device("cuda", self.device)
+            frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        out = resize(frame, size, filter, want=("f32", "u8"))
+        rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
+        L = _lib.lib()
+        H, W = rgb8.shape[:2]
+        ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_resized.jpg"), W, H, 3, rgb8.ctypes.data, 60)
+        ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_resized.bmp"), W, H, 3, rgb8.ctypes.data)
+        if not (ok_j and ok_b):
+            raise _lib.RtmError(-3, f"could not write {fileName}_resized.jpg/.bmp")
         return out["f32"]
 
     def write_denoised(self, fileName, _keep=False):
@@ -1279,6 +1309,72 @@ def defocus(color, depth, focus_distance, aperture=DEFOCUS_DEFAULTS["aperture"],
     out, ptr = _stage_tensors(s, dev, want, specs)
     _lib.check(_lib.lib().rtm_defocus(C.byref(prm), W, H, dev.index, color.data_ptr(), depth.data_ptr(), ptr("f32"), ptr("u8"),
                                       ptr("coc"), C.c_void_p(s.cuda_stream)), "rtm_defocus")
+    return out
+
+
+# include/rtm.h: RTM_RESIZE_DEFAULTS and the RTM_RESIZE_* filters, by name
+RESIZE_DEFAULTS = dict(_lib.RESIZE_DEFAULTS)
+RESIZE_FILTERS = _lib.RESIZE_FILTERS
+
+
+def _resize_args(size, filter=RESIZE_DEFAULTS["filter"]):
+    """resize()'s size and filter as (H, W, the RTM_RESIZE_* value); a ValueError names what the library would refuse.  No
+    device use."""
+    if not isinstance(filter, str) or filter not in RESIZE_FILTERS:
+        raise ValueError(f"filter is one of {RESIZE_FILTERS}, got {filter!r}")
+    ok = isinstance(size, (tuple, list)) and len(size) == 2 and all(
+        isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 1 <= int(v) <= 2147483647 for v in size)
+    if not ok:
+        raise ValueError(f"size is (H, W), two positive integers, got {size!r}")
+    return int(size[0]), int(size[1]), RESIZE_FILTERS.index(filter)
+
+
+def _resize_option(resize):
+    """Render's `resize`: None (or False, like Render's other stage arguments) for off, else (W, H) or (W, H, filter), checked,
+    as write_resized's parameters.  No device use."""
+    if resize is None or resize is False:
+        return None
+    if not isinstance(resize, (tuple, list)) or len(resize) not in (2, 3):
+        raise ValueError(f"resize is None, (W, H) or (W, H, filter), got {resize!r}")
+    prm = {"size": (resize[1], resize[0])}
+    if len(resize) == 3:
+        prm["filter"] = resize[2]
+    _resize_args(**prm)
+    return prm
+
+
+def resize(color, size, filter=RESIZE_DEFAULTS["filter"], want=("f32",), stream=None):
+    """Filtered resampling (include/rtm.h: rtm_resize) on the device: a frame or a plane brought to another size by a
+    separable filter, antialiased when it shrinks; run it in linear light, after defocus() and before bloom() and tonemap().
+    `color` is an (h, w, 3) float32 torch CUDA tensor or an (h, w) plane (any 4-byte-aligned contiguous view); size = (H, W),
+    any positive integers, the axes independent.  filter: one of RESIZE_FILTERS — "box" (the mean of what a destination pixel
+    covers), "triangle", "mitchell" (the default) or "lanczos3"; the last two have negative lobes and may undershoot 0 next to
+    a bright edge.  A pixel with a non-finite component contributes nothing; a destination pixel too few of whose taps count
+    is NaN.  Returns a dict of the names in `want`: "f32" float32 and "u8" uint8 (rtm_quantise of it), (H, W, 3) or (H, W).
+    The outputs are tensors of the call's own: a gather cannot run in place.  Enqueued on `stream` (a torch.cuda.Stream or a
+    raw hipStream_t handle; default: the current stream) with a work buffer allocated here; nothing waits for it and nothing
+    is copied to the host."""
+    H, W, which = _resize_args(size, filter)
+    _check_want(want, ("f32", "u8"))
+    import torch
+    _need_device("resize")
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
+            and color.numel() > 0 and (color.dim() == 2 or (color.dim() == 3 and color.shape[2] == 3))):
+        raise ValueError("color must be a contiguous, non-empty (h, w, 3) or (h, w) float32 CUDA tensor")
+    h, w = int(color.shape[0]), int(color.shape[1])
+    channels = 3 if color.dim() == 3 else 1
+    shape = (H, W, 3) if channels == 3 else (H, W)
+    dev = color.device
+    s = _stream_of(stream, dev)
+    L = _lib.lib()
+    prm = _lib.rtm_resize_params(which, channels)
+    work = L.rtm_resize_work_bytes(w, h, W, H, which, channels)
+    if work == C.c_size_t(-1).value:
+        raise ValueError(f"resizing {w}x{h} to {W}x{H} needs a work buffer larger than a size_t")
+    specs = {"f32": (shape, torch.float32), "u8": (shape, torch.uint8)}
+    out, ptr = _stage_tensors(s, dev, want, specs, max(256, work))
+    _lib.check(L.rtm_resize(C.byref(prm), w, h, W, H, dev.index, color.data_ptr(), ptr("work"), ptr("f32"), ptr("u8"),
+                            C.c_void_p(s.cuda_stream)), "rtm_resize")
     return out
 
 
