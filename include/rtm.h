@@ -695,6 +695,93 @@ typedef struct rtm_defocus_params { /* 12 bytes */
 int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream);
 
+/* ---- lens: radial distortion, lateral chromatic aberration and vignetting of a frame or a single-channel plane — a traced
+ * frame given the distortion of a plate's lens (DIRECT), a plate's distortion taken out (INVERSE), the AOV planes (depth,
+ * ids, mattes, alpha) warped consistently with the frame (NEAREST).  Opt-in, after rtm_defocus and before rtm_resize,
+ * rtm_bloom and rtm_tonemap, in linear light: every other stage and its defaults stay.  The one stage that resamples at
+ * per-pixel positions; input and output have the same size.
+ * Input: src (DEVICE, h x w x C floats, C = channels in {1, 3}, interleaved like out_f32; 4-byte alignment is enough).
+ *   1 positions  in double, in the order written, without contraction, so that a float64 restatement reproduces every
+ *                position bit for bit; k1, k2, zoom and chroma are widened from float first.  For destination pixel (X, Y):
+ *                cx = w / 2, cy = h / 2; dx = (X + 0.5) - cx, dy = (Y + 0.5) - cy; R2 = cx cx + cy cy; iz = 1.0 / zoom;
+ *                r2 = ((dx dx + dy dy) / R2) (iz iz), the squared radius normalised to the half diagonal, after the zoom.
+ *                DIRECT:  F = (1 + r2 (k1 + r2 k2)) iz.
+ *                INVERSE: r = sqrt(r2); rho solves rho g(rho^2) = r, g(t) = 1 + t (k1 + t k2), by exactly 12 Newton steps
+ *                from rho = r, each t = rho rho; rho = rho - (rho (1 + t (k1 + t k2)) - r) / (1 + t (3 k1 + t (5 k2)));
+ *                F = (r > 0 ? rho / r : 1.0) iz.
+ *                Channel c has m_c = 1 + chroma (1 - c) for C = 3 (R is scaled by 1 + chroma, G by 1, B by 1 - chroma) and
+ *                m = 1 for C = 1; F_c = F m_c; u = cx + dx F_c - 0.5, v = cy + dy F_c - 0.5: source pixel coordinates.
+ *                With the defaults F_c = 1.0 and u = X exactly.  DIRECT shows, at p, the source at p g(|p|^2); INVERSE the
+ *                source at D^-1(p): DIRECT and then INVERSE with the same k1, k2 (zoom 1, chroma 0) is the identity map.
+ *   2 border     a channel is INSIDE iff -0.5 <= u < w - 0.5 and -0.5 <= v < h - 0.5 (a NaN position is outside).  Otherwise
+ *                its output is border[c]'s word, bit for bit, and nothing else touches it (no vignette).
+ *   3 taps       a source pixel COUNTS iff all its C components are finite.  A tap outside the frame or one that does not
+ *                count is skipped, not clamped: the library's skip-and-renormalise rule.  fx = floor(u), t = u - fx, rows
+ *                alike.  BILINEAR: taps fx, fx + 1 with weights (1 - t, t).  BICUBIC (Catmull-Rom, which interpolates, so the
+ *                identity is exact): taps fx - 1 .. fx + 2 with w0 = (((2 - t) t - 1) t) / 2, w1 = (((3 t - 5) t) t + 2) / 2,
+ *                w2 = (((4 - 3 t) t + 1) t) / 2, w3 = (((t - 1) t) t) / 2.  The weights are evaluated in double and rounded
+ *                to float.  Then in float, without contraction, rows outer, columns inner, ascending: w = w^x_i w^y_j,
+ *                N = sum w c_q, D = sum w over the contributing taps; out = N / D when D >= 0.0625f, otherwise a quiet NaN:
+ *                the stage does not repair, and rtm_tonemap downstream still sees the pixel as not counting.  A frame whose
+ *                pixels all count never meets the threshold: every per-axis sum is 0.5 or more.
+ *   4 nearest    NEAREST copies the word of source pixel (floor(u + 0.5), floor(v + 0.5)) bit for bit, with no counting test
+ *                (an index that the rounding of u + 0.5 brings to w or h is w - 1 or h - 1): an int32 id plane viewed as
+ *                floats, a depth plane with +inf and a NaN all pass through.  border[] is not checked for finiteness with
+ *                NEAREST, so an id plane can take the word of -1.
+ *   5 vignette   after resampling, inside channels only, in float: rv = (float)((dx dx + dy dy) / R2) (the division in
+ *                double), q = 1 + (falloff falloff) rv, c4 = 1 / (q q), gain = 1 - vignette (1 - c4), out = out gain: the
+ *                cos^4 law of a lens whose half field angle at the frame's corner has the tangent `falloff`.  vignette = 0
+ *                gives gain = 1 exactly.  (NEAREST takes no vignette: it copies words.)
+ *   6 outputs    out_u8 (nullable) is rtm_quantise of (double)out_f32, out of range (NaN included) -> 0, as in the other
+ *                stages.
+ * It follows that the defaults, in either mode and with any filter, return every counting pixel == its input, and every
+ * word with NEAREST; and that a constant frame stays that constant at every inside pixel, within the tolerance, for any
+ * parameters with vignette = 0.
+ * The division N / D may be the device's fast form: against a float64 evaluation with the float-rounded weights every inside
+ * out_f32 component is within 1e-4 max(1, |ref|); NEAREST, which channels are inside and the border words are exact; where
+ * the output is NaN is exact for inputs whose reference D stays 1e-3 away from 1/16; out_u8 is exact given the call's own
+ * out_f32.  The call is stateless: no work buffer, no allocation, no per-(device, stream) state, no serialisation, no
+ * atomics; it only ENQUEUES one launch on `stream` of `device`, and the same inputs give the same bits on every call, on any
+ * stream, at any 4-byte alignment of src and out_f32.
+ * Null params or src_dev, both outputs null, a non-positive size, a parameter that is NaN, infinite or outside its range
+ * (|k1| <= 0.5, |k2| <= 0.25, zoom in [0.25, 4], chroma in [-0.05, 0.05], vignette in [0, 1], falloff in [0, 4]), a
+ * non-finite border with a filter other than NEAREST, mode, filter or channels out of range, chroma != 0 with channels = 1,
+ * NEAREST with chroma != 0 or vignette != 0, a float pointer that is not 4-byte aligned, an output equal to src_dev (a gather
+ * cannot run in place), a negative device, a radial map that folds over: RTM_ERR_INVALID_ARGUMENT, before any device call.
+ * The fold-over check, in double on the host: a = 3 k1, b = 5 k2, T = iz iz for DIRECT and 4 (iz iz) for INVERSE (the
+ * solve may look as far as rho = 2 iz); d(t) = 1 + t (a + t b), the derivative of rho g(rho^2) at t = rho^2, must be 0.25
+ * or more at t = T and, when b != 0 and tv = -a / (2 b) lies in 0 < tv < T, at tv (d(0) = 1); INVERSE also needs
+ * 1 + T (k1 + T k2) >= 0.5, so that a root exists in [0, 2 iz].
+ * A frame of 2^31 pixels or more, or of 2^24 tiles of 64 x 4 or more (a launch holds fewer than 2^32 lanes):
+ * RTM_ERR_UNSUPPORTED.
+ * rtm_lens_fit_zoom (HOST only, no device call) gives the zoom that hides the border: P(z) is true iff the parameters with
+ * zoom = z pass the fold-over check and every pixel of the frame's outermost rows and columns has all its channels inside,
+ * by the arithmetic of step 1.  lo = 0.25f, hi = 4.0f; if P(lo) the result is lo; if not P(hi): RTM_ERR_UNSUPPORTED;
+ * otherwise 24 times mid = (lo + hi) 0.5f in float, hi = mid if P(mid), else lo = mid, and the result is hi.  P is monotone
+ * in z, because the radial map is increasing wherever the check passes.  It reads k1, k2, chroma, mode and channels only
+ * (params->zoom is ignored) and holds k1, k2 and chroma to no range: a lens that no zoom in [0.25, 4] serves has no fit and
+ * gives RTM_ERR_UNSUPPORTED (no parameters that rtm_lens accepts get there: P(4) holds for all of them).  Null params or
+ * zoom_out, a non-positive size, a NaN or infinite k1, k2 or chroma, mode or channels out of range, chroma != 0 with
+ * channels = 1: RTM_ERR_INVALID_ARGUMENT; a frame of 2^31 pixels or more: RTM_ERR_UNSUPPORTED.
+ * Defaults: RTM_LENS_DEFAULTS below.  Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+enum { RTM_LENS_NEAREST = 0, RTM_LENS_BILINEAR = 1, RTM_LENS_BICUBIC = 2 }; /* filter */
+enum { RTM_LENS_DIRECT = 0, RTM_LENS_INVERSE = 1 };                         /* mode   */
+typedef struct rtm_lens_params { /* 48 bytes */
+    float k1, k2;     /* radial polynomial g(t) = 1 + t (k1 + t k2), t = squared normalised radius; |k1| <= 0.5, |k2| <= 0.25 */
+    float zoom;       /* in [0.25, 4]: magnification about the centre, applied before the polynomial                        */
+    float chroma;     /* in [-0.05, 0.05]: lateral chromatic aberration; R is scaled by 1 + chroma, G by 1, B by 1 - chroma  */
+    float vignette;   /* amount in [0, 1]                                                                                    */
+    float falloff;    /* in [0, 4]: tan of the half field angle at the frame's corner (cos^4 law)                            */
+    float border[3];  /* written, bit for bit, where a channel's source position lies outside the frame                      */
+    int32_t mode;     /* RTM_LENS_DIRECT / RTM_LENS_INVERSE                                                                  */
+    int32_t filter;   /* RTM_LENS_*                                                                                          */
+    int32_t channels; /* C: 1 (a plane) or 3 (a frame)                                                                       */
+} rtm_lens_params;
+#define RTM_LENS_DEFAULTS {0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 1.0f, {0.0f, 0.0f, 0.0f}, RTM_LENS_DIRECT, RTM_LENS_BICUBIC, 3}
+int rtm_lens(const rtm_lens_params* params, int32_t width, int32_t height, int device, const float* src_dev,
+             float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
+int rtm_lens_fit_zoom(const rtm_lens_params* params, int32_t width, int32_t height, float* zoom_out); /* host only */
+
 /* ---- resize: a frame or a single-channel plane brought to another size by a separable filter — thumbnails, a 4K trace
  * filtered down to 1080p, a plane (alpha, matte, variance, spp map) brought beside a frame of another size.  Opt-in, after
  * rtm_defocus and before rtm_bloom and rtm_tonemap, in linear light: every other stage and its defaults stay.  It is for

@@ -118,6 +118,19 @@ class rtm_defocus_params(C.Structure):  # include/rtm.h: rtm_defocus (12 bytes)
 DEFOCUS_DEFAULTS = {"aperture": 4.0, "max_radius": 8}  # RTM_DEFOCUS_DEFAULTS; the caller sets focus_distance
 
 
+class rtm_lens_params(C.Structure):  # include/rtm.h: rtm_lens (48 bytes)
+    _fields_ = [("k1", C.c_float), ("k2", C.c_float), ("zoom", C.c_float), ("chroma", C.c_float), ("vignette", C.c_float),
+                ("falloff", C.c_float), ("border", C.c_float * 3), ("mode", C.c_int32), ("filter", C.c_int32),
+                ("channels", C.c_int32)]
+
+
+LENS_FILTERS = ("nearest", "bilinear", "bicubic")  # RTM_LENS_NEAREST .. RTM_LENS_BICUBIC, in the enum's order
+LENS_MODES = ("direct", "inverse")  # RTM_LENS_DIRECT, RTM_LENS_INVERSE
+# RTM_LENS_DEFAULTS; channels follows the tensor
+LENS_DEFAULTS = {"k1": 0.0, "k2": 0.0, "zoom": 1.0, "chroma": 0.0, "vignette": 0.0, "falloff": 1.0, "border": 0.0,
+                 "mode": "direct", "filter": "bicubic"}
+
+
 class rtm_resize_params(C.Structure):  # include/rtm.h: rtm_resize (8 bytes)
     _fields_ = [("filter", C.c_int32), ("channels", C.c_int32)]
 
@@ -198,6 +211,8 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_defocus": (C.c_int, [_P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_lens": (C.c_int, [_P(rtm_lens_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_lens_fit_zoom": (C.c_int, [_P(rtm_lens_params), C.c_int32, C.c_int32, _P(C.c_float)]),
     "rtm_resize_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "rtm_resize": (C.c_int, [_P(rtm_resize_params), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p,
                              C.c_void_p, C.c_void_p, C.c_void_p]),

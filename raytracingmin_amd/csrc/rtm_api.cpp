@@ -138,6 +138,13 @@ int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height,
                 const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream) {
     RTM_GUARD(rtm::defocus(params, width, height, device, color_dev, depth_dev, out_f32_dev, out_u8_dev, coc_out_dev, stream))
 }
+int rtm_lens(const rtm_lens_params* params, int32_t width, int32_t height, int device, const float* src_dev, float* out_f32_dev,
+             uint8_t* out_u8_dev, void* stream) {
+    RTM_GUARD(rtm::lens(params, width, height, device, src_dev, out_f32_dev, out_u8_dev, stream))
+}
+int rtm_lens_fit_zoom(const rtm_lens_params* params, int32_t width, int32_t height, float* zoom_out) {
+    RTM_GUARD(rtm::lens_fit_zoom(params, width, height, zoom_out))
+}
 size_t rtm_resize_work_bytes(int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height, int32_t filter,
                              int32_t channels) {
     return rtm::resize_work_bytes(src_width, src_height, dst_width, dst_height, filter, channels);

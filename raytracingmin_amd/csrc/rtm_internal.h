@@ -83,6 +83,10 @@ int defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int
             float* out32, uint8_t* out8, float* coc_out, void* stream);
 int defocus_form_probe(int form, const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color,
                        const float* depth, float* out32, uint8_t* out8, float* coc_out, void* stream);
+// lens distortion, chromatic aberration, vignette (rtm_lens.hip)
+int lens(const rtm_lens_params* params, int32_t width, int32_t height, int device, const float* src, float* out32, uint8_t* out8,
+         void* stream);
+int lens_fit_zoom(const rtm_lens_params* params, int32_t width, int32_t height, float* zoom_out);
 // filtered resampling (rtm_resize.hip)
 size_t resize_work_bytes(int32_t src_width, int32_t src_height, int32_t dst_width, int32_t dst_height, int32_t filter,
                          int32_t channels);

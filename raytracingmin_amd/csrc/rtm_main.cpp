@@ -17,6 +17,10 @@
 //           [--dof [APERTURE]] [--focus DISTANCE | --focus-pixel X,Y] [--dof-radius R]
 //                                                (depth of field of the last stage by the depth plane: STEM_dof.bmp, .jpg; the
 //                                                defocused frame then is the last stage's for what follows)
+//           [--lens K1[,K2]] [--lens-inverse] [--lens-ca X] [--lens-vignette A[,F]] [--lens-zoom Z|auto]
+//           [--lens-filter nearest|bilinear|bicubic]
+//                                                (radial distortion, chromatic aberration and vignette of the last stage:
+//                                                STEM_lens.bmp, .jpg; that frame then is the last stage's for what follows)
 //           [--resize WxH [--resize-filter box|triangle|mitchell|lanczos3]]
 //                                                (the last stage's float frame resized on the device: STEM_resized.bmp, .jpg; the
 //                                                resized frame then is the last stage's for --display, --pfm, --display-pfm)
@@ -131,6 +135,17 @@ static void usage() {
         "            8); the focus is at the camera's target distance, at --focus DISTANCE, or at what pixel X,Y shows.  The\n"
         "            defocused frame then is the frame of the last stage for --pfm, --compare, --flip, --background and --display\n"
         "            (with --bloom: the glare of the defocused frame)\n"
+        "--lens K1[,K2] [--lens-inverse] [--lens-ca X] [--lens-vignette A[,F]] [--lens-zoom Z|auto]\n"
+        "            [--lens-filter nearest|bilinear|bicubic] : also write the last stage asked for (render, denoiser or --dof) through\n"
+        "            a lens on one GPU (rtm_lens, in linear light): STEM_lens.bmp and STEM_lens.jpg.  Any of --lens, --lens-ca,\n"
+        "            --lens-vignette, --lens-zoom switches the stage on.  K1, K2: the radial polynomial 1 + K1 r^2 + K2 r^4, r = 1 at\n"
+        "            the frame's corner (|K1| <= 0.5, |K2| <= 0.25; K1 < 0 is a barrel); --lens-inverse : take that distortion out\n"
+        "            instead of putting it in; --lens-ca X : lateral chromatic aberration, red scaled by 1 + X and blue by 1 - X\n"
+        "            (|X| <= 0.05); --lens-vignette A[,F] : cos^4 vignetting, amount A in [0, 1], F in [0, 4] the tangent of the\n"
+        "            half field angle at the corner (default 1); --lens-zoom Z : magnification in [0.25, 4] (default 1), auto : the\n"
+        "            smallest that hides the border (rtm_lens_fit_zoom); --lens-filter : default bicubic.  Where the source lies\n"
+        "            outside the frame the result is black.  The lens frame then is the frame of the last stage for --resize,\n"
+        "            --display (with --bloom), --pfm, --compare and --flip; it does not combine with --alpha, --matte or --background\n"
         "--resize WxH [--resize-filter box|triangle|mitchell|lanczos3] : also write the last stage asked for (render, denoiser or\n"
         "            --dof) resized to W x H on one GPU (rtm_resize, in linear light; default filter mitchell; antialiased when it\n"
         "            shrinks): STEM_resized.bmp and STEM_resized.jpg.  The resized frame then is the frame of the last stage for\n"
@@ -184,6 +199,8 @@ int main(int argc, char* argv[]) {
     rtm_bloom_params bloom_prm = RTM_BLOOM_DEFAULTS;
     int dof = 0, focus_given = 0, focus_pixel_given = 0, dof_radius_given = 0, focus_x = 0, focus_y = 0;
     rtm_defocus_params dof_prm = RTM_DEFOCUS_DEFAULTS;
+    int lens = 0, lens_inverse = 0, lens_filter_given = 0, lens_zoom_auto = 0;
+    rtm_lens_params lens_prm = RTM_LENS_DEFAULTS;
     int resize = 0, resize_filter_given = 0, resize_w = 0, resize_h = 0;
     rtm_resize_params resize_prm = RTM_RESIZE_DEFAULTS;
     int pfm = 0;
@@ -316,6 +333,65 @@ int main(int argc, char* argv[]) {
             focus_x = (int)x;
             focus_y = (int)y;
         }
+        else if (c == "--lens" || c == "--lens-ca" || c == "--lens-vignette") {
+            // one or two comma-separated numbers, all of the text, each in its range once rounded to float
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = m.find(',');
+            double v0 = 0.0, v1 = 0.0;
+            const bool two = comma != std::string::npos;
+            bool ok = parse_number(two ? m.substr(0, comma) : m, v0);
+            if (two) ok = ok && c != "--lens-ca" && parse_number(m.substr(comma + 1), v1);  // (--lens-ca takes one number)
+            const float f0 = (float)v0, f1 = (float)v1;  // (double first, as Python's float() then C float)
+            if (c == "--lens") {
+                ok = ok && f0 >= -0.5f && f0 <= 0.5f && (!two || (f1 >= -0.25f && f1 <= 0.25f));
+                lens_prm.k1 = f0;
+                if (two) lens_prm.k2 = f1;
+            } else if (c == "--lens-ca") {
+                ok = ok && f0 >= -0.05f && f0 <= 0.05f;
+                lens_prm.chroma = f0;
+            } else {
+                ok = ok && f0 >= 0.0f && f0 <= 1.0f && (!two || (f1 >= 0.0f && f1 <= 4.0f));
+                lens_prm.vignette = f0;
+                if (two) lens_prm.falloff = f1;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "%s takes %s, got %s\n", c.c_str(),
+                             c == "--lens"      ? "K1[,K2] with |K1| <= 0.5 and |K2| <= 0.25"
+                             : c == "--lens-ca" ? "a number in [-0.05, 0.05]"
+                                                : "A[,F] with A in [0, 1] and F in [0, 4]",
+                             m.c_str());
+                return 2;
+            }
+            lens = 1;
+        } else if (c == "--lens-zoom") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            double v = 0.0;
+            if (m == "auto")
+                lens_zoom_auto = 1;
+            else if (parse_number(m, v) && (float)v >= 0.25f && (float)v <= 4.0f) {
+                lens_zoom_auto = 0;
+                lens_prm.zoom = (float)v;
+            } else {
+                std::fprintf(stderr, "--lens-zoom takes auto or a number in [0.25, 4], got %s\n", m.c_str());
+                return 2;
+            }
+            lens = 1;
+        } else if (c == "--lens-inverse") {
+            lens_inverse = 1;
+            lens_prm.mode = RTM_LENS_INVERSE;
+        } else if (c == "--lens-filter") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            static const char* const names[] = {"nearest", "bilinear", "bicubic"};  // RTM_LENS_*, in the enum's order
+            int which = -1;
+            for (int k = 0; k < 3; ++k)
+                if (m == names[k]) which = k;
+            if (which < 0) {
+                std::fprintf(stderr, "--lens-filter takes nearest, bilinear or bicubic, got %s\n", m.c_str());
+                return 2;
+            }
+            lens_filter_given = 1;
+            lens_prm.filter = which;
+        }
         else if (c == "--resize") {
             // WxH: two whole numbers from 1, all of the text
             const std::string m = i + 1 < argc ? argv[++i] : "";
@@ -438,6 +514,14 @@ int main(int argc, char* argv[]) {
         {focus_given && focus_pixel_given, "--dof focuses at --focus DISTANCE or at --focus-pixel X,Y, not at both"},
         {dof && many, "--dof runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
         {dof && preview_only, "--preview-only skips the full render: it does not combine with --dof"},
+        {(lens_inverse || lens_filter_given) && !lens,
+         "--lens-inverse and --lens-filter require the lens stage: --lens, --lens-ca, --lens-vignette or --lens-zoom"},
+        {lens && many, "--lens runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {lens && preview_only, "--preview-only skips the full render: it does not combine with --lens"},
+        {lens && mattes,
+         "--lens does not combine with --alpha, --matte or --background: the coverage planes are not warped with the frame"},
+        {lens && lens_prm.filter == RTM_LENS_NEAREST && (lens_prm.chroma != 0.0f || lens_prm.vignette != 0.0f),
+         "--lens-filter nearest copies words: it does not combine with --lens-ca or --lens-vignette"},
         {resize_filter_given && !resize, "--resize-filter requires --resize WxH"},
         {resize && many, "--resize runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
         {resize && preview_only, "--preview-only skips the full render: it does not combine with --resize"},
@@ -505,7 +589,7 @@ int main(int argc, char* argv[]) {
     if (!compare_ref.empty() && !read_reference("--compare", compare_ref, st, reference)) return 1;
     if (!flip_ref.empty() && !read_reference("--flip", flip_ref, st, flip_reference)) return 1;
     // a later stage takes the float frame of the last one
-    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof || resize;
+    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof || lens || resize;
     if (dof) {  // the focus, known before anything is rendered: --focus, what --focus-pixel shows, else the camera's target
         if (focus_pixel_given) {
             if (focus_x >= st.width || focus_y >= st.height) {
@@ -530,6 +614,13 @@ int main(int argc, char* argv[]) {
         }
         std::printf("dof: focus %.6g, aperture %.6g, max radius %d\n", (double)dof_prm.focus_distance, (double)dof_prm.aperture,
                     dof_prm.max_radius);
+    }
+    if (lens && lens_zoom_auto) {  // the zoom that hides the border, known before anything is rendered (host only)
+        rc = rtm_lens_fit_zoom(&lens_prm, st.width, st.height, &lens_prm.zoom);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "--lens-zoom auto: %s (%s)\n", rtm_strerror(rc), rtm_last_error_detail());
+            return 2;
+        }
     }
     if (bloom)
         std::printf("bloom: threshold %.6g, knee %.6g, intensity %.6g, scatter %.6g, levels %d\n", (double)bloom_prm.threshold,
@@ -645,6 +736,13 @@ int main(int argc, char* argv[]) {
         rc = rtm_node_write_dof(&st, spheres.data(), n, &opt, &dof_prm, shown.empty() ? rgb32.data() : shown.data(), stem, err, &defocused);
         if (rc != RTM_OK) return fail("dof", rc, err);
         shown.swap(defocused);
+    }
+    if (lens) {  // of the last stage so far, in linear light; its frame then is the last stage's
+        std::vector<float> through;
+        rc = rtm_node_write_lens(&st, opt.device, &lens_prm, shown.empty() ? rgb32.data() : shown.data(), stem, err, &through);
+        if (rc != RTM_OK) return fail("lens", rc, err);
+        shown.swap(through);
+        std::printf("lens: %s_lens.bmp, %s_lens.jpg (zoom %.9g)\n", stem.c_str(), stem.c_str(), (double)lens_prm.zoom);
     }
     rtm_settings last_st = st;  // the last stage's size: the render's, unless --resize follows
     if (resize) {  // of the last stage so far, in linear light; its frame then is the last stage's

@@ -681,6 +681,28 @@ int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t
     return RTM_OK;
 }
 
+// --lens (rtm_node.h): rtm_lens of the frame on the default stream, then the two files.
+int rtm_node_write_lens(const rtm_settings* st, int device, const rtm_lens_params* prm, const float* f32_host, const std::string& stem,
+                        std::string& err, std::vector<float>* f32_out) {
+    if (prm->channels != 3) return fail(err, RTM_ERR_INVALID_ARGUMENT, "lens of a frame takes channels = 3");
+    const size_t vals = (size_t)st->width * st->height * 3;
+    std::vector<uint8_t> rgb8(vals);
+    {  // the device's part; what it holds is released before the files are written
+        if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+        DevBuf<float> color, out32;
+        DevBuf<uint8_t> out8;
+        if (!color.alloc(vals) || !out32.alloc(vals) || !out8.alloc(vals))
+            return fail(err, RTM_ERR_HIP, "no device memory for lens's buffers");
+        if (!color.upload(f32_host, vals)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+        const int rc = rtm_lens(prm, st->width, st->height, device, color.get(), out32.get(), out8.get(), nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, vals), vals))
+            return fail(err, RTM_ERR_HIP, "copying the lens frame back failed");
+    }
+    if (!write_jpg_bmp(stem + "_lens", st, rgb8.data())) return fail(err, RTM_ERR_IO, "cannot write the lens files of " + stem);
+    return RTM_OK;
+}
+
 // --resize (rtm_node.h): rtm_resize of the frame on the default stream, then the two files at the new size.
 int rtm_node_write_resized(const rtm_settings* st, int device, const rtm_resize_params* prm, int dst_width, int dst_height,
                            const float* f32_host, const std::string& stem, std::string& err, std::vector<float>* f32_out) {

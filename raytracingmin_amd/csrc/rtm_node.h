@@ -66,6 +66,11 @@ int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* p
 int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
                        const rtm_defocus_params* params, const float* f32_host, const std::string& stem, std::string& err,
                        std::vector<float>* f32_out);
+// Lens distortion, chromatic aberration and vignette (rtm_lens, rtm_cli --lens ...) of a float frame (HOST, height x width x 3)
+// on device `device`: one rtm_lens call on the default stream, then <stem>_lens.bmp and <stem>_lens.jpg (quality 60); the
+// float frame comes back in f32_out, for the stages that follow.
+int rtm_node_write_lens(const rtm_settings* st, int device, const rtm_lens_params* params, const float* f32_host,
+                        const std::string& stem, std::string& err, std::vector<float>* f32_out);
 // Resize (rtm_resize, rtm_cli --resize) of a float frame (HOST, height x width x 3) on device `device` to dst_width x dst_height:
 // one rtm_resize call on the default stream, then <stem>_resized.bmp and <stem>_resized.jpg (quality 60) at the new size; the
 // resized float frame comes back in f32_out, for the stages that follow.

@@ -558,7 +558,7 @@ class Renderer:
         return out, self.stats
 
     def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False,
-               dof=None, resize=None):
+               dof=None, resize=None, lens=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -581,6 +581,11 @@ class Renderer:
         frame) defocused by the frame's depth plane, with the focus at the camera's target distance unless the dict says
         otherwise.  The defocused frame then is the last stage: with tonemap, bloom and the display transform take it (bloom
         is lens glare, so it comes after the lens), and so does mattes' background.
+        lens=None or False: no lens.  lens=True (or a dict of lens()'s parameters: k1, k2, zoom, chroma, vignette, falloff,
+        border, mode, filter; zoom="auto" takes lens_fit_zoom's value) also writes <fileName>_lens.bmp and <fileName>_lens.jpg
+        (q=60): the last stage asked for (defocused, variance-denoised, denoised, else the frame) through that lens
+        (write_lens).  The lens frame then is the last stage for resize, tonemap and bloom.  It does not combine with mattes:
+        the coverage planes are not warped with the frame.
         resize=None: no resize.  resize=(W, H) or (W, H, filter) (width first, as rtm_cli --resize WxH; filter one of
         RESIZE_FILTERS, default "mitchell") also writes <fileName>_resized.bmp and <fileName>_resized.jpg (q=60): the last
         stage asked for (defocused, variance-denoised, denoised, else the frame) brought to W x H by resize() in linear light
@@ -625,6 +630,9 @@ class Renderer:
         resize_prm = _resize_option(resize)
         if resize_prm is not None and matte_prm is not None and matte_prm.get("background") is not None:
             raise ValueError("resize does not combine with mattes' background: the composite runs at the render's size")
+        lens_prm = _lens_option(lens, self.data.width, self.data.height)
+        if lens_prm is not None and matte_prm is not None:
+            raise ValueError("lens does not combine with mattes: the coverage planes are not warped with the frame")
         bloom_prm = _bloom_option(bloom)
         if bloom_prm is not None:
             if display is None:
@@ -661,13 +669,15 @@ class Renderer:
             self.write_aov(fileName)
         frame = None  # the f32 frame the display stage shows, when it is not self.image
         keep = display is not None or (matte_prm is not None and matte_prm.get("background") is not None) or dof_prm is not None
-        keep = keep or resize_prm is not None
+        keep = keep or resize_prm is not None or lens_prm is not None
         if denoise == "variance":
             frame = self.write_denoised_variance(fileName, _keep=keep)
         elif denoise:
             frame = self.write_denoised(fileName, _keep=keep)
         if dof_prm is not None:
             frame = self.write_dof(fileName, frame=frame, **dof_prm)
+        if lens_prm is not None:
+            frame = self.write_lens(fileName, frame=frame, **lens_prm)
         if resize_prm is not None:
             frame = self.write_resized(fileName, frame=frame, **resize_prm)
         if display is not None:
@@ -745,6 +755,26 @@ class Renderer:
         ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_dof.bmp"), W, H, 3, rgb8.ctypes.data)
         if not (ok_j and ok_b):
             raise _lib.RtmError(-3, f"could not write {fileName}_dof.jpg/.bmp")
+        return out["f32"]
+
+    def write_lens(self, fileName, frame=None, **params):
+        """<fileName>_lens.bmp and <fileName>_lens.jpg (q=60): lens(**params) of `frame`, an (H, W, 3) float32 CUDA tensor, or
+        of self.image rounded to float like out_f32 — what rtm_cli --lens writes.  params: lens()'s k1, k2, zoom, chroma,
+        vignette, falloff, border, mode, filter, with zoom="auto" for lens_fit_zoom's value.  Returns the float32 frame on the
+        device."""
+        import torch
+        params = _lens_option(params or True, self.data.width, self.data.height)
+        if frame is None:
+            dev = torch.device("cuda", self.device)
+            frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        out = _lens(frame, want=("f32", "u8"), **params)
+        rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
+        L = _lib.lib()
+        H, W = rgb8.shape[:2]
+        ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_lens.jpg"), W, H, 3, rgb8.ctypes.data, 60)
+        ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_lens.bmp"), W, H, 3, rgb8.ctypes.data)
+        if not (ok_j and ok_b):
+            raise _lib.RtmError(-3, f"could not write {fileName}_lens.jpg/.bmp")
         return out["f32"]
 
     def write_resized(self, fileName, size, frame=None, filter=_lib.RESIZE_DEFAULTS["filter"]):
@@ -1376,6 +1406,151 @@ def resize(color, size, filter=RESIZE_DEFAULTS["filter"], want=("f32",), stream=
     _lib.check(L.rtm_resize(C.byref(prm), w, h, W, H, dev.index, color.data_ptr(), ptr("work"), ptr("f32"), ptr("u8"),
                             C.c_void_p(s.cuda_stream)), "rtm_resize")
     return out
+
+
+# include/rtm.h: RTM_LENS_DEFAULTS, the RTM_LENS_* filters and modes, by name
+LENS_DEFAULTS = dict(_lib.LENS_DEFAULTS)
+LENS_FILTERS = _lib.LENS_FILTERS
+LENS_MODES = _lib.LENS_MODES
+_LENS_RANGES = {"k1": (-0.5, 0.5), "k2": (-0.25, 0.25), "zoom": (0.25, 4.0), "chroma": (-0.05, 0.05), "vignette": (0.0, 1.0),
+                "falloff": (0.0, 4.0)}
+
+
+def _lens_folds_over(k1, k2, zoom, inverse):
+    """rtm.h's fold-over check, in double like the library's: k1, k2, zoom as the float32 values the struct holds."""
+    k1, k2, iz = float(k1), float(k2), 1.0 / float(zoom)
+    a, b = 3.0 * k1, 5.0 * k2
+    T = 4.0 * (iz * iz) if inverse else iz * iz
+    if not 1.0 + T * (a + T * b) >= 0.25:
+        return True
+    if b != 0.0:
+        tv = -a / (2.0 * b)
+        if 0.0 < tv < T and not 1.0 + tv * (a + tv * b) >= 0.25:
+            return True
+    return bool(inverse) and not 1.0 + T * (k1 + T * k2) >= 0.5
+
+
+def _lens_params(channels=3, k1=LENS_DEFAULTS["k1"], k2=LENS_DEFAULTS["k2"], zoom=LENS_DEFAULTS["zoom"],
+                 chroma=LENS_DEFAULTS["chroma"], vignette=LENS_DEFAULTS["vignette"], falloff=LENS_DEFAULTS["falloff"],
+                 border=LENS_DEFAULTS["border"], mode=LENS_DEFAULTS["mode"], filter=LENS_DEFAULTS["filter"], fit=False):
+    """lens()'s parameters as an rtm_lens_params; a ValueError names what the library would refuse.  fit=True: for
+    lens_fit_zoom, which ignores zoom, holds k1, k2 and chroma to no range and makes the fold-over check part of its search.
+    No device use."""
+    if not isinstance(mode, str) or mode not in LENS_MODES:
+        raise ValueError(f"mode is one of {LENS_MODES}, got {mode!r}")
+    if not isinstance(filter, str) or filter not in LENS_FILTERS:
+        raise ValueError(f"filter is one of {LENS_FILTERS}, got {filter!r}")
+    vals = {}
+    for name, v in (("k1", k1), ("k2", k2), ("zoom", 1.0 if fit else zoom), ("chroma", chroma), ("vignette", vignette),
+                    ("falloff", falloff)):
+        lo, hi = _LENS_RANGES[name]
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool):
+            raise ValueError(f"{name} is a number in [{lo}, {hi}], got {v!r}")
+        with np.errstate(over="ignore", under="ignore"):
+            f = np.float32(v)  # as the library sees it: rounded to float
+        if fit and name in ("k1", "k2", "chroma"):
+            if not np.isfinite(f):
+                raise ValueError(f"{name} is a finite number, got {v!r}")
+        elif not np.float32(lo) <= f <= np.float32(hi):
+            raise ValueError(f"{name} is a number in [{lo}, {hi}], got {v!r}")
+        vals[name] = f
+    try:
+        words = np.ascontiguousarray(np.broadcast_to(np.asarray(border, dtype=np.float32), (3,)))  # a float32's bits are kept
+    except (TypeError, ValueError):
+        raise ValueError(f"border is a number or three, got {border!r}") from None
+    if filter != "nearest" and not np.all(np.isfinite(words)):
+        raise ValueError(f'border is finite unless filter is "nearest", got {border!r}')
+    if vals["chroma"] != 0.0 and channels == 1:
+        raise ValueError("chroma is 0 for a plane: it has no colours to separate")
+    if filter == "nearest" and (vals["chroma"] != 0.0 or vals["vignette"] != 0.0):
+        raise ValueError('filter "nearest" copies words: chroma and vignette are 0')
+    if not fit and _lens_folds_over(vals["k1"], vals["k2"], vals["zoom"], mode == "inverse"):
+        raise ValueError(f"the radial map folds over inside the frame with k1 {k1!r}, k2 {k2!r}, zoom {zoom!r}, mode {mode!r}")
+    prm = _lib.rtm_lens_params()
+    for name, f in vals.items():
+        setattr(prm, name, float(f))
+    C.memmove(prm.border, words.ctypes.data, 12)
+    prm.mode, prm.filter, prm.channels = LENS_MODES.index(mode), LENS_FILTERS.index(filter), channels
+    return prm
+
+
+def lens_fit_zoom(width, height, **params):
+    """The zoom that hides the border of lens(**params) on a width x height frame (include/rtm.h: rtm_lens_fit_zoom): the
+    smallest of its 24-step bisection of [0.25, 4] at which every pixel of the frame's outermost rows and columns has its
+    source inside the frame, as a Python float holding a float32.  params: lens()'s, of which k1, k2, chroma and mode are
+    read (zoom is ignored; channels=1 for a plane).  Host only: no device use.  RtmError (unsupported) when not even zoom 4
+    hides it, which takes a k1, k2 or chroma beyond what lens() accepts."""
+    for name, v in (("width", width), ("height", height)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 2147483647:
+            raise ValueError(f"{name} is a positive integer, got {v!r}")
+    unknown = set(params) - set(LENS_DEFAULTS) - {"channels"}
+    if unknown:
+        raise ValueError(f"lens_fit_zoom's parameters are {tuple(LENS_DEFAULTS) + ('channels',)}, got {sorted(unknown)}")
+    channels = params.pop("channels", 3)
+    if channels not in (1, 3):
+        raise ValueError(f"channels is 1 or 3, got {channels!r}")
+    prm = _lens_params(channels, fit=True, **params)
+    z = C.c_float()
+    _lib.check(_lib.lib().rtm_lens_fit_zoom(C.byref(prm), int(width), int(height), C.byref(z)), "rtm_lens_fit_zoom")
+    return float(z.value)
+
+
+def _lens_option(lens, width, height):
+    """Render's `lens`: None (or False, like Render's other stage arguments) for off, else the dict of lens()'s parameters
+    (True: the defaults), checked, with zoom="auto" replaced by lens_fit_zoom's value.  No device use."""
+    if lens is None or lens is False:
+        return None
+    if lens is not True and not isinstance(lens, dict):
+        raise ValueError(f"lens is None, False, True or a dict of {tuple(LENS_DEFAULTS)}, got {lens!r}")
+    prm = {} if lens is True else dict(lens)
+    unknown = set(prm) - set(LENS_DEFAULTS)
+    if unknown:
+        raise ValueError(f"lens's parameters are {tuple(LENS_DEFAULTS)}, got {sorted(unknown)}")
+    if isinstance(prm.get("zoom"), str):
+        if prm["zoom"] != "auto":
+            raise ValueError(f'zoom is a number or "auto", got {prm["zoom"]!r}')
+        prm["zoom"] = lens_fit_zoom(width, height, **{k: v for k, v in prm.items() if k != "zoom"})
+    _lens_params(3, **prm)
+    return prm
+
+
+def lens(color, k1=LENS_DEFAULTS["k1"], k2=LENS_DEFAULTS["k2"], zoom=LENS_DEFAULTS["zoom"], chroma=LENS_DEFAULTS["chroma"],
+         vignette=LENS_DEFAULTS["vignette"], falloff=LENS_DEFAULTS["falloff"], border=LENS_DEFAULTS["border"],
+         mode=LENS_DEFAULTS["mode"], filter=LENS_DEFAULTS["filter"], want=("f32",), stream=None):
+    """Lens distortion, lateral chromatic aberration and vignette (include/rtm.h: rtm_lens) on the device, at the frame's own
+    size; run it in linear light, after defocus() and before resize(), bloom() and tonemap().  `color` is an (H, W, 3)
+    float32 torch CUDA tensor or an (H, W) plane (any 4-byte-aligned contiguous view).  k1, k2: the radial polynomial
+    g(t) = 1 + t (k1 + t k2) over the squared radius t, 1 at the frame's corner (k1 < 0: a barrel); mode "direct" shows at p
+    the source at p g(|p|^2), "inverse" takes that distortion out; zoom in [0.25, 4] magnifies about the centre
+    (lens_fit_zoom gives the one that hides the border); chroma scales red by 1 + chroma and blue by 1 - chroma; vignette in
+    [0, 1] and falloff (the tangent of the half field angle at the corner) darken by the cos^4 law.  filter: one of
+    LENS_FILTERS; "nearest" copies words bit for bit (id planes, depth with +inf) and takes no chroma or vignette.  Where a
+    channel's source lies outside the frame the result is `border` (a number, or three for a frame; with "nearest" its bits
+    are kept, so np.int32(-1).view(np.float32) marks an id plane).  A pixel with a non-finite component contributes nothing; a
+    result too few of whose taps count is NaN.  A map that folds over inside the frame is a ValueError.  Returns a dict of the
+    names in `want`: "f32" float32 and "u8" uint8 (rtm_quantise of it), shaped like `color`.  The outputs are tensors of the
+    call's own: a gather cannot run in place.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default:
+    the current stream); nothing waits for it and nothing is copied to the host."""
+    channels = 1 if getattr(color, "ndim", 3) == 2 else 3
+    prm = _lens_params(channels, k1, k2, zoom, chroma, vignette, falloff, border, mode, filter)
+    _check_want(want, ("f32", "u8"))
+    import torch
+    _need_device("lens")
+    if not (isinstance(color, torch.Tensor) and color.is_cuda and color.dtype == torch.float32 and color.is_contiguous()
+            and color.numel() > 0 and (color.dim() == 2 or (color.dim() == 3 and color.shape[2] == 3))):
+        raise ValueError("color must be a contiguous, non-empty (H, W, 3) or (H, W) float32 CUDA tensor")
+    H, W = int(color.shape[0]), int(color.shape[1])
+    shape = tuple(color.shape)
+    dev = color.device
+    s = _stream_of(stream, dev)
+    specs = {"f32": (shape, torch.float32), "u8": (shape, torch.uint8)}
+    out, ptr = _stage_tensors(s, dev, want, specs)
+    _lib.check(_lib.lib().rtm_lens(C.byref(prm), W, H, dev.index, color.data_ptr(), ptr("f32"), ptr("u8"),
+                                   C.c_void_p(s.cuda_stream)), "rtm_lens")
+    return out
+
+
+_lens = lens  # for Renderer's methods, whose own parameter is named lens
 
 
 def tonemap_stats(words):
