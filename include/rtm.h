@@ -641,6 +641,108 @@ size_t rtm_bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
 int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color_dev,
               void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream);
 
+/* ---- grade: the colour decision — white balance (or any change of primaries) as a 3x3 matrix, exposure, contrast about a
+ * pivot, the ASC CDL's slope / offset / power, saturation, and an optional 3D look LUT gathered on the device.  Opt-in, a
+ * per-pixel transform of a device float frame: every other stage and its defaults stay.  The parametric steps are meant for
+ * linear light, after rtm_bloom (glare is light, so it is added before the colour decision) and before rtm_tonemap; a look
+ * LUT from a .cube file is display-referred and is meant for rtm_tonemap's float frame.  One call serves either or both.
+ * Input: color (DEVICE, h x w x 3 floats, interleaved like out_f32; 4-byte alignment is enough).  lut (DEVICE, 3 N^3 floats
+ * in .cube order, N = lut_size: entry (r, g, b) is the three floats at 3 (r + N (g + N b)), red fastest; the caller owns it;
+ * null iff lut_size = 0).  The arithmetic is float, without contraction, in the order written; pow, exp2, log2 and the
+ * divisions may be the device's fast forms.
+ * A pixel COUNTS iff its three components are finite.  A pixel that does not count is copied to out_f32 word for word: the
+ * stage does not repair, and rtm_tonemap downstream still sees the pixel as not counting.
+ * A step whose parameters all equal their defaults exactly (float ==, so -0 equals 0) is SKIPPED; the host decides this
+ * before the launch.  So RTM_GRADE_DEFAULTS copies every word of the frame bit for bit, -0 and NaN payloads included, and a
+ * skipped step rounds nothing.  For a counting pixel (r, g, b), in this order:
+ *   1 matrix      y_i = (m[3i] r + m[3i+1] g) + m[3i+2] b, m = matrix, row-major.  Default: the identity.
+ *   2 exposure    y = y G, G = (float)exp2((double)exposure), computed on the host.  Default: 0 stops.
+ *   3 contrast    y = pivot pow(max(y, 0) / pivot, contrast) per channel: a power curve through (pivot, pivot); it clips
+ *                 negative components to 0.  Defaults: contrast 1 at pivot 0.18 (both are the step's parameters: contrast 1
+ *                 at another pivot is a live step, which only clips).
+ *   4 CDL         per channel c: v = max(y slope_c + offset_c, 0), the product rounded, then the sum; y = v when
+ *                 power_c == 1, else pow(v, power_c), with pow(0, p) = 0.  Defaults: slope 1, offset 0, power 1.
+ *   5 saturation  L = (0.2126 y_R + 0.7152 y_G) + 0.0722 y_B (the library's luminance); y = L + saturation (y - L).
+ *                 Default: 1.  0 gives r = g = b = L.
+ *   6 LUT         (lut_size = N > 0) per channel c: s = (y - lo_c) inv_c with lo = lut_min, hi = lut_max and
+ *                 inv_c = (float)((double)(N - 1) / ((double)hi_c - (double)lo_c)) computed on the host;
+ *                 s = (s > 0) ? min(s, N - 1) : 0, so a NaN lands on 0 and +inf on N - 1; i = min((int)s, N - 2),
+ *                 f = s - i, in [0, 1].  With c_abc the entry at (i_R + a, i_G + b, i_B + c):
+ *                 TRILINEAR   the eight corners, blended along r, then g, then b, each blend as a + f (b - a).
+ *                 TETRAHEDRAL the three fractions in descending order f1 >= f2 >= f3, a tie taking the earlier channel
+ *                             first; c_1 is c000 moved one step along the first channel, c_2 along the first two;
+ *                             out = (((1 - f1) c000 + (f1 - f2) c_1) + (f2 - f3) c_2) + f3 c111.
+ *                 Both interpolants are continuous across cells and tetrahedra, both return a lattice point's entry at the
+ *                 lattice point, and both reproduce an affine table.
+ *   7 outputs     out_f32 is the result; out_u8 (nullable) is rtm_quantise of (double)out_f32, out of range (NaN included)
+ *                 -> 0, as in the other stages.
+ * Memory safety is part of the contract: for ANY input words and any accepted parameters, every read of lut lies inside its
+ * 3 N^3 floats; that is what the clamp of step 6 is written for.  An intermediate overflow (an infinity, or the NaN of
+ * inf - inf in step 5) gives IEEE's result without a LUT and a table entry with one.
+ * Against a float64 evaluation of the steps with the float-rounded G, inv_c and parameters, every out_f32 component of a
+ * counting pixel is within 1e-4 max(1, |ref|); pixels that do not count and the all-defaults copy are exact; out_u8 is exact
+ * given the call's own out_f32.  The call is stateless: no work buffer, no allocation, no per-(device, stream) state, no
+ * serialisation, no atomics; it only ENQUEUES one launch on `stream` of `device`, and the same inputs give the same bits on
+ * every call, on any stream, at any 4-byte alignment of color and out_f32.  out_f32_dev == color_dev grades in place, with
+ * the same bits as out of place.
+ * Null params or color_dev, both outputs null, a non-positive size, a parameter that is NaN, infinite or outside its range
+ * (|exposure| <= 32, contrast in [0.25, 4], pivot > 0, slope >= 0, power in [0.1, 10], saturation in [0, 4]; matrix, offset,
+ * lut_min and lut_max finite), lut_size neither 0 nor in 2..256, lut_interp out of range, lut_max_c <= lut_min_c, lut_dev
+ * null with lut_size > 0 or non-null with lut_size = 0, a float pointer that is not 4-byte aligned, lut_dev equal to an
+ * output, out_u8_dev == color_dev, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A frame of 2^31
+ * pixels or more: RTM_ERR_UNSUPPORTED.
+ * rtm_grade_white_balance (HOST only, no device call) gives the matrix for step 1 that takes a scene lit by a black body at
+ * `kelvin` to D65: the Bradford adaptation from that white to D65 (0.3127, 0.3290), expressed in linear Rec.709 / sRGB
+ * primaries, computed in double and rounded to float; the source white's linear RGB maps to three equal components.  The
+ * source white is Kang et al.'s (2002) cubic approximation of the Planckian locus, T = kelvin:
+ *   T <= 4000: x = -0.2661239e9 / T^3 - 0.2343589e6 / T^2 + 0.8776956e3 / T + 0.179910, otherwise
+ *              x = -3.0258469e9 / T^3 + 2.1070379e6 / T^2 + 0.2226347e3 / T + 0.240390;
+ *   T <= 2222: y = -1.1063814 x^3 - 1.34811020 x^2 + 2.18555832 x - 0.20219683,
+ *   T <= 4000: y = -0.9549476 x^3 - 1.37418593 x^2 + 2.09137015 x - 0.16748867, otherwise
+ *              y =  3.0817580 x^3 - 5.87338670 x^2 + 3.75112997 x - 0.37001483.
+ * `tint` is added to v in CIE 1960 (u, v): u = 4x / (-2x + 12y + 3), v = 6y / (-2x + 12y + 3) + tint, and back
+ * x = 3u / (2u - 8v + 4), y = 2v / (2u - 8v + 4); a positive tint is a greener source.  The RGB <-> XYZ matrices are derived
+ * from the Rec.709 primaries and D65; the cone response matrix is Bradford's.  kelvin in [1667, 25000], tint in
+ * [-0.05, 0.05]; a value out of range or not finite, or a null pointer: RTM_ERR_INVALID_ARGUMENT.
+ * rtm_lut_parse_cube / rtm_lut_load_cube (HOST only) read a 3D LUT in the Adobe / Resolve .cube text format, shaped like
+ * the scene loaders: `size` receives N, domain_min / domain_max the input domain per channel, `table` (capacity in floats)
+ * the 3 N^3 floats in the file's order, which is rtm_grade's; a null table with capacity 0 asks for the size and checks the
+ * whole text all the same.  Lines end in LF or CR LF; blank lines and lines that begin with # are skipped; TITLE "..." is
+ * ignored; LUT_3D_SIZE N; DOMAIN_MIN and DOMAIN_MAX with three numbers each (defaults 0 and 1); LUT_3D_INPUT_RANGE lo hi
+ * sets all three channels; then exactly N^3 rows of three numbers, each a decimal number that is finite as a float.
+ * RTM_ERR_PARSE, with "line K: ..." in rtm_last_error_detail(): an unknown keyword, a keyword after the first row, a size
+ * that is not a whole number in 2..256 or is given twice, a row before the size, a token that is no such number, a line with
+ * too few or too many numbers, more than N^3 rows, fewer (K is then the last line), no size at all, a domain with
+ * max <= min (K is the last domain line).  LUT_1D_SIZE or LUT_1D_INPUT_RANGE: RTM_ERR_UNSUPPORTED.  A file that cannot be
+ * opened: RTM_ERR_IO.  A table with capacity < 3 N^3: RTM_ERR_CAPACITY (size and the domain are set).  A null text with a
+ * length, a null path, size or domain pointer, a null table with a capacity: RTM_ERR_INVALID_ARGUMENT.
+ * Defaults: RTM_GRADE_DEFAULTS below.  Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+enum { RTM_GRADE_TRILINEAR = 0, RTM_GRADE_TETRAHEDRAL = 1 }; /* lut_interp */
+typedef struct rtm_grade_params { /* 120 bytes */
+    float matrix[9];    /* row-major 3x3, finite: white balance, any change of primaries                  */
+    float exposure;     /* stops, finite, |ev| <= 32                                                      */
+    float contrast;     /* in [0.25, 4]                                                                   */
+    float pivot;        /* finite, > 0: the value the contrast curve leaves where it is                   */
+    float slope[3];     /* ASC CDL: finite, >= 0                                                          */
+    float offset[3];    /* finite                                                                         */
+    float power[3];     /* in [0.1, 10]                                                                   */
+    float saturation;   /* in [0, 4]                                                                      */
+    int32_t lut_size;   /* 0: no LUT; else N in 2..256                                                    */
+    int32_t lut_interp; /* RTM_GRADE_*                                                                    */
+    float lut_min[3];   /* the LUT's input domain per channel, finite                                     */
+    float lut_max[3];   /* ... max > min                                                                  */
+} rtm_grade_params;
+#define RTM_GRADE_DEFAULTS                                                                                               \
+    {{1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f}, 0.0f, 1.0f, 0.18f, {1.0f, 1.0f, 1.0f}, {0.0f, 0.0f, 0.0f},     \
+     {1.0f, 1.0f, 1.0f}, 1.0f, 0, RTM_GRADE_TETRAHEDRAL, {0.0f, 0.0f, 0.0f}, {1.0f, 1.0f, 1.0f}}
+int rtm_grade(const rtm_grade_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+              const float* lut_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
+int rtm_grade_white_balance(float kelvin, float tint, float matrix_out[9]); /* host only */
+int rtm_lut_parse_cube(const char* text, size_t len, int32_t* size, float domain_min[3], float domain_max[3], float* table,
+                       size_t capacity); /* host only */
+int rtm_lut_load_cube(const char* path, int32_t* size, float domain_min[3], float domain_max[3], float* table,
+                      size_t capacity); /* host only */
+
 /* ---- depth of field (defocus): a focus distance and an aperture applied to a finished frame by its depth plane — a
  * depth-aware gather blur (scatter-as-gather) whose per-pixel circle of confusion follows the thin-lens law.  A focused
  * foreground stays sharp against a blurred background; a blurred foreground spills over what is behind it.  Opt-in, after the

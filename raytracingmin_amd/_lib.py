@@ -118,6 +118,18 @@ class rtm_defocus_params(C.Structure):  # include/rtm.h: rtm_defocus (12 bytes)
 DEFOCUS_DEFAULTS = {"aperture": 4.0, "max_radius": 8}  # RTM_DEFOCUS_DEFAULTS; the caller sets focus_distance
 
 
+class rtm_grade_params(C.Structure):  # include/rtm.h: rtm_grade (120 bytes)
+    _fields_ = [("matrix", C.c_float * 9), ("exposure", C.c_float), ("contrast", C.c_float), ("pivot", C.c_float),
+                ("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("saturation", C.c_float),
+                ("lut_size", C.c_int32), ("lut_interp", C.c_int32), ("lut_min", C.c_float * 3), ("lut_max", C.c_float * 3)]
+
+
+GRADE_INTERPS = ("trilinear", "tetrahedral")  # RTM_GRADE_TRILINEAR, RTM_GRADE_TETRAHEDRAL
+# RTM_GRADE_DEFAULTS; matrix None is the identity
+GRADE_DEFAULTS = {"matrix": None, "exposure": 0.0, "contrast": 1.0, "pivot": 0.18, "slope": 1.0, "offset": 0.0, "power": 1.0,
+                  "saturation": 1.0}
+
+
 class rtm_lens_params(C.Structure):  # include/rtm.h: rtm_lens (48 bytes)
     _fields_ = [("k1", C.c_float), ("k2", C.c_float), ("zoom", C.c_float), ("chroma", C.c_float), ("vignette", C.c_float),
                 ("falloff", C.c_float), ("border", C.c_float * 3), ("mode", C.c_int32), ("filter", C.c_int32),
@@ -211,6 +223,11 @@ SIGNATURES = {
                             C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_defocus": (C.c_int, [_P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_grade": (C.c_int, [_P(rtm_grade_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p]),
+    "rtm_grade_white_balance": (C.c_int, [C.c_float, C.c_float, _P(C.c_float)]),
+    "rtm_lut_parse_cube": (C.c_int, [C.c_char_p, C.c_size_t, _P(C.c_int32), _P(C.c_float), _P(C.c_float), C.c_void_p, C.c_size_t]),
+    "rtm_lut_load_cube": (C.c_int, [C.c_char_p, _P(C.c_int32), _P(C.c_float), _P(C.c_float), C.c_void_p, C.c_size_t]),
     "rtm_lens": (C.c_int, [_P(rtm_lens_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_lens_fit_zoom": (C.c_int, [_P(rtm_lens_params), C.c_int32, C.c_int32, _P(C.c_float)]),
     "rtm_resize_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -134,6 +134,20 @@ int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int
               float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream) {
     RTM_GUARD(rtm::bloom(params, width, height, device, color_dev, work_dev, out_f32_dev, out_u8_dev, bloom_out_dev, stream))
 }
+int rtm_grade(const rtm_grade_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+              const float* lut_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
+    RTM_GUARD(rtm::grade(params, width, height, device, color_dev, lut_dev, out_f32_dev, out_u8_dev, stream))
+}
+int rtm_grade_white_balance(float kelvin, float tint, float matrix_out[9]) {
+    RTM_GUARD(rtm::grade_white_balance(kelvin, tint, matrix_out))
+}
+int rtm_lut_parse_cube(const char* text, size_t len, int32_t* size, float domain_min[3], float domain_max[3], float* table,
+                       size_t capacity) {
+    RTM_GUARD(rtm::lut_parse_cube(text, len, size, domain_min, domain_max, table, capacity))
+}
+int rtm_lut_load_cube(const char* path, int32_t* size, float domain_min[3], float domain_max[3], float* table, size_t capacity) {
+    RTM_GUARD(rtm::lut_load_cube(path, size, domain_min, domain_max, table, capacity))
+}
 int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream) {
     RTM_GUARD(rtm::defocus(params, width, height, device, color_dev, depth_dev, out_f32_dev, out_u8_dev, coc_out_dev, stream))

@@ -78,6 +78,13 @@ int tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int
 size_t bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
 int bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color, void* work, float* out32,
           uint8_t* out8, float* bloom_out, void* stream);
+// colour grade (rtm_grade.hip), and its host-only helpers: the white balance matrix and the .cube reader (rtm_lut.cpp)
+int grade(const rtm_grade_params* params, int32_t width, int32_t height, int device, const float* color, const float* lut,
+          float* out32, uint8_t* out8, void* stream);
+int grade_white_balance(float kelvin, float tint, float* matrix_out);
+int lut_parse_cube(const char* text, size_t len, int32_t* size, float* domain_min, float* domain_max, float* table,
+                   size_t capacity);
+int lut_load_cube(const char* path, int32_t* size, float* domain_min, float* domain_max, float* table, size_t capacity);
 // depth of field (rtm_defocus.hip); the probe runs one form of the kernel (rtm_debug_defocus_form)
 int defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color, const float* depth,
             float* out32, uint8_t* out8, float* coc_out, void* stream);

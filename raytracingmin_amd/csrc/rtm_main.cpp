@@ -14,6 +14,12 @@
 //                                                (the display transform of the last stage: STEM_display.bmp, .jpg)
 //           [--bloom [INTENSITY]] [--bloom-threshold T] [--bloom-levels L]
 //                                                (with --display: bloom the frame before the display transform)
+//           [--grade-temperature K] [--grade-tint T] [--grade-exposure EV] [--grade-contrast C[,PIVOT]]
+//           [--grade-slope R,G,B|S] [--grade-offset R,G,B|S] [--grade-power R,G,B|S] [--grade-saturation S]
+//                                                (with --display: the colour grade of the frame, in linear light after --bloom
+//                                                and before the display transform)
+//           [--lut FILE.cube] [--lut-interp trilinear|tetrahedral]
+//                                                (with --display: a look LUT applied to the display transform's float frame)
 //           [--dof [APERTURE]] [--focus DISTANCE | --focus-pixel X,Y] [--dof-radius R]
 //                                                (depth of field of the last stage by the depth plane: STEM_dof.bmp, .jpg; the
 //                                                defocused frame then is the last stage's for what follows)
@@ -129,6 +135,17 @@ static void usage() {
         "            is given (rtm_bloom: a bright pass above luminance T, default 1, a pyramid of L levels, 1..8, default 6, and\n"
         "            INTENSITY, default 0.2, times the result added back in linear space): STEM_display.*, STEM_preview_display.*,\n"
         "            STEM_over_display.*, --display-pfm and what --flip sees are those of the bloomed frame\n"
+        "--grade-temperature K [--grade-tint T] --grade-exposure EV --grade-contrast C[,PIVOT] --grade-slope R,G,B|S\n"
+        "            --grade-offset R,G,B|S --grade-power R,G,B|S --grade-saturation S : with --display, grade every frame the\n"
+        "            display transform is given (rtm_grade, in linear light after --bloom): white balance from a source at K kelvin\n"
+        "            (1667..25000, tint T in [-0.05, 0.05], rtm_grade_white_balance) to D65, exposure in stops (|EV| <= 32), contrast\n"
+        "            C in [0.25, 4] about PIVOT (default 0.18), the ASC CDL's slope (>= 0), offset and power ([0.1, 10]), one number\n"
+        "            or three, saturation in [0, 4]; what is not given stays at its default and is skipped\n"
+        "--lut FILE.cube [--lut-interp trilinear|tetrahedral] : with --display, a display-referred look: the 3D LUT of the .cube\n"
+        "            file (rtm_lut_load_cube) applied to the display transform's float frame (rtm_grade; default tetrahedral); the\n"
+        "            8-bit files are then made from its result by a second rtm_tonemap that only clamps and dithers.\n"
+        "            STEM_display.*, STEM_preview_display.*, STEM_over_display.*, --display-pfm and what --flip sees are those\n"
+        "            of the graded frame\n"
         "--dof [APERTURE] [--focus DISTANCE | --focus-pixel X,Y] [--dof-radius R] : also write the depth of field (rtm_defocus) of\n"
         "            the last stage asked for on one GPU, by the frame's depth plane: STEM_dof.bmp and STEM_dof.jpg.  APERTURE: the\n"
         "            blur radius, in pixels, of a point at infinity (default 4); --dof-radius R : the largest radius, 1..16 (default\n"
@@ -197,6 +214,11 @@ int main(int argc, char* argv[]) {
     rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
     int bloom = 0;
     rtm_bloom_params bloom_prm = RTM_BLOOM_DEFAULTS;
+    int grade = 0, grade_temperature_given = 0, grade_tint_given = 0, lut_interp_given = 0;
+    float grade_kelvin = 6504.0f, grade_tint = 0.0f;
+    rtm_grade_params grade_prm = RTM_GRADE_DEFAULTS;
+    std::string lut_file;
+    rtm_node_lut look = {RTM_GRADE_DEFAULTS, {}};
     int dof = 0, focus_given = 0, focus_pixel_given = 0, dof_radius_given = 0, focus_x = 0, focus_y = 0;
     rtm_defocus_params dof_prm = RTM_DEFOCUS_DEFAULTS;
     int lens = 0, lens_inverse = 0, lens_filter_given = 0, lens_zoom_auto = 0;
@@ -292,6 +314,79 @@ int main(int argc, char* argv[]) {
                              c == "--bloom-levels" ? "a number of levels in 1..8" : "a finite number that is not negative", m.c_str());
                 return 2;
             }
+        }
+        else if (c.rfind("--grade-", 0) == 0) {
+            // one number, or for the CDL's three one or three (R,G,B), or C[,PIVOT]: all of the text, in range once rounded to float
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            float v[3] = {0.0f, 0.0f, 0.0f};
+            int count = 0;
+            bool ok = true;
+            for (size_t b = 0; ok && b <= m.size();) {
+                const size_t e = std::min(m.find(',', b), m.size());
+                double d = 0.0;
+                ok = count < 3 && parse_number(m.substr(b, e - b), d) && std::isfinite(v[count] = (float)d);  // (double first)
+                ++count;
+                b = e + 1;
+            }
+            const auto three = [&](float* dst, float lo, float hi) {
+                ok = ok && (count == 1 || count == 3);
+                for (int k = 0; ok && k < 3; ++k) {
+                    dst[k] = v[count == 1 ? 0 : k];
+                    ok = dst[k] >= lo && dst[k] <= hi;
+                }
+            };
+            const char* takes = "a finite number";
+            if (c == "--grade-temperature") {
+                takes = "a number of kelvin in [1667, 25000]";
+                ok = ok && count == 1 && v[0] >= 1667.0f && v[0] <= 25000.0f;
+                grade_kelvin = v[0];
+                grade_temperature_given = 1;
+            } else if (c == "--grade-tint") {
+                takes = "a number in [-0.05, 0.05]";
+                ok = ok && count == 1 && v[0] >= -0.05f && v[0] <= 0.05f;
+                grade_tint = v[0];
+                grade_tint_given = 1;
+            } else if (c == "--grade-exposure") {
+                takes = "a number of stops in [-32, 32]";
+                ok = ok && count == 1 && v[0] >= -32.0f && v[0] <= 32.0f;
+                grade_prm.exposure = v[0];
+            } else if (c == "--grade-contrast") {
+                takes = "C[,PIVOT] with C in [0.25, 4] and PIVOT positive";
+                ok = ok && count <= 2 && v[0] >= 0.25f && v[0] <= 4.0f && (count == 1 || v[1] > 0.0f);
+                grade_prm.contrast = v[0];
+                if (count == 2) grade_prm.pivot = v[1];
+            } else if (c == "--grade-slope") {
+                takes = "one number or R,G,B, none negative";
+                three(grade_prm.slope, 0.0f, INFINITY);
+            } else if (c == "--grade-offset") {
+                takes = "one finite number or R,G,B";
+                three(grade_prm.offset, -INFINITY, INFINITY);
+            } else if (c == "--grade-power") {
+                takes = "one number or R,G,B in [0.1, 10]";
+                three(grade_prm.power, 0.1f, 10.0f);
+            } else if (c == "--grade-saturation") {
+                takes = "a number in [0, 4]";
+                ok = ok && count == 1 && v[0] >= 0.0f && v[0] <= 4.0f;
+                grade_prm.saturation = v[0];
+            } else {
+                std::fprintf(stderr, "unknown option %s\n", c.c_str());
+                return 2;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "%s takes %s, got %s\n", c.c_str(), takes, m.c_str());
+                return 2;
+            }
+            grade = 1;
+        } else if (c == "--lut" && i + 1 < argc) {
+            lut_file = argv[++i];
+        } else if (c == "--lut-interp") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m != "trilinear" && m != "tetrahedral") {
+                std::fprintf(stderr, "--lut-interp takes trilinear or tetrahedral, got %s\n", m.c_str());
+                return 2;
+            }
+            lut_interp_given = 1;
+            look.params.lut_interp = m == "trilinear" ? RTM_GRADE_TRILINEAR : RTM_GRADE_TETRAHEDRAL;
         }
         else if (c == "--dof" || c == "--focus" || c == "--dof-radius") {
             // a number, all of it; --dof alone may stand without one (anything that is not a number is the next option)
@@ -495,6 +590,8 @@ int main(int argc, char* argv[]) {
         {denoise && many, "--denoise runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
         {denoise_variance && many,
          "--denoise-variance runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {(grade || !lut_file.empty()) && many,
+         "--grade-... and --lut run on one GPU: they do not combine with --gpus > 1, --virtual-strips or --force-rccl"},
         {display && many, "--display runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
         {preview_only && preview == 0, "--preview-only requires --preview F"},
         {preview != 0 && (preview < 2 || preview > 8), bad_preview.c_str()},
@@ -510,6 +607,10 @@ int main(int argc, char* argv[]) {
          "--display-pfm writes the display transform's float frame of the full render: it requires --display and does not combine "
          "with --preview-only"},
         {bloom && !display, "--bloom blooms the frame the display transform shows: it requires --display"},
+        {grade && !display, "--grade-... grades the frame the display transform shows: it requires --display"},
+        {!lut_file.empty() && !display, "--lut is a look on the display transform's frame: it requires --display"},
+        {lut_interp_given && lut_file.empty(), "--lut-interp requires --lut FILE.cube"},
+        {grade_tint_given && !grade_temperature_given, "--grade-tint shifts the white of a temperature: it requires --grade-temperature K"},
         {(focus_given || focus_pixel_given || dof_radius_given) && !dof, "--focus, --focus-pixel and --dof-radius require --dof"},
         {focus_given && focus_pixel_given, "--dof focuses at --focus DISTANCE or at --focus-pixel X,Y, not at both"},
         {dof && many, "--dof runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
@@ -588,6 +689,27 @@ int main(int argc, char* argv[]) {
     std::vector<float> reference, flip_reference;
     if (!compare_ref.empty() && !read_reference("--compare", compare_ref, st, reference)) return 1;
     if (!flip_ref.empty() && !read_reference("--flip", flip_ref, st, flip_reference)) return 1;
+    // --lut: read before anything is rendered, like the references; --grade-temperature: the matrix (host only)
+    if (!lut_file.empty()) {
+        int32_t n3 = 0;
+        rc = rtm_lut_load_cube(lut_file.c_str(), &n3, look.params.lut_min, look.params.lut_max, nullptr, 0);
+        if (rc == RTM_OK) {
+            look.table.resize((size_t)3 * n3 * n3 * n3);
+            rc = rtm_lut_load_cube(lut_file.c_str(), &n3, look.params.lut_min, look.params.lut_max, look.table.data(), look.table.size());
+        }
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "--lut: %s: %s (%s)\n", lut_file.c_str(), rtm_strerror(rc), rtm_last_error_detail());
+            return 1;
+        }
+        look.params.lut_size = n3;
+    }
+    if (grade_temperature_given) {
+        rc = rtm_grade_white_balance(grade_kelvin, grade_tint, grade_prm.matrix);
+        if (rc != RTM_OK) {
+            std::fprintf(stderr, "--grade-temperature: %s (%s)\n", rtm_strerror(rc), rtm_last_error_detail());
+            return 2;
+        }
+    }
     // a later stage takes the float frame of the last one
     const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof || lens || resize;
     if (dof) {  // the focus, known before anything is rendered: --focus, what --focus-pixel shows, else the camera's target
@@ -625,7 +747,22 @@ int main(int argc, char* argv[]) {
     if (bloom)
         std::printf("bloom: threshold %.6g, knee %.6g, intensity %.6g, scatter %.6g, levels %d\n", (double)bloom_prm.threshold,
                     (double)bloom_prm.knee, (double)bloom_prm.intensity, (double)bloom_prm.scatter, bloom_prm.levels);
-    // --display of one frame: bloomed first with --bloom, then STEM<suffix>_display.bmp / .jpg and their line, which gives
+    if (grade) {
+        std::printf("grade:");
+        if (grade_temperature_given) std::printf(" temperature %.9g, tint %.9g,", (double)grade_kelvin, (double)grade_tint);
+        std::printf(" exposure %.9g, contrast %.9g at pivot %.9g, slope %.9g %.9g %.9g, offset %.9g %.9g %.9g, power %.9g %.9g %.9g, "
+                    "saturation %.9g\n",
+                    (double)grade_prm.exposure, (double)grade_prm.contrast, (double)grade_prm.pivot, (double)grade_prm.slope[0],
+                    (double)grade_prm.slope[1], (double)grade_prm.slope[2], (double)grade_prm.offset[0], (double)grade_prm.offset[1],
+                    (double)grade_prm.offset[2], (double)grade_prm.power[0], (double)grade_prm.power[1], (double)grade_prm.power[2],
+                    (double)grade_prm.saturation);
+    }
+    if (!lut_file.empty())
+        std::printf("lut: %s, size %d, %s, domain %.9g %.9g %.9g to %.9g %.9g %.9g\n", lut_file.c_str(), look.params.lut_size,
+                    look.params.lut_interp == RTM_GRADE_TRILINEAR ? "trilinear" : "tetrahedral", (double)look.params.lut_min[0],
+                    (double)look.params.lut_min[1], (double)look.params.lut_min[2], (double)look.params.lut_max[0],
+                    (double)look.params.lut_max[1], (double)look.params.lut_max[2]);
+    // --display of one frame: bloomed first with --bloom, graded with --grade-..., then STEM<suffix>_display.bmp / .jpg and their line, which gives
     // the statistics for the frame itself (no suffix); the exit status, 0 when all went well
     const auto show = [&](const rtm_settings& fs, const float* frame, const std::string& suffix, std::vector<float>* f32_out) {
         std::string err;
@@ -635,9 +772,16 @@ int main(int argc, char* argv[]) {
             if (brc != RTM_OK) return fail("bloom", brc, err);
             frame = bloomed.data();
         }
+        std::vector<float> graded;
+        if (grade) {
+            const int grc = rtm_node_grade(&fs, opt.device, &grade_prm, frame, &graded, err);
+            if (grc != RTM_OK) return fail("grade", grc, err);
+            frame = graded.data();
+        }
         rtm_tonemap_stats ts;
         const std::string name = stem + suffix;
-        const int drc = rtm_node_write_display(&fs, opt.device, &display_prm, frame, name, &ts, err, f32_out);
+        const int drc = rtm_node_write_display(&fs, opt.device, &display_prm, frame, name, &ts, err, f32_out,
+                                               lut_file.empty() ? nullptr : &look);
         if (drc != RTM_OK) return fail("display", drc, err);
         if (suffix.empty())
             std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",

@@ -606,9 +606,11 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
     return write_denoised(true, st, objects, n, opt, f32_host, stem, err, f32_out);
 }
 
-// --display (rtm_node.h): rtm_tonemap of the frame on the default stream, then the two files.
+// --display (rtm_node.h): rtm_tonemap of the frame on the default stream, with --lut the look and the second rtm_tonemap
+// behind it, then the two files.
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* prm, const float* f32_host,
-                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err, std::vector<float>* f32_out) {
+                           const std::string& stem, rtm_tonemap_stats* stats, std::string& err, std::vector<float>* f32_out,
+                           const rtm_node_lut* lut) {
     const size_t pix = (size_t)st->width * st->height;
     std::vector<uint8_t> rgb8(pix * 3);
     rtm_tonemap_stats got;
@@ -618,21 +620,48 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
         const size_t work_bytes = rtm_tonemap_work_bytes(st->width, st->height);
         DevBuf<float> color;
         DevBuf<uint8_t> out8;
-        DevBuf<float> out32;  // only when f32_out is asked for
+        DevBuf<float> out32;  // only when f32_out is asked for, or the look takes it
+        DevBuf<float> table;  // only with a look
         DevBuf<void> work;    // hipMalloc's alignment is 256 bytes or more, what rtm_tonemap asks of work_dev
         DevBuf<rtm_tonemap_stats> stats_dev;
-        if (!color.alloc(pix * 3) || !out8.alloc(pix * 3) || !out32.alloc(pix * 3, f32_out != nullptr) || !work.alloc(work_bytes) ||
-            !stats_dev.alloc(1))
+        if (!color.alloc(pix * 3) || !out8.alloc(pix * 3) || !out32.alloc(pix * 3, f32_out != nullptr || lut != nullptr) ||
+            !table.alloc(lut ? lut->table.size() : 0, lut != nullptr) || !work.alloc(work_bytes) || !stats_dev.alloc(1))
             return fail(err, RTM_ERR_HIP, "no device memory for the display transform's buffers");
         if (!color.upload(f32_host, pix * 3)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
-        const int rc = rtm_tonemap(prm, st->width, st->height, device, color.get(), work.get(), out32.get(), out8.get(), stats_dev.get(),
-                                   nullptr);
+        if (lut && !table.upload(lut->table.data(), lut->table.size())) return fail(err, RTM_ERR_HIP, "copying the LUT to the device failed");
+        int rc = rtm_tonemap(prm, st->width, st->height, device, color.get(), work.get(), out32.get(), lut ? nullptr : out8.get(),
+                             stats_dev.get(), nullptr);
+        if (rc == RTM_OK && lut) {
+            rtm_tonemap_params store = RTM_TONEMAP_DEFAULTS;  // the look's frame to 8 bits: clamp and dither, nothing else
+            store.op = RTM_TONEMAP_CLAMP;
+            store.transfer = RTM_TRANSFER_LINEAR;
+            store.auto_exposure = 0;
+            store.ev = 0.0f;
+            store.dither = prm->dither;
+            rc = rtm_grade(&lut->params, st->width, st->height, device, out32.get(), table.get(), out32.get(), nullptr, nullptr);
+            if (rc == RTM_OK)
+                rc = rtm_tonemap(&store, st->width, st->height, device, out32.get(), work.get(), out32.get(), out8.get(), nullptr, nullptr);
+        }
         if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
         if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, pix * 3), pix * 3) || !stats_dev.download(&got, 1))
             return fail(err, RTM_ERR_HIP, "copying the display frame back failed");
     }
     if (stats) *stats = got;
     if (!write_jpg_bmp(stem + "_display", st, rgb8.data())) return fail(err, RTM_ERR_IO, "cannot write the display files of " + stem);
+    return RTM_OK;
+}
+
+// --grade-... (rtm_node.h): rtm_grade of the frame, in place, on the default stream.
+int rtm_node_grade(const rtm_settings* st, int device, const rtm_grade_params* prm, const float* f32_host,
+                   std::vector<float>* f32_out, std::string& err) {
+    if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+    const size_t vals = (size_t)st->width * st->height * 3;
+    DevBuf<float> color;
+    if (!color.alloc(vals)) return fail(err, RTM_ERR_HIP, "no device memory for the grade's buffer");
+    if (!color.upload(f32_host, vals)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+    const int rc = rtm_grade(prm, st->width, st->height, device, color.get(), nullptr, color.get(), nullptr, nullptr);
+    if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+    if (!color.download(sized(f32_out, vals), vals)) return fail(err, RTM_ERR_HIP, "copying the graded frame back failed");
     return RTM_OK;
 }
 

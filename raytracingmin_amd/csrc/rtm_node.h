@@ -52,9 +52,21 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
 // written next to the image: <stem>_display.jpg (quality 60) and <stem>_display.bmp.  stats (nullable) receives the frame
 // statistics and the exposure that was applied; f32_out (nullable) the transform's float frame (rtm_tonemap's out_f32), for a
 // stage that follows (--flip, --display-pfm).
+// lut (nullable, rtm_cli --lut): a display-referred look.  The table is copied to the device, rtm_grade applies it in place
+// to the transform's float frame, and the 8-bit files and f32_out are made from that frame by a second rtm_tonemap call
+// that only clamps and dithers: {CLAMP, LINEAR, no auto exposure, ev 0, params->dither}.
+struct rtm_node_lut {
+    rtm_grade_params params;   // RTM_GRADE_DEFAULTS but for lut_size, lut_interp, lut_min, lut_max
+    std::vector<float> table;  // 3 lut_size^3 floats in .cube order
+};
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* params, const float* f32_host,
                            const std::string& stem, rtm_tonemap_stats* stats, std::string& err,
-                           std::vector<float>* f32_out = nullptr);
+                           std::vector<float>* f32_out = nullptr, const rtm_node_lut* lut = nullptr);
+// The parametric colour grade (rtm_grade without a LUT, rtm_cli --grade-...) of a float frame (HOST, height x width x 3) on
+// device `device`: the frame is copied to the device, graded in place by one call on the default stream and copied back
+// into f32_out, for the display transform that follows.
+int rtm_node_grade(const rtm_settings* st, int device, const rtm_grade_params* params, const float* f32_host,
+                   std::vector<float>* f32_out, std::string& err);
 // Bloom (rtm_bloom, rtm_cli --bloom) of a float frame (HOST, height x width x 3) on device `device`: the frame is copied to the
 // device, bloomed in place by one call on the default stream and copied back into f32_out, for the display transform that
 // follows.

@@ -558,7 +558,7 @@ class Renderer:
         return out, self.stats
 
     def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False,
-               dof=None, resize=None, lens=None):
+               dof=None, resize=None, lens=None, grade=None, lut=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -575,6 +575,11 @@ class Renderer:
         bloom=True (or a dict of bloom()'s parameters: threshold, knee, intensity, scatter, levels) blooms every frame the
         display transform is given (write_display's bloom), so the _display, _over_display and _preview_display files are
         those of the bloomed last stage.  It needs tonemap: linear HDR through the reference's quantiser would only clip.
+        grade=None or False: no grade.  grade (a dict of grade()'s parametric arguments: matrix, exposure, contrast, pivot,
+        slope, offset, power, saturation, with temperature and tint as a shorthand for white_balance's matrix) grades every
+        frame the display transform is given, in linear light after the bloom (write_display's grade).  lut (the path of a
+        .cube file, or load_cube's dict) is a display-referred look applied to the display transform's float frame
+        (write_display's lut).  Both need tonemap; a file that does not load raises before anything is rendered.
         dof=None or False: no depth of field.  dof=True (or a dict of focus_distance or focus_pixel, aperture, max_radius:
         write_dof's parameters) also writes
         <fileName>_dof.bmp and <fileName>_dof.jpg (q=60): the last stage asked for (variance-denoised, denoised, else the
@@ -638,6 +643,14 @@ class Renderer:
             if display is None:
                 raise ValueError("bloom needs tonemap: it is applied to the frame the display transform shows")
             display["bloom"] = bloom_prm  # write_display's
+        grade_prm, lut_prm = _grade_option(grade), _lut_option(lut)
+        if grade_prm is not None or lut_prm is not None:
+            if display is None:
+                raise ValueError("grade and lut need tonemap: they are applied inside the display path")
+            display["grade"] = grade_prm  # write_display's
+            if lut_prm is not None:  # (as load_cube's dict, which write_display checks again)
+                display["lut"] = {"table": lut_prm["table"], "domain_min": lut_prm["lut_domain"][0],
+                                  "domain_max": lut_prm["lut_domain"][1], "interp": lut_prm["interp"]}
         if adaptive is not None:
             if passes > 1:
                 raise ValueError("adaptive and passes > 1 do not combine")
@@ -692,21 +705,38 @@ class Renderer:
                 self.write_display(fileName + "_preview", frame=shown, **display)
         return rgb8
 
-    def write_display(self, fileName, frame=None, bloom=None, **params):
+    def write_display(self, fileName, frame=None, bloom=None, grade=None, lut=None, **params):
         """<fileName>_display.bmp and <fileName>_display.jpg (q=60): the display transform tonemap(**params) (default: the
         ACES curve at automatic exposure, sRGB, dithered) of `frame`, an (H, W, 3) float32 CUDA tensor, or of self.image
         rounded to float like out_f32 — what rtm_cli --display writes.  bloom=True (or a dict of bloom()'s parameters) blooms
-        the frame first, what rtm_cli --display --bloom writes; `frame` itself is left as it is.  Returns the (H, W, 3) uint8
-        pixels."""
+        the frame first, what rtm_cli --display --bloom writes; `frame` itself is left as it is.  grade (a dict of grade()'s
+        parametric arguments: matrix, exposure, contrast, pivot, slope, offset, power, saturation, with temperature and tint as
+        a shorthand for white_balance's matrix) grades the frame in linear light, after the bloom and before the display
+        transform: what rtm_cli --display --grade-... writes.  lut (the path of a .cube file, or load_cube's dict, which may
+        name an "interp") is a display-referred look: it is applied to the display transform's float frame, and the 8-bit
+        pixels are then made from its result by a second tonemap() that only clamps and dithers (op "clamp", transfer
+        "linear", exposure 0, the same dither): what rtm_cli --display --lut writes.  Returns the (H, W, 3) uint8 pixels."""
         import torch
         _tonemap_params(**params)
         bloom_prm = _bloom_option(bloom)
+        grade_prm = _grade_option(grade)
+        lut_prm = _lut_option(lut)
         if frame is None:
             dev = torch.device("cuda", self.device)
             frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
         if bloom_prm is not None:
             frame = _bloom(frame, **bloom_prm)["f32"]
-        rgb8 = np.ascontiguousarray(tonemap(frame, want=("u8",), **params)["u8"].cpu().numpy())
+        if grade_prm is not None:
+            frame = _grade(frame, **grade_prm)["f32"]
+        if lut_prm is None:
+            shown = tonemap(frame, want=("u8",), **params)["u8"]
+        else:
+            look = tonemap(frame, want=("f32",), **params)["f32"]
+            table = torch.from_numpy(lut_prm["table"]).to(look.device)
+            _grade(look, lut=table, lut_domain=lut_prm["lut_domain"], interp=lut_prm["interp"], out_f32=look)
+            shown = tonemap(look, op="clamp", transfer="linear", exposure=0.0, dither=params.get("dither", TONEMAP_DEFAULTS["dither"]),
+                            want=("u8",))["u8"]
+        rgb8 = np.ascontiguousarray(shown.cpu().numpy())
         L = _lib.lib()
         H, W = rgb8.shape[:2]  # the frame's own size: the render's, unless it was resized
         ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_display.jpg"), W, H, 3, rgb8.ctypes.data, 60)
@@ -1551,6 +1581,205 @@ def lens(color, k1=LENS_DEFAULTS["k1"], k2=LENS_DEFAULTS["k2"], zoom=LENS_DEFAUL
 
 
 _lens = lens  # for Renderer's methods, whose own parameter is named lens
+
+
+# include/rtm.h: RTM_GRADE_DEFAULTS and the RTM_GRADE_* interpolations, by name
+GRADE_DEFAULTS = dict(_lib.GRADE_DEFAULTS)
+GRADE_INTERPS = _lib.GRADE_INTERPS
+_GRADE_OPTION_KEYS = tuple(GRADE_DEFAULTS) + ("temperature", "tint")
+_LUT_KEYS = ("table", "domain_min", "domain_max", "size", "interp")
+
+
+def _is_number(v):
+    return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool)
+
+
+def _f32(v):
+    with np.errstate(over="ignore", under="ignore"):
+        return np.float32(v)  # as the library sees it: rounded to float
+
+
+def _grade_three(name, v, what):
+    """A number or three as three float32; the ValueError names `what` is asked of them."""
+    try:
+        a = np.asarray(v)
+        if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+            raise TypeError
+        with np.errstate(over="ignore", under="ignore"):
+            return np.ascontiguousarray(np.broadcast_to(a.astype(np.float32), (3,)))
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} is {what}, one number or three, got {v!r}") from None
+
+
+def _grade_params(matrix=GRADE_DEFAULTS["matrix"], exposure=GRADE_DEFAULTS["exposure"], contrast=GRADE_DEFAULTS["contrast"],
+                  pivot=GRADE_DEFAULTS["pivot"], slope=GRADE_DEFAULTS["slope"], offset=GRADE_DEFAULTS["offset"],
+                  power=GRADE_DEFAULTS["power"], saturation=GRADE_DEFAULTS["saturation"], lut_size=0,
+                  lut_domain=((0, 0, 0), (1, 1, 1)), interp="tetrahedral"):
+    """grade()'s parameters as an rtm_grade_params; a ValueError names what the library would refuse.  No device use."""
+    if not isinstance(interp, str) or interp not in GRADE_INTERPS:
+        raise ValueError(f"interp is one of {GRADE_INTERPS}, got {interp!r}")
+    prm = _lib.rtm_grade_params()
+    if matrix is None:
+        m = np.eye(3, dtype=np.float32)
+    else:
+        try:
+            m = np.asarray(matrix)
+            if m.dtype == np.bool_ or not (np.issubdtype(m.dtype, np.integer) or np.issubdtype(m.dtype, np.floating)) or m.shape != (3, 3):
+                raise TypeError
+            with np.errstate(over="ignore", under="ignore"):
+                m = np.ascontiguousarray(m.astype(np.float32))
+        except (TypeError, ValueError):
+            raise ValueError(f"matrix is None or a 3 x 3 array of finite numbers, got {matrix!r}") from None
+        if not np.all(np.isfinite(m)):
+            raise ValueError(f"matrix is None or a 3 x 3 array of finite numbers, got {matrix!r}")
+    C.memmove(prm.matrix, m.ctypes.data, 36)
+    ranges = (("exposure", exposure, -32.0, 32.0, "a number of stops in [-32, 32]"),
+              ("contrast", contrast, 0.25, 4.0, "a number in [0.25, 4]"),
+              ("pivot", pivot, None, None, "a finite positive number"),
+              ("saturation", saturation, 0.0, 4.0, "a number in [0, 4]"))
+    for name, v, lo, hi, what in ranges:
+        f = _f32(v) if _is_number(v) else None
+        if f is None or not np.isfinite(f) or (lo is not None and not np.float32(lo) <= f <= np.float32(hi)) or (lo is None and not f > 0):
+            raise ValueError(f"{name} is {what}, got {v!r}")
+        setattr(prm, name, float(f))
+    s = _grade_three("slope", slope, "finite and not negative")
+    o = _grade_three("offset", offset, "finite")
+    p = _grade_three("power", power, "in [0.1, 10]")
+    if not (np.all(np.isfinite(s)) and np.all(s >= 0)):
+        raise ValueError(f"slope is finite and not negative, one number or three, got {slope!r}")
+    if not np.all(np.isfinite(o)):
+        raise ValueError(f"offset is finite, one number or three, got {offset!r}")
+    if not np.all((p >= np.float32(0.1)) & (p <= np.float32(10.0))):
+        raise ValueError(f"power is in [0.1, 10], one number or three, got {power!r}")
+    for field, words in ((prm.slope, s), (prm.offset, o), (prm.power, p)):
+        C.memmove(field, words.ctypes.data, 12)
+    if isinstance(lut_size, bool) or not isinstance(lut_size, (int, np.integer)) or not (lut_size == 0 or 2 <= lut_size <= 256):
+        raise ValueError(f"the lut's size is in 2..256, got {lut_size!r}")
+    try:
+        lo, hi = lut_domain
+        lo, hi = _grade_three("lut_domain's min", lo, "finite"), _grade_three("lut_domain's max", hi, "finite")
+    except (TypeError, ValueError):
+        raise ValueError(f"lut_domain is (min, max), each a finite number or three, with max > min, got {lut_domain!r}") from None
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(hi > lo)):
+        raise ValueError(f"lut_domain is (min, max), each a finite number or three, with max > min, got {lut_domain!r}")
+    C.memmove(prm.lut_min, lo.ctypes.data, 12)
+    C.memmove(prm.lut_max, hi.ctypes.data, 12)
+    prm.lut_size, prm.lut_interp = int(lut_size), GRADE_INTERPS.index(interp)
+    return prm
+
+
+def white_balance(kelvin, tint=0.0):
+    """The 3 x 3 float32 matrix (row-major, for grade()'s `matrix`) that takes a scene lit by a black body at `kelvin` to D65
+    (include/rtm.h: rtm_grade_white_balance): the Bradford adaptation from that white to D65 in linear Rec.709 primaries.
+    kelvin in [1667, 25000]; tint in [-0.05, 0.05] moves the source white along v of CIE 1960 (u, v), positive towards
+    green.  Host only: no device use."""
+    if not _is_number(kelvin) or not 1667.0 <= _f32(kelvin) <= 25000.0:
+        raise ValueError(f"kelvin is a number in [1667, 25000], got {kelvin!r}")
+    if not _is_number(tint) or not np.float32(-0.05) <= _f32(tint) <= np.float32(0.05):
+        raise ValueError(f"tint is a number in [-0.05, 0.05], got {tint!r}")
+    m = (C.c_float * 9)()
+    _lib.check(_lib.lib().rtm_grade_white_balance(float(_f32(kelvin)), float(_f32(tint)), m), "rtm_grade_white_balance")
+    return np.array(m, dtype=np.float32).reshape(3, 3)
+
+
+def load_cube(path):
+    """A 3D LUT from a .cube file (include/rtm.h: rtm_lut_load_cube): a dict of "table", an (N, N, N, 3) float32 NumPy array
+    indexed [b][g][r] (the file's order, red fastest), "domain_min" and "domain_max" (three floats each) and "size" N.
+    RtmError names the line of a file that does not parse.  Host only: no device use."""
+    L = _lib.lib()
+    name = os.fsencode(path)
+    n = C.c_int32()
+    lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
+    _lib.check(L.rtm_lut_load_cube(name, C.byref(n), lo, hi, None, 0), f"rtm_lut_load_cube({os.fsdecode(name)})")
+    table = np.empty((n.value, n.value, n.value, 3), dtype=np.float32)
+    _lib.check(L.rtm_lut_load_cube(name, C.byref(n), lo, hi, table.ctypes.data, table.size), f"rtm_lut_load_cube({os.fsdecode(name)})")
+    return {"table": table, "domain_min": tuple(float(v) for v in lo), "domain_max": tuple(float(v) for v in hi), "size": int(n.value)}
+
+
+def _grade_option(grade):
+    """Render's and write_display's `grade`: None (or False) for off, else the dict of grade()'s parametric arguments (True:
+    the defaults), checked, with temperature and tint replaced by white_balance's matrix.  No device use."""
+    if grade is None or grade is False:
+        return None
+    if grade is not True and not isinstance(grade, dict):
+        raise ValueError(f"grade is None, False, True or a dict of {_GRADE_OPTION_KEYS}, got {grade!r}")
+    prm = {} if grade is True else dict(grade)
+    unknown = set(prm) - set(_GRADE_OPTION_KEYS)
+    if unknown:
+        raise ValueError(f"grade's parameters are {_GRADE_OPTION_KEYS}, got {sorted(unknown)}")
+    if "temperature" in prm or "tint" in prm:
+        if "temperature" not in prm:
+            raise ValueError("tint shifts the white of a temperature: give temperature too")
+        if prm.get("matrix") is not None:
+            raise ValueError("grade takes a matrix or a temperature, not both")
+        prm["matrix"] = white_balance(prm.pop("temperature"), prm.pop("tint", 0.0))
+    _grade_params(**prm)
+    return prm
+
+
+def _lut_option(lut):
+    """Render's and write_display's `lut`: None for off, a path of a .cube file, or load_cube's dict (which may also name an
+    "interp" of GRADE_INTERPS), checked.  A file that does not load raises here.  No device use."""
+    if lut is None or lut is False:
+        return None
+    if isinstance(lut, (str, bytes, os.PathLike)):
+        lut = load_cube(lut)
+    if not isinstance(lut, dict):
+        raise ValueError(f"lut is None, the path of a .cube file or load_cube's dict, got {lut!r}")
+    unknown = set(lut) - set(_LUT_KEYS)
+    if unknown or "table" not in lut:
+        raise ValueError(f"a lut's keys are {_LUT_KEYS} (table is required), got {sorted(lut)}")
+    table = lut["table"]
+    if not (isinstance(table, np.ndarray) and table.dtype == np.float32 and table.ndim == 4 and table.shape[3] == 3
+            and table.shape[0] == table.shape[1] == table.shape[2] and 2 <= table.shape[0] <= 256):
+        raise ValueError("a lut's table is an (N, N, N, 3) float32 NumPy array indexed [b][g][r], N in 2..256")
+    if lut.get("size", table.shape[0]) != table.shape[0]:
+        raise ValueError(f"a lut's size is its table's, {table.shape[0]}, got {lut['size']!r}")
+    out = {"table": np.ascontiguousarray(table), "lut_domain": (lut.get("domain_min", (0, 0, 0)), lut.get("domain_max", (1, 1, 1))),
+           "interp": lut.get("interp", "tetrahedral")}
+    _grade_params(lut_size=table.shape[0], lut_domain=out["lut_domain"], interp=out["interp"])
+    return out
+
+
+def grade(color, matrix=GRADE_DEFAULTS["matrix"], exposure=GRADE_DEFAULTS["exposure"], contrast=GRADE_DEFAULTS["contrast"],
+          pivot=GRADE_DEFAULTS["pivot"], slope=GRADE_DEFAULTS["slope"], offset=GRADE_DEFAULTS["offset"], power=GRADE_DEFAULTS["power"],
+          saturation=GRADE_DEFAULTS["saturation"], lut=None, lut_domain=((0, 0, 0), (1, 1, 1)), interp="tetrahedral", want=("f32",),
+          stream=None, out_f32=None):
+    """The colour grade (include/rtm.h: rtm_grade) on the device, a per-pixel transform in this order: `matrix` (3 x 3,
+    row-major: white_balance()'s, or any change of primaries), `exposure` in stops, `contrast` as a power curve about `pivot`,
+    the ASC CDL's `slope`, `offset` and `power` (a number, or three for R, G, B), `saturation` about the Rec.709 luminance,
+    then `lut`, an (N, N, N, 3) float32 CUDA tensor indexed [b][g][r] (load_cube's table on the device) whose input domain is
+    lut_domain = (min, max), interpolated by `interp`, one of GRADE_INTERPS.  Run the parametric steps in linear light, after
+    bloom() and before tonemap(); a look LUT from a .cube file belongs on tonemap()'s "f32".  `color` is an (H, W, 3)
+    float32 torch CUDA tensor (any 4-byte-aligned contiguous view).  A step left at its default is skipped, so the defaults
+    copy the frame bit for bit; a pixel with a non-finite component is copied as it is.  Returns a dict of the names in
+    `want`: "f32" (H, W, 3) float32 and "u8" (H, W, 3) uint8 (rtm_quantise of it).  out_f32: the tensor to write "f32" into;
+    `color` itself grades in place.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the
+    current stream); nothing waits for it and nothing is copied to the host."""
+    import torch
+    n = 0
+    if lut is not None:
+        if not (isinstance(lut, torch.Tensor) and lut.dtype == torch.float32 and lut.dim() == 4 and lut.shape[3] == 3
+                and lut.shape[0] == lut.shape[1] == lut.shape[2] and 2 <= lut.shape[0] <= 256 and lut.is_contiguous()):
+            raise ValueError("lut must be a contiguous (N, N, N, 3) float32 CUDA tensor indexed [b][g][r], N in 2..256")
+        n = int(lut.shape[0])
+    prm = _grade_params(matrix, exposure, contrast, pivot, slope, offset, power, saturation, n, lut_domain, interp)
+    _check_want(want, ("f32", "u8"))
+    _need_device("grade")
+    H, W = _frame_size(color, "color", non_empty=True)
+    dev = color.device
+    if lut is not None and lut.device != dev:
+        raise ValueError(f"lut must be a contiguous (N, N, N, 3) float32 CUDA tensor on {dev}")
+    _check_out_f32(out_f32, want, H, W, dev)
+    s = _stream_of(stream, dev)
+    specs = {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8)}
+    out, ptr = _stage_tensors(s, dev, want, specs, out_f32=out_f32)
+    _lib.check(_lib.lib().rtm_grade(C.byref(prm), W, H, dev.index, color.data_ptr(), lut.data_ptr() if lut is not None else None,
+                                    ptr("f32"), ptr("u8"), C.c_void_p(s.cuda_stream)), "rtm_grade")
+    return out
+
+
+_grade = grade  # for Renderer's methods, whose own parameter is named grade
 
 
 def tonemap_stats(words):
