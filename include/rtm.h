@@ -426,6 +426,60 @@ typedef struct rtm_composite_params {
 int rtm_composite(const rtm_composite_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                   const float* alpha_dev, const float* background_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream);
 
+/* ---- firefly: a rank-order outlier clamp and the repair of non-finite pixels — what a path tracer leaves at low sample
+ * counts: isolated pixels far brighter than everything around them, and now and then a NaN.  Opt-in, right after the render
+ * and before every other stage: the denoisers spread a firefly into a blob and a NaN over the frame, rtm_tonemap's L_max takes
+ * a firefly for the white point, rtm_bloom makes a glare star of it.  Every other stage and its defaults stay.
+ * Input: color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32; 4-byte alignment is enough).  Arithmetic in
+ * float, without contraction, in exactly this order, so that a float32 restatement reproduces every decision bit for bit.
+ *   1 counting   a pixel COUNTS iff its three components are finite.  l = (0.2126f c_R + 0.7152f c_G) + 0.0722f c_B
+ *                (rtm_tonemap's lum), Y = l > 0 ? l : +0.0f.  (No l of a counting pixel is NaN; one that overflows is +inf.)
+ *   2 neighbours q = p + (dx, dy), dx and dy in -radius..radius, q != p.  Taps outside the frame or not counting are skipped,
+ *                not clamped (the library's rule).  n is the number of taps left.
+ *   3 statistic  S is the rank-th largest Y_q over those taps, counted with multiplicity (sorted descending, index rank - 1).
+ *                A selection: exact, and ties cannot matter.  With n < rank the pixel has no statistic.
+ *   4 threshold  T = (k S) + floor, two roundings.  An overflow to +inf is kept as the float it is: nothing exceeds it.
+ *   5 decision   a counting pixel with a statistic is a FIREFLY iff Y_p > T.  Its out_f32 is c_p (T / Y_p) per channel: the
+ *                chroma is kept, the luminance is brought down to the threshold.  Y_p > T >= 0, so the divisor is positive;
+ *                the output is continuous in c_p across the threshold, so the division may be the device's fast form.  Every
+ *                other counting pixel's out_f32 is its input, bit for bit.
+ *   6 the rest   a pixel that does not count: with repair = 0 its out_f32 is its input's words; with repair = 1 it is the
+ *                per-channel mean of the counting taps' colours (the sum in float, dy outer and dx inner, then one division
+ *                by (float)n; a sum that overflows is kept as the float it is), and (+0, +0, +0) when n = 0.  Either way it
+ *                contributes to no other pixel's window.
+ *   7 outputs    mask_out_dev (nullable, height x width bytes): 0 unchanged, 1 clamped, 2 repaired (a pixel that does not
+ *                count keeps 0 with repair = 0).  threshold_out_dev (nullable, height x width floats): T, or +inf for a pixel
+ *                without a statistic or one that does not count.  out_u8 (nullable) is rtm_quantise of (double)out_f32, out
+ *                of range (NaN included) -> 0, as in the other stages.
+ * It follows that a frame in which no pixel exceeds its threshold and every pixel counts is copied bit for bit; that a
+ * constant frame is copied bit for bit (k >= 1, floor >= 0); and that the luminance of an output pixel never exceeds its
+ * input's.  With the defaults (radius 1, rank 3) every pixel of a uniformly bright axis-aligned rectangle of at least 2 x 2
+ * pixels keeps its words, however dark the surround: a convex corner pixel has three neighbours inside the rectangle.  That
+ * is why the default rank is 3: a light seen directly must not be eaten at its rim.  With the defaults a cluster of up to
+ * three fireflies is still caught (each has at most two bright neighbours).  A one-pixel-wide bright line is clamped at rank
+ * 3 and kept at rank 2 (an inner pixel of it has two bright neighbours; its two end pixels have one, and go at rank 2 too).
+ * Against a float64 evaluation of c_p (T / Y_p) from the float T and Y_p, and of the repair mean, every changed component is
+ * within 1e-4 max(1, |ref|); mask_out and threshold_out are exact; out_u8 is exact given the call's own out_f32.
+ * No atomics, no state, no work buffer: the call allocates nothing and only ENQUEUES one launch on `stream`; the same inputs
+ * give the same bits on every call, on any stream, at any 4-byte alignment.  Null params or color_dev, all four outputs
+ * null, a non-positive size, radius outside 1..3, rank outside 1..8, k NaN, infinite or below 1, floor NaN, infinite, negative
+ * or -0.0, repair outside {0, 1}, a float pointer that is not 4-byte aligned, any output equal to color_dev (a gather cannot
+ * run in place), two outputs equal to each other, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A
+ * frame of 2^31 pixels or more, or one of 2^23 or more tiles of 32 x 16 pixels (ceil(width / 32) ceil(height / 16): a launch
+ * has one 512-lane block a tile): RTM_ERR_UNSUPPORTED, as rtm_defocus.
+ * Defaults: RTM_FIREFLY_DEFAULTS below (what Renderer.Render(firefly=True) and rtm_cli --firefly use).  Added after
+ * RTM_ABI_VERSION 5 without changing it: callers look the symbol up. */
+typedef struct rtm_firefly_params { /* 20 bytes */
+    int32_t radius; /* 1..3: the window is (2 radius + 1)^2, the centre excluded                                          */
+    int32_t rank;   /* 1..8: the neighbour statistic is the rank-th LARGEST luminance (1 = the maximum)                   */
+    float k;        /* finite, >= 1: how far above that statistic a pixel may be                                          */
+    float floor;    /* finite, >= 0 (not -0.0): added to the threshold, so that dark regions keep faint detail            */
+    int32_t repair; /* 0 / 1: replace a pixel that does not count by the mean of its counting neighbours                  */
+} rtm_firefly_params;
+#define RTM_FIREFLY_DEFAULTS {1, 3, 4.0f, 0.01f, 1} /* of rtm_firefly_params */
+int rtm_firefly(const rtm_firefly_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                float* out_f32_dev, uint8_t* out_u8_dev, uint8_t* mask_out_dev, float* threshold_out_dev, void* stream);
+
 /* ---- denoiser: an edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) guided by the AOVs above, with the albedo
  * demodulated (SVGF-style) and no temporal part ----
  * Inputs: a frame of width x height pixels; color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32); the

@@ -111,6 +111,13 @@ class rtm_bloom_params(C.Structure):  # include/rtm.h: rtm_bloom (20 bytes)
                 ("levels", C.c_int32)]
 
 
+class rtm_firefly_params(C.Structure):  # include/rtm.h: rtm_firefly (20 bytes)
+    _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("k", C.c_float), ("floor", C.c_float), ("repair", C.c_int32)]
+
+
+FIREFLY_DEFAULTS = {"radius": 1, "rank": 3, "k": 4.0, "floor": 0.01, "repair": True}  # RTM_FIREFLY_DEFAULTS
+
+
 class rtm_defocus_params(C.Structure):  # include/rtm.h: rtm_defocus (12 bytes)
     _fields_ = [("focus_distance", C.c_float), ("aperture", C.c_float), ("max_radius", C.c_int32)]
 
@@ -221,6 +228,8 @@ SIGNATURES = {
     "rtm_bloom_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rtm_bloom": (C.c_int, [_P(rtm_bloom_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_firefly": (C.c_int, [_P(rtm_firefly_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_defocus": (C.c_int, [_P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_grade": (C.c_int, [_P(rtm_grade_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

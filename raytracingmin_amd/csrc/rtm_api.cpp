@@ -148,6 +148,10 @@ int rtm_lut_parse_cube(const char* text, size_t len, int32_t* size, float domain
 int rtm_lut_load_cube(const char* path, int32_t* size, float domain_min[3], float domain_max[3], float* table, size_t capacity) {
     RTM_GUARD(rtm::lut_load_cube(path, size, domain_min, domain_max, table, capacity))
 }
+int rtm_firefly(const rtm_firefly_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                float* out_f32_dev, uint8_t* out_u8_dev, uint8_t* mask_out_dev, float* threshold_out_dev, void* stream) {
+    RTM_GUARD(rtm::firefly(params, width, height, device, color_dev, out_f32_dev, out_u8_dev, mask_out_dev, threshold_out_dev, stream))
+}
 int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream) {
     RTM_GUARD(rtm::defocus(params, width, height, device, color_dev, depth_dev, out_f32_dev, out_u8_dev, coc_out_dev, stream))

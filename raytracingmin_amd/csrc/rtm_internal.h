@@ -85,6 +85,9 @@ int grade_white_balance(float kelvin, float tint, float* matrix_out);
 int lut_parse_cube(const char* text, size_t len, int32_t* size, float* domain_min, float* domain_max, float* table,
                    size_t capacity);
 int lut_load_cube(const char* path, int32_t* size, float* domain_min, float* domain_max, float* table, size_t capacity);
+// the firefly clamp and the repair of non-finite pixels (rtm_firefly.hip)
+int firefly(const rtm_firefly_params* params, int32_t width, int32_t height, int device, const float* color, float* out32,
+            uint8_t* out8, uint8_t* mask_out, float* threshold_out, void* stream);
 // depth of field (rtm_defocus.hip); the probe runs one form of the kernel (rtm_debug_defocus_form)
 int defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color, const float* depth,
             float* out32, uint8_t* out8, float* coc_out, void* stream);

@@ -8,6 +8,8 @@
 //           [--adaptive T [--adaptive-min M]]   (tile-adaptive sampling on one GPU, + STEM_spp.pfm)
 //           [--passes N]                         (progressive: the frame's samples in N passes on one GPU, same image)
 //           [--aov]                              (first-hit feature buffers next to the image: STEM_depth/_normal/_albedo.pfm, .bmp)
+//           [--firefly [K]] [--firefly-rank N] [--firefly-radius R] [--firefly-floor F] [--firefly-keep-nonfinite]
+//                                                (the firefly clamp of the frame, before every stage below: STEM_firefly.bmp, .jpg)
 //           [--denoise]                          (the à-trous denoiser next to the image: STEM_denoised.bmp, .jpg)
 //           [--denoise-variance]                 (the variance-guided one: STEM_denoised_var.bmp, .jpg, STEM_variance.pfm)
 //           [--display [clamp|reinhard|aces]] [--exposure auto|EV] [--linear] [--no-dither]
@@ -122,6 +124,14 @@ static void usage() {
         "        STEM_albedo.pfm and the quantised STEM_normal.bmp (0.5 n + 0.5), STEM_albedo.bmp\n"
         "--adaptive T [--adaptive-min M] : tile-adaptive sampling on one GPU (rtm_render_adaptive, threshold T, first pass\n"
         "             M samples, default 16); also writes STEM_spp.pfm, the samples each pixel traced\n"
+        "--firefly [K] [--firefly-rank N] [--firefly-radius R] [--firefly-floor F] [--firefly-keep-nonfinite] : also write the frame\n"
+        "            with its fireflies clamped on one GPU (rtm_firefly): STEM_firefly.bmp and STEM_firefly.jpg.  A pixel whose\n"
+        "            luminance exceeds K (default 4, at least 1) times the N-th largest luminance (1..8, default 3) among its\n"
+        "            (2R+1)^2 - 1 neighbours (R in 1..3, default 1), plus F (default 0.01, not negative), is scaled down to that\n"
+        "            threshold; a pixel with a non-finite component becomes the mean of its finite neighbours, unless\n"
+        "            --firefly-keep-nonfinite is given.  Prints one line 'firefly: {...}', the counts of clamped and repaired pixels\n"
+        "            as JSON.  The cleaned frame then is the frame every later stage takes: --denoise, --denoise-variance, --dof,\n"
+        "            --lens, --resize, --display (with --bloom), --pfm, --compare, --flip and --background\n"
         "--denoise : also write the frame denoised on one GPU (rtm_denoise at its default parameters, guided by the\n"
         "            frame's first-hit feature buffers): STEM_denoised.bmp and STEM_denoised.jpg\n"
         "--denoise-variance : also write the frame through the variance-guided denoiser on one GPU (rtm_denoise_variance at\n"
@@ -219,6 +229,8 @@ int main(int argc, char* argv[]) {
     rtm_grade_params grade_prm = RTM_GRADE_DEFAULTS;
     std::string lut_file;
     rtm_node_lut look = {RTM_GRADE_DEFAULTS, {}};
+    int firefly = 0, firefly_rank_given = 0, firefly_radius_given = 0, firefly_floor_given = 0, firefly_keep_given = 0;
+    rtm_firefly_params firefly_prm = RTM_FIREFLY_DEFAULTS;
     int dof = 0, focus_given = 0, focus_pixel_given = 0, dof_radius_given = 0, focus_x = 0, focus_y = 0;
     rtm_defocus_params dof_prm = RTM_DEFOCUS_DEFAULTS;
     int lens = 0, lens_inverse = 0, lens_filter_given = 0, lens_zoom_auto = 0;
@@ -387,6 +399,39 @@ int main(int argc, char* argv[]) {
             }
             lut_interp_given = 1;
             look.params.lut_interp = m == "trilinear" ? RTM_GRADE_TRILINEAR : RTM_GRADE_TETRAHEDRAL;
+        }
+        else if (c == "--firefly" || c == "--firefly-rank" || c == "--firefly-radius" || c == "--firefly-floor") {
+            // a number, all of it; --firefly alone may stand without one (anything that is not a number is the next option)
+            const std::string m = i + 1 < argc ? argv[i + 1] : "";
+            double v = 0.0;
+            const bool number = parse_number(m, v);
+            bool ok = number || c == "--firefly";
+            if (number) ++i;
+            const float f = (float)v;  // (double first, as Python's float() then C float)
+            if (c == "--firefly") {
+                firefly = 1;
+                if (number) ok = std::isfinite(firefly_prm.k = f) && f >= 1.0f;
+            } else if (c == "--firefly-floor") {
+                firefly_floor_given = 1;
+                if (number) ok = std::isfinite(firefly_prm.floor = f) && f >= 0.0f && !std::signbit(f);
+            } else {
+                const bool is_rank = c == "--firefly-rank";
+                (is_rank ? firefly_rank_given : firefly_radius_given) = 1;
+                ok = number && v == std::floor(v) && v >= 1.0 && v <= (is_rank ? 8.0 : 3.0);
+                if (ok) (is_rank ? firefly_prm.rank : firefly_prm.radius) = (int)v;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "%s takes %s, got %s\n", c.c_str(),
+                             c == "--firefly"          ? "a finite number that is at least 1"
+                             : c == "--firefly-floor"  ? "a finite number that is not negative (nor -0.0)"
+                             : c == "--firefly-rank"   ? "an integer in 1..8"
+                                                       : "an integer in 1..3",
+                             m.c_str());
+                return 2;
+            }
+        } else if (c == "--firefly-keep-nonfinite") {
+            firefly_keep_given = 1;
+            firefly_prm.repair = 0;
         }
         else if (c == "--dof" || c == "--focus" || c == "--dof-radius") {
             // a number, all of it; --dof alone may stand without one (anything that is not a number is the next option)
@@ -611,6 +656,10 @@ int main(int argc, char* argv[]) {
         {!lut_file.empty() && !display, "--lut is a look on the display transform's frame: it requires --display"},
         {lut_interp_given && lut_file.empty(), "--lut-interp requires --lut FILE.cube"},
         {grade_tint_given && !grade_temperature_given, "--grade-tint shifts the white of a temperature: it requires --grade-temperature K"},
+        {(firefly_rank_given || firefly_radius_given || firefly_floor_given || firefly_keep_given) && !firefly,
+         "--firefly-rank, --firefly-radius, --firefly-floor and --firefly-keep-nonfinite require --firefly"},
+        {firefly && many, "--firefly runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {firefly && preview_only, "--preview-only skips the full render: it does not combine with --firefly"},
         {(focus_given || focus_pixel_given || dof_radius_given) && !dof, "--focus, --focus-pixel and --dof-radius require --dof"},
         {focus_given && focus_pixel_given, "--dof focuses at --focus DISTANCE or at --focus-pixel X,Y, not at both"},
         {dof && many, "--dof runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
@@ -810,7 +859,7 @@ int main(int argc, char* argv[]) {
 
     const size_t vals = (size_t)st.width * st.height * 3;
     std::vector<uint8_t> rgb8(vals);
-    std::vector<float> rgb32(dump_f32.empty() && !denoise && !denoise_variance && !want_last ? 0 : vals);
+    std::vector<float> rgb32(dump_f32.empty() && !firefly && !denoise && !denoise_variance && !want_last ? 0 : vals);
     float* const out32 = rgb32.empty() ? nullptr : rgb32.data();
     rtm_stats stats;
     std::vector<uint32_t> tile_samples;
@@ -862,28 +911,37 @@ int main(int argc, char* argv[]) {
         std::printf("aov: %s_depth.pfm, %s_normal.pfm, %s_albedo.pfm, %s_normal.bmp, %s_albedo.bmp\n", stem.c_str(), stem.c_str(),
                     stem.c_str(), stem.c_str(), stem.c_str());
     }
+    std::vector<float> cleaned;  // --firefly's frame: what every stage below takes for the render's
+    if (firefly) {
+        size_t clamped = 0, repaired = 0;
+        rc = rtm_node_write_firefly(&st, opt.device, &firefly_prm, rgb32.data(), stem, err, &cleaned, &clamped, &repaired);
+        if (rc != RTM_OK) return fail("firefly", rc, err);
+        std::printf("firefly: {\"clamped\": %llu, \"repaired\": %llu, \"pixels\": %llu}\n", (unsigned long long)clamped,
+                    (unsigned long long)repaired, (unsigned long long)st.width * (unsigned long long)st.height);
+    }
+    const float* const frame32 = firefly ? cleaned.data() : rgb32.data();
     std::vector<float> shown;  // the float frame of the last stage, when --display, --pfm or --compare follows a denoiser
     if (denoise) {
-        rc = rtm_node_write_denoised(&st, spheres.data(), n, &opt, rgb32.data(), stem, err,
+        rc = rtm_node_write_denoised(&st, spheres.data(), n, &opt, frame32, stem, err,
                                      want_last && !denoise_variance ? &shown : nullptr);
         if (rc != RTM_OK) return fail("denoise", rc, err);
         std::printf("denoise: %s_denoised.bmp, %s_denoised.jpg\n", stem.c_str(), stem.c_str());
     }
     if (denoise_variance) {
-        rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, rgb32.data(), stem, err, want_last ? &shown : nullptr);
+        rc = rtm_node_write_denoised_variance(&st, spheres.data(), n, &opt, frame32, stem, err, want_last ? &shown : nullptr);
         if (rc != RTM_OK) return fail("denoise-variance", rc, err);
         std::printf("denoise-variance: %s_denoised_var.bmp, %s_denoised_var.jpg, %s_variance.pfm\n", stem.c_str(), stem.c_str(),
                     stem.c_str());
     }
     if (dof) {  // of the last stage so far; its frame then is the last stage's
         std::vector<float> defocused;
-        rc = rtm_node_write_dof(&st, spheres.data(), n, &opt, &dof_prm, shown.empty() ? rgb32.data() : shown.data(), stem, err, &defocused);
+        rc = rtm_node_write_dof(&st, spheres.data(), n, &opt, &dof_prm, shown.empty() ? frame32 : shown.data(), stem, err, &defocused);
         if (rc != RTM_OK) return fail("dof", rc, err);
         shown.swap(defocused);
     }
     if (lens) {  // of the last stage so far, in linear light; its frame then is the last stage's
         std::vector<float> through;
-        rc = rtm_node_write_lens(&st, opt.device, &lens_prm, shown.empty() ? rgb32.data() : shown.data(), stem, err, &through);
+        rc = rtm_node_write_lens(&st, opt.device, &lens_prm, shown.empty() ? frame32 : shown.data(), stem, err, &through);
         if (rc != RTM_OK) return fail("lens", rc, err);
         shown.swap(through);
         std::printf("lens: %s_lens.bmp, %s_lens.jpg (zoom %.9g)\n", stem.c_str(), stem.c_str(), (double)lens_prm.zoom);
@@ -891,7 +949,7 @@ int main(int argc, char* argv[]) {
     rtm_settings last_st = st;  // the last stage's size: the render's, unless --resize follows
     if (resize) {  // of the last stage so far, in linear light; its frame then is the last stage's
         std::vector<float> resized;
-        rc = rtm_node_write_resized(&st, opt.device, &resize_prm, resize_w, resize_h, shown.empty() ? rgb32.data() : shown.data(), stem,
+        rc = rtm_node_write_resized(&st, opt.device, &resize_prm, resize_w, resize_h, shown.empty() ? frame32 : shown.data(), stem,
                                     err, &resized);
         if (rc != RTM_OK) return fail("resize", rc, err);
         shown.swap(resized);
@@ -899,7 +957,7 @@ int main(int argc, char* argv[]) {
         last_st.height = resize_h;
         std::printf("resize: %s_resized.bmp, %s_resized.jpg (%d x %d)\n", stem.c_str(), stem.c_str(), resize_w, resize_h);
     }
-    const float* last = shown.empty() ? rgb32.data() : shown.data();
+    const float* last = shown.empty() ? frame32 : shown.data();
     std::vector<float> displayed;  // the display transform's float frame, when --display-pfm or --flip follows --display
     if (display && show(last_st, last, "", display_pfm || !flip_ref.empty() ? &displayed : nullptr) != 0) return 1;
     if (display_pfm) {

@@ -683,6 +683,36 @@ int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* p
     return RTM_OK;
 }
 
+// --firefly (rtm_node.h): rtm_firefly of the frame on the default stream, the mask counted on the host, then the two files.
+int rtm_node_write_firefly(const rtm_settings* st, int device, const rtm_firefly_params* prm, const float* f32_host,
+                           const std::string& stem, std::string& err, std::vector<float>* f32_out, size_t* clamped,
+                           size_t* repaired) {
+    const size_t pix = (size_t)st->width * st->height, vals = pix * 3;
+    std::vector<uint8_t> rgb8(vals), mask(pix);
+    {  // the device's part; what it holds is released before the files are written
+        if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+        DevBuf<float> color, out32;
+        DevBuf<uint8_t> out8, mask_dev;
+        if (!color.alloc(vals) || !out32.alloc(vals) || !out8.alloc(vals) || !mask_dev.alloc(pix))
+            return fail(err, RTM_ERR_HIP, "no device memory for firefly's buffers");
+        if (!color.upload(f32_host, vals)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+        const int rc = rtm_firefly(prm, st->width, st->height, device, color.get(), out32.get(), out8.get(), mask_dev.get(), nullptr,
+                                   nullptr);
+        if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+        if (!frame_back(out8, rgb8.data(), out32, sized(f32_out, vals), vals) || !mask_dev.download(mask.data(), pix))
+            return fail(err, RTM_ERR_HIP, "copying the cleaned frame back failed");
+    }
+    size_t ones = 0, twos = 0;
+    for (const uint8_t m : mask) {
+        ones += m == 1;
+        twos += m == 2;
+    }
+    if (clamped) *clamped = ones;
+    if (repaired) *repaired = twos;
+    if (!write_jpg_bmp(stem + "_firefly", st, rgb8.data())) return fail(err, RTM_ERR_IO, "cannot write the firefly files of " + stem);
+    return RTM_OK;
+}
+
 // --dof (rtm_node.h): the depth plane and rtm_defocus of the frame behind it on the default stream, then the two files.
 int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
                        const rtm_defocus_params* prm, const float* f32_host, const std::string& stem, std::string& err,

@@ -72,6 +72,13 @@ int rtm_node_grade(const rtm_settings* st, int device, const rtm_grade_params* p
 // follows.
 int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* params, const float* f32_host,
                    std::vector<float>* f32_out, std::string& err);
+// The firefly clamp (rtm_firefly, rtm_cli --firefly) of a float frame (HOST, height x width x 3) on device `device`: the frame
+// is copied to the device, one rtm_firefly call on the default stream, the frame and the mask are copied back, then
+// <stem>_firefly.bmp and <stem>_firefly.jpg (quality 60).  clamped and repaired receive the counts of the mask's 1s and 2s,
+// taken on the host; the cleaned float frame comes back in f32_out, for the stages that follow.
+int rtm_node_write_firefly(const rtm_settings* st, int device, const rtm_firefly_params* params, const float* f32_host,
+                           const std::string& stem, std::string& err, std::vector<float>* f32_out, size_t* clamped,
+                           size_t* repaired);
 // Depth of field (rtm_defocus, rtm_cli --dof) of a float frame (HOST, height x width x 3) on device opt->device: the frame's depth
 // plane (rtm_render_aov), one rtm_defocus call behind it on the default stream, then <stem>_dof.bmp and <stem>_dof.jpg
 // (quality 60); the defocused float frame comes back in f32_out, for the stages that follow.

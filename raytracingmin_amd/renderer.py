@@ -558,7 +558,7 @@ class Renderer:
         return out, self.stats
 
     def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False,
-               dof=None, resize=None, lens=None, grade=None, lut=None):
+               dof=None, resize=None, lens=None, grade=None, lut=None, firefly=None):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -599,6 +599,11 @@ class Renderer:
         preview=F also writes <fileName>_preview.bmp and <fileName>_preview.jpg (q=60): the frame traced at 1 / F of the
         resolution in each axis, denoised there and upsampled by the AOVs (write_preview); with tonemap, the display transform
         of the preview as well, as <fileName>_preview_display.bmp / .jpg.  F must divide the width and the height.
+        firefly=None or False: no firefly clamp.  firefly=True (or a dict of firefly()'s parameters: radius, rank, k, floor,
+        repair) also writes <fileName>_firefly.bmp and <fileName>_firefly.jpg (q=60): the frame just rendered (plain, passes or
+        adaptive) with its fireflies clamped and its non-finite pixels repaired (write_firefly).  The cleaned frame then is what
+        every stage that follows takes: denoise, denoise="variance", dof, lens, resize, bloom and the display transform, and
+        mattes' background.  The plain files and self.image do not change; the preview is a trace of its own and is not cleaned.
         mattes=True (or a dict of write_mattes' parameters: layers, ids, background) also writes <fileName>_alpha.pfm, with ids
         <fileName>_matte.pfm / .bmp, and with background <fileName>_over.bmp / .jpg: the last stage asked for (plain, denoised,
         variance-denoised) over that background; with tonemap, its display transform as well, as <fileName>_over_display.bmp /
@@ -629,6 +634,7 @@ class Renderer:
             if unknown:
                 raise ValueError(f"tonemap's parameters are {tuple(TONEMAP_DEFAULTS)}, got {sorted(unknown)}")
             _tonemap_params(**display)  # a bad parameter raises here, before anything is rendered
+        firefly_prm = _firefly_option(firefly)
         dof_prm = _dof_option(dof, self.data.width, self.data.height)
         if dof_prm is not None and dof_prm.get("focus_distance") is None:  # a miss raises here, before anything is rendered
             dof_prm["focus_distance"] = self.focus_distance(dof_prm.pop("focus_pixel", None))
@@ -683,10 +689,12 @@ class Renderer:
         frame = None  # the f32 frame the display stage shows, when it is not self.image
         keep = display is not None or (matte_prm is not None and matte_prm.get("background") is not None) or dof_prm is not None
         keep = keep or resize_prm is not None or lens_prm is not None
+        if firefly_prm is not None:  # right after the render: every stage below takes the cleaned frame
+            frame = self.write_firefly(fileName, **firefly_prm)
         if denoise == "variance":
-            frame = self.write_denoised_variance(fileName, _keep=keep)
+            frame = self.write_denoised_variance(fileName, _keep=keep, frame=frame)
         elif denoise:
-            frame = self.write_denoised(fileName, _keep=keep)
+            frame = self.write_denoised(fileName, _keep=keep, frame=frame)
         if dof_prm is not None:
             frame = self.write_dof(fileName, frame=frame, **dof_prm)
         if lens_prm is not None:
@@ -744,6 +752,28 @@ class Renderer:
         if not (ok_j and ok_b):
             raise _lib.RtmError(-3, f"could not write {fileName}_display.jpg/.bmp")
         return rgb8
+
+    def write_firefly(self, fileName, frame=None, **params):
+        """<fileName>_firefly.bmp and <fileName>_firefly.jpg (q=60): firefly(**params) of `frame`, an (H, W, 3) float32 CUDA
+        tensor, or of self.image rounded to float like out_f32 — what rtm_cli --firefly writes.  params: firefly()'s radius,
+        rank, k, floor, repair.  self.firefly_counts then holds what rtm_cli prints: {"clamped", "repaired", "pixels"},
+        counted from the mask.  Returns the cleaned float32 frame on the device."""
+        import torch
+        params = _firefly_option(params or True)
+        if frame is None:
+            dev = torch.device("cuda", self.device)
+            frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        out = _firefly(frame, want=("f32", "u8", "mask"), **params)
+        rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
+        mask = out["mask"].cpu().numpy()
+        self.firefly_counts = {"clamped": int((mask == 1).sum()), "repaired": int((mask == 2).sum()), "pixels": int(mask.size)}
+        L = _lib.lib()
+        H, W = rgb8.shape[:2]
+        ok_j = L.rtm_write_jpg(os.fsencode(fileName + "_firefly.jpg"), W, H, 3, rgb8.ctypes.data, 60)
+        ok_b = L.rtm_write_bmp(os.fsencode(fileName + "_firefly.bmp"), W, H, 3, rgb8.ctypes.data)
+        if not (ok_j and ok_b):
+            raise _lib.RtmError(-3, f"could not write {fileName}_firefly.jpg/.bmp")
+        return out["f32"]
 
     def focus_distance(self, pixel=None):
         """A focus distance for defocus(), in the depth plane's units.  Without a pixel: |camera.target - camera.origin|,
@@ -826,14 +856,17 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write {fileName}_resized.jpg/.bmp")
         return out["f32"]
 
-    def write_denoised(self, fileName, _keep=False):
+    def write_denoised(self, fileName, _keep=False, frame=None):
         """<fileName>_denoised.jpg (q=60) and <fileName>_denoised.bmp: self.image (the frame just rendered) rounded to float
         like out_f32, filtered by denoise() at the default parameters with the frame's four AOVs as guides, quantised on
         the device — what rtm_cli --denoise writes.  Returns the (H, W, 3) uint8 pixels (Render's _keep: the filtered float32
-        frame on the device instead, for the display stage; the files are the same)."""
+        frame on the device instead, for the display stage; the files are the same).  frame: an (H, W, 3) float32 CUDA tensor
+        to filter instead of self.image (Render's: the frame write_firefly cleaned)."""
         import torch
         dev = torch.device("cuda", self.device)
-        color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        color = frame
+        if color is None:
+            color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
         guides = self.render_aov()
         out = denoise(color, guides, want=("u8", "f32") if _keep else ("u8",))
         rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
@@ -845,14 +878,16 @@ class Renderer:
             raise _lib.RtmError(-3, f"could not write {fileName}_denoised.jpg/.bmp")
         return out["f32"] if _keep else rgb8
 
-    def write_denoised_variance(self, fileName, _keep=False):
+    def write_denoised_variance(self, fileName, _keep=False, frame=None):
         """<fileName>_denoised_var.jpg (q=60), <fileName>_denoised_var.bmp and <fileName>_variance.pfm: self.image rounded to
         float like out_f32, filtered by denoise_variance() at the default parameters with the frame's four AOVs as guides,
         and the variance estimate v0 — what rtm_cli --denoise-variance writes.  Returns the (H, W, 3) uint8 pixels (Render's
-        _keep: as write_denoised)."""
+        _keep and frame: as write_denoised)."""
         import torch
         dev = torch.device("cuda", self.device)
-        color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
+        color = frame
+        if color is None:
+            color = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
         out = denoise_variance(color, self.render_aov(), want=("u8", "var", "f32") if _keep else ("u8", "var"))
         rgb8 = np.ascontiguousarray(out["u8"].cpu().numpy())
         var = np.ascontiguousarray(out["var"].cpu().numpy())
@@ -1288,6 +1323,75 @@ def bloom(color, threshold=BLOOM_DEFAULTS["threshold"], knee=BLOOM_DEFAULTS["kne
 
 
 _bloom = bloom  # for Renderer's methods, whose own parameter is named bloom
+
+
+# include/rtm.h: RTM_FIREFLY_DEFAULTS
+FIREFLY_DEFAULTS = dict(_lib.FIREFLY_DEFAULTS)
+
+
+def _firefly_params(radius=FIREFLY_DEFAULTS["radius"], rank=FIREFLY_DEFAULTS["rank"], k=FIREFLY_DEFAULTS["k"],
+                    floor=FIREFLY_DEFAULTS["floor"], repair=FIREFLY_DEFAULTS["repair"]):
+    """firefly()'s parameters as an rtm_firefly_params; a ValueError names what the library would refuse.  No device use."""
+    for name, v, lo, hi in (("radius", radius, 1, 3), ("rank", rank, 1, 8)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} is an integer in {lo}..{hi}, got {v!r}")
+    for name, v in (("k", k), ("floor", floor)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not np.isfinite(float(v)):
+            raise ValueError(f"{name} is a finite number, got {v!r}")
+    # as the library sees them: rounded to float
+    with np.errstate(over="ignore", under="ignore"):
+        kf, ff = float(np.float32(k)), float(np.float32(floor))
+    if not (np.isfinite(kf) and kf >= 1.0):
+        raise ValueError(f"k is a finite number that is at least 1, got {k!r}")
+    if not (np.isfinite(ff) and ff >= 0.0) or np.signbit(ff):
+        raise ValueError(f"floor is a finite number that is not negative (nor -0.0), got {floor!r}")
+    if not isinstance(repair, (bool, np.bool_)) and not (isinstance(repair, (int, np.integer)) and int(repair) in (0, 1)):
+        raise ValueError(f"repair is False or True (0 or 1), got {repair!r}")
+    return _lib.rtm_firefly_params(int(radius), int(rank), kf, ff, int(bool(repair)))
+
+
+def _firefly_option(firefly):
+    """Render's `firefly`: None (or False) for off, else the dict of firefly()'s parameters (True: the defaults), checked."""
+    if firefly is None or firefly is False:
+        return None
+    if firefly is not True and not isinstance(firefly, dict):
+        raise ValueError(f"firefly is None, False, True or a dict of {tuple(FIREFLY_DEFAULTS)}, got {firefly!r}")
+    prm = {} if firefly is True else dict(firefly)
+    unknown = set(prm) - set(FIREFLY_DEFAULTS)
+    if unknown:
+        raise ValueError(f"firefly's parameters are {tuple(FIREFLY_DEFAULTS)}, got {sorted(unknown)}")
+    _firefly_params(**prm)
+    return prm
+
+
+def firefly(color, radius=FIREFLY_DEFAULTS["radius"], rank=FIREFLY_DEFAULTS["rank"], k=FIREFLY_DEFAULTS["k"],
+            floor=FIREFLY_DEFAULTS["floor"], repair=FIREFLY_DEFAULTS["repair"], want=("f32",), stream=None):
+    """The firefly clamp (include/rtm.h: rtm_firefly) on the device: a pixel whose luminance exceeds k times the rank-th
+    largest luminance of its (2 radius + 1)^2 - 1 neighbours, plus floor, is scaled down to that threshold, chroma kept; with
+    `repair` a pixel with a non-finite component becomes the mean of its finite neighbours.  Run it right after the render,
+    before denoise(), denoise_variance(), defocus(), lens(), resize(), bloom() and tonemap().  `color` is an (H, W, 3) float32
+    torch CUDA tensor (any 4-byte-aligned contiguous view).  radius 1..3; rank 1..8 (1: the maximum; the default 3 keeps the
+    rim of a bright rectangle and still catches clusters of three); k >= 1; floor >= 0.  Returns a dict of the names in
+    `want`: "f32" (H, W, 3) float32, "u8" (H, W, 3) uint8 (rtm_quantise of it), "mask" (H, W) uint8 (0 unchanged, 1 clamped,
+    2 repaired), "threshold" (H, W) float32 (+inf where a pixel has none).  The outputs are tensors of the call's own: a
+    gather cannot run in place.  Enqueued on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current
+    stream); nothing waits for it and nothing is copied to the host."""
+    prm = _firefly_params(radius, rank, k, floor, repair)
+    _check_want(want, ("f32", "u8", "mask", "threshold"))
+    import torch
+    _need_device("firefly")
+    H, W = _frame_size(color, "color", non_empty=True)
+    dev = color.device
+    s = _stream_of(stream, dev)
+    specs = {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8), "mask": ((H, W), torch.uint8),
+             "threshold": ((H, W), torch.float32)}
+    out, ptr = _stage_tensors(s, dev, want, specs)
+    _lib.check(_lib.lib().rtm_firefly(C.byref(prm), W, H, dev.index, color.data_ptr(), ptr("f32"), ptr("u8"), ptr("mask"),
+                                      ptr("threshold"), C.c_void_p(s.cuda_stream)), "rtm_firefly")
+    return out
+
+
+_firefly = firefly  # for Renderer's methods, whose own parameter is named firefly
 
 
 # include/rtm.h: RTM_DEFOCUS_DEFAULTS (focus_distance has no default: the caller sets it)
