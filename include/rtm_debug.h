@@ -44,7 +44,11 @@ extern "C" {
  * two draws — the angle 2 pi m1 2^-24 and r2 = m2 2^-24 —, unused x 3), b unused, out = (nd.x, nd.y, nd.z, 1 where the lane set
  * the block's `bad` flag, 0 x 4).  No component of w may be zero (such a lane is another branch's in the render loops).
  * 59: from one reciprocal root, k = sqrt(r2) / y, without the orthonormal basis (csrc/rtm_path.h: bounce_nd_fused), as the block
- * runs it; 60: with the basis built, a refined reciprocal and a root (bounce_nd_basis) — the reference of 59. */
+ * runs it; 60: with the basis built, a refined reciprocal and a root (bounce_nd_basis) — the reference of 59.
+ * Ops 61 / 62: op 55's search on op 55's records (a, b, n and the waves as there), out = (distance, hit id or -1, 1 where the
+ * ray's wave took the acceptance's general chain, 1 where it took the seven-sphere block instead of the pairs, 1 where it asked
+ * the far-root question a second time, 0 x 3).  61: as the render kernels run it, no far-root sum for a pair's wall
+ * (csrc/rtm_path.h: accept_batch_lane's WALLS); 62: the sum formed for every candidate — the reference of 61. */
 int rtm_debug_math_probe(int op, const double* a, const double* b, size_t n, double* out);
 /* The tolerance row's sin / cos table as the HOST builds it for every device (no device is touched; runs in the CPU test
  * suite): out[2 i], out[2 i + 1] = sin, cos of i 2 pi / entries, evaluated in long double and rounded to double once.  The

@@ -147,7 +147,11 @@ static void launch_row(const RenderParams& P, unsigned grid, size_t lds_pad, hip
 // 59 / 60 a bounce direction before its Normalize, records and lanes as 57 / 58, a = (w.x, w.y, w.z, m1, m2, -, -, -) with w the
 // turned normal (no zero component) and m1, m2 the odd integers of the bounce's two draws, out = (nd.x, nd.y, nd.z, 1 where the
 // lane set `bad`, 0 ..): 59 from one reciprocal root, without the basis (rtm_path.h: bounce_nd_fused, as the shading block runs
-// it), 60 with the basis built (bounce_nd_basis: the form of rounds 2 to 13, its reference)
+// it), 60 with the basis built (bounce_nd_basis: the form of rounds 2 to 13, its reference),
+// 61 / 62 op 55's search on op 55's records, out = (distance, hit id, 1 where the ray's wave took the general acceptance chain,
+// 1 where it took the seven-sphere block, 1 where it asked the far-root question a second time, 0 ..): 61 as the render kernels
+// run it — a pair's wall forms no t2 (rtm_path.h: accept_batch_lane's WALLS) —, 62 with t2 formed for every candidate (the form
+// of rounds 10 to 14, its reference)
 __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, const double* __restrict__ b, size_t n,
                                       double* __restrict__ out, const double2* __restrict__ tab) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -172,20 +176,24 @@ __global__ void tol_math_probe_kernel(int op, const double* __restrict__ a, cons
         out[i] = (i & 7) == 0 ? bb : (i & 7) == 1 ? D4 : 0.0;
         return;
     }
-    if (op == 55 || op == 56) {  // (as above: every thread of a record computes it; a wave holds 8 rays)
+    if (op == 55 || op == 56 || op == 61 || op == 62) {  // (as above: every thread of a record computes it; a wave holds 8 rays)
         const size_t j = i & ~(size_t)7;
         double dis = DBL_MAX;
         int hit = -1;
-        bool fell_back = false;
+        bool fell_back = false, general = false, again = false;
         if (b && n >= 56 && j + 7 < n) {
             const D3 org = d3(a[j], a[j + 1], a[j + 2]), dir = d3(a[j + 3], a[j + 4], a[j + 5]);
             SceneGlobal sc{};
             sc.v.geom = reinterpret_cast<const double4*>(b);
             sc.v.n = 7;
             if (op == 55) sphere_chunk<MathFast, 7, SceneGlobal, false, kAxisSigCornell7Pairs>(sc, 0, org, dir, dis, hit, &fell_back);
+            else if (op == 61) sphere_chunk<MathFast, 7, SceneGlobal, false, kAxisSigCornell7Pairs>(sc, 0, org, dir, dis, hit, &fell_back, &general, &again);
+            else if (op == 62) sphere_chunk<MathFast, 7, SceneGlobal, false, kAxisSigCornell7Pairs, true>(sc, 0, org, dir, dis, hit, &fell_back, &general, &again);
             else sphere_chunk<MathFast, 7, SceneGlobal, false, kAxisSigCornell7Walls>(sc, 0, org, dir, dis, hit);
         }
-        out[i] = (i & 7) == 0 ? dis : (i & 7) == 1 ? (double)hit : (i & 7) == 2 ? (fell_back ? 1.0 : 0.0) : 0.0;
+        const bool f2 = op >= 61 ? general : fell_back, f3 = op >= 61 && fell_back;
+        const unsigned s = (unsigned)(i & 7);
+        out[i] = s == 0u ? dis : s == 1u ? (double)hit : s == 2u ? (f2 ? 1.0 : 0.0) : s == 3u ? (f3 ? 1.0 : 0.0) : s == 4u ? (again ? 1.0 : 0.0) : 0.0;
         return;
     }
     if (op == 57 || op == 58) {  // ONE lane per record (a wave holds 64 records: the caller mixes the two kinds of lane in it)

@@ -956,20 +956,65 @@ __device__ __forceinline__ void accept_batch(const double (&b)[K], const double 
 // accept_batch<K, true> for candidates whose sphere index is a PER-LANE value (the tolerance unit's wall pairs, sphere_chunk:
 // each lane tests the wall of a pair that ITS ray heads for).  idx[k] ascends with k in every lane, so ties still go to the
 // lower index — in the packed minimum by the index field, in the general updates by their order.
-template <int K>
+//   WALLS (bit k: candidate k is the wall of an opposite pair that the lane's ray heads for) — such a candidate forms no t2 on
+//   the hot path.  Its far root could only count from an origin on that very wall with the ray parallel to it to within about
+//   2e-3, so the question "does some lane have a far root" is first asked with a LARGER mask that needs t1 alone:
+//       le = t1 <= 0.001 (false for a NaN t1),   far' |= le,   t1v's high word = le ? 0x7FF80000 : t1's
+//   — a subtraction, a compare, the low word's and-or and a select per candidate, where the form with t2 (WALLS' bit clear: the
+//   lamp's slot, and rtm_debug_math_probe op 62, which keeps it for every candidate) has an addition and a compare more.  The
+//   bits of (dis, hit_object) are that form's in every trip:
+//   1. far' contains far.  The term of far is (t2 >= 1e-5f) & ~(t1 > 0.001); t2 >= 1e-5f needs sq not NaN, and then t1 = b - sq
+//      is no NaN either unless b is one (t2 is, too) or b = sq = +inf — which a wall candidate never has: b = |c| |d_a| - o.d
+//      is +inf only with -o.d = +inf or |d_a| infinite, and either leaves the other wall's b_u = -|c| |d_a| - o.d at +inf or NaN,
+//      so the lane is unproven and its wave runs the seven-sphere block.  "Not NaN and not above 0.001" is le.
+//   2. Where far' == 0, far == 0: the form with t2 takes the packed minimum as well, and from operands that v_min_f64 cannot
+//      tell apart.  No wall candidate has t1 <= 0.001, so each one's t1 is above 0.001 — t1v = t1 with the index bits, as in
+//      that form — or NaN, and then it is a QUIET NaN already: v_rsq_f64 of a negative discriminant returns one, every fma and
+//      the subtraction behind it hand a quiet NaN on (an arithmetic instruction never returns a signalling one), and so does
+//      the full sqrt of the rescaling branch.  The and-or touches the low word alone; the quiet bit is in the high word.
+//      v_min_f64 returns its other operand for a quiet NaN whatever the payload says: 0x7FF80000 over the high word, as in
+//      that form, or t1's own.  What this needs: v_min_f64 on the RAW bits — no v_max_f64 x, x (canonicalise) in front of the
+//      chain, which is why the chain is spelled in assembly —, and `best` itself is never NaN (DBL_MAX on entry).
+//   3. Where far' != 0 (rare) the question is asked again in full, far itself from b + sq of every candidate, and the trip
+//      then does what the form with t2 does: the packed minimum where far == 0 — a wall candidate with le has 0x7FF80000 there
+//      in both forms, the others are as in 2. —, the general accept_update chain from the same b and sq otherwise.  (The two
+//      chains do NOT return the same dis: the packed minimum's carries the index in its last three bits.  A trip may
+//      therefore not change chains, and does not.)
+//   The price is the second question in a trip where a wall candidate has t1 <= 0.001 and t2 < 1e-5f — the ray grazes away
+//   from the wall it starts on while its axis component still points at it, b = |c| |d_a| - o.d < 1e-5 — and in every trip that
+//   takes the general chain anyway (profiles/r15/accept_walls.md has the counts).
+//   `general`: set where the general chain ran, `asked_again` where far was formed (the probe ops alone pass them).
+template <int K, unsigned WALLS = 0u>
 __device__ __forceinline__ void accept_batch_lane(const double (&b)[K], const double (&sq)[K], const uint32_t (&idx)[K],
-                                                  double& dis, int& hit_object) {
+                                                  double& dis, int& hit_object, bool* general = nullptr,
+                                                  bool* asked_again = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)
     static_assert(K <= 7, "three bits of index, 7 = none");
     double t1v[K];
-    unsigned long long far = 0ull;
+    unsigned long long far = 0ull;  // (far' where WALLS has bits)
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-        const double t1 = b[k] - sq[k], t2 = b[k] + sq[k];
-        const unsigned long long near = __builtin_amdgcn_ballot_w64(t1 > 0.001);
-        far |= __builtin_amdgcn_ballot_w64(t2 >= (double)1e-5f) & ~near;
+        const double t1 = b[k] - sq[k];
         const uint32_t lo = ((uint32_t)__double2loint(t1) & ~7u) | idx[k];
-        t1v[k] = __hiloint2double((int)sel_u32_mask(near, (uint32_t)__double2hiint(t1), 0x7FF80000u), (int)lo);
+        if (((WALLS >> k) & 1u) != 0u) {
+            const unsigned long long le = __builtin_amdgcn_ballot_w64(t1 <= 0.001);
+            far |= le;
+            t1v[k] = __hiloint2double((int)sel_u32_mask(le, 0x7FF80000u, (uint32_t)__double2hiint(t1)), (int)lo);
+        } else {
+            const double t2 = b[k] + sq[k];
+            const unsigned long long near = __builtin_amdgcn_ballot_w64(t1 > 0.001);
+            far |= __builtin_amdgcn_ballot_w64(t2 >= (double)1e-5f) & ~near;
+            t1v[k] = __hiloint2double((int)sel_u32_mask(near, (uint32_t)__double2hiint(t1), 0x7FF80000u), (int)lo);
+        }
+    }
+    if (WALLS != 0u && far != 0ull) {  // 3.: far itself
+        if (asked_again) *asked_again = true;
+        far = 0ull;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double t1 = b[k] - sq[k], t2 = b[k] + sq[k];
+            far |= __builtin_amdgcn_ballot_w64(t2 >= (double)1e-5f) & ~__builtin_amdgcn_ballot_w64(t1 > 0.001);
+        }
     }
     if (far == 0ull) {
         double best = dis;  // DBL_MAX: index field 7
@@ -984,6 +1029,7 @@ __device__ __forceinline__ void accept_batch_lane(const double (&b)[K], const do
         return;
     }
 #endif
+    if (general) *general = true;
 #pragma unroll
     for (int k = 0; k < K; ++k) accept_update(b[k], sq[k], (int)idx[k], dis, hit_object);
 }
@@ -1237,9 +1283,22 @@ __device__ __forceinline__ void sphere_chunk_g(const double4 (&g)[K], const int 
 // spheres whose geometry is fetched together inside a chunk (profiles/r1: 7 at once 202.7 ms, 4: 195.6,
 // 3: 194.5, 2: 194.2 ms on the same box; SGPR spills 44 -> 10)
 constexpr int kGeomPhase = 2;
-template <class M, int K, class Scene, bool EARLY_OUT = false, unsigned SIG = 0u>
+// (kAxisPairsBit: the candidate slots that hold a pair's wall — accept_batch_lane's WALLS; K spheres, KMP the pairs' members)
+constexpr unsigned pair_wall_slots(const int K, const unsigned KMP) {
+    unsigned slots = 0u;
+    for (int k = 0; k < K; ++k) {
+        const int rank = __builtin_popcount(KMP & ((1u << k) - 1u));
+        if (((KMP >> k) & 1u) != 0u && (rank & 1) == 0) slots |= 1u << (k - rank / 2);
+    }
+    return slots;
+}
+static_assert(pair_wall_slots(7, 0x7Eu) == 0xEu, "the Cornell box: the lamp in slot 0, a wall pair in each of slots 1 to 3");
+// (ACCEPT_T2, the pairs path: every candidate's acceptance with t2 formed, the form of rounds 10 to 14 — rtm_debug_math_probe
+// op 62 alone asks for it, the reference of op 61; accept_general / accept_again: accept_batch_lane's `general` / `asked_again`)
+template <class M, int K, class Scene, bool EARLY_OUT = false, unsigned SIG = 0u, bool ACCEPT_T2 = false>
 __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, const D3 org, const D3 dir,
-                                             double& dis, int& hit_object, bool* pairs_fell_back = nullptr) {
+                                             double& dis, int& hit_object, bool* pairs_fell_back = nullptr,
+                                             bool* accept_general = nullptr, bool* accept_again = nullptr) {
     static_assert(SIG == 0u || (K > kGeomPhase && K < 8 && !EARLY_OUT), "an axis signature names the spheres of ONE exact chunk");
     constexpr int PH = kGeomPhase;
     if constexpr (K > PH && !EARLY_OUT) {
@@ -1290,7 +1349,8 @@ __device__ __forceinline__ void sphere_chunk(const Scene& sc, const int i0, cons
                         if (member && (rank & 1) != 0) continue;
                         idx[k - rank / 2] = member ? pair_index((SIG >> (2 * k)) & 3u, dir, i0 + k) : (uint32_t)(i0 + k);
                     }
-                    accept_batch_lane<KC>(pb, psq, idx, dis, hit_object);
+                    accept_batch_lane<KC, ACCEPT_T2 ? 0u : pair_wall_slots(K, KMP)>(pb, psq, idx, dis, hit_object, accept_general,
+                                                                                   accept_again);
                     return;
                 }
                 if (pairs_fell_back) *pairs_fell_back = true;  // (rtm_debug_math_probe op 55 alone passes one)
