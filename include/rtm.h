@@ -695,6 +695,68 @@ size_t rtm_bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
 int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color_dev,
               void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream);
 
+/* ---- local tone operator: exposure fusion (Mertens et al.) on luminance — three synthetic exposures of the one frame, blended
+ * per pixel by how well each is exposed, through a Laplacian pyramid so that the blend follows the frame's regions and not its
+ * pixels.  Chroma is kept.  It REPLACES rtm_tonemap's curve: the output is display-linear, nominally in [0, 1], and rtm_tonemap
+ * then runs as {CLAMP, transfer, auto_exposure 0, dither, ev 0} (one launch) for the transfer function and the store.  Opt-in:
+ * every other stage and its defaults stay.
+ * Input: color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32; 4-byte alignment is enough).  Arithmetic in
+ * float, without contraction.  lum(c) = (0.2126 c_R + 0.7152 c_G) + 0.0722 c_B (rtm_tonemap's).
+ *   1 counting    a pixel COUNTS iff its three components are finite.  A pixel that does not count is (0, 0, 0) for steps
+ *                 2-6 and (0, 0, 0) in out_f32 and out_u8, as in rtm_tonemap: it is black for the pyramid and it is not
+ *                 repaired (rtm_firefly upstream is the repair).
+ *   2 exposed     xc = max(c, 0) per channel, Y = lum(xc), A = anchor (stats_dev ? stats_dev->exposure : 1),
+ *     luminance   x = min(A Y, 1e6f).  stats_dev is a nullable DEVICE rtm_tonemap_stats that the kernels read: no host sync.
+ *                 Filled by an earlier rtm_tonemap call on the same stream, it makes the anchor that call's own E.
+ *   3 exposures   e_0 = exp2(shadows), e_1 = 1, e_2 = exp2(-highlights); I_k = (e_k x) / (1 + e_k x): simple Reinhard,
+ *                 display-linear, in [0, 1).
+ *   4 well-       v_k = sqrt(I_k), w_k = exp(-(v_k - 0.5)^2 / (2 sigma^2)), w^_k = w_k / (w_0 + w_1 + w_2).  With
+ *     exposedness sigma >= 0.1 the exponent is >= -12.5: no w_k underflows and the sum is positive.
+ *   5 pyramids    levels l = 0..L with rtm_bloom's sizes (W_l = ceil(W_{l-1} / 2), H_l likewise; a side that has reached 1
+ *                 stays 1).  GI_0 = I and GW_0 = w^, three channels each; GI_l and GW_l are rtm_bloom's down filter (step 3
+ *                 there) of level l-1: k = {1, 3, 3, 1} / 8 over the taps 2X-1 .. 2X+2, taps outside skipped and the rest
+ *                 renormalised, the horizontal pass first.  up_l is rtm_bloom's up filter (step 4 there) from level l+1 to
+ *                 W_l x H_l: the (1/4, 3/4) pair, skip and renormalise.
+ *   6 blend and   R_L = sum_k GW_L,k GI_L,k; for l = L-1 .. 0: R_l = sum_k GW_l,k (GI_l,k - up_l(GI_{l+1,k})) + up_l(R_{l+1});
+ *     collapse    F = min(max(R_0, 0), 1).  L = 0 is the pointwise blend F = sum_k w^_k I_k.
+ *   7 apply       r = F / max(x, 1e-4f); out_f32 = xc (A r) per channel.  The luminance of a counting pixel with
+ *                 1e-4 <= A Y <= 1e6 is F.  Above 1e6 the pixel is brighter than F, and the display transform's clamp takes it
+ *                 to white.  An overflow is kept as the float it is.
+ *   8 outputs     out_f32; out_u8 (nullable) is rtm_quantise of (double)out_f32, out of range (NaN included) -> 0, as in the
+ *                 other stages; fused_out_dev (nullable, height x width floats) receives F at every pixel (at a pixel that
+ *                 does not count: the F of a black pixel there).
+ * It follows that (a) shadows = highlights = 0 gives F = x / (1 + x) at every L, within the tolerance: the three pyramids are
+ * equal and the weights sum to one; (b) a constant frame gives, at every L, what L = 0 gives; (c) L = 0 is a pointwise
+ * function of the pixel; (d) there are no atomics and no state: the same inputs give the same bits on every call, on any
+ * stream, at any 4-byte alignment of color.
+ * exp, sqrt, exp2 and the divisions may be the device's fast forms: against a float64 evaluation of the steps above every
+ * out_f32 component and every fused_out value is within 1e-4 max(1, |ref|); out_u8 is exact given the call's own out_f32.
+ * work_dev: DEVICE, 256-byte aligned, rtm_tonemap_local_work_bytes = the sum over l = 1..L of 2 round256(16 W_l H_l) bytes:
+ * two planes of 16-byte records per level, (GI_0, GI_1, GI_2, R) and (GW_0, GW_1, GW_2, unused); level 0 is never stored.  0 for
+ * a non-positive size, levels outside 0..8 and levels 0, SIZE_MAX when the frame (12 bytes a pixel) or the sum does not fit a
+ * size_t.  levels 0 needs no work buffer and accepts a null work_dev.  The call allocates nothing, keeps no per-(device,
+ * stream) state, needs no serialisation and only ENQUEUES 2L launches on `stream`, one for L = 0.  out_f32_dev == color_dev
+ * (in place) is allowed: the apply kernel reads its pixel before it writes it, and the pyramid is read from color earlier, in
+ * stream order.  Null params or color_dev, a null work_dev with levels > 0, all three outputs null, a non-positive size, a
+ * NaN, infinite or out-of-range parameter, a float or stats pointer that is not 4-byte aligned, a work_dev that is not 256-byte
+ * aligned, work_dev equal to any other buffer, fused_out_dev or stats_dev equal to color_dev or out_f32_dev, out_u8_dev equal
+ * to color_dev, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A frame of 2^31 pixels or more:
+ * RTM_ERR_UNSUPPORTED, as rtm_tonemap.
+ * Defaults: RTM_TONEMAP_LOCAL_DEFAULTS below, the customary ones of this operator (what Renderer.Render(local=True) and
+ * rtm_cli --display local use).  Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+typedef struct rtm_tonemap_local_params { /* 20 bytes */
+    float anchor;      /* finite, > 0: the exposure in front of the operator                  */
+    float shadows;     /* finite, in [0, 8]: stops the shadow exposure is opened by           */
+    float highlights;  /* finite, in [0, 8]: stops the highlight exposure is closed by        */
+    float sigma;       /* in [0.1, 1]: width of the well-exposedness weight about 0.5         */
+    int32_t levels;    /* L, 0..8; 0 = the pointwise blend                                     */
+} rtm_tonemap_local_params;
+#define RTM_TONEMAP_LOCAL_DEFAULTS {1.0f, 2.0f, 2.0f, 0.25f, 5} /* of rtm_tonemap_local_params */
+size_t rtm_tonemap_local_work_bytes(int32_t width, int32_t height, int32_t levels);
+int rtm_tonemap_local(const rtm_tonemap_local_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                      const rtm_tonemap_stats* stats_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                      float* fused_out_dev, void* stream);
+
 /* ---- grade: the colour decision — white balance (or any change of primaries) as a 3x3 matrix, exposure, contrast about a
  * pivot, the ASC CDL's slope / offset / power, saturation, and an optional 3D look LUT gathered on the device.  Opt-in, a
  * per-pixel transform of a device float frame: every other stage and its defaults stay.  The parametric steps are meant for

@@ -111,6 +111,11 @@ class rtm_bloom_params(C.Structure):  # include/rtm.h: rtm_bloom (20 bytes)
                 ("levels", C.c_int32)]
 
 
+class rtm_tonemap_local_params(C.Structure):  # include/rtm.h: rtm_tonemap_local (20 bytes)
+    _fields_ = [("anchor", C.c_float), ("shadows", C.c_float), ("highlights", C.c_float), ("sigma", C.c_float),
+                ("levels", C.c_int32)]
+
+
 class rtm_firefly_params(C.Structure):  # include/rtm.h: rtm_firefly (20 bytes)
     _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("k", C.c_float), ("floor", C.c_float), ("repair", C.c_int32)]
 
@@ -228,6 +233,9 @@ SIGNATURES = {
     "rtm_bloom_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rtm_bloom": (C.c_int, [_P(rtm_bloom_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_tonemap_local_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "rtm_tonemap_local": (C.c_int, [_P(rtm_tonemap_local_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_firefly": (C.c_int, [_P(rtm_firefly_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_defocus": (C.c_int, [_P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

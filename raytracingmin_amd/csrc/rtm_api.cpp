@@ -134,6 +134,15 @@ int rtm_bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int
               float* out_f32_dev, uint8_t* out_u8_dev, float* bloom_out_dev, void* stream) {
     RTM_GUARD(rtm::bloom(params, width, height, device, color_dev, work_dev, out_f32_dev, out_u8_dev, bloom_out_dev, stream))
 }
+size_t rtm_tonemap_local_work_bytes(int32_t width, int32_t height, int32_t levels) {
+    return rtm::tonemap_local_work_bytes(width, height, levels);
+}
+int rtm_tonemap_local(const rtm_tonemap_local_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+                      const rtm_tonemap_stats* stats_dev, void* work_dev, float* out_f32_dev, uint8_t* out_u8_dev,
+                      float* fused_out_dev, void* stream) {
+    RTM_GUARD(rtm::tonemap_local(params, width, height, device, color_dev, stats_dev, work_dev, out_f32_dev, out_u8_dev,
+                                 fused_out_dev, stream))
+}
 int rtm_grade(const rtm_grade_params* params, int32_t width, int32_t height, int device, const float* color_dev,
               const float* lut_dev, float* out_f32_dev, uint8_t* out_u8_dev, void* stream) {
     RTM_GUARD(rtm::grade(params, width, height, device, color_dev, lut_dev, out_f32_dev, out_u8_dev, stream))

@@ -98,6 +98,7 @@ __device__ inline void bl_filter_tile(const float* fine, const int* lead, float*
     dst[(size_t)Y * Wc + X] = make_float4(o[0], o[1], o[2], 0.0f);
 }
 
+#ifndef RTM_BLOOM_FILTERS_ONLY  // rtm_tonemap_local_kernel.h shares the filters above and bl_up_taps, not the kernels
 // color -> level 1.  Fine row r of the tile starts at float a = 3 ((2 Y0 - 1 + r) W + 2 X0 - 1) of the frame; its slots
 // are the dwordx4s from a rounded down to a multiple of four, so lead = a mod 4 floats precede the first pixel.  VEC: color
 // is 16-byte aligned and a slot that lies inside the frame's floats is one dwordx4 load; the plain path reads the same floats
@@ -174,6 +175,8 @@ __global__ __launch_bounds__(kBlBlock) void bloom_down_kernel(const int Wf, cons
     bl_filter_tile(fine, lead, hor, X0, Y0, Wf, Hf, Wc, Hc, dst);
 }
 
+#endif  // RTM_BLOOM_FILTERS_ONLY
+
 // The taps and weights of step 4 for the fine index x over a coarse side of n: t0 and t1 are in the frame (an outside tap
 // is moved onto the other one and weighs 0, which leaves the 3/4 tap with the whole weight: 0.75 / 0.75)
 __device__ inline void bl_up_taps(const int x, const int n, int& t0, int& t1, float& w0, float& w1) {
@@ -193,6 +196,7 @@ __device__ inline void bl_up_taps(const int x, const int n, int& t0, int& t1, fl
     }
 }
 
+#ifndef RTM_BLOOM_FILTERS_ONLY
 // up(coarse)(x, y): the horizontal pairs first, then the rows
 __device__ inline float4 bl_up(const float4* __restrict__ coarse, const int Wc, const int Hc, const int x, const int y) {
     int x0, x1, y0, y1;
@@ -264,6 +268,8 @@ __global__ __launch_bounds__(kBlPixTileX * kBlPixTileY) void bloom_combine_kerne
         out8[p + 2] = bl_quantise(__uint_as_float(wb));
     }
 }
+
+#endif  // RTM_BLOOM_FILTERS_ONLY
 
 }  // namespace rtm
 #endif

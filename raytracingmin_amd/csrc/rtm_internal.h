@@ -78,6 +78,10 @@ int tonemap(const rtm_tonemap_params* params, int32_t width, int32_t height, int
 size_t bloom_work_bytes(int32_t width, int32_t height, int32_t levels);
 int bloom(const rtm_bloom_params* params, int32_t width, int32_t height, int device, const float* color, void* work, float* out32,
           uint8_t* out8, float* bloom_out, void* stream);
+// the local tone operator (rtm_tonemap_local.hip)
+size_t tonemap_local_work_bytes(int32_t width, int32_t height, int32_t levels);
+int tonemap_local(const rtm_tonemap_local_params* params, int32_t width, int32_t height, int device, const float* color,
+                  const rtm_tonemap_stats* stats, void* work, float* out32, uint8_t* out8, float* fused_out, void* stream);
 // colour grade (rtm_grade.hip), and its host-only helpers: the white balance matrix and the .cube reader (rtm_lut.cpp)
 int grade(const rtm_grade_params* params, int32_t width, int32_t height, int device, const float* color, const float* lut,
           float* out32, uint8_t* out8, void* stream);

@@ -12,8 +12,10 @@
 //                                                (the firefly clamp of the frame, before every stage below: STEM_firefly.bmp, .jpg)
 //           [--denoise]                          (the à-trous denoiser next to the image: STEM_denoised.bmp, .jpg)
 //           [--denoise-variance]                 (the variance-guided one: STEM_denoised_var.bmp, .jpg, STEM_variance.pfm)
-//           [--display [clamp|reinhard|aces]] [--exposure auto|EV] [--linear] [--no-dither]
+//           [--display [clamp|reinhard|aces|local]] [--exposure auto|EV] [--linear] [--no-dither]
 //                                                (the display transform of the last stage: STEM_display.bmp, .jpg)
+//           [--local-shadows S] [--local-highlights S] [--local-sigma V] [--local-levels N]
+//                                                (with --display local: the local tone operator's parameters)
 //           [--bloom [INTENSITY]] [--bloom-threshold T] [--bloom-levels L]
 //                                                (with --display: bloom the frame before the display transform)
 //           [--grade-temperature K] [--grade-tint T] [--grade-exposure EV] [--grade-contrast C[,PIVOT]]
@@ -137,10 +139,15 @@ static void usage() {
         "--denoise-variance : also write the frame through the variance-guided denoiser on one GPU (rtm_denoise_variance at\n"
         "            its default parameters; for frames whose noise is uneven, such as --adaptive's): STEM_denoised_var.bmp,\n"
         "            STEM_denoised_var.jpg and STEM_variance.pfm, the per-pixel variance estimate\n"
-        "--display [clamp|reinhard|aces] : also write the display transform (rtm_tonemap; default aces) of the last stage\n"
+        "--display [clamp|reinhard|aces|local] : also write the display transform (rtm_tonemap; default aces) of the last stage\n"
         "            asked for on one GPU (the --denoise-variance frame, else the --denoise frame, else the frame itself):\n"
         "            STEM_display.bmp and STEM_display.jpg.  --exposure auto|EV : Reinhard's log-average key 0.18 (default) or\n"
         "            a fixed number of stops; --linear : no sRGB transfer function; --no-dither : the truncating 8-bit store\n"
+        "            local : the local tone operator in the curve's stead (rtm_tonemap_local: exposure fusion on luminance at\n"
+        "            that exposure, after --bloom and --grade-..., then the clamp, the transfer function and the store).\n"
+        "            --local-shadows S --local-highlights S : the stops, 0..8, the shadow exposure is opened and the highlight\n"
+        "            exposure closed by (default 2 and 2); --local-sigma V : the width of the well-exposedness weight, 0.1..1\n"
+        "            (default 0.25); --local-levels N : the depth of the pyramid, 0..8 (default 5; 0 blends per pixel)\n"
         "--bloom [INTENSITY] [--bloom-threshold T] [--bloom-levels L] : with --display, bloom every frame the display transform\n"
         "            is given (rtm_bloom: a bright pass above luminance T, default 1, a pyramid of L levels, 1..8, default 6, and\n"
         "            INTENSITY, default 0.2, times the result added back in linear space): STEM_display.*, STEM_preview_display.*,\n"
@@ -224,6 +231,8 @@ int main(int argc, char* argv[]) {
     rtm_tonemap_params display_prm = RTM_TONEMAP_DEFAULTS;
     int bloom = 0;
     rtm_bloom_params bloom_prm = RTM_BLOOM_DEFAULTS;
+    int local = 0, local_flag_given = 0;
+    rtm_tonemap_local_params local_prm = RTM_TONEMAP_LOCAL_DEFAULTS;
     int grade = 0, grade_temperature_given = 0, grade_tint_given = 0, lut_interp_given = 0;
     float grade_kelvin = 6504.0f, grade_tint = 0.0f;
     rtm_grade_params grade_prm = RTM_GRADE_DEFAULTS;
@@ -289,7 +298,32 @@ int main(int argc, char* argv[]) {
             if (m == "clamp") display_prm.op = RTM_TONEMAP_CLAMP;
             else if (m == "reinhard") display_prm.op = RTM_TONEMAP_REINHARD;
             else if (m == "aces") display_prm.op = RTM_TONEMAP_ACES;
-            if (m == "clamp" || m == "reinhard" || m == "aces") ++i;  // anything else is the next option: the default curve
+            else if (m == "local") local = 1;
+            if (m == "clamp" || m == "reinhard" || m == "aces" || m == "local") ++i;  // anything else is the next option: the default curve
+        } else if (c == "--local-shadows" || c == "--local-highlights" || c == "--local-sigma" || c == "--local-levels") {
+            // a number, all of it, in range once rounded to float
+            const std::string m = i + 1 < argc ? argv[i + 1] : "";
+            double v = 0.0;
+            bool ok = parse_number(m, v);
+            if (ok) ++i;
+            local_flag_given = 1;
+            const float f = (float)v;
+            if (c == "--local-levels") {
+                ok = ok && v == std::floor(v) && v >= 0.0 && v <= 8.0;
+                if (ok) local_prm.levels = (int)v;
+            } else if (c == "--local-sigma") {
+                ok = ok && std::isfinite(f) && f >= 0.1f && f <= 1.0f;
+                local_prm.sigma = f;
+            } else {
+                ok = ok && std::isfinite(f) && f >= 0.0f && f <= 8.0f;
+                (c == "--local-shadows" ? local_prm.shadows : local_prm.highlights) = f;
+            }
+            if (!ok) {
+                std::fprintf(stderr, "%s takes %s, got %s\n", c.c_str(),
+                             c == "--local-levels" ? "a number of levels in 0..8"
+                             : c == "--local-sigma" ? "a number in 0.1..1" : "a number of stops in 0..8", m.c_str());
+                return 2;
+            }
         } else if (c == "--exposure" && i + 1 < argc) {
             const std::string m = argv[++i];
             double ev = 0.0;
@@ -651,6 +685,9 @@ int main(int argc, char* argv[]) {
         {display_pfm && (!display || preview_only),
          "--display-pfm writes the display transform's float frame of the full render: it requires --display and does not combine "
          "with --preview-only"},
+        {local_flag_given && !local,
+         "--local-shadows, --local-highlights, --local-sigma and --local-levels set the local tone operator: they require "
+         "--display local"},
         {bloom && !display, "--bloom blooms the frame the display transform shows: it requires --display"},
         {grade && !display, "--grade-... grades the frame the display transform shows: it requires --display"},
         {!lut_file.empty() && !display, "--lut is a look on the display transform's frame: it requires --display"},
@@ -796,6 +833,9 @@ int main(int argc, char* argv[]) {
     if (bloom)
         std::printf("bloom: threshold %.6g, knee %.6g, intensity %.6g, scatter %.6g, levels %d\n", (double)bloom_prm.threshold,
                     (double)bloom_prm.knee, (double)bloom_prm.intensity, (double)bloom_prm.scatter, bloom_prm.levels);
+    if (local)
+        std::printf("local: shadows %.6g, highlights %.6g, sigma %.6g, levels %d\n", (double)local_prm.shadows,
+                    (double)local_prm.highlights, (double)local_prm.sigma, local_prm.levels);
     if (grade) {
         std::printf("grade:");
         if (grade_temperature_given) std::printf(" temperature %.9g, tint %.9g,", (double)grade_kelvin, (double)grade_tint);
@@ -830,7 +870,7 @@ int main(int argc, char* argv[]) {
         rtm_tonemap_stats ts;
         const std::string name = stem + suffix;
         const int drc = rtm_node_write_display(&fs, opt.device, &display_prm, frame, name, &ts, err, f32_out,
-                                               lut_file.empty() ? nullptr : &look);
+                                               lut_file.empty() ? nullptr : &look, local ? &local_prm : nullptr);
         if (drc != RTM_OK) return fail("display", drc, err);
         if (suffix.empty())
             std::printf("display: %s_display.bmp, %s_display.jpg (log-average %.6g, max luminance %.6g, exposure %.6g, %u pixels)\n",

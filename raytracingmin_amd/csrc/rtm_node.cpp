@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -607,10 +608,11 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
 }
 
 // --display (rtm_node.h): rtm_tonemap of the frame on the default stream, with --lut the look and the second rtm_tonemap
-// behind it, then the two files.
+// behind it, then the two files.  --display local: a statistics-only rtm_tonemap, rtm_tonemap_local in place, and an
+// rtm_tonemap that only clamps, encodes and stores in the curve's stead.
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* prm, const float* f32_host,
                            const std::string& stem, rtm_tonemap_stats* stats, std::string& err, std::vector<float>* f32_out,
-                           const rtm_node_lut* lut) {
+                           const rtm_node_lut* lut, const rtm_tonemap_local_params* local) {
     const size_t pix = (size_t)st->width * st->height;
     std::vector<uint8_t> rgb8(pix * 3);
     rtm_tonemap_stats got;
@@ -624,13 +626,36 @@ int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap
         DevBuf<float> table;  // only with a look
         DevBuf<void> work;    // hipMalloc's alignment is 256 bytes or more, what rtm_tonemap asks of work_dev
         DevBuf<rtm_tonemap_stats> stats_dev;
+        DevBuf<void> pyramid;  // only with the local operator at levels > 0
+        const size_t pyramid_bytes = local ? rtm_tonemap_local_work_bytes(st->width, st->height, local->levels) : 0;
+        if (pyramid_bytes == SIZE_MAX) return fail(err, RTM_ERR_INVALID_ARGUMENT, "the local tone operator's frame size is out of range");
         if (!color.alloc(pix * 3) || !out8.alloc(pix * 3) || !out32.alloc(pix * 3, f32_out != nullptr || lut != nullptr) ||
-            !table.alloc(lut ? lut->table.size() : 0, lut != nullptr) || !work.alloc(work_bytes) || !stats_dev.alloc(1))
+            !table.alloc(lut ? lut->table.size() : 0, lut != nullptr) || !work.alloc(work_bytes) || !stats_dev.alloc(1) ||
+            !pyramid.alloc(pyramid_bytes, pyramid_bytes != 0))
             return fail(err, RTM_ERR_HIP, "no device memory for the display transform's buffers");
         if (!color.upload(f32_host, pix * 3)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
         if (lut && !table.upload(lut->table.data(), lut->table.size())) return fail(err, RTM_ERR_HIP, "copying the LUT to the device failed");
-        int rc = rtm_tonemap(prm, st->width, st->height, device, color.get(), work.get(), out32.get(), lut ? nullptr : out8.get(),
+        int rc;
+        if (local) {
+            // the statistics of the shown curve's key (and the line rtm_cli prints), then the operator in place with that
+            // call's E by stream order, or with 2^ev in the anchor; the curve left to rtm_tonemap is the clamp
+            rtm_tonemap_local_params fuse = *local;
+            fuse.anchor = prm->auto_exposure ? 1.0f : exp2f(prm->ev);
+            rtm_tonemap_params store = *prm;
+            store.op = RTM_TONEMAP_CLAMP;
+            store.auto_exposure = 0;
+            store.ev = 0.0f;
+            rc = rtm_tonemap(prm, st->width, st->height, device, color.get(), work.get(), nullptr, nullptr, stats_dev.get(), nullptr);
+            if (rc == RTM_OK)
+                rc = rtm_tonemap_local(&fuse, st->width, st->height, device, color.get(), prm->auto_exposure ? stats_dev.get() : nullptr,
+                                       pyramid.get(), color.get(), nullptr, nullptr, nullptr);
+            if (rc == RTM_OK)
+                rc = rtm_tonemap(&store, st->width, st->height, device, color.get(), work.get(), out32.get(), lut ? nullptr : out8.get(),
+                                 nullptr, nullptr);
+        } else {
+            rc = rtm_tonemap(prm, st->width, st->height, device, color.get(), work.get(), out32.get(), lut ? nullptr : out8.get(),
                              stats_dev.get(), nullptr);
+        }
         if (rc == RTM_OK && lut) {
             rtm_tonemap_params store = RTM_TONEMAP_DEFAULTS;  // the look's frame to 8 bits: clamp and dither, nothing else
             store.op = RTM_TONEMAP_CLAMP;

@@ -55,13 +55,18 @@ int rtm_node_write_denoised_variance(const rtm_settings* st, const rtm_object* o
 // lut (nullable, rtm_cli --lut): a display-referred look.  The table is copied to the device, rtm_grade applies it in place
 // to the transform's float frame, and the 8-bit files and f32_out are made from that frame by a second rtm_tonemap call
 // that only clamps and dithers: {CLAMP, LINEAR, no auto exposure, ev 0, params->dither}.
+// local (nullable, rtm_cli --display local): the local tone operator (rtm_tonemap_local) in the tone curve's stead.  A
+// statistics-only rtm_tonemap call with params' key fills stats; the operator runs in place on the frame's device copy with
+// anchor 1 and those statistics (automatic exposure) or with anchor 2^ev and none; then rtm_tonemap runs as {CLAMP,
+// params->transfer, no auto exposure, ev 0, params->dither}, and the look, if any, follows as above.  local->anchor is ignored.
 struct rtm_node_lut {
     rtm_grade_params params;   // RTM_GRADE_DEFAULTS but for lut_size, lut_interp, lut_min, lut_max
     std::vector<float> table;  // 3 lut_size^3 floats in .cube order
 };
 int rtm_node_write_display(const rtm_settings* st, int device, const rtm_tonemap_params* params, const float* f32_host,
                            const std::string& stem, rtm_tonemap_stats* stats, std::string& err,
-                           std::vector<float>* f32_out = nullptr, const rtm_node_lut* lut = nullptr);
+                           std::vector<float>* f32_out = nullptr, const rtm_node_lut* lut = nullptr,
+                           const rtm_tonemap_local_params* local = nullptr);
 // The parametric colour grade (rtm_grade without a LUT, rtm_cli --grade-...) of a float frame (HOST, height x width x 3) on
 // device `device`: the frame is copied to the device, graded in place by one call on the default stream and copied back
 // into f32_out, for the display transform that follows.

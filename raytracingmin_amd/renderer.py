@@ -558,7 +558,7 @@ class Renderer:
         return out, self.stats
 
     def Render(self, fileName, passes=1, aov=False, denoise=False, adaptive=None, tonemap=False, preview=None, mattes=None, bloom=False,
-               dof=None, resize=None, lens=None, grade=None, lut=None, firefly=None):
+               dof=None, resize=None, lens=None, grade=None, lut=None, firefly=None, local=False):
         """src/Renderer.cpp:200-258: render, quantise, write <fileName>.jpg and <fileName>.bmp.  passes > 1 renders the
         frame progressively on the device (Renderer.progressive): the same files and the same self.image.  aov=True also
         writes the first-hit feature buffers (write_aov: <fileName>_depth/_normal/_albedo.pfm, _normal/_albedo.bmp).
@@ -575,6 +575,9 @@ class Renderer:
         bloom=True (or a dict of bloom()'s parameters: threshold, knee, intensity, scatter, levels) blooms every frame the
         display transform is given (write_display's bloom), so the _display, _over_display and _preview_display files are
         those of the bloomed last stage.  It needs tonemap: linear HDR through the reference's quantiser would only clip.
+        local=True (or a dict of tonemap_local()'s shadows, highlights, sigma, levels) replaces the tone curve of every frame the
+        display transform is given by the local tone operator (write_display's local): exposure fusion on luminance at
+        tonemap's exposure, then the transfer function and the dithered store.  It needs tonemap.
         grade=None or False: no grade.  grade (a dict of grade()'s parametric arguments: matrix, exposure, contrast, pivot,
         slope, offset, power, saturation, with temperature and tint as a shorthand for white_balance's matrix) grades every
         frame the display transform is given, in linear light after the bloom (write_display's grade).  lut (the path of a
@@ -649,6 +652,11 @@ class Renderer:
             if display is None:
                 raise ValueError("bloom needs tonemap: it is applied to the frame the display transform shows")
             display["bloom"] = bloom_prm  # write_display's
+        local_prm = _local_option(local)
+        if local_prm is not None:
+            if display is None:
+                raise ValueError("local needs tonemap: it replaces the tone curve of the display transform")
+            display["local"] = local_prm  # write_display's
         grade_prm, lut_prm = _grade_option(grade), _lut_option(lut)
         if grade_prm is not None or lut_prm is not None:
             if display is None:
@@ -713,7 +721,7 @@ class Renderer:
                 self.write_display(fileName + "_preview", frame=shown, **display)
         return rgb8
 
-    def write_display(self, fileName, frame=None, bloom=None, grade=None, lut=None, **params):
+    def write_display(self, fileName, frame=None, bloom=None, grade=None, lut=None, local=None, **params):
         """<fileName>_display.bmp and <fileName>_display.jpg (q=60): the display transform tonemap(**params) (default: the
         ACES curve at automatic exposure, sRGB, dithered) of `frame`, an (H, W, 3) float32 CUDA tensor, or of self.image
         rounded to float like out_f32 — what rtm_cli --display writes.  bloom=True (or a dict of bloom()'s parameters) blooms
@@ -723,12 +731,18 @@ class Renderer:
         transform: what rtm_cli --display --grade-... writes.  lut (the path of a .cube file, or load_cube's dict, which may
         name an "interp") is a display-referred look: it is applied to the display transform's float frame, and the 8-bit
         pixels are then made from its result by a second tonemap() that only clamps and dithers (op "clamp", transfer
-        "linear", exposure 0, the same dither): what rtm_cli --display --lut writes.  Returns the (H, W, 3) uint8 pixels."""
+        "linear", exposure 0, the same dither): what rtm_cli --display --lut writes.  local=True (or a dict of
+        tonemap_local()'s shadows, highlights, sigma, levels) replaces the tone curve by the local tone operator, after the
+        grade: with exposure "auto" a statistics-only tonemap() of the frame gives the exposure on the device and the anchor
+        is 1, with exposure EV the anchor is 2^EV; the fused frame then goes through a tonemap() that only clamps (op "clamp",
+        the same transfer and dither, exposure 0).  `op` and `white` are then unused: what rtm_cli --display local writes.
+        Returns the (H, W, 3) uint8 pixels."""
         import torch
         _tonemap_params(**params)
         bloom_prm = _bloom_option(bloom)
         grade_prm = _grade_option(grade)
         lut_prm = _lut_option(lut)
+        local_prm = _local_option(local)
         if frame is None:
             dev = torch.device("cuda", self.device)
             frame = torch.from_numpy(np.ascontiguousarray(self.image, dtype=np.float64)).to(dev).to(torch.float32)
@@ -736,6 +750,13 @@ class Renderer:
             frame = _bloom(frame, **bloom_prm)["f32"]
         if grade_prm is not None:
             frame = _grade(frame, **grade_prm)["f32"]
+        if local_prm is not None:  # the operator is the curve; what follows only clamps, encodes and stores
+            auto = isinstance(params.get("exposure", TONEMAP_DEFAULTS["exposure"]), str)
+            stats = tonemap(frame, want=("stats",), **params)["stats"] if auto else None
+            anchor = 1.0 if auto else float(np.exp2(np.float32(params["exposure"])))
+            frame = tonemap_local(frame, anchor=anchor, stats=stats, want=("f32",), **local_prm)["f32"]
+            params = {"op": "clamp", "transfer": params.get("transfer", TONEMAP_DEFAULTS["transfer"]), "exposure": 0.0,
+                      "dither": params.get("dither", TONEMAP_DEFAULTS["dither"])}
         if lut_prm is None:
             shown = tonemap(frame, want=("u8",), **params)["u8"]
         else:
@@ -1323,6 +1344,80 @@ def bloom(color, threshold=BLOOM_DEFAULTS["threshold"], knee=BLOOM_DEFAULTS["kne
 
 
 _bloom = bloom  # for Renderer's methods, whose own parameter is named bloom
+
+
+# include/rtm.h: RTM_TONEMAP_LOCAL_DEFAULTS
+TONEMAP_LOCAL_DEFAULTS = {"anchor": 1.0, "shadows": 2.0, "highlights": 2.0, "sigma": 0.25, "levels": 5}
+
+
+def _tonemap_local_params(anchor=TONEMAP_LOCAL_DEFAULTS["anchor"], shadows=TONEMAP_LOCAL_DEFAULTS["shadows"],
+                          highlights=TONEMAP_LOCAL_DEFAULTS["highlights"], sigma=TONEMAP_LOCAL_DEFAULTS["sigma"],
+                          levels=TONEMAP_LOCAL_DEFAULTS["levels"]):
+    """tonemap_local()'s parameters as an rtm_tonemap_local_params; a ValueError names what the library would refuse.  No
+    device use."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or not 0 <= int(levels) <= 8:
+        raise ValueError(f"levels is an integer in 0..8, got {levels!r}")
+    for name, v in (("anchor", anchor), ("shadows", shadows), ("highlights", highlights), ("sigma", sigma)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not np.isfinite(float(v)):
+            raise ValueError(f"{name} is a finite number, got {v!r}")
+    anchor, shadows, highlights, sigma = float(anchor), float(shadows), float(highlights), float(sigma)
+    if not (anchor > 0.0 and np.isfinite(np.float32(anchor)) and np.float32(anchor) > 0):
+        raise ValueError(f"anchor is positive (and a float), got {anchor!r}")
+    if not (0.0 <= shadows <= 8.0 and 0.0 <= highlights <= 8.0):
+        raise ValueError(f"shadows and highlights are in [0, 8], got {shadows!r} and {highlights!r}")
+    if not (np.float32(0.1) <= np.float32(sigma) <= 1.0):
+        raise ValueError(f"sigma is in [0.1, 1], got {sigma!r}")
+    return _lib.rtm_tonemap_local_params(anchor, shadows, highlights, sigma, int(levels))
+
+
+def _local_option(local):
+    """Render's and write_display's `local`: None for off, else the dict of tonemap_local()'s parameters (without anchor, which
+    the display path sets from the exposure), checked.  No device use."""
+    if local is None or local is False:
+        return None
+    if local is not True and not isinstance(local, dict):
+        raise ValueError(f"local is False, True or a dict of tonemap_local()'s parameters, got {local!r}")
+    prm = {} if local is True else dict(local)
+    allowed = tuple(k for k in TONEMAP_LOCAL_DEFAULTS if k != "anchor")
+    unknown = set(prm) - set(allowed)
+    if unknown:
+        raise ValueError(f"local's parameters are {allowed}, got {sorted(unknown)}")
+    _tonemap_local_params(**prm)
+    return prm
+
+
+def tonemap_local(color, anchor=TONEMAP_LOCAL_DEFAULTS["anchor"], shadows=TONEMAP_LOCAL_DEFAULTS["shadows"],
+                  highlights=TONEMAP_LOCAL_DEFAULTS["highlights"], sigma=TONEMAP_LOCAL_DEFAULTS["sigma"],
+                  levels=TONEMAP_LOCAL_DEFAULTS["levels"], want=("f32", "u8", "fused"), stats=None, stream=None, out_f32=None):
+    """The local tone operator (include/rtm.h: rtm_tonemap_local) on the device: exposure fusion on luminance, chroma kept.
+    It replaces tonemap()'s curve: the result is display-linear, nominally in [0, 1]; follow it with tonemap(op="clamp",
+    exposure=0.0) for the transfer function and the dithered store.  `color` is an (H, W, 3) float32 torch CUDA tensor (any
+    4-byte-aligned contiguous view).  anchor: the exposure in front of the operator; shadows, highlights in [0, 8]: the stops
+    by which the shadow exposure is opened and the highlight exposure closed; sigma in [0.1, 1]: the width of the
+    well-exposedness weight; levels 0..8: the depth of the pyramid, 0 the pointwise blend.  stats: tonemap()'s "stats" tensor
+    (4 int32 words on the device), whose exposure then multiplies the anchor, read by the kernels without a host sync.
+    Returns a dict of the names in `want`: "f32" (H, W, 3) float32, "u8" (H, W, 3) uint8 (rtm_quantise of it), "fused"
+    (H, W) float32 (the fused luminance F).  out_f32: the tensor to write "f32" into; `color` itself maps in place.  Enqueued
+    on `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream) with a work buffer allocated
+    here; nothing waits for it and nothing is copied to the host."""
+    prm = _tonemap_local_params(anchor, shadows, highlights, sigma, levels)
+    _check_want(want, ("f32", "u8", "fused"))
+    import torch
+    _need_device("tonemap_local")
+    H, W = _frame_size(color, "color", non_empty=True)
+    dev = color.device
+    if stats is not None and not (isinstance(stats, torch.Tensor) and stats.device == dev and stats.dtype == torch.int32
+                                  and stats.numel() == 4 and stats.is_contiguous()):
+        raise ValueError(f'stats is tonemap()\'s "stats": a contiguous tensor of 4 int32 words on {dev}')
+    _check_out_f32(out_f32, want, H, W, dev)
+    s = _stream_of(stream, dev)
+    L = _lib.lib()
+    specs = {"f32": ((H, W, 3), torch.float32), "u8": ((H, W, 3), torch.uint8), "fused": ((H, W), torch.float32)}
+    out, ptr = _stage_tensors(s, dev, want, specs, max(256, L.rtm_tonemap_local_work_bytes(W, H, prm.levels)), out_f32=out_f32)
+    _lib.check(L.rtm_tonemap_local(C.byref(prm), W, H, dev.index, color.data_ptr(), None if stats is None else stats.data_ptr(),
+                                   ptr("work"), ptr("f32"), ptr("u8"), ptr("fused"), C.c_void_p(s.cuda_stream)),
+               "rtm_tonemap_local")
+    return out
 
 
 # include/rtm.h: RTM_FIREFLY_DEFAULTS
