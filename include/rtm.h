@@ -1275,6 +1275,82 @@ size_t rtm_flip_work_bytes(int32_t width, int32_t height);
 int rtm_flip(const rtm_flip_params* params, int32_t width, int32_t height, int device, const float* a_dev,
              const float* b_dev, void* work_dev, rtm_flip_result* result_out_dev, float* map_out_dev, void* stream);
 
+/* ---- scopes: what ONE frame holds — per-channel histograms, a per-column waveform / RGB parade, and from the histogram, on
+ * the host, percentiles and an exposure suggestion.  rtm_compare and rtm_flip measure a pair of frames; rtm_tonemap knows a
+ * frame's log-average and L_max only.  Opt-in; no other stage and no default changes.
+ * Input: color (DEVICE, height x width x 3 floats, RGB-interleaved like out_f32; 4-byte alignment is enough).  Every count is
+ * an integer and every bin is taken from a float's 32-bit word or from one stated double product, so a float32 restatement
+ * reproduces every word of both outputs.
+ *   1 counting   a pixel COUNTS iff its three components are finite (the library's rule).  `pixels` counts those that do,
+ *                `not_counting` those that do not; a pixel that does not count enters nothing else.
+ *   2 channels   channel 0 is Y, 1 is R, 2 is G, 3 is B.  R, G and B are the components' own words.
+ *                l = (0.2126f c_R + 0.7152f c_G) + 0.0722f c_B in float, without contraction (rtm_tonemap's lum), and
+ *                Y = l > 0 ? l : +0.0f.  An l that overflowed to +inf is a value like any other: it lands in `above`.
+ *   3 LOG2 bins  (mode RTM_SCOPE_LOG2, for a scene-referred frame) 8 bins a stop from 2^-16 up to, not including, 2^16,
+ *                read from the value's bit pattern: no logarithm is evaluated and no bin edge depends on a fast-math form.
+ *                With u the value's 32-bit word: the value is BELOW when the sign bit is set or (u >> 20) < 888 (that is
+ *                +-0, denormals and everything under 2^-16, so it does not matter whether the device flushes denormals);
+ *                otherwise b = (u >> 20) - 888, and the value is ABOVE when b > 255, else it is in bins[c][b].  Bin b holds
+ *                [2^e (1 + j/8), the next bin's lower edge) with e = (b >> 3) - 16 and j = b & 7; bin 128 starts at 1.0,
+ *                0.18 is in bin 107, and 65536 is the first value above.
+ *   4 CODE bins  (mode RTM_SCOPE_CODE, for a display-referred frame in [0, 1]) v < 0 is BELOW, v > 1 is ABOVE, otherwise
+ *                the bin is (int)(255.0 * (double)v): the byte rtm_quantise stores.  -0.0f is bin 0 and 1.0 is bin 255.
+ *   5 histogram  hist_out_dev (nullable): bins[c][b], below[c] and above[c] over the counting pixels, pixels, not_counting,
+ *                reserved = 0.
+ *   6 waveform   waveform_out_dev (nullable, [4][256][columns] words): frame column x belongs to output column
+ *                (int64)x * columns / width, and waveform[c][b][oc] counts the counting pixels of those columns whose channel
+ *                c is in bin b; BELOW is counted in row 0 and ABOVE in row 255: clipped values pile up at the scope's edges.
+ * It follows that, for every c, below[c] + sum_b bins[c][b] + above[c] == pixels; that pixels + not_counting == width height;
+ * and that sum_oc waveform[c][b][oc] == bins[c][b] for 0 < b < 255, == bins[c][0] + below[c] for b = 0 and
+ * == bins[c][255] + above[c] for b = 255.
+ * The counts are exact and order-free, so this stage uses INTEGER ATOMICS ONLY (on LDS and on the outputs' words): the same
+ * inputs give the same words on every call, on any stream, at any 4-byte alignment.  No state, no work buffer: the call
+ * zeroes its own outputs on `stream`, allocates nothing and only ENQUEUES (the zeroing and one launch).  Null params or
+ * color_dev, both outputs null, a non-positive size, mode out of range, columns outside 1..width when a waveform is asked for
+ * (ignored without one), a pointer that is not 4-byte aligned, an output equal to color_dev or to the other output, a negative
+ * device: RTM_ERR_INVALID_ARGUMENT, before any device call.  A frame of 2^31 pixels or more: RTM_ERR_UNSUPPORTED.
+ *
+ * rtm_scope_draw turns a waveform into a picture (DEVICE, 256 rows of RGB bytes, bin 255 on top): a value is
+ * min(255, (uint64)count * gain).  RTM_SCOPE_LUMA: columns wide, plane 0 in all three bytes.  RTM_SCOPE_OVERLAY: columns wide,
+ * byte k from plane 1 + k.  RTM_SCOPE_PARADE: 3 columns wide, the panels R, G, B side by side, each in its own byte with the
+ * other two bytes 0.  One launch on `stream`, no atomics.  Null pointers, columns < 1, layout out of range, gain 0, a
+ * misaligned waveform_dev, out_u8_dev equal to waveform_dev, a negative device: RTM_ERR_INVALID_ARGUMENT, before any device
+ * call; columns of 2^21 or more: RTM_ERR_UNSUPPORTED.
+ *
+ * The rest is HOST ONLY (a histogram copied to the host; no device call), in double:
+ * rtm_scope_bin_range: the range [lo, hi) of bin 0..255 as floats.  LOG2: step 3's edges (hi of bin 255 is 65536).  CODE: lo
+ *   is the smallest float whose bin is `bin` (0 for bin 0) and hi the next bin's lo; bin 255 holds 1.0 alone: lo = hi = 1.
+ * rtm_scope_percentile of channel c: N = pixels.  N == 0: value 1, bin -2 (rtm_tonemap's n == 0 rule).  t = percent / 100 N,
+ *   cum = below[c].  t <= cum: value 0, bin -1.  Otherwise the first bin b with n_b > 0 and cum + n_b >= t (cum running over
+ *   the bins before it): value = lo_b + (t - cum) / n_b (hi_b - lo_b), rounded to float, bin b.  Past the last bin: the
+ *   range's upper end (65536 or 1) and bin 256.  value_out and bin_out are each nullable, not both.
+ * rtm_scope_exposure: ev = log2(target / value), value being channel Y's LOG2 percentile, clamped to rtm_tonemap's +-32 and
+ *   rounded to float; value <= 0 gives ev = 0.  rtm_tonemap with auto_exposure = 0 and this ev puts that percentile at target.
+ * Null pointers, mode out of range, a bin or a channel out of range, a percent outside [0, 100] or NaN, a target that is not
+ * positive and finite: RTM_ERR_INVALID_ARGUMENT.
+ * Defaults: RTM_SCOPE_DEFAULTS below (what rtm_cli --scopes uses for the linear frame).  Added after RTM_ABI_VERSION 5 without
+ * changing it: callers look the symbols up. */
+enum { RTM_SCOPE_LOG2 = 0, RTM_SCOPE_CODE = 1 };
+enum { RTM_SCOPE_LUMA = 0, RTM_SCOPE_OVERLAY = 1, RTM_SCOPE_PARADE = 2 };
+typedef struct rtm_scope_params { /* 8 bytes */
+    int32_t mode;    /* RTM_SCOPE_LOG2 or RTM_SCOPE_CODE                                      */
+    int32_t columns; /* waveform columns, 1..width; ignored without a waveform                */
+} rtm_scope_params;
+#define RTM_SCOPE_DEFAULTS {RTM_SCOPE_LOG2, 256} /* an initializer of rtm_scope_params */
+typedef struct rtm_scope_histogram { /* 4144 bytes, no padding */
+    uint32_t bins[4][256]; /* channel 0 = Y, 1 = R, 2 = G, 3 = B */
+    uint32_t below[4], above[4];
+    uint32_t pixels, not_counting, reserved[2]; /* reserved = 0 */
+} rtm_scope_histogram;
+int rtm_scopes(const rtm_scope_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+               rtm_scope_histogram* hist_out_dev, uint32_t* waveform_out_dev, void* stream);
+int rtm_scope_draw(int32_t columns, int32_t layout, uint32_t gain, int device, const uint32_t* waveform_dev,
+                   uint8_t* out_u8_dev, void* stream);
+int rtm_scope_bin_range(int32_t mode, int32_t bin, float* lo, float* hi);
+int rtm_scope_percentile(const rtm_scope_histogram* hist_host, int32_t mode, int32_t channel, double percent,
+                         float* value_out, int32_t* bin_out);
+int rtm_scope_exposure(const rtm_scope_histogram* hist_host, double percent, double target, float* ev_out);
+
 /* RTM_OK, or RTM_ERR_UNSUPPORTED when a render enqueued on (device, stream) since the last report
  * overflowed its hit records.  Waits for the stream's queued work (hipStreamSynchronize). */
 int rtm_stream_status(int device, void* stream);

@@ -186,6 +186,23 @@ class rtm_flip_result(C.Structure):  # what rtm_flip leaves in result_out_dev: 1
                 ("nonfinite", C.c_uint64), ("argmax_x", C.c_int32), ("argmax_y", C.c_int32), ("hist", C.c_uint32 * 256)]
 
 
+SCOPE_MODES = {"log2": 0, "code": 1}  # include/rtm.h: RTM_SCOPE_LOG2, RTM_SCOPE_CODE
+SCOPE_LAYOUTS = {"luma": 0, "overlay": 1, "parade": 2}  # RTM_SCOPE_LUMA, RTM_SCOPE_OVERLAY, RTM_SCOPE_PARADE
+SCOPE_CHANNELS = ("y", "r", "g", "b")  # the histogram's and the waveform's channel order
+
+
+class rtm_scope_params(C.Structure):  # include/rtm.h: rtm_scopes (8 bytes)
+    _fields_ = [("mode", C.c_int32), ("columns", C.c_int32)]
+
+
+class rtm_scope_histogram(C.Structure):  # what rtm_scopes leaves in hist_out_dev: 4144 bytes, no padding
+    _fields_ = [("bins", (C.c_uint32 * 256) * 4), ("below", C.c_uint32 * 4), ("above", C.c_uint32 * 4), ("pixels", C.c_uint32),
+                ("not_counting", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+SCOPE_DEFAULTS = {"mode": "log2", "columns": 256}  # RTM_SCOPE_DEFAULTS
+
+
 # every symbol include/rtm.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -259,6 +276,11 @@ SIGNATURES = {
     "rtm_flip_work_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "rtm_flip": (C.c_int, [_P(rtm_flip_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_scopes": (C.c_int, [_P(rtm_scope_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_scope_draw": (C.c_int, [C.c_int32, C.c_int32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtm_scope_bin_range": (C.c_int, [C.c_int32, C.c_int32, _P(C.c_float), _P(C.c_float)]),
+    "rtm_scope_percentile": (C.c_int, [_P(rtm_scope_histogram), C.c_int32, C.c_int32, C.c_double, _P(C.c_float), _P(C.c_int32)]),
+    "rtm_scope_exposure": (C.c_int, [_P(rtm_scope_histogram), C.c_double, C.c_double, _P(C.c_float)]),
     "rtm_render_device": (C.c_int, [_P(rtm_settings), C.c_void_p, C.c_size_t, C.c_int,
                                     _P(rtm_options), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, _P(rtm_stats)]),

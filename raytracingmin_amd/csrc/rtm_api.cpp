@@ -161,6 +161,22 @@ int rtm_firefly(const rtm_firefly_params* params, int32_t width, int32_t height,
                 float* out_f32_dev, uint8_t* out_u8_dev, uint8_t* mask_out_dev, float* threshold_out_dev, void* stream) {
     RTM_GUARD(rtm::firefly(params, width, height, device, color_dev, out_f32_dev, out_u8_dev, mask_out_dev, threshold_out_dev, stream))
 }
+int rtm_scopes(const rtm_scope_params* params, int32_t width, int32_t height, int device, const float* color_dev,
+               rtm_scope_histogram* hist_out_dev, uint32_t* waveform_out_dev, void* stream) {
+    RTM_GUARD(rtm::scopes(params, width, height, device, color_dev, hist_out_dev, waveform_out_dev, stream))
+}
+int rtm_scope_draw(int32_t columns, int32_t layout, uint32_t gain, int device, const uint32_t* waveform_dev, uint8_t* out_u8_dev,
+                   void* stream) {
+    RTM_GUARD(rtm::scope_draw(columns, layout, gain, device, waveform_dev, out_u8_dev, stream))
+}
+int rtm_scope_bin_range(int32_t mode, int32_t bin, float* lo, float* hi) { RTM_GUARD(rtm::scope_bin_range(mode, bin, lo, hi)) }
+int rtm_scope_percentile(const rtm_scope_histogram* hist_host, int32_t mode, int32_t channel, double percent, float* value_out,
+                         int32_t* bin_out) {
+    RTM_GUARD(rtm::scope_percentile(hist_host, mode, channel, percent, value_out, bin_out))
+}
+int rtm_scope_exposure(const rtm_scope_histogram* hist_host, double percent, double target, float* ev_out) {
+    RTM_GUARD(rtm::scope_exposure(hist_host, percent, target, ev_out))
+}
 int rtm_defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color_dev,
                 const float* depth_dev, float* out_f32_dev, uint8_t* out_u8_dev, float* coc_out_dev, void* stream) {
     RTM_GUARD(rtm::defocus(params, width, height, device, color_dev, depth_dev, out_f32_dev, out_u8_dev, coc_out_dev, stream))

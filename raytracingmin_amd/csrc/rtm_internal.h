@@ -92,6 +92,15 @@ int lut_load_cube(const char* path, int32_t* size, float* domain_min, float* dom
 // the firefly clamp and the repair of non-finite pixels (rtm_firefly.hip)
 int firefly(const rtm_firefly_params* params, int32_t width, int32_t height, int device, const float* color, float* out32,
             uint8_t* out8, uint8_t* mask_out, float* threshold_out, void* stream);
+// the frame scopes (rtm_scope.hip): histograms and the waveform on the device, the picture of a waveform, and the host-only
+// readers of a histogram
+int scopes(const rtm_scope_params* params, int32_t width, int32_t height, int device, const float* color,
+           rtm_scope_histogram* hist_out, uint32_t* waveform_out, void* stream);
+int scope_draw(int32_t columns, int32_t layout, uint32_t gain, int device, const uint32_t* waveform, uint8_t* out8, void* stream);
+int scope_bin_range(int32_t mode, int32_t bin, float* lo, float* hi);
+int scope_percentile(const rtm_scope_histogram* hist, int32_t mode, int32_t channel, double percent, float* value_out,
+                     int32_t* bin_out);
+int scope_exposure(const rtm_scope_histogram* hist, double percent, double target, float* ev_out);
 // depth of field (rtm_defocus.hip); the probe runs one form of the kernel (rtm_debug_defocus_form)
 int defocus(const rtm_defocus_params* params, int32_t width, int32_t height, int device, const float* color, const float* depth,
             float* out32, uint8_t* out8, float* coc_out, void* stream);

@@ -10,6 +10,10 @@
 //           [--aov]                              (first-hit feature buffers next to the image: STEM_depth/_normal/_albedo.pfm, .bmp)
 //           [--firefly [K]] [--firefly-rank N] [--firefly-radius R] [--firefly-floor F] [--firefly-keep-nonfinite]
 //                                                (the firefly clamp of the frame, before every stage below: STEM_firefly.bmp, .jpg)
+//           [--scopes [--scopes-columns N] [--scopes-layout luma|overlay|parade]]
+//                                                (histograms, percentiles and the waveform of the last frame and of the display
+//                                                 frame: one line scopes: {...}, STEM_scopes.json, STEM_waveform.bmp)
+//           [--expose-percentile P[,TARGET]]     (with --display: the exposure that puts luminance percentile P at TARGET)
 //           [--denoise]                          (the à-trous denoiser next to the image: STEM_denoised.bmp, .jpg)
 //           [--denoise-variance]                 (the variance-guided one: STEM_denoised_var.bmp, .jpg, STEM_variance.pfm)
 //           [--display [clamp|reinhard|aces|local]] [--exposure auto|EV] [--linear] [--no-dither]
@@ -134,6 +138,17 @@ static void usage() {
         "            --firefly-keep-nonfinite is given.  Prints one line 'firefly: {...}', the counts of clamped and repaired pixels\n"
         "            as JSON.  The cleaned frame then is the frame every later stage takes: --denoise, --denoise-variance, --dof,\n"
         "            --lens, --resize, --display (with --bloom), --pfm, --compare, --flip and --background\n"
+        "--scopes [--scopes-columns N] [--scopes-layout luma|overlay|parade] : measure the last linear float frame (the frame --pfm\n"
+        "            would write) on one GPU (rtm_scopes): per-channel histograms of Y, R, G, B at 8 bins a stop from 2^-16 to 2^16,\n"
+        "            and, with --display, the display frame's at the 256 8-bit code values.  Prints one line 'scopes: {...}' as\n"
+        "            JSON: the pixels that count and that do not, the luminance percentiles 1, 50, 99 and 99.9, the share of\n"
+        "            pixels below and above the bins per channel, the same under \"display\" for the display frame; writes\n"
+        "            STEM_scopes.json (that object plus the full histograms) and STEM_waveform.bmp, the waveform (rtm_scope_draw)\n"
+        "            of the display frame when there is one, else of the linear frame: N columns (default min(256, width)), 256\n"
+        "            rows, layout luma (default), overlay or parade (three panels), gain max(1, 2040 / height) per count\n"
+        "--expose-percentile P[,TARGET] : with --display and a global curve, run the display transform at the exposure that puts\n"
+        "            the luminance percentile P (0..100) of the frame it takes at TARGET (default 0.18): rtm_scope_exposure of that\n"
+        "            frame's histogram, in --exposure's stead; the stops chosen are printed, in the scopes: line with --scopes\n"
         "--denoise : also write the frame denoised on one GPU (rtm_denoise at its default parameters, guided by the\n"
         "            frame's first-hit feature buffers): STEM_denoised.bmp and STEM_denoised.jpg\n"
         "--denoise-variance : also write the frame through the variance-guided denoiser on one GPU (rtm_denoise_variance at\n"
@@ -246,6 +261,9 @@ int main(int argc, char* argv[]) {
     rtm_lens_params lens_prm = RTM_LENS_DEFAULTS;
     int resize = 0, resize_filter_given = 0, resize_w = 0, resize_h = 0;
     rtm_resize_params resize_prm = RTM_RESIZE_DEFAULTS;
+    int scopes = 0, scopes_columns = 0, scopes_columns_given = 0, scopes_layout = RTM_SCOPE_LUMA, scopes_layout_given = 0;
+    int expose = 0, exposure_given = 0;
+    double expose_percent = 0.0, expose_target = 0.18;
     int pfm = 0;
     std::string dump_f32, compare_ref, flip_ref;
     int display_pfm = 0, flip_map = 0, flip_ppd_given = 0;
@@ -327,6 +345,7 @@ int main(int argc, char* argv[]) {
         } else if (c == "--exposure" && i + 1 < argc) {
             const std::string m = argv[++i];
             double ev = 0.0;
+            exposure_given = 1;
             if (m == "auto") {
                 display_prm.auto_exposure = 1;
                 display_prm.ev = 0.0f;
@@ -594,6 +613,40 @@ int main(int argc, char* argv[]) {
             resize_filter_given = 1;
             resize_prm.filter = which;
         }
+        else if (c == "--scopes") scopes = 1;
+        else if (c == "--scopes-columns") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            double v = 0.0;
+            scopes_columns_given = 1;
+            if (!parse_number(m, v) || v != std::floor(v) || v < 1.0 || v > 2147483647.0) {
+                std::fprintf(stderr, "--scopes-columns takes a whole number of columns from 1, got %s\n", m.c_str());
+                return 2;
+            }
+            scopes_columns = (int)v;
+        } else if (c == "--scopes-layout") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            scopes_layout_given = 1;
+            if (m == "luma") scopes_layout = RTM_SCOPE_LUMA;
+            else if (m == "overlay") scopes_layout = RTM_SCOPE_OVERLAY;
+            else if (m == "parade") scopes_layout = RTM_SCOPE_PARADE;
+            else {
+                std::fprintf(stderr, "--scopes-layout takes luma, overlay or parade, got %s\n", m.c_str());
+                return 2;
+            }
+        } else if (c == "--expose-percentile") {
+            // P or P,TARGET: a percent in [0, 100] and a positive finite target
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            const size_t comma = m.find(',');
+            expose = 1;
+            bool ok = parse_number(m.substr(0, comma), expose_percent) && expose_percent >= 0.0 && expose_percent <= 100.0;
+            if (ok && comma != std::string::npos)
+                ok = parse_number(m.substr(comma + 1), expose_target) && std::isfinite(expose_target) && expose_target > 0.0;
+            if (!ok) {
+                std::fprintf(stderr, "--expose-percentile takes P or P,TARGET, a percent in 0..100 and a positive target, got %s\n",
+                             m.c_str());
+                return 2;
+            }
+        }
         else if (c == "--pfm") pfm = 1;
         else if (c == "--compare" && i + 1 < argc) compare_ref = argv[++i];
         else if (c == "--display-pfm") display_pfm = 1;
@@ -697,6 +750,16 @@ int main(int argc, char* argv[]) {
          "--firefly-rank, --firefly-radius, --firefly-floor and --firefly-keep-nonfinite require --firefly"},
         {firefly && many, "--firefly runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
         {firefly && preview_only, "--preview-only skips the full render: it does not combine with --firefly"},
+        {(scopes_columns_given || scopes_layout_given) && !scopes, "--scopes-columns and --scopes-layout require --scopes"},
+        {scopes && many, "--scopes runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {scopes && preview_only, "--preview-only skips the full render: it does not combine with --scopes"},
+        {expose && many,
+         "--expose-percentile runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
+        {expose && preview_only, "--preview-only skips the full render: it does not combine with --expose-percentile"},
+        {expose && !display, "--expose-percentile sets the display transform's exposure: it requires --display"},
+        {expose && exposure_given, "--expose-percentile chooses the exposure: it does not combine with --exposure"},
+        {expose && local,
+         "--expose-percentile needs a global curve: it does not combine with --display local, which takes its own exposures"},
         {(focus_given || focus_pixel_given || dof_radius_given) && !dof, "--focus, --focus-pixel and --dof-radius require --dof"},
         {focus_given && focus_pixel_given, "--dof focuses at --focus DISTANCE or at --focus-pixel X,Y, not at both"},
         {dof && many, "--dof runs on one GPU: it does not combine with --gpus > 1, --virtual-strips or --force-rccl"},
@@ -797,7 +860,7 @@ int main(int argc, char* argv[]) {
         }
     }
     // a later stage takes the float frame of the last one
-    const bool want_last = display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof || lens || resize;
+    const bool want_last = scopes || display || pfm || !compare_ref.empty() || !flip_ref.empty() || background || dof || lens || resize;
     if (dof) {  // the focus, known before anything is rendered: --focus, what --focus-pixel shows, else the camera's target
         if (focus_pixel_given) {
             if (focus_x >= st.width || focus_y >= st.height) {
@@ -853,6 +916,7 @@ int main(int argc, char* argv[]) {
                     (double)look.params.lut_max[1], (double)look.params.lut_max[2]);
     // --display of one frame: bloomed first with --bloom, graded with --grade-..., then STEM<suffix>_display.bmp / .jpg and their line, which gives
     // the statistics for the frame itself (no suffix); the exit status, 0 when all went well
+    float chosen_ev = 0.0f;  // --expose-percentile's stops for the frame itself
     const auto show = [&](const rtm_settings& fs, const float* frame, const std::string& suffix, std::vector<float>* f32_out) {
         std::string err;
         std::vector<float> bloomed;
@@ -867,9 +931,23 @@ int main(int argc, char* argv[]) {
             if (grc != RTM_OK) return fail("grade", grc, err);
             frame = graded.data();
         }
+        rtm_tonemap_params shown_prm = display_prm;
+        if (expose) {  // the exposure from the histogram of the frame the transform is about to take
+            const rtm_scope_params sp = RTM_SCOPE_DEFAULTS;
+            rtm_scope_histogram hist;
+            int erc = rtm_node_scopes(&fs, opt.device, &sp, frame, &hist, RTM_SCOPE_LUMA, 1, nullptr, err);
+            if (erc != RTM_OK) return fail("expose-percentile", erc, err);
+            shown_prm.auto_exposure = 0;
+            erc = rtm_scope_exposure(&hist, expose_percent, expose_target, &shown_prm.ev);
+            if (erc != RTM_OK) return fail("expose-percentile", erc, rtm_last_error_detail());
+            if (suffix.empty()) chosen_ev = shown_prm.ev;
+            std::printf("expose-percentile: %s%s at %s percent to %s, exposure %s\n", stem.c_str(), suffix.c_str(),
+                        json_number(expose_percent).c_str(), json_number(expose_target).c_str(),
+                        json_number((double)shown_prm.ev).c_str());
+        }
         rtm_tonemap_stats ts;
         const std::string name = stem + suffix;
-        const int drc = rtm_node_write_display(&fs, opt.device, &display_prm, frame, name, &ts, err, f32_out,
+        const int drc = rtm_node_write_display(&fs, opt.device, &shown_prm, frame, name, &ts, err, f32_out,
                                                lut_file.empty() ? nullptr : &look, local ? &local_prm : nullptr);
         if (drc != RTM_OK) return fail("display", drc, err);
         if (suffix.empty())
@@ -999,7 +1077,7 @@ int main(int argc, char* argv[]) {
     }
     const float* last = shown.empty() ? frame32 : shown.data();
     std::vector<float> displayed;  // the display transform's float frame, when --display-pfm or --flip follows --display
-    if (display && show(last_st, last, "", display_pfm || !flip_ref.empty() ? &displayed : nullptr) != 0) return 1;
+    if (display && show(last_st, last, "", display_pfm || scopes || !flip_ref.empty() ? &displayed : nullptr) != 0) return 1;
     if (display_pfm) {
         if (rtm_write_pfm((stem + "_display.pfm").c_str(), last_st.width, last_st.height, 3, displayed.data()) != 1) {
             std::fprintf(stderr, "cannot write %s_display.pfm\n", stem.c_str());
@@ -1013,6 +1091,78 @@ int main(int argc, char* argv[]) {
             return 1;
         }
         std::printf("pfm: %s.pfm\n", stem.c_str());
+    }
+    if (scopes) {  // the last linear frame in stops, the display frame in code values, the waveform of the one that is shown
+        rtm_scope_params sp = RTM_SCOPE_DEFAULTS;
+        sp.columns = scopes_columns_given ? scopes_columns : std::min(sp.columns, last_st.width);
+        if (sp.columns > last_st.width) {
+            std::fprintf(stderr, "--scopes-columns %d exceeds the frame's width %d\n", sp.columns, last_st.width);
+            return 2;
+        }
+        const uint32_t gain = (uint32_t)std::max(1, 2040 / last_st.height);
+        // one frame's object: the line's fields, and with `full` the counts
+        const auto describe = [](const rtm_scope_histogram& h, int mode, bool full) {
+            std::string s = std::string("{\"mode\": \"") + (mode == RTM_SCOPE_LOG2 ? "log2" : "code") + "\", \"pixels\": " +
+                            std::to_string(h.pixels) + ", \"not_counting\": " + std::to_string(h.not_counting) + ", \"percentiles\": {";
+            const double percents[4] = {1.0, 50.0, 99.0, 99.9};
+            const char* const keys[4] = {"1", "50", "99", "99.9"};
+            for (int k = 0; k < 4; ++k) {
+                float v = 0.0f;
+                (void)rtm_scope_percentile(&h, mode, 0, percents[k], &v, nullptr);
+                s += std::string(k ? ", \"" : "\"") + keys[k] + "\": " + json_number((double)v);
+            }
+            s += "}";
+            const auto list = [&](const char* name, const uint32_t* v, int count, bool share) {
+                s += std::string(", \"") + name + "\": [";
+                for (int k = 0; k < count; ++k)
+                    s += std::string(k ? ", " : "") +
+                         (share ? json_number(h.pixels ? (double)v[k] / (double)h.pixels : 0.0) : std::to_string(v[k]));
+                s += "]";
+            };
+            list("below", h.below, 4, true);
+            list("above", h.above, 4, true);
+            if (full) {
+                s += ", \"histogram\": {\"bins\": [";
+                for (int c = 0; c < 4; ++c) {
+                    s += c ? ", [" : "[";
+                    for (int b = 0; b < 256; ++b) s += std::string(b ? ", " : "") + std::to_string(h.bins[c][b]);
+                    s += "]";
+                }
+                s += "]";
+                list("below", h.below, 4, false);
+                list("above", h.above, 4, false);
+                s += "}";
+            }
+            return s + "}";
+        };
+        rtm_scope_histogram lin, disp;
+        std::vector<uint8_t> picture;
+        rc = rtm_node_scopes(&last_st, opt.device, &sp, last, &lin, scopes_layout, gain, display ? nullptr : &picture, err);
+        if (rc != RTM_OK) return fail("scopes", rc, err);
+        if (display) {
+            sp.mode = RTM_SCOPE_CODE;
+            rc = rtm_node_scopes(&last_st, opt.device, &sp, displayed.data(), &disp, scopes_layout, gain, &picture, err);
+            if (rc != RTM_OK) return fail("scopes", rc, err);
+        }
+        std::string line, doc;
+        for (int full = 0; full < 2; ++full) {
+            std::string s = describe(lin, RTM_SCOPE_LOG2, full != 0);
+            s.pop_back();  // the frame's object stays open for what belongs to the run
+            if (display) s += ", \"display\": " + describe(disp, RTM_SCOPE_CODE, full != 0);
+            if (expose) s += ", \"exposure\": " + json_number((double)chosen_ev);
+            s += "}";
+            (full ? doc : line) = s;
+        }
+        std::printf("scopes: %s\n", line.c_str());
+        FILE* f = std::fopen((stem + "_scopes.json").c_str(), "wb");
+        const bool wrote = f && std::fwrite(doc.data(), 1, doc.size(), f) == doc.size();
+        if (f) std::fclose(f);
+        const int picture_w = sp.columns * (scopes_layout == RTM_SCOPE_PARADE ? 3 : 1);
+        if (!wrote || rtm_write_bmp((stem + "_waveform.bmp").c_str(), picture_w, 256, 3, picture.data()) != 1) {
+            std::fprintf(stderr, "cannot write %s_scopes.json or %s_waveform.bmp\n", stem.c_str(), stem.c_str());
+            return 1;
+        }
+        std::printf("waveform: %s_waveform.bmp (%d x 256, gain %u), %s_scopes.json\n", stem.c_str(), picture_w, gain, stem.c_str());
     }
     if (!compare_ref.empty()) {
         rtm_compare_result cr;

@@ -738,6 +738,29 @@ int rtm_node_write_firefly(const rtm_settings* st, int device, const rtm_firefly
     return RTM_OK;
 }
 
+// --scopes (rtm_node.h): rtm_scopes of the frame on the default stream, and rtm_scope_draw of its waveform.
+int rtm_node_scopes(const rtm_settings* st, int device, const rtm_scope_params* prm, const float* f32_host,
+                    rtm_scope_histogram* hist, int layout, uint32_t gain, std::vector<uint8_t>* picture, std::string& err) {
+    const size_t vals = (size_t)st->width * st->height * 3;
+    if (const int rc = open_device(device, err); rc != RTM_OK) return rc;
+    const size_t words = picture ? (size_t)4 * 256 * (size_t)(prm->columns > 0 ? prm->columns : 0) : 0;
+    const size_t bytes = picture ? (size_t)256 * 3 * (size_t)prm->columns * (layout == RTM_SCOPE_PARADE ? 3 : 1) : 0;
+    DevBuf<float> color;
+    DevBuf<rtm_scope_histogram> hist_dev;
+    DevBuf<uint32_t> wave;
+    DevBuf<uint8_t> drawn;
+    if (!color.alloc(vals) || !hist_dev.alloc(1) || !wave.alloc(words, picture != nullptr) || !drawn.alloc(bytes, picture != nullptr))
+        return fail(err, RTM_ERR_HIP, "no device memory for the scopes' buffers");
+    if (!color.upload(f32_host, vals)) return fail(err, RTM_ERR_HIP, "copying the frame to the device failed");
+    int rc = rtm_scopes(prm, st->width, st->height, device, color.get(), hist_dev.get(), picture ? wave.get() : nullptr, nullptr);
+    if (rc == RTM_OK && picture) rc = rtm_scope_draw(prm->columns, layout, gain, device, wave.get(), drawn.get(), nullptr);
+    if (rc != RTM_OK) return fail(err, rc, rtm_last_error_detail());
+    if (picture) picture->resize(bytes);
+    if (!hist_dev.download(hist, 1) || (picture && !drawn.download(picture->data(), bytes)))
+        return fail(err, RTM_ERR_HIP, "copying the scopes back failed");
+    return RTM_OK;
+}
+
 // --dof (rtm_node.h): the depth plane and rtm_defocus of the frame behind it on the default stream, then the two files.
 int rtm_node_write_dof(const rtm_settings* st, const rtm_object* objects, size_t n, const rtm_options* opt,
                        const rtm_defocus_params* prm, const float* f32_host, const std::string& stem, std::string& err,

@@ -84,6 +84,12 @@ int rtm_node_bloom(const rtm_settings* st, int device, const rtm_bloom_params* p
 int rtm_node_write_firefly(const rtm_settings* st, int device, const rtm_firefly_params* params, const float* f32_host,
                            const std::string& stem, std::string& err, std::vector<float>* f32_out, size_t* clamped,
                            size_t* repaired);
+// The frame scopes (rtm_scopes, rtm_cli --scopes and --expose-percentile) of a float frame (HOST, height x width x 3) on device
+// `device`: the frame is copied to the device, one rtm_scopes call on the default stream, and the histogram is copied back.
+// With `picture` the call also takes the waveform (params->columns wide), draws it with rtm_scope_draw (layout, gain) and copies
+// the picture back: 256 rows of params->columns RGB pixels, of 3 params->columns for the parade.
+int rtm_node_scopes(const rtm_settings* st, int device, const rtm_scope_params* params, const float* f32_host,
+                    rtm_scope_histogram* hist, int layout, uint32_t gain, std::vector<uint8_t>* picture, std::string& err);
 // Depth of field (rtm_defocus, rtm_cli --dof) of a float frame (HOST, height x width x 3) on device opt->device: the frame's depth
 // plane (rtm_render_aov), one rtm_defocus call behind it on the default stream, then <stem>_dof.bmp and <stem>_dof.jpg
 // (quality 60); the defocused float frame comes back in f32_out, for the stages that follow.

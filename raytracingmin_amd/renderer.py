@@ -201,6 +201,51 @@ class Renderer:
         torch.cuda.current_stream(dev).synchronize()
         return flip_result(out["result"])
 
+    def _scope_frame(self, frame):
+        """`frame` (an (H, W, 3) array or tensor; None: self.image) on this renderer's device as contiguous float32."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        v = self.image if frame is None else frame
+        v = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v))
+        return v.to(dev).to(torch.float32).contiguous()
+
+    def scopes(self, frame=None, **params):
+        """scopes() of a frame of this renderer, decoded on the host.  frame=None: the last rendered image (self.image)
+        rounded to float like out_f32; else an (H, W, 3) array or tensor.  params: scopes()'s mode, columns, want.  Returns a
+        dict of the names in `want`: "histogram" as scope_histogram() gives it, "waveform" a (4, 256, columns) uint32 array."""
+        import torch
+        color = self._scope_frame(frame)
+        out = scopes(color, **params)
+        torch.cuda.current_stream(color.device).synchronize()
+        got = {}
+        if "histogram" in out:
+            got["histogram"] = scope_histogram(out["histogram"])
+        if "waveform" in out:
+            got["waveform"] = out["waveform"].cpu().numpy().view(np.uint32)
+        return got
+
+    def write_scopes(self, fileName, frame=None, mode=_lib.SCOPE_DEFAULTS["mode"], columns=None, layout="luma", gain=None):
+        """<fileName>_scopes.json and <fileName>_waveform.bmp of one frame — what rtm_cli --scopes writes of it.  frame=None:
+        the last rendered image; mode "log2" for a linear frame, "code" for a display frame.  columns: the waveform's, default
+        min(256, W); layout "luma", "overlay" or "parade"; gain: default max(1, 2040 // H).  The JSON object is scope_summary()
+        of the frame plus "histogram": {"bins", "below", "above"}, the counts.  Returns that object."""
+        import json
+        import torch
+        color = self._scope_frame(frame)
+        H, W = int(color.shape[0]), int(color.shape[1])
+        columns = min(SCOPE_DEFAULTS["columns"], W) if columns is None else columns
+        gain = max(1, 2040 // H) if gain is None else gain
+        out = scopes(color, mode=mode, columns=columns, want=("histogram", "waveform"))
+        picture = np.ascontiguousarray(scope_draw(out["waveform"], layout=layout, gain=gain).cpu().numpy())
+        hist = scope_histogram(out["histogram"])
+        doc = scope_summary(hist, mode)
+        doc["histogram"] = {"bins": hist["bins"].tolist(), "below": hist["below"].tolist(), "above": hist["above"].tolist()}
+        with open(fileName + "_scopes.json", "w") as f:
+            json.dump(doc, f)
+        if not _lib.lib().rtm_write_bmp(os.fsencode(fileName + "_waveform.bmp"), picture.shape[1], 256, 3, picture.ctypes.data):
+            raise _lib.RtmError(-3, f"could not write {fileName}_waveform.bmp")
+        return doc
+
     # ---- device-resident render: outputs are torch tensors on the GPU ------------------------
     def render_rows_device(self, row_begin=0, row_end=None, want=("f32",), stats=True,
                            stream=None, band=None):
@@ -2112,6 +2157,143 @@ def flip_result(words):
     out["weighted_first_quartile"] = _flip_weighted_quantile(out["hist"], 0.25)
     out["weighted_third_quartile"] = _flip_weighted_quantile(out["hist"], 0.75)
     return out
+
+
+# include/rtm.h: RTM_SCOPE_DEFAULTS
+SCOPE_DEFAULTS = dict(_lib.SCOPE_DEFAULTS)
+SCOPE_PERCENTILES = (1.0, 50.0, 99.0, 99.9)  # what rtm_cli --scopes and Renderer.write_scopes report of channel Y
+
+
+def _scope_enum(name, value, table):
+    if value not in table:
+        raise ValueError(f"{name} is one of {tuple(table)}, got {value!r}")
+    return table[value]
+
+
+def _scope_int(name, v, lo, hi=None):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo or (hi is not None and int(v) > hi):
+        raise ValueError(f"{name} is an integer {f'in {lo}..{hi}' if hi is not None else f'from {lo}'}, got {v!r}")
+    return int(v)
+
+
+def scopes(color, mode=SCOPE_DEFAULTS["mode"], columns=SCOPE_DEFAULTS["columns"], want=("histogram",), stream=None):
+    """The frame scopes (include/rtm.h: rtm_scopes) on the device: per-channel histograms (Y, R, G, B) of `color`, an
+    (H, W, 3) float32 torch CUDA tensor (any 4-byte-aligned contiguous view), and its per-column waveform.  mode "log2": 8
+    bins a stop from 2^-16 to 2^16, for a linear frame; "code": the 256 8-bit code values, for a display frame in [0, 1].
+    columns: the waveform's columns, 1..W (ignored without "waveform").  Returns a dict of the names in `want`: "histogram" a
+    1036-word int32 tensor holding the bits of rtm_scope_histogram (scope_histogram() reads it on the host; scope_percentile()
+    and scope_exposure() take it as it is), "waveform" a (4, 256, columns) int32 tensor of counts, values below the bins in
+    row 0 and above them in row 255.  Exact integer counts by integer atomics: every call gives the same words.  Enqueued on
+    `stream` (a torch.cuda.Stream or a raw hipStream_t handle; default: the current stream); nothing waits for it and nothing
+    is copied to the host."""
+    _check_want(want, ("histogram", "waveform"))
+    prm = _lib.rtm_scope_params(_scope_enum("mode", mode, _lib.SCOPE_MODES), 0)
+    import torch
+    _need_device("scopes")
+    H, W = _frame_size(color, "color", non_empty=True)
+    if "waveform" in want:
+        prm.columns = _scope_int("columns", columns, 1, W)
+    dev = color.device
+    s = _stream_of(stream, dev)
+    specs = {"histogram": (C.sizeof(_lib.rtm_scope_histogram) // 4, torch.int32),
+             "waveform": ((4, 256, max(1, prm.columns)), torch.int32)}
+    out, ptr = _stage_tensors(s, dev, want, specs)
+    _lib.check(_lib.lib().rtm_scopes(C.byref(prm), W, H, dev.index, color.data_ptr(), ptr("histogram"), ptr("waveform"),
+                                     C.c_void_p(s.cuda_stream)), "rtm_scopes")
+    return out
+
+
+def _scope_record(hist):
+    """An rtm_scope_histogram on the host of scopes()'s "histogram" tensor, its words as an array, or scope_histogram()'s dict."""
+    if isinstance(hist, _lib.rtm_scope_histogram):
+        return hist
+    if isinstance(hist, dict):
+        raw = np.concatenate([np.asarray(hist["bins"], np.uint32).reshape(-1), np.asarray(hist["below"], np.uint32),
+                              np.asarray(hist["above"], np.uint32),
+                              np.array([hist["pixels"], hist["not_counting"], 0, 0], np.uint32)])
+    else:
+        raw = np.ascontiguousarray(hist.cpu().numpy() if hasattr(hist, "cpu") else hist).reshape(-1).view(np.uint32)
+    if raw.size != C.sizeof(_lib.rtm_scope_histogram) // 4:
+        raise ValueError(f"a histogram is {C.sizeof(_lib.rtm_scope_histogram) // 4} words, got {raw.size}")
+    return _lib.rtm_scope_histogram.from_buffer_copy(raw.tobytes())
+
+
+def scope_histogram(words):
+    """scopes()'s "histogram" tensor as a dict of rtm_scope_histogram's fields: "bins" a (4, 256) uint32 array (channels Y, R,
+    G, B), "below" and "above" uint32 arrays of 4, "pixels" and "not_counting" ints.  Copies the record's 1036 words to the
+    host (synchronise the stream that wrote them first when it is not the current one)."""
+    rec = _scope_record(words)
+    return {"bins": np.ctypeslib.as_array(rec.bins).astype(np.uint32).reshape(4, 256), "below": np.array(rec.below[:], np.uint32),
+            "above": np.array(rec.above[:], np.uint32), "pixels": int(rec.pixels), "not_counting": int(rec.not_counting)}
+
+
+def scope_draw(waveform, layout="luma", gain=1, stream=None):
+    """The picture of a waveform (include/rtm.h: rtm_scope_draw) on the device: `waveform` is scopes()'s (4, 256, columns) int32
+    tensor.  layout "luma" (channel Y in grey), "overlay" (R, G, B in their own bytes) or "parade" (three panels side by side);
+    a value is min(255, count * gain), gain an integer from 1.  Returns a (256, columns, 3) uint8 tensor, (256, 3 columns, 3)
+    for the parade, bin 255 on top.  Enqueued on `stream`."""
+    lay = _scope_enum("layout", layout, _lib.SCOPE_LAYOUTS)
+    gain = _scope_int("gain", gain, 1, 0xFFFFFFFF)
+    import torch
+    _need_device("scope_draw")
+    if not (isinstance(waveform, torch.Tensor) and waveform.is_cuda and waveform.dtype == torch.int32 and waveform.dim() == 3
+            and tuple(waveform.shape[:2]) == (4, 256) and waveform.shape[2] >= 1 and waveform.is_contiguous()):
+        raise ValueError("waveform must be a contiguous (4, 256, columns) int32 CUDA tensor")
+    columns = int(waveform.shape[2])
+    dev = waveform.device
+    s = _stream_of(stream, dev)
+    out, ptr = _stage_tensors(s, dev, ("u8",), {"u8": ((256, columns * (3 if layout == "parade" else 1), 3), torch.uint8)})
+    _lib.check(_lib.lib().rtm_scope_draw(columns, lay, gain, dev.index, waveform.data_ptr(), ptr("u8"), C.c_void_p(s.cuda_stream)),
+               "rtm_scope_draw")
+    return out["u8"]
+
+
+def scope_bin_range(mode, bin):
+    """(lo, hi) of a histogram bin 0..255 in `mode` ("log2" or "code"), as floats (include/rtm.h: rtm_scope_bin_range).  No
+    device use."""
+    lo, hi = C.c_float(), C.c_float()
+    _lib.check(_lib.lib().rtm_scope_bin_range(_scope_enum("mode", mode, _lib.SCOPE_MODES), _scope_int("bin", bin, 0, 255),
+                                              C.byref(lo), C.byref(hi)), "rtm_scope_bin_range")
+    return lo.value, hi.value
+
+
+def _scope_channel(channel):
+    if isinstance(channel, str):
+        return _scope_enum("channel", channel, {k: i for i, k in enumerate(_lib.SCOPE_CHANNELS)})
+    return _scope_int("channel", channel, 0, 3)
+
+
+def scope_percentile(hist, percent, channel="y", mode=SCOPE_DEFAULTS["mode"]):
+    """The value under which `percent` of the counting pixels' channel lies (include/rtm.h: rtm_scope_percentile), linear
+    inside its bin: (value, bin).  `hist` is scopes()'s "histogram" tensor (copied to the host here), its words or
+    scope_histogram()'s dict; `mode` the mode it was taken in; channel "y", "r", "g", "b" or 0..3.  bin is -2 for a frame
+    without a counting pixel (value 1), -1 when the percentile lies below the bins (value 0), 256 past the last one."""
+    value, bin_ = C.c_float(), C.c_int32()
+    rec = _scope_record(hist)
+    _lib.check(_lib.lib().rtm_scope_percentile(C.byref(rec), _scope_enum("mode", mode, _lib.SCOPE_MODES), _scope_channel(channel),
+                                               float(percent), C.byref(value), C.byref(bin_)), "rtm_scope_percentile")
+    return value.value, bin_.value
+
+
+def scope_exposure(hist, percent, target=0.18):
+    """The exposure in stops that puts the `percent` percentile of a "log2" histogram's luminance at `target`
+    (include/rtm.h: rtm_scope_exposure): tonemap(color, exposure=ev).  Clamped to +-32; 0 when the percentile is 0."""
+    ev = C.c_float()
+    rec = _scope_record(hist)
+    _lib.check(_lib.lib().rtm_scope_exposure(C.byref(rec), float(percent), float(target), C.byref(ev)), "rtm_scope_exposure")
+    return ev.value
+
+
+def scope_summary(hist, mode=SCOPE_DEFAULTS["mode"]):
+    """What rtm_cli --scopes prints of one frame: {"mode", "pixels", "not_counting", "percentiles" (of Y at 1, 50, 99 and 99.9,
+    keyed by the percent's text), "below" and "above" (the share of the counting pixels outside the bins, per channel Y, R, G,
+    B)}.  `hist` as scope_percentile() takes it."""
+    rec = _scope_record(hist)
+    n = int(rec.pixels)
+    share = lambda v: [int(x) / n if n else 0.0 for x in v]
+    return {"mode": mode, "pixels": n, "not_counting": int(rec.not_counting),
+            "percentiles": {f"{p:g}": scope_percentile(rec, p, 0, mode)[0] for p in SCOPE_PERCENTILES},
+            "below": share(rec.below), "above": share(rec.above)}
 
 
 def plan_passes(n_samples, passes=None, samples_per_pass=None):
