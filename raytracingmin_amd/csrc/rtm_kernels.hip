@@ -139,14 +139,20 @@ struct DevMem {
         return RTM_OK;
     }
     // Stream-ordered allocation on the library's own stream, waited for here (nothing else is ever queued on that
-    // stream, so the wait is for the allocation alone): the block is usable on every stream on return, and its
-    // release (reset) does not wait for the device.
+    // stream, so the wait is for the allocation and its first touch alone): the block is usable on every stream on
+    // return, and its release (reset) does not wait for the device.  The block is written once by the device before the
+    // host sees it: a scene's small tables are filled by hipMemcpy from pageable memory, which may store through the
+    // host's mapping of device memory, and such a store is not ordered against work the driver still has queued on pages
+    // it hands out (tests/test_pipeline_gpu.py: rtm_cli --firefly --denoise lost the colour table of the denoise stage's
+    // scene in one run of ten, and with it the albedo plane).  A device write is ordered behind that work, and the wait
+    // below then covers it.
     int alloc_pooled(size_t bytes, int device) {
         reset();
         hipStream_t st = pool_stream(device);
         if (!st) return alloc(bytes);
         RTM_HIP_CHECK(hipMallocAsync(&p, bytes ? bytes : 1, st));
         pooled_device = device;
+        RTM_HIP_CHECK(hipMemsetAsync(p, 0, bytes ? bytes : 1, st));
         RTM_HIP_CHECK(hipStreamSynchronize(st));
         return RTM_OK;
     }
