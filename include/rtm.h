@@ -239,6 +239,42 @@ int rtm_scene_create_device(const rtm_sphere* spheres_dev, size_t n_spheres, int
 int rtm_scene_destroy(rtm_scene* scene);
 size_t rtm_scene_size(const rtm_scene* scene);
 
+/* ---- ray queries on a scene: "what does this ray hit?" and "is this segment blocked?" for rays of the caller's ----
+ * Rays live on the scene's device: org_dev and dir_dev hold n_rays x 3 doubles, a row per ray (rtm_path_trace_batch's layout;
+ * a contiguous (n, 3) float64 tensor).
+ * rtm_scene_nearest: for ray i, object and t are exactly what the loop of src/Renderer.cpp:58-73 leaves in hitObject and dis
+ * over the scene's objects in index order — Intersect in the reference's arithmetic (src/SettingData.cpp:197-226; the
+ * build-defined square for a plane), accepted when tmp_dis < dis && tmp_dis > 0, so the lowest index wins ties — bit for bit,
+ * for every ray: directions of any length, origins anywhere; a ray with a non-finite component hits nothing.  normal is what
+ * Intersect reports for the winning object in RTM_MODE_REPAIRED: Normalize((org + dir t) - centre) with the reference's
+ * float-length Normalize for a sphere, m_normal for a plane.  It is NOT turned towards the ray, and there is no mode argument.
+ * rtm_scene_occluded: out[i] = 1 exactly when that t satisfies t < tmax[i] (strictly; a miss never does), else 0.  A tmax that
+ * is NaN, zero or negative is never occluded; a null tmax_dev stands for +infinity everywhere: any hit occludes.  An object's
+ * accepted t does not depend on the other objects, so this is "some object's Intersect reports a hit with 0 < t < tmax", and
+ * where the scene has a grid the search stops at the first such hit instead of looking for the nearest.
+ * The scene has no other effect on the answers: one with a grid, one without, one built by rtm_scene_create_device give the
+ * same bits for the same objects.  What it decides is the cost.  A scene with a grid (see rtm_scene_create) serves through it
+ * every ray with |d.d - 1| <= 4e-7 — any direction normalised in double precision; normalising is the caller's business — and
+ * an origin within the grid's reach, about two scene diagonals from the scene.  Any other ray makes its whole wave (the 64
+ * consecutive rays it is among) run the loop over all objects: correct, and slow for a large scene.
+ * Both calls only ENQUEUE one kernel on `stream` on the scene's device: no allocation, no copy, no host synchronisation.
+ * They are serialised with the other calls on that (device, stream) and recorded as a use of the scene (rtm_scene_destroy
+ * right after the call is safe).  The outputs must not overlap the ray buffers or each other (not checked).
+ * n_rays == 0: RTM_OK, nothing is enqueued.  A null scene, org_dev, dir_dev or out_dev, an out_dev whose planes are all null,
+ * a pointer that is not aligned to its element (8 bytes for doubles, 4 for object), n_rays > 0x7FFFFFFF:
+ * RTM_ERR_INVALID_ARGUMENT with a text in rtm_last_error_detail, before any device call.
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbols up. */
+typedef struct rtm_hit_buffers { /* DEVICE pointers on the scene's device; any may be null, not all */
+    int32_t* object; /* n_rays: index of the hit object in the scene's order, -1 on a miss             */
+    double* t;       /* n_rays: the loop's dis; +infinity on a miss                                     */
+    double* normal;  /* n_rays x 3: Intersect's out_normal of the hit object; +0 on a miss              */
+} rtm_hit_buffers;
+int rtm_scene_nearest(const rtm_scene* scene, const double* org_dev, const double* dir_dev, size_t n_rays,
+                      const rtm_hit_buffers* out_dev, void* stream);
+int rtm_scene_occluded(const rtm_scene* scene, const double* org_dev, const double* dir_dev,
+                       const double* tmax_dev /* n_rays, nullable: +infinity */, size_t n_rays,
+                       uint8_t* out_dev /* n_rays: 1 occluded, 0 not */, void* stream);
+
 /* ---- the hot path: Renderer::Render's pixel/sample loop (src/Renderer.cpp:215-250) ----
  * Renders rows [row_begin,row_end) of the image into caller-owned DEVICE buffers; any of the
  * three outputs may be null.  Layout is the reference's: row-major, row 0 first, RGB interleaved

@@ -91,6 +91,16 @@ int rtm_debug_grid_build(const rtm_sphere* spheres, size_t n, uint64_t* info, do
  * the scene's device. */
 int rtm_debug_scene_grid(const rtm_scene* scene, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items,
                          size_t items_cap, int32_t* big, size_t big_cap, uint64_t extra[2]);
+/* rtm_scene_nearest's (any = 0) or rtm_scene_occluded's (any = 1) search of a scene that has a grid, through the grid walk's
+ * counting instantiation (csrc/rtm_path.h: GridWalk's COUNT): the sphere tests and the cell steps each ray took, so that a test
+ * can see the occlusion walk's early exit.  DEVICE buffers and the contract of those calls: only enqueues on `stream`, same
+ * refusals (every output null counts as one).  Outputs, each n_rays long and nullable: any = 0: object and t as
+ * rtm_scene_nearest writes them, occluded = t < tmax as rtm_scene_occluded defines it; any = 1: occluded as
+ * rtm_scene_occluded writes it, object and t = the hit that decided it (not necessarily the nearest; -1 and +infinity where
+ * nothing occludes).  RTM_ERR_UNSUPPORTED: the scene has no grid. */
+int rtm_debug_scene_query(const rtm_scene* scene, int any, const double* org_dev, const double* dir_dev, const double* tmax_dev,
+                          size_t n_rays, int32_t* out_object_dev, double* out_t_dev, uint8_t* out_occluded_dev,
+                          uint32_t* out_tests_dev, uint32_t* out_steps_dev, void* stream);
 /* What the host finds in a sphere array when it flattens it into the kernels' tables, on the HOST (no device is touched; runs in
  * the CPU test suite): facts[0] = two bits per sphere for the first 32 — 1 / 2 / 3: the centre's only coordinate that is not
  * +-0 is x / y / z (the axis-signature instantiations of the exact-n kernels, csrc/rtm_path.h: sphere_disc) —, facts[1] bit 0:

@@ -69,6 +69,10 @@ class rtm_aov_buffers(C.Structure):  # DEVICE pointers, any may be null (include
     _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("object", C.c_void_p)]
 
 
+class rtm_hit_buffers(C.Structure):  # DEVICE pointers, any may be null but not all (include/rtm.h: rtm_scene_nearest)
+    _fields_ = [("object", C.c_void_p), ("t", C.c_void_p), ("normal", C.c_void_p)]
+
+
 class rtm_matte_buffers(C.Structure):  # DEVICE pointers, any may be null but not all (include/rtm.h: rtm_render_mattes)
     _fields_ = [("id", C.c_void_p), ("coverage", C.c_void_p), ("alpha", C.c_void_p)]
 
@@ -219,6 +223,8 @@ SIGNATURES = {
     "rtm_scene_create": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_int, _P(C.c_void_p)]),
     "rtm_scene_create_device": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, _P(C.c_void_p)]),
     "rtm_scene_create_objects": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, _P(C.c_void_p)]),
+    "rtm_scene_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _P(rtm_hit_buffers), C.c_void_p]),
+    "rtm_scene_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "rtm_scene_destroy": (C.c_int, [C.c_void_p]),
     "rtm_scene_size": (C.c_size_t, [C.c_void_p]),
     "rtm_stream_status": (C.c_int, [C.c_int, C.c_void_p]),
@@ -334,6 +340,8 @@ DEBUG_SIGNATURES = {
                                        C.c_size_t, C.c_void_p, C.c_size_t]),
     "rtm_debug_scene_grid": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                        C.c_void_p]),
+    "rtm_debug_scene_query": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_debug_denoise_variance_kernel": (C.c_int, [C.c_int, _P(rtm_denoise_var_params), C.c_int32, C.c_int32, C.c_int,
                                                     _P(rtm_aov_buffers), C.c_void_p, C.c_void_p, C.c_void_p]),
     "rtm_debug_defocus_form": (C.c_int, [C.c_int, _P(rtm_defocus_params), C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p,

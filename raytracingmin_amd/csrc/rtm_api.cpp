@@ -67,6 +67,14 @@ int rtm_scene_parse_json_objects(const char* text, size_t len, int literal_loade
                                  rtm_object* objects, size_t capacity, size_t* n_objects) {
     RTM_GUARD(rtm::scene_parse_json_objects(text, len, literal_loader, settings, objects, capacity, n_objects))
 }
+int rtm_scene_nearest(const rtm_scene* scene, const double* org_dev, const double* dir_dev, size_t n_rays,
+                      const rtm_hit_buffers* out_dev, void* stream) {
+    RTM_GUARD(rtm::scene_nearest(scene, org_dev, dir_dev, n_rays, out_dev, stream))
+}
+int rtm_scene_occluded(const rtm_scene* scene, const double* org_dev, const double* dir_dev, const double* tmax_dev, size_t n_rays,
+                       uint8_t* out_dev, void* stream) {
+    RTM_GUARD(rtm::scene_occluded(scene, org_dev, dir_dev, tmax_dev, n_rays, out_dev, stream))
+}
 int rtm_scene_destroy(rtm_scene* scene) { RTM_GUARD(rtm::scene_destroy(scene)) }
 size_t rtm_scene_size(const rtm_scene* scene) { return rtm::scene_size(scene); }
 int rtm_stream_status(int device, void* stream) { RTM_GUARD(rtm::stream_status(device, stream)) }
@@ -293,6 +301,12 @@ int rtm_debug_grid_build(const rtm_sphere* sp, size_t n, uint64_t* info, double*
 int rtm_debug_scene_grid(const rtm_scene* scene, uint64_t* info, uint32_t* ranges, size_t ranges_cap, uint32_t* items,
                          size_t items_cap, int32_t* big, size_t big_cap, uint64_t extra[2]) {
     RTM_GUARD(rtm::scene_grid_probe(scene, info, ranges, ranges_cap, items, items_cap, big, big_cap, extra))
+}
+int rtm_debug_scene_query(const rtm_scene* scene, int any, const double* org_dev, const double* dir_dev, const double* tmax_dev,
+                          size_t n_rays, int32_t* out_object_dev, double* out_t_dev, uint8_t* out_occluded_dev,
+                          uint32_t* out_tests_dev, uint32_t* out_steps_dev, void* stream) {
+    RTM_GUARD(rtm::scene_query_probe(scene, any, org_dev, dir_dev, tmax_dev, n_rays, out_object_dev, out_t_dev, out_occluded_dev,
+                                     out_tests_dev, out_steps_dev, stream))
 }
 int rtm_debug_scene_facts(const rtm_sphere* sp, size_t n, uint64_t facts[2]) { RTM_GUARD(rtm::scene_facts_host(sp, n, facts)) }
 int rtm_debug_zero_term_facts(const rtm_sphere* sp, size_t n, uint64_t facts[2]) { RTM_GUARD(rtm::zero_term_facts_host(sp, n, facts)) }

@@ -34,6 +34,14 @@ int scene_create_device(const rtm_sphere* sp_dev, size_t n, int device, void* st
 int scene_create_objects(const rtm_object* objs, size_t n, int device, rtm_scene** out);
 int intersect_objects_batch(const rtm_object* objs, const double* org, const double* dir, size_t n, int mode,
                             int32_t* out_hit, double* out_t, double* out_normal);
+// ray queries on a scene object (rtm_query.hip); the probe runs the grid walk's counting instantiations (rtm_debug_scene_query)
+int scene_nearest(const rtm_scene* scene, const double* org, const double* dir, size_t n_rays, const rtm_hit_buffers* out,
+                  void* stream);
+int scene_occluded(const rtm_scene* scene, const double* org, const double* dir, const double* tmax, size_t n_rays, uint8_t* out,
+                   void* stream);
+int scene_query_probe(const rtm_scene* scene, int any, const double* org, const double* dir, const double* tmax, size_t n_rays,
+                      int32_t* out_object, double* out_t, uint8_t* out_occluded, uint32_t* out_tests, uint32_t* out_steps,
+                      void* stream);
 int scene_destroy(rtm_scene* sc);
 size_t scene_size(const rtm_scene* sc);
 int stream_status(int device, void* stream);

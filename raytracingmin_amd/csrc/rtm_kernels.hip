@@ -2604,3 +2604,5 @@ int device_count(int* count) {
 #include "rtm_matte.hip"
 // rtm_scene_create_device: the device build of a scene's grid, and rtm_debug_scene_grid (rtm_scene is private to this unit)
 #include "rtm_grid_build.hip"
+// rtm_scene_nearest, rtm_scene_occluded and rtm_debug_scene_query: ray queries on a scene object (same reason)
+#include "rtm_query.hip"

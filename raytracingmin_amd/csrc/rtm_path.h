@@ -1504,14 +1504,23 @@ __device__ __forceinline__ void object_chunk(const Scene& sc, const int i0, cons
 // spheres the geometric ray passes at a distance) take the exhaustive loop; rays with a non-finite component hit
 // nothing in the reference loop either (every t is NaN or infinite).
 // Spheres in `big` (padded box over too many cells) are tested for every ray.
+//
+// ANY (any_hit_grid: "is there a hit with 0 < t < limit", rtm_query_kernel.h).  Every object's accepted t is independent
+// of the others, so the loop's dis is below the limit exactly when SOME object's Intersect reports a hit that the loop's
+// acceptance would take from dis = limit.  The walk therefore starts with dis = limit and best = -1: `t < dis` then reads
+// "t occludes" (the tie clause needs i < -1), and a lane is decided at its first acceptance, whichever object that is.
+// A lane that accepts nothing is decided by the same end test: at the first cell whose exit lies at or beyond the limit
+// every sphere with a hit before that exit — so every sphere with a hit before the limit — has been tested.  A limit
+// that is not positive (the caller maps NaN there) admits no t at all: such a lane is decided before it starts.  The big
+// list and the exhaustive loop are wave-uniform; a wave leaves them once no lane is undecided.
 constexpr int kGridBatch = 4;  // records in flight per trip of the walk (profiles/r3/grid_crossover.txt)
 constexpr int kGridShadeAt8 = 5;  // the render loop shades when this many eighths of a wave's lanes have finished their walks
 
 // One ray's walk through the grid, as per-lane state that can be advanced a trip at a time: the render kernel's lanes
 // walk independently and are shaded in groups (rtm_grid_kernel.h), the probe runs it to the end.
-template <class M, class Scene, bool COUNT = false>
+template <class M, class Scene, bool COUNT = false, bool ANY = false>
 struct GridWalk {
-    double dis;  // the nearest accepted hit so far (DBL_MAX: none) and its object
+    double dis;  // the nearest accepted hit so far (DBL_MAX: none) and its object; ANY: the limit until a hit is accepted
     int best;
     double tmx, tmy, tmz;  // parameter at which the ray leaves the NEXT cell's predecessor planes (Amanatides & Woo's tMax)
     double tdx, tdy, tdz;  // parameter per cell along each axis, signed like the direction (inf: never)
@@ -1588,12 +1597,15 @@ struct GridWalk {
         nj = range.x;
         nje = range.y;
     }
+    // ANY: this lane's answer is still open — nothing accepted yet, and a limit that admits something
+    __device__ __forceinline__ bool undecided() const { return best < 0 && dis > 0.0; }
     // Start the walk of (org, dir): the big list, the box, the guards.  Returns whether there is a walk to advance
     // (false: dis / best are final — a miss of the box, a non-finite ray, or the exhaustive loop has run).
+    // ANY: the caller has set dis to the ray's limit.
     __device__ __forceinline__ bool begin(const Scene& sc, const D3 org, const D3 dir) {
         HdrPtr G = header(sc);
         best = -1;
-        dis = DBL_MAX;
+        if constexpr (!ANY) dis = DBL_MAX;
         pending = 0u;
         if constexpr (COUNT) tests = steps = 0;
         const int n_big = G->n_big;
@@ -1605,6 +1617,8 @@ struct GridWalk {
                 consider_plane(sc.v.plane + (size_t)i * 16, i, org, dir);
             else
                 consider(i, g, org, dir);
+            if constexpr (ANY)
+                if (__builtin_amdgcn_ballot_w64(undecided()) == 0) break;
         }
         bool live = __builtin_isfinite(org.x) && __builtin_isfinite(org.y) && __builtin_isfinite(org.z) &&
                     __builtin_isfinite(dir.x) && __builtin_isfinite(dir.y) && __builtin_isfinite(dir.z);
@@ -1644,6 +1658,8 @@ struct GridWalk {
         if (__builtin_amdgcn_ballot_w64(exhaustive) != 0) {  // (never, for a camera within two scene diagonals and unit directions)
             const int n = sc.n();
             for (int i = 0; i < n; ++i) {
+                if constexpr (ANY)
+                    if (__builtin_amdgcn_ballot_w64(exhaustive && undecided()) == 0) break;
                 const double4 g = sc.geom_uniform(i);
                 if (!exhaustive) continue;
                 if (sc.v.plane != nullptr && __double2hiint(g.w) < 0) {  // (in the big list too: tested twice, same result)
@@ -1654,6 +1670,7 @@ struct GridWalk {
             }
         }
         live = live && !exhaustive;
+        if constexpr (ANY) live = live && undecided();
         // 3D-DDA over the cells from the entry point on (Amanatides & Woo).  The search is bound by memory latency as much
         // as by arithmetic (a cell's list is a dependent load behind the cell's offsets), so every trip has ONE round of
         // loads in flight: up to kGridBatch records of the current cell (self-contained: centre, r*r and the sphere's index
@@ -1750,6 +1767,8 @@ struct GridWalk {
             dis = accept ? t : dis;
             best = accept ? i : best;
         }
+        if constexpr (ANY)
+            if (best >= 0) return false;  // decided; what is left in the queue goes with the next begin()
         // the walk's end seen in the trip that settles it, not by the test at the top of the next one: a trip per cast less
         // (round 4, profiles/r4/grid_early_end.txt: 192.1 -> 183.9 ms for the configs[4] frame)
         if (pending == 0u && j >= jend && (dis <= t_exit || !next_ok)) return false;
@@ -1763,6 +1782,25 @@ __device__ __forceinline__ int nearest_hit_grid(const Scene& sc, const D3 org, c
                                                 unsigned* n_tests = nullptr, unsigned* n_steps = nullptr) {
     GridWalk<M, Scene, COUNT> W;
     W.attach_queue(queue_lds, queue_lanes, queue_lane);
+    bool walking = W.begin(sc, org, dir);
+    while (walking) walking = W.advance(sc, org, dir);
+    if constexpr (COUNT) {
+        *n_tests = W.tests;
+        *n_steps = W.steps;
+    }
+    dis = W.dis;
+    return W.best;
+}
+
+// Whether (org, dir) hits anything at 0 < t < dis (in: the limit, at most DBL_MAX; not positive: nothing): an object that
+// does and its t in dis, or -1 with dis unchanged.  The same walk with its ANY flag (see above kGridBatch).
+template <class M, class Scene, bool COUNT = false>
+__device__ __forceinline__ int any_hit_grid(const Scene& sc, const D3 org, const D3 dir, double& dis,
+                                            unsigned char* queue_lds, int queue_lanes, int queue_lane,
+                                            unsigned* n_tests = nullptr, unsigned* n_steps = nullptr) {
+    GridWalk<M, Scene, COUNT, true> W;
+    W.attach_queue(queue_lds, queue_lanes, queue_lane);
+    W.dis = dis;
     bool walking = W.begin(sc, org, dir);
     while (walking) walking = W.advance(sc, org, dir);
     if constexpr (COUNT) {

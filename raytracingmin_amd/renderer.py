@@ -426,6 +426,62 @@ class Renderer:
                                              C.c_void_p(hip_stream)), "rtm_render_aov")
         return out
 
+    # ---- ray queries on the scene (rtm_scene_nearest, rtm_scene_occluded) ---------------------
+    QUERY_PLANES = ("object", "t", "normal")
+
+    def _query_rays(self, org, direction, tmax=None):
+        """(n, device) of a ray batch: org and direction contiguous (n, 3) float64 CUDA tensors on the renderer's device,
+        tmax None or a contiguous (n,) one.  Anything else: ValueError, before the library is called."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = org.shape[0] if isinstance(org, torch.Tensor) and org.dim() == 2 else -1
+        for name, v, shape, text in (("org", org, (n, 3), "(n, 3)"), ("direction", direction, (n, 3), "(n, 3)"),
+                                     ("tmax", tmax, (n,), "(n,)")):
+            if v is None and name == "tmax":
+                continue
+            if not (isinstance(v, torch.Tensor) and v.device == dev and v.dtype == torch.float64 and n >= 0
+                    and tuple(v.shape) == shape and v.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {text} float64 tensor on {dev}")
+        return n, dev
+
+    def nearest(self, org, direction, want=("object", "t"), stream=None):
+        """What each ray hits first in the renderer's scene (include/rtm.h: rtm_scene_nearest): a dict of torch CUDA tensors,
+        "object" (n,) int32 (-1: nothing), "t" (n,) float64 (+inf: nothing), "normal" (n, 3) float64 — Intersect's normal of the
+        hit object, not turned towards the ray (zeros: nothing).  org and direction are contiguous (n, 3) float64 tensors on the
+        renderer's device; directions are the caller's to normalise (any length is answered exactly; only unit ones take a large
+        scene's grid).  Only the planes named in `want` are allocated and computed.  Enqueued on `stream` (default: the current
+        stream); nothing waits for it."""
+        import torch
+        _need_device("Renderer")
+        _check_want(want, self.QUERY_PLANES)
+        n, dev = self._query_rays(org, direction)
+        s = _stream_of(stream, dev)
+        layout = {"object": ((n,), torch.int32), "t": ((n,), torch.float64), "normal": ((n, 3), torch.float64)}
+        out, ptr = _stage_tensors(s, dev, want, layout)
+        bufs = _lib.rtm_hit_buffers()
+        for k in out:
+            setattr(bufs, k, ptr(k))
+        if n > 0:
+            _lib.check(_lib.lib().rtm_scene_nearest(self._scene_handle(), C.c_void_p(org.data_ptr()), C.c_void_p(direction.data_ptr()),
+                                                    n, C.byref(bufs), C.c_void_p(s.cuda_stream)), "rtm_scene_nearest")
+        return out
+
+    def occluded(self, org, direction, tmax=None, stream=None):
+        """Whether each ray hits anything before tmax (include/rtm.h: rtm_scene_occluded): an (n,) bool CUDA tensor, True where
+        nearest()'s t is < tmax, strictly.  tmax: a contiguous (n,) float64 tensor on the renderer's device, or None for "any
+        hit"; an entry that is NaN, zero or negative is never occluded.  A scene with a grid stops at the first such hit
+        instead of finding the nearest.  Enqueued on `stream` (default: the current stream); nothing waits for it."""
+        import torch
+        _need_device("Renderer")
+        n, dev = self._query_rays(org, direction, tmax)
+        s = _stream_of(stream, dev)
+        out, ptr = _stage_tensors(s, dev, ("occluded",), {"occluded": ((n,), torch.uint8)})
+        if n > 0:
+            _lib.check(_lib.lib().rtm_scene_occluded(self._scene_handle(), C.c_void_p(org.data_ptr()), C.c_void_p(direction.data_ptr()),
+                                                     C.c_void_p(tmax.data_ptr()) if tmax is not None else None, n,
+                                                     C.c_void_p(ptr("occluded")), C.c_void_p(s.cuda_stream)), "rtm_scene_occluded")
+        return out["occluded"].view(torch.bool)
+
     def write_aov(self, fileName):
         """<fileName>_depth.pfm, _normal.pfm, _albedo.pfm (exact float planes) and _normal.bmp (quantised 0.5 n + 0.5),
         _albedo.bmp (quantised albedo) of the whole frame — what rtm_cli --aov writes."""
