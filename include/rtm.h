@@ -275,6 +275,63 @@ int rtm_scene_occluded(const rtm_scene* scene, const double* org_dev, const doub
                        const double* tmax_dev /* n_rays, nullable: +infinity */, size_t n_rays,
                        uint8_t* out_dev /* n_rays: 1 occluded, 0 not */, void* stream);
 
+/* ---- radiance queries on a scene: "how much light arrives along this ray?" for rays of the caller's ----
+ * Rays as for the ray queries above: org_dev and dir_dev hold n_rays x 3 doubles on the scene's device, a row per ray.
+ * For ray i and s = 0 .. S-1 (S = params->samples), L_s is png::PathTracing (src/Renderer.cpp:57-117) on (org_i, dir_i) with
+ * the generator stream (seed, pixel = key_base + i, sample = s) — exactly what rtm_path_trace_batch computes for that key,
+ * bit for bit, max_bounces, the mode and RTM_MODE_HOST_TRIG included.  radiance_i is the sum over s ascending, from +0.0, of
+ * t_s = L_s / (double)S per component; with RTM_RADIANCE_CLAMP each t_s first goes through the clamp of src/Renderer.cpp:241
+ * (std::min<double>(std::max<double>(v, 0), 1.0f)).  Every multiply, add and divide is separately rounded.
+ * That is the reference's own accumulation of a pixel's samples (src/Renderer.cpp:240-242) at superSamples == 1: with the
+ * clamp, key_base = 0 and the rays of a camera's pixels in row-major order, radiance is rtm_render_scene's out_f64 for the
+ * same settings, bit for bit.  Without the clamp it is the plain mean of the samples, for probes and baking.
+ * casts_i and draws_i count the nearest-hit loops run and the generator calls made for ray i over all its samples, modulo 2^32.
+ * Directions of any length, origins anywhere; a ray with a non-finite component hits nothing and returns +0 (one cast per
+ * sample, no draw).  The scene decides only the cost, as for the ray queries: one with a grid, one without, one built by
+ * rtm_scene_create_device give the same bits; a ray the grid cannot serve (see above) sends its wave, for that cast, through
+ * the loop over all objects.
+ * Parallelism is over RAYS only: one GPU lane per ray traces that ray's S samples one after the other (which is what keeps
+ * the sum in sample order).  A call with few rays and many samples leaves the device idle; repeat the rays instead, each copy
+ * under its own key (key_base + its row), and combine the copies' means.
+ * The contract is the ray queries', with one addition.  Every argument is checked before any device call, and a refusal
+ * leaves a text in rtm_last_error_detail: a null scene, org_dev, dir_dev, params or out_dev, an out_dev whose planes are all
+ * null, a pointer that is not aligned to its element (8 bytes for doubles, 4 for casts and draws), n_rays > 0x7FFFFFFF,
+ * key_base + n_rays > 2^32, samples == 0, max_bounces < -1, flag bits other than RTM_RADIANCE_CLAMP, a nonzero reserved, a mode
+ * that is neither RTM_MODE_LITERAL nor RTM_MODE_REPAIRED with or without RTM_MODE_HOST_TRIG: RTM_ERR_INVALID_ARGUMENT;
+ * RTM_MODE_SURFACE_SAMPLE: RTM_ERR_UNSUPPORTED.  n_rays == 0: RTM_OK, nothing is enqueued.  Otherwise the call only ENQUEUES on
+ * `stream` on the scene's device, is serialised with the other calls on that (device, stream) and recorded as a use of the
+ * scene.  The outputs must not overlap the ray buffers or each other (not checked).
+ * The addition: hit records.  The kernel keeps 16 levels per path on chip; a call with 0 <= max_bounces <= 16 needs no more
+ * and touches no work buffer.  Any other call takes the deeper levels from the record pool the library keeps for (device,
+ * stream), exactly as a render does (see rtm_render_scene): the first call on the pair that needs the pool — and, with
+ * RTM_MODE_HOST_TRIG, the first on the device that needs the trig table — sets it up, which may allocate and wait once;
+ * steady-state calls do neither.  A lane takes one pool slot of 960 levels the first time one of its paths needs it and keeps it
+ * for all its samples, so the pool is sized to the call: one slot (3 840 bytes) per ray, rounded up to 64 rays, for at most
+ * 262 144 rays (960 MiB); a call with more rays runs as launches of 262 144, one behind the other on the stream.  The number
+ * of rays therefore never exhausts the pool.  What remains is the depth of ONE path, the render's 976 bounces: max_bounces >
+ * 976 is refused with RTM_ERR_UNSUPPORTED like a render's, and with max_bounces = -1 a path that reaches level 976 is
+ * truncated there (that sample contributes 0, its casts and draws up to there are counted, the ray's other samples are
+ * traced normally) and raises the stream's sticky overflow flag, which rtm_stream_status reports and clears.
+ * rtm_release_scratch / rtm_stream_release free the pool.
+ * Added after RTM_ABI_VERSION 5 without changing it: callers look the symbol up. */
+#define RTM_RADIANCE_CLAMP 1u
+typedef struct rtm_radiance_params { /* 32 bytes */
+    int32_t mode;        /* RTM_MODE_REPAIRED or RTM_MODE_LITERAL, optionally | RTM_MODE_HOST_TRIG               */
+    int32_t max_bounces; /* -1: the reference's unlimited recursion; >= 0: the build's depth cap (rtm_options)   */
+    uint64_t seed;
+    uint32_t samples;    /* S >= 1                                                                               */
+    uint32_t key_base;   /* ray i draws sample s from the stream (seed, pixel = key_base + i, sample = s)        */
+    uint32_t flags;      /* RTM_RADIANCE_CLAMP or 0                                                              */
+    uint32_t reserved;   /* 0                                                                                    */
+} rtm_radiance_params;
+typedef struct rtm_radiance_buffers { /* DEVICE pointers on the scene's device; any may be null, not all; 24 bytes */
+    double* radiance;    /* n_rays x 3                                                                            */
+    uint32_t* casts;     /* n_rays: nearest-hit loops run for the ray, all samples, modulo 2^32                   */
+    uint32_t* draws;     /* n_rays: generator calls, likewise                                                     */
+} rtm_radiance_buffers;
+int rtm_scene_radiance(const rtm_scene* scene, const double* org_dev, const double* dir_dev, size_t n_rays,
+                       const rtm_radiance_params* params, const rtm_radiance_buffers* out_dev, void* stream);
+
 /* ---- the hot path: Renderer::Render's pixel/sample loop (src/Renderer.cpp:215-250) ----
  * Renders rows [row_begin,row_end) of the image into caller-owned DEVICE buffers; any of the
  * three outputs may be null.  Layout is the reference's: row-major, row 0 first, RGB interleaved

@@ -73,6 +73,18 @@ class rtm_hit_buffers(C.Structure):  # DEVICE pointers, any may be null but not 
     _fields_ = [("object", C.c_void_p), ("t", C.c_void_p), ("normal", C.c_void_p)]
 
 
+RADIANCE_CLAMP = 1  # RTM_RADIANCE_CLAMP
+
+
+class rtm_radiance_params(C.Structure):  # include/rtm.h: rtm_scene_radiance; 32 bytes
+    _fields_ = [("mode", C.c_int32), ("max_bounces", C.c_int32), ("seed", C.c_uint64), ("samples", C.c_uint32),
+                ("key_base", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class rtm_radiance_buffers(C.Structure):  # DEVICE pointers, any may be null but not all (include/rtm.h: rtm_scene_radiance)
+    _fields_ = [("radiance", C.c_void_p), ("casts", C.c_void_p), ("draws", C.c_void_p)]
+
+
 class rtm_matte_buffers(C.Structure):  # DEVICE pointers, any may be null but not all (include/rtm.h: rtm_render_mattes)
     _fields_ = [("id", C.c_void_p), ("coverage", C.c_void_p), ("alpha", C.c_void_p)]
 
@@ -225,6 +237,8 @@ SIGNATURES = {
     "rtm_scene_create_objects": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, _P(C.c_void_p)]),
     "rtm_scene_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _P(rtm_hit_buffers), C.c_void_p]),
     "rtm_scene_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "rtm_scene_radiance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _P(rtm_radiance_params),
+                                     _P(rtm_radiance_buffers), C.c_void_p]),
     "rtm_scene_destroy": (C.c_int, [C.c_void_p]),
     "rtm_scene_size": (C.c_size_t, [C.c_void_p]),
     "rtm_stream_status": (C.c_int, [C.c_int, C.c_void_p]),

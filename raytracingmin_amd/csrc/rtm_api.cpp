@@ -75,6 +75,10 @@ int rtm_scene_occluded(const rtm_scene* scene, const double* org_dev, const doub
                        uint8_t* out_dev, void* stream) {
     RTM_GUARD(rtm::scene_occluded(scene, org_dev, dir_dev, tmax_dev, n_rays, out_dev, stream))
 }
+int rtm_scene_radiance(const rtm_scene* scene, const double* org_dev, const double* dir_dev, size_t n_rays,
+                       const rtm_radiance_params* params, const rtm_radiance_buffers* out_dev, void* stream) {
+    RTM_GUARD(rtm::scene_radiance(scene, org_dev, dir_dev, n_rays, params, out_dev, stream))
+}
 int rtm_scene_destroy(rtm_scene* scene) { RTM_GUARD(rtm::scene_destroy(scene)) }
 size_t rtm_scene_size(const rtm_scene* scene) { return rtm::scene_size(scene); }
 int rtm_stream_status(int device, void* stream) { RTM_GUARD(rtm::stream_status(device, stream)) }

@@ -42,6 +42,9 @@ int scene_occluded(const rtm_scene* scene, const double* org, const double* dir,
 int scene_query_probe(const rtm_scene* scene, int any, const double* org, const double* dir, const double* tmax, size_t n_rays,
                       int32_t* out_object, double* out_t, uint8_t* out_occluded, uint32_t* out_tests, uint32_t* out_steps,
                       void* stream);
+// radiance queries on a scene object (rtm_radiance.hip)
+int scene_radiance(const rtm_scene* scene, const double* org, const double* dir, size_t n_rays, const rtm_radiance_params* params,
+                   const rtm_radiance_buffers* out, void* stream);
 int scene_destroy(rtm_scene* sc);
 size_t scene_size(const rtm_scene* sc);
 int stream_status(int device, void* stream);

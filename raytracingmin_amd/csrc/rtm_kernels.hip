@@ -2606,3 +2606,5 @@ int device_count(int* count) {
 #include "rtm_grid_build.hip"
 // rtm_scene_nearest, rtm_scene_occluded and rtm_debug_scene_query: ray queries on a scene object (same reason)
 #include "rtm_query.hip"
+// rtm_scene_radiance: radiance queries on a scene object (same reason; it also takes the stream contexts' record pool)
+#include "rtm_radiance.hip"

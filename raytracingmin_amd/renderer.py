@@ -482,6 +482,44 @@ class Renderer:
                                                      C.c_void_p(ptr("occluded")), C.c_void_p(s.cuda_stream)), "rtm_scene_occluded")
         return out["occluded"].view(torch.bool)
 
+    # ---- radiance queries on the scene (rtm_scene_radiance) ------------------------------------
+    RADIANCE_PLANES = ("radiance", "casts", "draws")
+
+    def radiance(self, org, direction, samples=1, key_base=0, clamp=False, want=("radiance",), stream=None):
+        """How much light arrives along each ray in the renderer's scene (include/rtm.h: rtm_scene_radiance): a dict of torch
+        CUDA tensors, "radiance" (n, 3) float64 — the sum over s < samples, in order, of PathTracing(ray i; stream (seed,
+        key_base + i, s)) / samples, each term clamped to [0, 1] first when `clamp` (then rays equal to a camera's pixels with
+        key_base 0 give render()'s frame at superSamples 1, bit for bit) —, "casts" and "draws" (n,) uint32: the nearest-hit
+        loops and generator calls of ray i over all its samples, modulo 2^32.  The renderer's mode, max_bounces, seed and
+        host-trig setting apply.  org and direction are contiguous (n, 3) float64 tensors on the renderer's device.  One lane
+        traces all samples of a ray: few rays with many samples under-fill the device — repeat the rays, each copy has its own
+        key.  Only the planes named in `want` are allocated and computed.  Enqueued on `stream` (default: the current stream);
+        nothing waits for it (the first call that needs the record pool or the trig table sets it up).  With max_bounces -1 or
+        above 16 the call keeps a pool of hit records sized to its rays (3 840 bytes per ray, at most 960 MiB; more than 262 144
+        rays run as several launches), so the number of rays never costs a path; a single path that reaches 976 bounces is
+        truncated (its sample adds 0) and stream_status() then raises; max_bounces above 976 is refused."""
+        import torch
+        _need_device("Renderer")
+        _check_want(want, self.RADIANCE_PLANES)
+        n, dev = self._query_rays(org, direction)
+        samples, key_base = int(samples), int(key_base)
+        if samples < 1 or samples > 0xFFFFFFFF:
+            raise ValueError(f"samples must be in [1, 2^32), got {samples}")
+        if key_base < 0 or key_base + n > 1 << 32:
+            raise ValueError(f"key_base must be >= 0 with key_base + n <= 2^32, got {key_base} for {n} rays")
+        s = _stream_of(stream, dev)
+        layout = {"radiance": ((n, 3), torch.float64), "casts": ((n,), torch.uint32), "draws": ((n,), torch.uint32)}
+        out, ptr = _stage_tensors(s, dev, want, layout)
+        bufs = _lib.rtm_radiance_buffers()
+        for k in out:
+            setattr(bufs, k, ptr(k))
+        prm = _lib.rtm_radiance_params(self.mode & ~_lib.MODE_COUNT_TESTS, self.max_bounces, self.seed, samples, key_base,
+                                       _lib.RADIANCE_CLAMP if clamp else 0, 0)
+        if n > 0:
+            _lib.check(_lib.lib().rtm_scene_radiance(self._scene_handle(), C.c_void_p(org.data_ptr()), C.c_void_p(direction.data_ptr()),
+                                                     n, C.byref(prm), C.byref(bufs), C.c_void_p(s.cuda_stream)), "rtm_scene_radiance")
+        return out
+
     def write_aov(self, fileName):
         """<fileName>_depth.pfm, _normal.pfm, _albedo.pfm (exact float planes) and _normal.bmp (quantised 0.5 n + 0.5),
         _albedo.bmp (quantised albedo) of the whole frame — what rtm_cli --aov writes."""
